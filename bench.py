@@ -4,6 +4,7 @@
   python bench.py [--gpus N] [--steps K] [--warmup W]                 (driver contract; N = 1 by default)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
   python bench.py --gpus 8 --scene bunny --width 1920 --height 1080 --spp 4096 --scaling strong      (configs[4] as written)
+  python bench.py ... --dump-outputs DIR                                  (also write the films the timed path returned)
 
 A "step" is one full pass of the hot path over the workload: one frame rendered through the C ABI (jp_render), scene
 already resident in HBM, film download included.  The HEADLINE workload is BASELINE.json
@@ -14,6 +15,11 @@ bunny scene of main.cc:64-111 at 800x600, 2048 spp) and -- round 4 -- configs[4]
 one GPU: the N = 1 figure an 8-GPU run of that frame divides by; each is timed over its own region of >= --min-seconds (default 10 s);
 their figures are summarised in `config.sub` of the one stdout line, the full sub-records (roofline, cpu_baseline,
 l2_vs_cpu_ref) are written to stderr as one `configs_detail {...}` line.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the film (H, W, 3 float32) that the last timed step of each workload
+returned: DIR/film.npy for the headline, DIR/configs<i>_film.npy for each sub-record.  Scenes, seeds and sample counts depend on
+the arguments alone, so two builds run with the same arguments can be compared film for film.  The files stay under 64 MB in
+all; a film larger than its share is written as a fixed, seeded sample of its pixels ((n, 3), in pixel order).
 
 At N > 1 the row bands of the film (the reference's FRenderTask unit, integrator.cc:53: 20 rows; here the largest height
 <= 20 that deals evenly) are dealt round-robin to the ranks, each rank renders its bands into a device film that is zero
@@ -56,6 +62,7 @@ B_SHADE_PER_SURVIVOR = 32 + 40                # next ray write + path state writ
 B_SHADE_PER_SHADOW_RAY = 48                   # shadow ray + contribution + pixel write
 B_SHADOW_PER_RAY = 48                         # the same record read back
 B_PER_SEGMENT, B_PER_SHADOW, B_FILM_PER_PIXEL = 160, 96, 12
+DUMP_BYTES = 64 * 1000 * 1000                 # --dump-outputs: at most this many bytes written in all
 
 # BASELINE.json configs -> (scene key, width, height, spp)
 CONFIGS = {
@@ -87,6 +94,22 @@ def load_profile_constants():
         except Exception:
             continue
     return {}
+
+
+def dump_outputs(d, films):
+    """--dump-outputs: every film as d/<name>.npy.  If they do not fit DUMP_BYTES together, each film larger than an equal share
+    is replaced by the same seeded sample of its pixels in every run"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // len(films) - 4096                  # (room for the .npy header)
+    big = sum(f.nbytes for f in films.values()) > DUMP_BYTES - 4096 * len(films)
+    for name, f in films.items():
+        f = np.ascontiguousarray(f, np.float32)
+        if big and f.nbytes > share:
+            px = f.reshape(-1, f.shape[-1])
+            keep = np.random.default_rng(1234).choice(px.shape[0], share // px[0].nbytes, replace=False)
+            f = px[np.sort(keep)]
+        np.save(os.path.join(d, name + ".npy"), f)
 
 
 def r4(x):
@@ -179,7 +202,10 @@ def main():
     ap.add_argument("--no-exclusive", action="store_true", help="skip the extra single-lane step behind roofline.alone (profiling runs: keeps rocprofv3's per-kernel averages to the timed configuration)")
     ap.add_argument("--band-rows", type=int, default=0, help="band height for sharding / lanes (0: largest height <= 20 that deals evenly)")
     ap.add_argument("--cpu-bands", type=int, default=2, help="20-row bands rendered by the CPU oracle at the full spp (Cornell parity sample)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the film each workload's last timed step returned as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")     # the pool's driver supports dmabuf IPC only: RCCL across processes fails without it (already exported on the GPU boxes)
     import numpy as np
@@ -325,7 +351,7 @@ def main():
                 rec["cpu_baseline"], rec["l2_vs_cpu_ref"] = cpu_and_parity(scene_key, scene, film, W, H, spp_total)
             else:
                 rec["cpu_baseline"], rec["l2_vs_cpu_ref"] = None, None
-        return rec, band_rows, lanes
+        return rec, band_rows, lanes, film
 
     def cpu_and_parity(scene_key, scene, film, W, H, spp_total):
         """oracle/ is the checker here, never the thing measured (rank 0, N = 1)"""
@@ -491,13 +517,18 @@ def main():
     if custom:
         sub_ids = [] if args.configs == "1,2,3,4" else sub_ids          # a custom headline runs alone unless sub-records are asked for
     head_in_sub = (not custom) and 2 in sub_ids
-    head, band_rows, lanes = run_workload(hk, hw, hh, hspp, args.steps, args.warmup, with_cpu=not head_in_sub)
+    head, band_rows, lanes, film = run_workload(hk, hw, hh, hspp, args.steps, args.warmup, with_cpu=not head_in_sub)
+    films = {"film": film}
     subs = {}
     for i in sub_ids:
         k, w, h, s = CONFIGS[i]
-        rec, _, _ = run_workload(k, w, h, s, 0, 1, min_seconds=args.min_seconds, parity_fn=(parity_config4 if i == 4 else None))
+        rec, _, _, film = run_workload(k, w, h, s, 0, 1, min_seconds=args.min_seconds, parity_fn=(parity_config4 if i == 4 else None))
         if rank == 0:
             subs["configs[%d]" % i] = rec
+            if args.dump_outputs:
+                films["configs%d_film" % i] = film
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, films)
     if rank == 0:
         if head_in_sub:                                       # the headline's CPU / parity legs are those of its long sub-record
             head["cpu_baseline"] = subs["configs[2]"]["cpu_baseline"]; head["l2_vs_cpu_ref"] = subs["configs[2]"]["l2_vs_cpu_ref"]

@@ -2,8 +2,10 @@
 library: it must load without a GPU and export every symbol include/jetpbrt_amd.h declares.  No compute call
 is made here."""
 import ctypes as C
+import hashlib
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -297,12 +299,15 @@ def test_film_writers_equal_the_reference_writers_byte_for_byte(H, tmp_path):
     assert (np.diff(thr) >= 0).all() and thr[0] > 0 and thr[-1] <= 1.0
     table = np.searchsorted(thr, np.clip(x, 0, 1), side="right").astype(np.uint8)        # what k_tonemap8 computes
     assert np.array_equal(table, want)
-    if H.have_ref():                                              # live, where the reference library exists: a larger random set
-        rng = np.random.default_rng(5)
-        xr = np.concatenate([rng.random(200000), rng.random(50000) ** 8]).astype(np.float32)
-        yr = np.zeros(xr.size, np.uint8)
-        H.ref_lib().ref_gamma_encode(H.ptr(xr), xr.size, H.ptr(yr))
-        assert np.array_equal(np.searchsorted(thr, xr, side="right").astype(np.uint8), yr)
+    # a larger random set against the reference's bytes for it (their SHA-256: tests/golden/make_golden_vs_reference.py)
+    xr = gamma_sample()
+    want = str(np.load(os.path.join(H.GOLDEN, "vs_reference.npz"))["gamma_sha256"])
+    assert hashlib.sha256(np.searchsorted(thr, xr, side="right").astype(np.uint8).tobytes()).hexdigest() == want
+
+
+def gamma_sample():
+    rng = np.random.default_rng(5)
+    return np.concatenate([rng.random(200000), rng.random(50000) ** 8]).astype(np.float32)
 
 
 def test_kernel_register_budgets(H, tmp_path):
@@ -313,7 +318,7 @@ def test_kernel_register_budgets(H, tmp_path):
     import subprocess
     csrc = os.path.join(H.REPO, "jet-pbrt_amd", "csrc")
     subprocess.run(["make", "-s", "asm"], cwd=csrc, check=True)
-    out = subprocess.run(["python", os.path.join(H.REPO, "tools", "resource_table.py")], stdout=subprocess.PIPE, text=True, check=True).stdout
+    out = subprocess.run([sys.executable, os.path.join(H.REPO, "tools", "resource_table.py")], stdout=subprocess.PIPE, text=True, check=True).stdout
     rows = {}
     for line in out.splitlines()[1:]:
         m = re.match(r"(.+?)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)\s+(\d+)$", line)
