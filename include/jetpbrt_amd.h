@@ -296,6 +296,42 @@ int  jp_bsdf(JpContext* ctx, const JpBsdfDesc* desc, int32_t n, const float* nor
 int  jp_trace(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax,
               int32_t* hit, float* t, int32_t* prim, float* normal);
 
+/* Texture-mapped materials (additive to ABI 7; INTEGRATION.md "Textures").  A material's main colour -- MATTE diffuseColor, MIRROR specularColor,
+ * PLASTIC Kd (its Qd then follows the sampled Kd at every shading point, material.h:94-98) -- may come from a texture of texture.h / texture.cc,
+ * sampled on the device at every bounce of the path integrator.  Textures on GLASS / METAL are refused ([0..2] is eta there).
+ *   SOLID    the colour tex_color[0..2]
+ *   CHECKER  odd tex_color[0..2] where sinf(10x) * sinf(10y) * sinf(10z) < 0 at the world hit point, else even tex_color[3..5]
+ *   IMAGE    nearest texel of FImageTexture::Sample: u, v clamped to [0, 1], v flipped, i = (int)(u * width), j = (int)(v * height), each
+ *            clamped to size - 1 (a NaN coordinate: texel 0 on its axis); colour (1.0f / 255.0f) * byte
+ * uv per shape: FRectangle::GetUV, FDisk::GetUV, FSphere::GetUV on (p - center) / radius, triangles by barycentrics of the normal equations. */
+enum { JP_TEXTURE_SOLID = 0, JP_TEXTURE_CHECKER = 1, JP_TEXTURE_IMAGE = 2 };
+typedef struct JpTextures {
+    int32_t struct_bytes;                    /* sizeof(JpTextures) of the caller                                                    */
+    int32_t n_textures;
+    const int32_t *tex_type;                 /* JP_TEXTURE_*                                                                        */
+    const float   *tex_color;                /* 6 per texture: SOLID [0..2]; CHECKER odd [0..2], even [3..5]                         */
+    const int32_t *tex_width, *tex_height;   /* IMAGE (1 .. 16384 each)                                                             */
+    const int64_t *tex_offset;               /* IMAGE: byte offset of its top-left texel in `texels`                                */
+    int64_t n_texel_bytes; const uint8_t *texels;   /* RGB8, row-major, top row first, 3*width bytes per row                       */
+    int32_t n_materials;   const int32_t *mat_texture;   /* == JpScene.n_materials; -1 = the material's own colour                 */
+    int32_t n_triangles;   const float *tri_uv;          /* == JpScene.n_triangles; uv0 uv1 uv2 (6 floats); NULL = 0               */
+} JpTextures;
+typedef struct JpTextureInfo {
+    int32_t struct_bytes, n_textures, n_textured_materials;
+    int64_t texel_bytes_device;              /* bytes of the device's RGBA8 texel pool                                              */
+    int32_t textured_last_render;            /* the last jp_render* ran k_texel + k_shade_tex                                       */
+} JpTextureInfo;
+/* jp_upload_scene plus the textures (validated completely on the host: JP_ERR_INVALID_ARGUMENT with a message, the context stays usable).
+ * textures NULL or n_textures 0: exactly jp_upload_scene, which in turn drops the texture state of an earlier textured upload.  A textured scene
+ * renders with the path integrator (the Whitted integrator returns JP_ERR_UNSUPPORTED, the debug integrator ignores textures) and the per-bounce
+ * launches (JpOptions.fused falls back, fused_last_render 0). */
+int  jp_upload_scene_textured(JpContext* ctx, const JpScene* scene, const JpTextures* textures);
+int  jp_get_texture_info(JpContext* ctx, JpTextureInfo* out);
+/* test hook / utility, like jp_trace: closest hit, then the shape's uv (2n floats) and the colour the textured slot takes there (3n floats;
+ * untextured materials: mat_params[0..2]; glass, metal, no material, no hit: 0); prim: the caller's primitive index, -1 if none */
+int  jp_surface(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax,
+                int32_t* prim, float* uv, float* albedo);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,48 @@ class JpBsdfDesc(C.Structure):
                 ("fr_eta_i", C.c_float * 3), ("fr_eta_t", C.c_float * 3), ("fr_k", C.c_float * 3), ("exponent", C.c_float)]
 
 
+JP_TEXTURE_SOLID, JP_TEXTURE_CHECKER, JP_TEXTURE_IMAGE = 0, 1, 2
+
+
+class JpTextures(C.Structure):
+    """include/jetpbrt_amd.h: JpTextures (jp_upload_scene_textured); struct_bytes = sizeof(JpTextures)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_textures", C.c_int32), ("tex_type", _ip), ("tex_color", _fp),
+                ("tex_width", _ip), ("tex_height", _ip), ("tex_offset", C.POINTER(C.c_int64)),
+                ("n_texel_bytes", C.c_int64), ("texels", C.POINTER(C.c_uint8)),
+                ("n_materials", C.c_int32), ("mat_texture", _ip), ("n_triangles", C.c_int32), ("tri_uv", _fp)]
+
+
+class JpTextureInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_textures", C.c_int32), ("n_textured_materials", C.c_int32),
+                ("texel_bytes_device", C.c_int64), ("textured_last_render", C.c_int32)]
+
+
+def textures(tex_type, tex_color, mat_texture, n_triangles=0, tri_uv=None, images=()):
+    """A JpTextures over numpy arrays (kept alive on the returned object as ._keep).  tex_type / tex_color (n, 6) / mat_texture as in the
+    header; images: {texture index: (H, W, 3) uint8 array} -- their texels are packed one after another."""
+    import numpy as np
+    n = len(tex_type)
+    tt = np.ascontiguousarray(tex_type, np.int32); tc = np.ascontiguousarray(np.asarray(tex_color, np.float32).reshape(n, 6))
+    w = np.zeros(n, np.int32); h = np.zeros(n, np.int32); off = np.zeros(n, np.int64)
+    chunks, at = [], 0
+    for k, img in dict(images).items():
+        img = np.ascontiguousarray(img, np.uint8)
+        h[k], w[k], off[k] = img.shape[0], img.shape[1], at
+        chunks.append(img.reshape(-1)); at += img.size
+    tx = np.ascontiguousarray(np.concatenate(chunks) if chunks else np.zeros(1, np.uint8))
+    mt = np.ascontiguousarray(mat_texture, np.int32)
+    t = JpTextures()
+    t.struct_bytes = C.sizeof(JpTextures); t.n_textures = n
+    t.tex_type = tt.ctypes.data_as(_ip); t.tex_color = tc.ctypes.data_as(_fp); t.tex_width = w.ctypes.data_as(_ip); t.tex_height = h.ctypes.data_as(_ip)
+    t.tex_offset = off.ctypes.data_as(C.POINTER(C.c_int64)); t.n_texel_bytes = at; t.texels = tx.ctypes.data_as(C.POINTER(C.c_uint8))
+    t.n_materials = len(mt); t.mat_texture = mt.ctypes.data_as(_ip); t.n_triangles = n_triangles
+    uv = None
+    if tri_uv is not None:
+        uv = np.ascontiguousarray(tri_uv, np.float32); t.tri_uv = uv.ctypes.data_as(_fp)
+    t._keep = (tt, tc, w, h, off, tx, mt, uv)
+    return t
+
+
 JP_BSDF_LAMBERT, JP_BSDF_MIRROR, JP_BSDF_FRESNEL_SPECULAR, JP_BSDF_MICROFACET_REFLECTION, JP_BSDF_MICROFACET_TRANSMISSION, JP_BSDF_PHONG = range(6)
 JP_DIST_TROWBRIDGE_REITZ, JP_DIST_BECKMANN = 0, 1
 JP_FRESNEL_CONDUCTOR, JP_FRESNEL_DIELECTRIC, JP_FRESNEL_NOOP = 0, 1, 2
@@ -153,6 +195,16 @@ def host_lib():
         L.jp_host_render_ldr.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]
         L.jp_host_gamma_encode.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.jp_host_bsdf_class.argtypes = [C.c_int, _fp, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, _fp, _fp, _fp, _fp, _fp]
+        L.jp_host_texture_solid.argtypes = [C.c_void_p, _fp]
+        L.jp_host_texture_checker.argtypes = [C.c_void_p, _fp, _fp]
+        L.jp_host_texture_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.jp_host_texture_image_file.argtypes = [C.c_void_p, C.c_char_p]
+        L.jp_host_mat_matte_tex.argtypes = [C.c_void_p, C.c_int]
+        L.jp_host_mat_mirror_tex.argtypes = [C.c_void_p, C.c_int]
+        L.jp_host_mat_plastic_tex.argtypes = [C.c_void_p, C.c_int, _fp, C.c_float, C.c_int]
+        L.jp_host_mat_set_texture.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.jp_host_flatten_textures.restype = C.POINTER(JpTextures)
+        L.jp_host_flatten_textures.argtypes = [C.c_void_p]
         L.jp_host_render_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         _host = L
     return _host
@@ -183,6 +235,9 @@ def hip_lib():
         L.jp_render_rgb8.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_void_p, C.c_void_p]
         L.jp_gamma_thresholds.argtypes = [C.c_void_p]
         L.jp_bsdf.argtypes = [C.c_void_p, C.POINTER(JpBsdfDesc), C.c_int32] + [C.c_void_p] * 10
+        L.jp_upload_scene_textured.argtypes = [C.c_void_p, C.POINTER(JpScene), C.POINTER(JpTextures)]
+        L.jp_get_texture_info.argtypes = [C.c_void_p, C.POINTER(JpTextureInfo)]
+        L.jp_surface.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
         _hip = L
     return _hip
 
@@ -218,8 +273,29 @@ class Context:
         o.struct_bytes = C.sizeof(JpOptions)
         self._check(self.lib.jp_set_options(self.h, C.byref(o)))
 
-    def upload(self, scene_ptr):
-        self._check(self.lib.jp_upload_scene(self.h, scene_ptr))
+    def upload(self, scene_ptr, textures=None):
+        """jp_upload_scene, or jp_upload_scene_textured when `textures` (a JpTextures or a pointer to one) is given"""
+        if textures is None:
+            self._check(self.lib.jp_upload_scene(self.h, scene_ptr))
+        else:
+            self._check(self.lib.jp_upload_scene_textured(self.h, scene_ptr, textures if isinstance(textures, C._Pointer) else C.byref(textures)))
+
+    def texture_info(self):
+        i = JpTextureInfo()
+        i.struct_bytes = C.sizeof(JpTextureInfo)
+        self._check(self.lib.jp_get_texture_info(self.h, C.byref(i)))
+        return i
+
+    def surface(self, origin, direction, tmin, tmax):
+        """jp_surface: closest hit, the shape's uv and the colour of the textured slot -> (prim (n,), uv (n, 2), albedo (n, 3))"""
+        import numpy as np
+        n = origin.shape[0]
+        o = np.ascontiguousarray(origin, np.float32); d = np.ascontiguousarray(direction, np.float32)
+        t0 = np.ascontiguousarray(tmin, np.float32); t1 = np.ascontiguousarray(tmax, np.float32)
+        prim = np.zeros(n, np.int32); uv = np.zeros((n, 2), np.float32); alb = np.zeros((n, 3), np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_surface(self.h, n, p(o), p(d), p(t0), p(t1), p(prim), p(uv), p(alb)))
+        return prim, uv, alb
 
     def render(self, params):
         import numpy as np

@@ -85,3 +85,17 @@ __device__ __forceinline__ unsigned int wave_take(unsigned int* ctr, unsigned in
 	return (unsigned int)__builtin_amdgcn_readfirstlane((int)v);
 }
 
+
+// ---- textures (k_texel, k_shade_tex, jp_surface; jp_tex.h) -------------------------------------------------------------
+// A separate kernel argument: SceneView, Queues and RenderConst stay as they are, so the kernels of untextured scenes do not change.
+#define JP_TEX_IMAGE_TAG 0x80000000u   // side word: RGB8 of the texel in the low 24 bits (R in bits 0-7)
+#define JP_TEX_COLOR_TAG 0x40000000u   // side word: index into TexView::col in the low 30 bits (SOLID 2t, CHECKER odd 2t / even 2t + 1)
+struct TexView
+{
+	const int4* desc;            // per texture: (JP_TEXTURE_*, width, height, first texel in the pool)
+	const float4* col;           // two per texture: SOLID colour, -; CHECKER odd, even
+	const unsigned int* texels;  // RGBA8 pool, one aligned 4-byte load per lookup
+	const int* mat_tex;          // per material: texture index, -1 = the material's own colour
+	const float2* prim_uv;       // three per primitive of the caller's order (uv0 uv1 uv2 of a triangle; 0 for other shapes)
+	unsigned int* side;          // one word per queue position (cap entries of the context's queue set)
+};

@@ -20,6 +20,7 @@
 // and appends to region b of the output queues with a running offset, so compaction needs no global atomic and the
 // layout is deterministic.  Launches are asynchronous on one stream, no host round trip inside a batch.
 #include "jp_common.h"
+#include "jp_tex.h"
 #include "jp_xbsdf.h"
 
 #include <cstdio>
@@ -219,8 +220,9 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 #ifndef JP_SHADE_TILE
 #define JP_SHADE_TILE 8192
 #endif
-template <bool kTab, bool kPrims, bool kStage, bool kSort>
-__global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt)
+// kTex (k_shade_tex, textured scenes): the textured slot of a material's closure comes from the word k_texel left for the queue position.
+template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex>
+__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv)
 {
 	static_assert(kTab || !kPrims, "k_shade: primitive records in LDS only together with the tables");
 	constexpr int kWaves = JP_BLOCK / 64, kMaxSeg = (JP_SHADE_TILE / JP_BLOCK) * kWaves;  // (pass, wave) segments of a tile, in queue order
@@ -353,14 +355,14 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, Rend
 	// The tile is shaded in 64-path chunks that the waves take from an LDS counter: a wave with expensive paths (a chunk of the
 	// microfacet class) takes fewer chunks, and no wave waits for another before the end of the tile.  The records of the chunk
 	// a wave takes next are fetched while it shades the current one (software prefetch).
-	float4 ro_n = make_float4(0, 0, 0, 0), rd_n = ro_n, rb_n = ro_n; float2 h_n = make_float2(0, 0);
+	float4 ro_n = make_float4(0, 0, 0, 0), rd_n = ro_n, rb_n = ro_n; float2 h_n = make_float2(0, 0); unsigned int s_n = 0;
 	// Chunks are taken from the END of the sorted tile: the expensive classes (plastic, metal) sort last, and taking them first
 	// leaves the cheap chunks to even out the waves before the barrier at the end of the tile.
 	JP_TS(1);                                                     // [1] partition
 	const unsigned int nch = (count + 63u) >> 6;
 	unsigned int tk = wave_take(&s_ctr[0], 1u);                  // wave-uniform
 	unsigned int c0 = (nch - 1u - tk) << 6;                      // first tile position of the wave's chunk (meaningful while tk < nch)
-	if (tk < nch && c0 + lane < count) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; }
+	if (tk < nch && c0 + lane < count) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; }
 	while (tk < nch)
 	{
 		const bool valid = c0 + lane < count;
@@ -370,17 +372,17 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, Rend
 		JP_TS(3);                                                 // [3] wait for the prefetched records (and for the stores before them)
 #endif
 #ifdef JP_SHADE_NO_PREFETCH
-		if (valid) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; }
-		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n;
+		if (valid) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; }
+		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n;
 		tk = wave_take(&s_ctr[0], 1u); c0 = (nch - 1u - tk) << 6;
 #else
-		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n;
+		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n;
 		tk = wave_take(&s_ctr[0], 1u); c0 = (nch - 1u - tk) << 6;
 		if (tk < nch && c0 + lane < count)
 		{
 			const unsigned int pos = c0 + lane;
 			const unsigned int i1 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos);
-			ro_n = q.ray_o[cur][i1]; rd_n = q.ray_d[cur][i1]; rb_n = q.beta[cur][i1]; h_n = q.hit[i1];
+			ro_n = q.ray_o[cur][i1]; rd_n = q.ray_d[cur][i1]; rb_n = q.beta[cur][i1]; h_n = q.hit[i1]; if (kTex) s_n = tv.side[i1];
 		}
 #endif
 		bool shaded = false, wantNee = false, alive = false;
@@ -443,7 +445,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, Rend
 					float up = 0.f;
 					const int mtype = mat_type[mat];
 					if (mtype == JP_MAT_PLASTIC) up = rngf(rc, key, dim++);   // material.cc:14
-					make_closure(mats, mtype, mat, up, c);
+					if (kTex && sw != 0u) make_closure_tex(mats, mtype, mat, up, tex_color(tv, sw), c);
+					else make_closure(mats, mtype, mat, up, c);
 #ifdef JP_DBG_SKIP_FRAME
 					fr.n = N; fr.s = mk(N.y, N.z, N.x); fr.t = mk(N.z, N.x, N.y);
 #else
@@ -600,6 +603,12 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, Rend
 		if (run_q) atomicAdd(&cnt->n_queue[nxt], run_q);
 		if (run_sh) atomicAdd(&cnt->n_shadow, run_sh);
 	}
+}
+template <bool kTab, bool kPrims, bool kStage, bool kSort>
+__global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt)
+{
+	const TexView tv = {};
+	shade_body<kTab, kPrims, kStage, kSort, false>(sc, q, rc, cur, cnt, tv);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1115,6 +1124,76 @@ __global__ void __launch_bounds__(JP_BLOCK) k_trace(SceneView sc, int depth, int
 			else N = normalize(p - xyz(sc.prims[4 * h]));
 		}
 		nrm[3 * i] = N.x; nrm[3 * i + 1] = N.y; nrm[3 * i + 2] = N.z;
+	}
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// textures (jp_tex.h; DESIGN.md "Textures"): k_texel between extend and shade, k_shade_tex, and the test hook k_surface
+// ---------------------------------------------------------------------------------------------------------------------
+// k_texel: for every queued ray of the block's region that hit a textured material, the uv of the hit and the texture's answer as
+// one 32-bit side word at the ray's queue position (0: no texture).  Kept out of k_shade, whose registers sit at the 3-wave line: this
+// kernel is small enough for 8 waves per SIMD, which hides the latency of the dependent gather hit -> primitive -> texel.
+__global__ void __launch_bounds__(JP_BLOCK, 8) k_texel(SceneView sc, Queues q, int cur, TexView tv)
+{
+	const unsigned int b = blockIdx.x, n = q.blk_q[cur][b], rbase = b * q.R;
+	for (unsigned int j = threadIdx.x; j < n; j += JP_BLOCK)
+	{
+		const unsigned int i = rbase + j;
+		const float2 h = q.hit[i];
+		const int pi = __float_as_int(h.y);
+		unsigned int w = 0u;
+		if (pi >= 0)
+		{
+			const int4 meta = sc.meta[pi];
+			const int t = meta.y >= 0 ? tv.mat_tex[meta.y] : -1;
+			if (t >= 0)
+			{
+				const float4 ro = q.ray_o[cur][i], rd = q.ray_d[cur][i];
+				const V3 p = xyz(ro) + h.x * xyz(rd);                               // ray(distance), as k_shade forms it
+				w = tex_sample(tv, t, tex_uv(sc.prims, tv, pi, meta.x, p), p);
+			}
+		}
+		tv.side[i] = w;
+	}
+}
+
+template <bool kTab, bool kPrims, bool kStage, bool kSort>
+__global__ void __launch_bounds__(JP_BLOCK) k_shade_tex(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, TexView tv)
+{
+	shade_body<kTab, kPrims, kStage, kSort, true>(sc, q, rc, cur, cnt, tv);
+}
+
+// k_surface (jp_surface): the closest hit of k_trace's walk, then the uv k_texel computes and the colour k_shade_tex puts in the textured
+// slot (untextured matte / mirror / plastic: mat_params[0..2]; glass, metal, no material, no hit: 0)
+template <int kMode>
+__global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, int depth, int n, const float* o, const float* d, const float* tmin, const float* tmax_in,
+                                                      int* prim, float* uv, float* albedo)
+{
+	SceneAccess<kMode> acc(sc, depth);
+	for (int i = blockIdx.x * JP_BLOCK + threadIdx.x; i < n; i += gridDim.x * JP_BLOCK)
+	{
+		const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+		float tmax = tmax_in[i];
+		const int h = acc.template trace<false>(sc, ro, rd, tmin[i], tmax);
+		float2 st = make_float2(0.f, 0.f); V3 a = splat(0);
+		prim[i] = -1;
+		if (h >= 0)
+		{
+			const int4 meta = sc.meta[h];
+			const V3 p = ro + tmax * rd;
+			prim[i] = meta.x;
+			st = tex_uv(sc.prims, tv, h, meta.x, p);
+			const int mat = meta.y;
+			if (mat >= 0)
+			{
+				const int mtype = sc.mat_type[mat];
+				const int t = tv.mat_tex ? tv.mat_tex[mat] : -1;
+				if (t >= 0) a = tex_color(tv, tex_sample(tv, t, st, p));
+				else if (mtype == JP_MAT_MATTE || mtype == JP_MAT_MIRROR || mtype == JP_MAT_PLASTIC) a = xyz(sc.mats[4 * mat]);
+			}
+		}
+		uv[2 * i] = st.x; uv[2 * i + 1] = st.y;
+		albedo[3 * i] = a.x; albedo[3 * i + 1] = a.y; albedo[3 * i + 2] = a.z;
 	}
 }
 

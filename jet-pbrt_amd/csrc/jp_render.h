@@ -103,6 +103,13 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 			budget = (size_t)sbatch / 2 * (size_t)npix * per;              // half the batch
 		}
 		c->q.cap = cap; c->q.R = R;
+		const bool tex = c->textured && rp->integrator == JP_INTEGRATOR_PATH;
+		if (tex && c->side_n < cap)
+		{   // the side words of k_texel: one per queue position, allocated for textured scenes only
+			if (c->d_side) { HIP_TRY(hipStreamSynchronize(c->stream)); hipFree(c->d_side); } c->d_side = nullptr; c->side_n = 0;
+			HIP_TRY(hipMalloc((void**)&c->d_side, (size_t)cap * sizeof(unsigned int))); c->side_n = cap;
+		}
+		TexView tv = c->tv; tv.side = c->d_side;
 		{   // spill area of the walkers' stacks: the words a thread may need beyond the ones kept in LDS
 			const int deep = std::max(std::max(c->stack_depth, c->stack_depth_q4), c->trav_mode == 3 ? (int)(c->lds_bytes_shadow / (JP_BLOCK * sizeof(int))) : 0);
 			const size_t need = c->persist && deep >= c->stack_lds_words ? (size_t)(deep - c->stack_lds_words + 1) * G * JP_BLOCK : 1;   // (+1: Walker<4> keeps one LDS word as a dump slot)
@@ -167,6 +174,19 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 					else if (c->trav_mode == 1) hipLaunchKernelGGL(k_extend<1>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, cur, c->stack_depth, c->d_cnt);
 					else hipLaunchKernelGGL(k_extend<0>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, cur, c->stack_depth, c->d_cnt);
 				}
+				if (tex)
+				{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
+					Stamper t(c, CLS_SHADE);
+					hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, c->sv, c->q, cur, tv);
+					const bool st = c->stage_nee;
+					#define JP_LAUNCH_SHADE(A, B, C) do { if (c->shade_sort) hipLaunchKernelGGL((k_shade_tex<A, B, C, true>), dim3(grid), dim3(JP_BLOCK), c->shade_lds_bytes, c->stream, c->sv, c->q, rc, cur, c->d_cnt, tv); \
+					                                   else hipLaunchKernelGGL((k_shade_tex<A, B, C, false>), dim3(grid), dim3(JP_BLOCK), c->shade_lds_bytes, c->stream, c->sv, c->q, rc, cur, c->d_cnt, tv); } while (0)
+					if (c->shade_prims_in_lds) { if (st) JP_LAUNCH_SHADE(true, true, true); else JP_LAUNCH_SHADE(true, true, false); }
+					else if (c->tables_in_lds) { if (st) JP_LAUNCH_SHADE(true, false, true); else JP_LAUNCH_SHADE(true, false, false); }
+					else JP_LAUNCH_SHADE(false, false, false);
+					#undef JP_LAUNCH_SHADE
+				}
+				else
 				{
 					Stamper t(c, CLS_SHADE);
 					const bool st = c->stage_nee;
@@ -252,6 +272,8 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 	l->persist = c->persist; l->vote = c->vote; l->shade_sort = c->shade_sort; l->class_mask = c->class_mask;
 	l->has_null_material = c->has_null_material; l->tables_in_lds = c->tables_in_lds; l->stage_nee = c->stage_nee; l->shade_lds_bytes = c->shade_lds_bytes;
 	l->profiling = c->profiling;
+	l->tv = c->tv; l->textured = c->textured;                        // (the lane's side array is its own, allocated with its queues)
+	if (!l->textured && l->d_side) { hipStreamSynchronize(l->stream); hipFree(l->d_side); l->d_side = nullptr; l->side_n = 0; }   // untextured scene: not kept
 	l->opt = c->opt;                                                 // render_one(lane) reads max_slots / compact_regions from its own context
 }
 
@@ -270,6 +292,7 @@ bool fused_eligible(const JpContext* c, const JpRenderParams* rp)
 	if (c->is_lane || !c->have_scene || rp->integrator != JP_INTEGRATOR_PATH) return false;
 	if (!c->tables_in_lds || c->n_planes > 4) return false;          // (its own LDS budget: render_fused shrinks the region until the layout fits)
 	if (c->cert) return false;                                       // the certified walk lives in the per-bounce traversal kernels
+	if (c->textured) return false;                                   // textures: k_texel + k_shade_tex live in the per-bounce launches
 	if (c->trav_mode == 2) return c->shade_prims_in_lds;
 	return c->trav_mode == 0 || c->trav_mode == 3 || c->trav_mode == 5;
 }
@@ -417,8 +440,10 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
-	c->last_lanes = 1; c->last_fused = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0;
+	if (c->textured && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample textures (scene uploaded by jp_upload_scene_textured)");
 	if (fused_eligible(c, rp)) return render_fused(c, rp, film_dev, sync);
+	c->last_textured = c->textured && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
 	// Gsamples/s).  JETPBRT_LANES = 1 .. 4 forces a count, JETPBRT_LANE_ROWS the group height.
@@ -643,6 +668,56 @@ int jp_trace(JpContext* c, int32_t n, const float* origin, const float* dir, con
 		if (e != hipSuccess) rc = fail(JP_ERR_DEVICE, std::string("jp_trace: ") + hipGetErrorString(e));
 	} while (0);
 	hipFree(d_o); hipFree(d_d); hipFree(d_t0); hipFree(d_t1); hipFree(d_t); hipFree(d_n); hipFree(d_hit); hipFree(d_prim);
+	return rc;
+}
+
+int jp_get_texture_info(JpContext* c, JpTextureInfo* out)
+{
+	if (!c || !out) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_texture_info: null argument");
+	if (out->struct_bytes < (int32_t)sizeof(int32_t)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_texture_info: set JpTextureInfo.struct_bytes to sizeof(JpTextureInfo)");
+	JpTextureInfo i; std::memset(&i, 0, sizeof(i));
+	i.n_textures = c->textured ? c->n_textures : 0; i.n_textured_materials = c->n_tex_mats; i.texel_bytes_device = c->texel_bytes; i.textured_last_render = c->last_textured;
+	const size_t n = std::min((size_t)out->struct_bytes, sizeof(i));
+	i.struct_bytes = (int32_t)n;
+	std::memcpy(out, &i, n);                                                   // (a shorter struct of the caller is truncated)
+	return JP_OK;
+}
+
+int jp_surface(JpContext* c, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, int32_t* prim, float* uv, float* albedo)
+{
+	if (!c || n < 0 || !origin || !dir || !tmin || !tmax || !prim || !uv || !albedo) return fail(JP_ERR_INVALID_ARGUMENT, "jp_surface: null argument");
+	if (!c->have_scene) return fail(JP_ERR_NO_SCENE, "jp_surface: no scene uploaded");
+	if (n == 0) return JP_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	float *d_in = nullptr, *d_uv = nullptr, *d_a = nullptr; int* d_prim = nullptr;
+	int rc = JP_OK;
+	do
+	{
+		if (hipMalloc((void**)&d_in, (size_t)n * 32) != hipSuccess || hipMalloc((void**)&d_uv, (size_t)n * 8) != hipSuccess || hipMalloc((void**)&d_a, (size_t)n * 12) != hipSuccess
+		    || hipMalloc((void**)&d_prim, (size_t)n * 4) != hipSuccess) { rc = fail(JP_ERR_DEVICE, "jp_surface: out of device memory"); break; }
+		float *d_o = d_in, *d_d = d_in + 3 * (size_t)n, *d_t0 = d_in + 6 * (size_t)n, *d_t1 = d_in + 7 * (size_t)n;
+		hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
+		hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
+		const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
+		const size_t q4lds = (size_t)c->stack_depth_q4 * JP_BLOCK * sizeof(int);
+		const TexView tv = c->tv;
+		// the walk jp_trace takes by default (what the render's closest-hit rays walk)
+		if (c->trav_mode == 5 && c->cert && q4lds <= 64 * 1024) hipLaunchKernelGGL(k_surface<6>, dim3(grid), dim3(JP_BLOCK), q4lds, c->stream, c->sv, tv, c->stack_depth_q4, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+		else if (c->trav_mode == 5) hipLaunchKernelGGL(k_surface<5>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, tv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+		else if (c->use_q4 && q4lds <= 64 * 1024) hipLaunchKernelGGL(k_surface<4>, dim3(grid), dim3(JP_BLOCK), q4lds, c->stream, c->sv, tv, c->stack_depth_q4, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+		else if (c->trav_mode == 2) hipLaunchKernelGGL(k_surface<2>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, tv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+		else if (c->trav_mode == 1) hipLaunchKernelGGL(k_surface<1>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, tv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+		else hipLaunchKernelGGL(k_surface<0>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, tv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+		hipError_t e = hipGetLastError();
+		if (e == hipSuccess)
+		{
+			hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream); hipMemcpyAsync(uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream);
+			hipMemcpyAsync(albedo, d_a, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream);
+			e = hipStreamSynchronize(c->stream);
+		}
+		if (e != hipSuccess) rc = fail(JP_ERR_DEVICE, std::string("jp_surface: ") + hipGetErrorString(e));
+	} while (0);
+	hipFree(d_in); hipFree(d_uv); hipFree(d_a); hipFree(d_prim);
 	return rc;
 }
 

@@ -96,13 +96,22 @@ struct JpContext
 	Queues fq = {}; std::vector<void*> fbufs; unsigned int fcap = 0; int fplanes = 0; size_t flacc_n = 0;
 	unsigned int* d_jobs = nullptr; size_t jobs_n = 0;
 	int last_fused = 0, last_region = 0, last_wgs = 0;
+	// textures (jp_upload_scene_textured): the tables belong to the parent context and reach the lanes through `tv` (its side pointer is
+	// set per launch); every context owns the side array of its own queue set (k_texel -> k_shade_tex, one word per queue position)
+	TexView tv = {}; bool textured = false; int n_textures = 0, n_tex_mats = 0; long long texel_bytes = 0; int last_textured = 0;
+	void *d_tex_desc = nullptr, *d_tex_col = nullptr, *d_texels = nullptr, *d_mat_tex = nullptr, *d_prim_uv = nullptr;
+	unsigned int* d_side = nullptr; size_t side_n = 0;
 };
 
 static void free_scene(JpContext* c)
 {
-	void** ps[] = { &c->d_flat, &c->d_wide, &c->d_q4, &c->d_refbox, &c->d_nodes, &c->d_prims, &c->d_meta, &c->d_mats, &c->d_mat_type, &c->d_lights, &c->d_shade_tab };
+	void** ps[] = { &c->d_flat, &c->d_wide, &c->d_q4, &c->d_refbox, &c->d_nodes, &c->d_prims, &c->d_meta, &c->d_mats, &c->d_mat_type, &c->d_lights, &c->d_shade_tab,
+	                &c->d_tex_desc, &c->d_tex_col, &c->d_texels, &c->d_mat_tex, &c->d_prim_uv };
 	for (void** p : ps) { if (*p) hipFree(*p); *p = nullptr; }
 	c->have_scene = false;
+	c->tv = TexView(); c->textured = false; c->n_textures = c->n_tex_mats = 0; c->texel_bytes = 0;   // (jp_upload_scene drops the textures of an earlier textured upload)
+	if (c->d_side) hipFree(c->d_side);                             // ... and the side array only textured frames use (callers synchronise first)
+	c->d_side = nullptr; c->side_n = 0;
 }
 static void free_queues(JpContext* c)
 {
@@ -332,6 +341,7 @@ int jp_destroy_context(JpContext* c)
 	free_queues(c);
 	free_fused(c);
 	if (c->d_pix_acc) hipFree(c->d_pix_acc);
+	if (c->d_side) hipFree(c->d_side);
 	if (c->d_spill) hipFree(c->d_spill);
 	if (c->d_film) hipFree(c->d_film);
 	if (c->h_film) hipHostFree(c->h_film);

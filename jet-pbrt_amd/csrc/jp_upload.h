@@ -724,3 +724,101 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	return JP_OK;
 }
 
+
+// ---- textures: validation on the host, then the scene, then the texture tables (TexView) ------------------------------------------
+extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const JpTextures* t)
+{
+	if (!c || !s) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: null argument");
+	if (!t) return jp_upload_scene(c, s);
+	if (t->struct_bytes < (int32_t)sizeof(JpTextures)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: JpTextures.struct_bytes smaller than this library's JpTextures");
+	if (t->n_textures < 0 || t->n_textures > (1 << 28)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: n_textures out of range");
+	if (t->n_textures == 0) return jp_upload_scene(c, s);
+	const int nt = t->n_textures;
+	if (!t->tex_type || !t->tex_color) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: null tex_type / tex_color");
+	if (t->n_materials != s->n_materials) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: n_materials differs from the scene's");
+	if (t->n_triangles != s->n_triangles) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: n_triangles differs from the scene's");
+	if (t->n_materials > 0 && (!t->mat_texture || !s->mat_type)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: null mat_texture");
+	long long pool = 0;                                                // texels of the device pool (RGBA8)
+	for (int i = 0; i < nt; i++)
+	{
+		const int ty = t->tex_type[i];
+		if (ty < JP_TEXTURE_SOLID || ty > JP_TEXTURE_IMAGE) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: unknown texture type");
+		if (ty == JP_TEXTURE_IMAGE)
+		{
+			if (!t->tex_width || !t->tex_height || !t->tex_offset || !t->texels) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: image texture without tex_width / tex_height / tex_offset / texels");
+			const long long w = t->tex_width[i], h = t->tex_height[i], off = t->tex_offset[i];
+			if (w < 1 || w > 16384 || h < 1 || h > 16384) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: image size out of range (1 .. 16384 per side)");
+			if (off < 0 || t->n_texel_bytes < 0 || off > t->n_texel_bytes - 3 * w * h) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: image texels beyond n_texel_bytes");
+			pool += w * h;
+		}
+		else
+		{
+			const int nc = ty == JP_TEXTURE_CHECKER ? 6 : 3;
+			for (int k = 0; k < nc; k++) if (!std::isfinite(t->tex_color[6 * (size_t)i + k])) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: colour not finite");
+		}
+	}
+	if (pool > 0x7fffffffll) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: more than 2^31 texels in all");
+	int ntm = 0;
+	for (int m = 0; m < t->n_materials; m++)
+	{
+		const int k = t->mat_texture[m];
+		if (k < -1 || k >= nt) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: mat_texture out of range");
+		if (k < 0) continue;
+		const int mt = s->mat_type[m];
+		if (mt != JP_MAT_MATTE && mt != JP_MAT_MIRROR && mt != JP_MAT_PLASTIC) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: a texture on a glass or metal material (its [0..2] is eta, not a colour)");
+		ntm++;
+	}
+	if (s->n_primitives > 0 && (!s->prim_shape_type || !s->prim_shape_index)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene_textured: null array");
+	const int st = jp_upload_scene(c, s);                              // (validates the scene; drops the textures of an earlier upload)
+	if (st != JP_OK) return st;
+	if (ntm == 0) return JP_OK;                                        // textures no material uses: the untextured scene, exactly
+
+	// ---- device tables ----
+	std::vector<int4> desc(nt); std::vector<float4> col(2 * (size_t)nt); std::vector<unsigned int> texels((size_t)pool);
+	size_t at = 0;
+	for (int i = 0; i < nt; i++)
+	{
+		const float* cc = t->tex_color + 6 * (size_t)i;
+		desc[i] = make_int4(t->tex_type[i], 0, 0, 0);
+		col[2 * i] = make_float4(0, 0, 0, 0); col[2 * i + 1] = make_float4(0, 0, 0, 0);
+		if (t->tex_type[i] == JP_TEXTURE_IMAGE)
+		{
+			const int w = t->tex_width[i], h = t->tex_height[i];
+			desc[i].y = w; desc[i].z = h; desc[i].w = (int)at;
+			const uint8_t* src = t->texels + t->tex_offset[i];
+			for (size_t k = 0; k < (size_t)w * h; k++) texels[at + k] = (unsigned int)src[3 * k] | ((unsigned int)src[3 * k + 1] << 8) | ((unsigned int)src[3 * k + 2] << 16) | 0xff000000u;
+			at += (size_t)w * h;
+		}
+		else
+		{
+			col[2 * i] = make_float4(cc[0], cc[1], cc[2], 0);
+			if (t->tex_type[i] == JP_TEXTURE_CHECKER) col[2 * i + 1] = make_float4(cc[3], cc[4], cc[5], 0);
+		}
+	}
+	std::vector<int> mt(t->mat_texture, t->mat_texture + t->n_materials);
+	std::vector<float2> puv(3 * (size_t)s->n_primitives, make_float2(0, 0));
+	if (t->tri_uv)
+		for (int p = 0; p < s->n_primitives; p++)
+			if (s->prim_shape_type[p] == JP_SHAPE_TRIANGLE)
+			{
+				const float* u = t->tri_uv + 6 * (size_t)s->prim_shape_index[p];
+				for (int k = 0; k < 3; k++) puv[3 * (size_t)p + k] = make_float2(u[2 * k], u[2 * k + 1]);
+			}
+	auto put = [&](void** d, const void* src, size_t bytes) -> bool {
+		if (bytes == 0) return true;
+		if (hipMalloc(d, bytes) != hipSuccess) return false;
+		return hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
+	};
+	if (!put(&c->d_tex_desc, desc.data(), desc.size() * sizeof(int4)) || !put(&c->d_tex_col, col.data(), col.size() * sizeof(float4))
+	    || !put(&c->d_texels, texels.data(), texels.size() * sizeof(unsigned int)) || !put(&c->d_mat_tex, mt.data(), mt.size() * sizeof(int))
+	    || !put(&c->d_prim_uv, puv.data(), puv.size() * sizeof(float2)))
+	{
+		free_scene(c);
+		return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: out of device memory for the texture tables");
+	}
+	c->tv = TexView();
+	c->tv.desc = (const int4*)c->d_tex_desc; c->tv.col = (const float4*)c->d_tex_col; c->tv.texels = (const unsigned int*)c->d_texels;
+	c->tv.mat_tex = (const int*)c->d_mat_tex; c->tv.prim_uv = (const float2*)c->d_prim_uv;
+	c->textured = true; c->n_textures = nt; c->n_tex_mats = ntm; c->texel_bytes = (long long)texels.size() * 4;
+	return JP_OK;
+}

@@ -13,6 +13,7 @@ struct HostScene
 {
 	std::shared_ptr<FScene> scene;
 	std::vector<std::shared_ptr<FMaterial>> mats;
+	std::vector<std::shared_ptr<FTexture>> texs;
 	FlatScene flat; bool flattened = false;
 	std::unique_ptr<FGpuPathIntegrator> integ; int integDepth = -1;
 	std::string error;
@@ -50,6 +51,24 @@ int jp_host_mat_glass(void* h, float eta, const float* kr, const float* kt) { Ho
 int jp_host_mat_plastic(void* h, const float* kd, const float* ks, float rough, int remap) { HostScene* hs = (HostScene*)h; hs->mats.push_back(hs->scene->CreateMaterial<FPlasticMaterial>(C3(kd), C3(ks), rough, remap != 0)); return (int)hs->mats.size() - 1; }
 int jp_host_mat_metal(void* h, const float* eta, const float* k, float ur, float vr, int remap) { HostScene* hs = (HostScene*)h; hs->mats.push_back(hs->scene->CreateMaterial<FMetalMaterial>(C3(eta), C3(k), ur, vr, remap != 0)); return (int)hs->mats.size() - 1; }
 
+// textures (FSolidColor / FCheckerTexture / FImageTexture) -> handle index; materials that take one (-1: none)
+int jp_host_texture_solid(void* h, const float* rgb) { HostScene* hs = (HostScene*)h; hs->texs.push_back(std::make_shared<FSolidColor>(C3(rgb))); return (int)hs->texs.size() - 1; }
+int jp_host_texture_checker(void* h, const float* odd, const float* even) { HostScene* hs = (HostScene*)h; hs->texs.push_back(std::make_shared<FCheckerTexture>(C3(odd), C3(even))); return (int)hs->texs.size() - 1; }
+int jp_host_texture_image(void* h, const unsigned char* rgb8, int w, int hgt) { HostScene* hs = (HostScene*)h; hs->texs.push_back(std::make_shared<FImageTexture>(rgb8, w, hgt)); return (int)hs->texs.size() - 1; }
+int jp_host_texture_image_file(void* h, const char* path) { HostScene* hs = (HostScene*)h; hs->texs.push_back(std::make_shared<FImageTexture>(path)); return (int)hs->texs.size() - 1; }
+int jp_host_mat_matte_tex(void* h, int tex) { HostScene* hs = (HostScene*)h; if (tex < 0 || tex >= (int)hs->texs.size()) return -1; hs->mats.push_back(hs->scene->CreateMaterial<FMatteMaterial>(hs->texs[tex])); return (int)hs->mats.size() - 1; }
+int jp_host_mat_mirror_tex(void* h, int tex) { HostScene* hs = (HostScene*)h; if (tex < 0 || tex >= (int)hs->texs.size()) return -1; hs->mats.push_back(hs->scene->CreateMaterial<FMirrorMaterial>(hs->texs[tex])); return (int)hs->mats.size() - 1; }
+int jp_host_mat_plastic_tex(void* h, int tex, const float* ks, float rough, int remap)
+{ HostScene* hs = (HostScene*)h; if (tex < 0 || tex >= (int)hs->texs.size()) return -1; hs->mats.push_back(hs->scene->CreateMaterial<FPlasticMaterial>(hs->texs[tex], C3(ks), rough, remap != 0)); return (int)hs->mats.size() - 1; }
+// FMaterial::texture of any material (FlattenScene refuses one on glass / metal): 0, or -1 for a bad index
+int jp_host_mat_set_texture(void* h, int mat, int tex)
+{
+	HostScene* hs = (HostScene*)h;
+	if (mat < 0 || mat >= (int)hs->mats.size() || tex < -1 || tex >= (int)hs->texs.size()) return -1;
+	hs->mats[mat]->texture = tex >= 0 ? hs->texs[tex] : nullptr; hs->flattened = false;
+	return 0;
+}
+
 int jp_host_scene_mesh(void* h, const char* path, int flip_normal, int flip_handedness, const float* offset, float scale, int mat, const float* radiance)
 {
 	HostScene* hs = (HostScene*)h;
@@ -85,6 +104,14 @@ const JpScene* jp_host_flatten(void* h)
 	HostScene* hs = (HostScene*)h;
 	if (!hs->flattened) { if (!FlattenScene(*hs->scene, hs->flat, &hs->error)) return nullptr; hs->flattened = true; }
 	return &hs->flat.view;
+}
+
+// the flattened textures (valid with jp_host_flatten's view; n_textures 0 for a scene without a textured material)
+const JpTextures* jp_host_flatten_textures(void* h)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!jp_host_flatten(h)) return nullptr;
+	return &hs->flat.textures;
 }
 
 // FGpuPathIntegrator(maxdepth).Render(scene, FCounterSampler(spp, seed), film, numthreads) -> rgb (added onto zeros)

@@ -10,7 +10,10 @@
 
 #include <algorithm>
 #include <cstring>
+#include <cctype>
 #include <fstream>
+#include <iostream>
+#include <iterator>
 
 namespace jetpbrt
 {
@@ -95,4 +98,105 @@ bool FFilm::SaveAsImage(const std::string& filename, EImageType imgType) const
 	return false;
 }
 
+} // namespace jetpbrt
+
+// ---- image readers of FImageTexture (texture.cc reads with stb_image; here: the two formats this library writes) ---------------
+namespace jetpbrt
+{
+namespace
+{
+// PPM header token: skips whitespace and '#' comments
+bool PpmToken(const std::vector<uint8_t>& f, size_t& at, long& v)
+{
+	for (;;)
+	{
+		while (at < f.size() && std::isspace(f[at])) at++;
+		if (at < f.size() && f[at] == '#') { while (at < f.size() && f[at] != '\n') at++; continue; }
+		break;
+	}
+	if (at >= f.size() || !std::isdigit(f[at])) return false;
+	v = 0;
+	while (at < f.size() && std::isdigit(f[at])) { v = v * 10 + (f[at] - '0'); if (v > (1l << 30)) return false; at++; }
+	return true;
+}
+uint32_t Get32(const std::vector<uint8_t>& b, size_t at) { return (uint32_t)b[at] | ((uint32_t)b[at + 1] << 8) | ((uint32_t)b[at + 2] << 16) | ((uint32_t)b[at + 3] << 24); }
+uint16_t Get16(const std::vector<uint8_t>& b, size_t at) { return (uint16_t)(b[at] | (b[at + 1] << 8)); }
+}
+
+bool ReadImageRGB8(const char* filename, std::vector<uint8_t>& rgb, int& width, int& height)
+{
+	rgb.clear(); width = height = 0;
+	if (!filename) return false;
+	std::ifstream in(filename, std::ios::binary);
+	if (!in) return false;
+	std::vector<uint8_t> f((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+	if (f.size() >= 2 && f[0] == 'P' && f[1] == '6')
+	{   // binary PPM, maxval 255: one whitespace byte after the maxval, then rows top first
+		size_t at = 2; long w = 0, h = 0, mx = 0;
+		if (!PpmToken(f, at, w) || !PpmToken(f, at, h) || !PpmToken(f, at, mx)) return false;
+		if (mx != 255 || w < 1 || h < 1 || w > 16384 || h > 16384 || at >= f.size() || !std::isspace(f[at])) return false;
+		at++;
+		const size_t n = (size_t)w * h * 3;
+		if (f.size() - at < n) return false;
+		rgb.assign(f.begin() + at, f.begin() + at + n);
+		width = (int)w; height = (int)h;
+		return true;
+	}
+	if (f.size() >= 54 && f[0] == 'B' && f[1] == 'M')
+	{   // uncompressed 24 / 32-bit BMP: BGR(A) rows padded to 4 bytes, bottom-up (a negative height: top-down)
+		const uint32_t off = Get32(f, 10), hdr = Get32(f, 14);
+		if (hdr < 40) return false;
+		const int32_t w = (int32_t)Get32(f, 18), hs = (int32_t)Get32(f, 22);
+		const uint16_t planes = Get16(f, 26), bpp = Get16(f, 28);
+		const uint32_t comp = Get32(f, 30);
+		if (planes != 1 || (bpp != 24 && bpp != 32) || !(comp == 0 || (comp == 3 && bpp == 32))) return false;
+		// channel positions in a little-endian pixel: B G R (X) unless BI_BITFIELDS masks say otherwise; a mask must select one whole byte
+		int shift[3] = { 16, 8, 0 };                                  // R, G, B
+		if (comp == 3)
+		{   // the masks follow a 40-byte header, and sit at the same place inside a V4 / V5 header
+			if (f.size() < 66) return false;
+			for (int k = 0; k < 3; k++)
+			{
+				const uint32_t m = Get32(f, 54 + 4 * k);
+				int sh = -1;
+				for (int b = 0; b < 4; b++) if (m == (0xffu << (8 * b))) sh = 8 * b;
+				if (sh < 0) return false;
+				shift[k] = sh;
+			}
+			if (shift[0] == shift[1] || shift[0] == shift[2] || shift[1] == shift[2]) return false;
+		}
+		const long long h = hs < 0 ? -(long long)hs : hs;
+		if (w < 1 || h < 1 || w > 16384 || h > 16384) return false;
+		const size_t bytes = bpp / 8, row = ((size_t)w * bytes + 3) & ~(size_t)3;
+		if (off > f.size() || f.size() - off < row * (size_t)h) return false;
+		rgb.resize((size_t)w * h * 3);
+		for (long long y = 0; y < h; y++)
+		{
+			const size_t src = off + row * (size_t)(hs < 0 ? y : h - 1 - y);
+			for (int x = 0; x < w; x++)
+			{
+				uint8_t* o = &rgb[3 * ((size_t)y * w + x)];
+				const uint8_t* p = &f[src + bytes * x];
+				for (int k = 0; k < 3; k++) o[k] = p[shift[k] / 8];
+			}
+		}
+		width = w; height = (int)h;
+		return true;
+	}
+	return false;
+}
+
+FImageTexture::FImageTexture(const char* filename) : width(0), height(0)
+{
+	if (!ReadImageRGB8(filename, data, width, height))
+	{
+		std::cerr << "ERROR: Could not load texture image file" << (filename ? filename : "") << ".\n";   // texture.cc (the reference's message)
+		data.clear(); width = height = 0;
+	}
+}
+
+FImageTexture::FImageTexture(const uint8_t* rgb8, int w, int h) : width(0), height(0)
+{
+	if (rgb8 && w > 0 && h > 0) { data.assign(rgb8, rgb8 + (size_t)w * h * 3); width = w; height = h; }
+}
 } // namespace jetpbrt

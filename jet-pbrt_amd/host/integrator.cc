@@ -26,6 +26,7 @@ struct HipApi
 	int (*get_counters)(JpContext*, JpCounters*) = nullptr;
 	int (*abi_version)() = nullptr;
 	int (*set_options)(JpContext*, const JpOptions*) = nullptr;
+	int (*upload_scene_textured)(JpContext*, const JpScene*, const JpTextures*) = nullptr;   // (looked up, needed by textured scenes only)
 	std::string error;
 };
 
@@ -51,6 +52,7 @@ HipApi& Api()
 		api.bsdf = (decltype(api.bsdf))dlsym(api.lib, "jp_bsdf");
 		api.abi_version = (int (*)())dlsym(api.lib, "jp_abi_version");
 		api.set_options = (int (*)(JpContext*, const JpOptions*))dlsym(api.lib, "jp_set_options");
+		api.upload_scene_textured = (int (*)(JpContext*, const JpScene*, const JpTextures*))dlsym(api.lib, "jp_upload_scene_textured");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
 		else if (api.abi_version() != JP_ABI_VERSION)            // a stale build would be handed structs of another size (JpCounters, JpBuildInfo, JpOptions)
@@ -114,7 +116,11 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 	{
 		FlatScene flat; std::string err;
 		if (!FlattenScene(*scene, flat, &err)) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", err.c_str()); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
-		lastStatus = api.upload_scene(ctx, &flat.view);
+		// a scene with a textured material goes through jp_upload_scene_textured; any other makes exactly the calls it always made
+		const bool textured = flat.textures.n_textures > 0;
+		if (textured && !api.upload_scene_textured) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_upload_scene_textured\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+		auto upload = [&]() { return textured ? api.upload_scene_textured(ctx, &flat.view, &flat.textures) : api.upload_scene(ctx, &flat.view); };
+		lastStatus = upload();
 		if (lastStatus == JP_ERR_UNSUPPORTED && flat.view.n_bvh_nodes == 0)
 		{   // FScene::deviceBuild, but the device-built tree was refused (deeper than the traversal stack): build the SAH tree
 			// on the host for this upload -- a different hierarchy, the same GPU path
@@ -124,7 +130,7 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			BuildBVH(pb, flat.bvh, 4);
 			flat.view.n_bvh_nodes = (int)flat.bvh.left.size(); flat.view.bvh_bounds = flat.bvh.bounds.data(); flat.view.bvh_left = flat.bvh.left.data(); flat.view.bvh_right = flat.bvh.right.data();
 			flat.view.n_bvh_prim_indices = (int)flat.bvh.prim_index.size(); flat.view.bvh_prim_index = flat.bvh.prim_index.data();
-			lastStatus = api.upload_scene(ctx, &flat.view);
+			lastStatus = upload();
 		}
 		if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
 		uploaded = scene;

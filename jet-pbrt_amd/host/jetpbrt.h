@@ -86,8 +86,10 @@ class FTriangle : public FShape                                  // shape.h:277-
 {
 public:
 	FTriangle(const FPoint3& p0, const FPoint3& p1, const FPoint3& p2, bool flip_normal = false);
+	FTriangle(const FPoint3& p0, const FPoint3& p1, const FPoint3& p2, const FPoint2& uv0, const FPoint2& uv1, const FPoint2& uv2, bool flip_normal = false);   // shape.h:280
 	int Kind() const override { return JP_SHAPE_TRIANGLE; }
 	FPoint3 p0, p1, p2; FNormal3 normal;
+	FPoint2 uv0, uv1, uv2;                                       // texture coordinates of the vertices (0 unless given)
 };
 
 class FRectangle : public FShape                                 // shape.h:380-472, shape.cc:76-95
@@ -117,9 +119,49 @@ public:
 	FPoint3 position; FVector3 normal; Float radius;             // normal normalised by the constructor (shape.h:194)
 };
 
-// triangulated OBJ ingest with the reference's transform order (shape.cc:23-68): z flip, scale, offset
+// triangulated OBJ ingest with the reference's transform order (shape.cc:23-68): z flip, scale, offset; `vt` texture coordinates ride along
+// untransformed (faces v, v/vt, v/vt/vn, v//vn; negative indices count back; a face without vt gets uv 0)
 bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangle>>& outTriangles, bool flip_normal = false,
                       bool bFlipHandedness = false, const FVector3& offset = FVector3(0, 0, 0), Float inScale = 1.f);
+
+// ---- textures (texture.h / texture.cc): descriptions, sampled on the device (JpTextures) ------------------------
+class FTexture
+{
+public:
+	virtual ~FTexture() {}
+	virtual int Kind() const = 0;                                // JP_TEXTURE_*
+};
+class FSolidColor : public FTexture                              // texture.h
+{
+public:
+	FSolidColor() {}
+	FSolidColor(const FColor& c) : color(c) {}
+	FSolidColor(Float r, Float g, Float b) : color(r, g, b) {}
+	int Kind() const override { return JP_TEXTURE_SOLID; }
+	FColor color;
+};
+class FCheckerTexture : public FTexture                          // texture.h, texture.cc (Sample)
+{
+public:
+	FCheckerTexture(const FColor& t0, const FColor& t1) : odd(t0), even(t1) {}
+	int Kind() const override { return JP_TEXTURE_CHECKER; }
+	FColor odd, even;
+};
+class FImageTexture : public FTexture                            // texture.h, texture.cc (constructor, Sample)
+{
+public:
+	const static int bytes_per_pixel = 3;
+	FImageTexture() : width(0), height(0) {}
+	// binary PPM (P6, maxval 255) or uncompressed 24 / 32-bit BMP (film_io.cc); anything else prints the reference's error and samples
+	// as solid cyan (0, 1, 1), the reference's debugging aid
+	FImageTexture(const char* filename);
+	FImageTexture(const uint8_t* rgb8, int w, int h);           // RGB8, row-major, top row first
+	int Kind() const override { return data.empty() ? JP_TEXTURE_SOLID : JP_TEXTURE_IMAGE; }
+	std::vector<uint8_t> data;                                   // empty: no image (solid cyan)
+	int width, height;
+};
+// image readers of film_io.cc: RGB8, top row first; false for any other format or a file that cannot be read
+bool ReadImageRGB8(const char* filename, std::vector<uint8_t>& rgb, int& width, int& height);
 
 // ---- materials: parameter holders with a flatten hook -------------------------------------------------------
 class FMaterial
@@ -128,18 +170,24 @@ public:
 	virtual ~FMaterial() {}
 	virtual int Kind() const = 0;                                // JP_MAT_*
 	virtual void Flatten(float out[JP_MAT_PARAM_STRIDE]) const = 0;
+	// the texture of the main colour (matte, mirror, plastic); FlattenScene refuses one on glass or metal, whose [0..2] is eta
+	std::shared_ptr<FTexture> texture;
 };
 Float RoughnessToAlpha(Float roughness);                         // microfacet.h:85-90
 
 class FMatteMaterial : public FMaterial                          // material.h:27-41
-{ public: FMatteMaterial(const FColor& c) : diffuseColor(c) {} int Kind() const override { return JP_MAT_MATTE; } void Flatten(float*) const override; FColor diffuseColor; };
+{ public: FMatteMaterial(const FColor& c) : diffuseColor(c) {} FMatteMaterial(const std::shared_ptr<FTexture>& tex) { texture = tex; }
+  int Kind() const override { return JP_MAT_MATTE; } void Flatten(float*) const override; FColor diffuseColor; };
 class FMirrorMaterial : public FMaterial                         // material.h:45-59
-{ public: FMirrorMaterial(const FColor& c) : specularColor(c) {} int Kind() const override { return JP_MAT_MIRROR; } void Flatten(float*) const override; FColor specularColor; };
+{ public: FMirrorMaterial(const FColor& c) : specularColor(c) {} FMirrorMaterial(const std::shared_ptr<FTexture>& tex) { texture = tex; }
+  int Kind() const override { return JP_MAT_MIRROR; } void Flatten(float*) const override; FColor specularColor; };
 class FGlassMaterial : public FMaterial                          // material.h:63-81
 { public: FGlassMaterial(Float eta, const FColor& kr = FColor(1, 1, 1), const FColor& kt = FColor(1, 1, 1)) : eta(eta), Kr(kr), Kt(kt) {}
   int Kind() const override { return JP_MAT_GLASS; } void Flatten(float*) const override; Float eta; FColor Kr, Kt; };
 class FPlasticMaterial : public FMaterial                        // material.h:85-110, material.cc:12-29
 { public: FPlasticMaterial(const FColor& Kd, const FColor& Ks, Float roughness, bool remapRoughness);
+  // textured Kd: Qd follows the sampled Kd at every shading point (Ld = Kd.Luminance(), Qd = Ld / (Ld + Ks.Luminance()), on the device)
+  FPlasticMaterial(const std::shared_ptr<FTexture>& tex, const FColor& Ks, Float roughness, bool remapRoughness);
   int Kind() const override { return JP_MAT_PLASTIC; } void Flatten(float*) const override; FColor Kd, Ks; Float roughness; bool remapRoughness; Float Qd; };
 class FMetalMaterial : public FMaterial                          // material.h:113-137, material.cc:31-43
 { public: FMetalMaterial(const FColor& eta, const FColor& k, Float ur, Float vr, bool remap) : eta(eta), k(k), uRoughness(ur), vRoughness(vr), remapRoughness(remap) {}
@@ -371,6 +419,13 @@ struct FlatScene
 	std::vector<int32_t> prim_shape_type, prim_shape_index, prim_material, prim_light, mat_type, light_type, light_prim;
 	std::vector<float> mat_params, light_radiance, light_vec;
 	FlatBVH bvh;
+	// textures (jp_upload_scene_textured): filled only for a scene with a textured material (textures.n_textures == 0 otherwise);
+	// shared textures are flattened once (by pointer)
+	JpTextures textures;
+	std::vector<int32_t> tex_type, tex_width, tex_height, mat_texture;
+	std::vector<float> tex_color, tri_uv;
+	std::vector<int64_t> tex_offset;
+	std::vector<uint8_t> texels;
 };
 bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error = nullptr);
 

@@ -51,6 +51,12 @@ FTriangle::FTriangle(const FPoint3& a, const FPoint3& b, const FPoint3& c, bool 
 	worldBox = bbox;
 }
 
+FTriangle::FTriangle(const FPoint3& a, const FPoint3& b, const FPoint3& c, const FPoint2& t0, const FPoint2& t1, const FPoint2& t2, bool flip_normal)
+	: FTriangle(a, b, c, flip_normal)
+{
+	uv0 = t0; uv1 = t1; uv2 = t2;
+}
+
 FRectangle::FRectangle(const FPoint3& a, const FPoint3& b, const FPoint3& c, const FPoint3& d, bool flip_normal) : p0(a), p1(b), p2(c), p3(d)
 {
 	normal = Normalize(Cross(p1 - p0, p2 - p0));                          // shape.h:388-390
@@ -97,7 +103,8 @@ bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangl
 	std::ifstream file(filename);
 	if (!file.is_open()) { fprintf(stderr, "load triangle mesh failed. %s\n", filename); return false; }
 	std::vector<FVector3> pos;
-	std::vector<int> face;
+	std::vector<FPoint2> tex;
+	std::vector<int> face, faceT;                                        // position / texture coordinate index per face vertex (-1: none)
 	std::string line;
 	auto xform = [&](FVector3 v) {
 		if (bFlipHandedness) v.z = -v.z;
@@ -115,9 +122,15 @@ bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangl
 			float x = strtof(p, &e); p = e; float y = strtof(p, &e); p = e; float z = strtof(p, &e);
 			pos.push_back(FVector3(x, y, z));
 		}
+		else if (s[0] == 'v' && s[1] == 't' && (s[2] == ' ' || s[2] == '\t'))
+		{
+			char* e = nullptr; const char* p = s + 2;
+			float u = strtof(p, &e); p = e; float v = strtof(p, &e);
+			tex.push_back(FPoint2(u, v));
+		}
 		else if (s[0] == 'f' && (s[1] == ' ' || s[1] == '\t'))
 		{
-			face.clear();
+			face.clear(); faceT.clear();
 			const char* p = s + 1;
 			for (;;)
 			{
@@ -128,12 +141,26 @@ bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangl
 				if (idx < 0) idx = (long)pos.size() + idx + 1;
 				if (idx < 1 || idx > (long)pos.size()) { fprintf(stderr, "load triangle mesh failed. %s: face index out of range\n", filename); out.clear(); return false; }
 				face.push_back((int)idx - 1);
-				p = e; while (*p && *p != ' ' && *p != '\t') p++;             // skip /vt/vn
+				int ti = -1;
+				p = e;
+				if (*p == '/' && p[1] != '/' && p[1] != ' ' && p[1] != '\t' && p[1] != 0)   // v/vt or v/vt/vn (v//vn: no texture coordinate)
+				{
+					long t = strtol(p + 1, &e, 10);
+					if (e != p + 1)
+					{
+						if (t < 0) t = (long)tex.size() + t + 1;
+						if (t < 1 || t > (long)tex.size()) { fprintf(stderr, "load triangle mesh failed. %s: texture coordinate index out of range\n", filename); out.clear(); return false; }
+						ti = (int)t - 1;
+					}
+				}
+				faceT.push_back(ti);
+				while (*p && *p != ' ' && *p != '\t') p++;                    // skip the rest of the vertex (/vn)
 			}
+			auto uv = [&](size_t k) { return faceT[k] >= 0 ? tex[faceT[k]] : FPoint2(0, 0); };   // untransformed
 			for (size_t k = 1; k + 1 < face.size(); k++)                      // triangles as given; polygons as a fan
 			{
 				FVector3 v0 = xform(pos[face[0]]), v1 = xform(pos[face[k]]), v2 = xform(pos[face[k + 1]]);
-				out.push_back(std::make_shared<FTriangle>(v0, v1, v2, flip_normal));
+				out.push_back(std::make_shared<FTriangle>(v0, v1, v2, uv(0), uv(k), uv(k + 1), flip_normal));
 			}
 		}
 	}
@@ -148,6 +175,7 @@ Float RoughnessToAlpha(Float roughness)                                  // micr
 	return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
 }
 static void zero(float* o) { for (int i = 0; i < JP_MAT_PARAM_STRIDE; i++) o[i] = 0.f; }
+// (a textured material keeps its colour fields at 0: the device takes the slot from the texture)
 void FMatteMaterial::Flatten(float* o) const { zero(o); o[0] = diffuseColor.r; o[1] = diffuseColor.g; o[2] = diffuseColor.b; }
 void FMirrorMaterial::Flatten(float* o) const { zero(o); o[0] = specularColor.r; o[1] = specularColor.g; o[2] = specularColor.b; }
 void FGlassMaterial::Flatten(float* o) const { zero(o); o[0] = eta; o[1] = Kr.r; o[2] = Kr.g; o[3] = Kr.b; o[4] = Kt.r; o[5] = Kt.g; o[6] = Kt.b; }
@@ -155,6 +183,10 @@ FPlasticMaterial::FPlasticMaterial(const FColor& kd, const FColor& ks, Float rou
 {
 	Float Ld = Kd.Luminance(), Ls = Ks.Luminance(), L = Ld + Ls;          // material.h:94-98
 	Qd = Ld / L;
+}
+FPlasticMaterial::FPlasticMaterial(const std::shared_ptr<FTexture>& tex, const FColor& ks, Float rough, bool remap) : Ks(ks), roughness(rough), remapRoughness(remap), Qd(0)
+{
+	texture = tex;
 }
 void FPlasticMaterial::Flatten(float* o) const
 {
@@ -271,6 +303,35 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 		out.mat_params.insert(out.mat_params.end(), p, p + JP_MAT_PARAM_STRIDE);
 	}
 	for (size_t i = 0; i < scene.lights.size(); i++) lightRef[scene.lights[i].get()] = (int)i;
+	// textures: one entry per distinct FTexture (by pointer); an image that failed to load is the reference's solid cyan
+	std::map<const FTexture*, int> texRef;
+	for (size_t i = 0; i < scene.materials.size(); i++)
+	{
+		const FMaterial& M = *scene.materials[i];
+		const FTexture* T = M.texture.get();
+		out.mat_texture.push_back(-1);
+		if (!T) continue;
+		if (M.Kind() != JP_MAT_MATTE && M.Kind() != JP_MAT_MIRROR && M.Kind() != JP_MAT_PLASTIC) return fail("FlattenScene: a texture on a glass or metal material (its colour slot holds eta)");
+		auto ti = texRef.find(T);
+		if (ti == texRef.end())
+		{
+			const int k = (int)out.tex_type.size();
+			float col[6] = { 0, 0, 0, 0, 0, 0 }; int w = 0, h = 0; int64_t off = 0;
+			int kind = T->Kind();
+			if (const FSolidColor* sc = dynamic_cast<const FSolidColor*>(T)) { col[0] = sc->color.r; col[1] = sc->color.g; col[2] = sc->color.b; }
+			else if (const FCheckerTexture* ct = dynamic_cast<const FCheckerTexture*>(T)) { col[0] = ct->odd.r; col[1] = ct->odd.g; col[2] = ct->odd.b; col[3] = ct->even.r; col[4] = ct->even.g; col[5] = ct->even.b; }
+			else if (const FImageTexture* it = dynamic_cast<const FImageTexture*>(T))
+			{
+				if (it->data.empty() || it->width <= 0 || it->height <= 0) { kind = JP_TEXTURE_SOLID; col[0] = 0; col[1] = 1; col[2] = 1; }   // texture.cc: "solid cyan as a debugging aid"
+				else { w = it->width; h = it->height; off = (int64_t)out.texels.size(); out.texels.insert(out.texels.end(), it->data.begin(), it->data.end()); }
+			}
+			else return fail("FlattenScene: unknown texture class");
+			out.tex_type.push_back(kind); out.tex_color.insert(out.tex_color.end(), col, col + 6);
+			out.tex_width.push_back(w); out.tex_height.push_back(h); out.tex_offset.push_back(off);
+			ti = texRef.insert(std::make_pair(T, k)).first;
+		}
+		out.mat_texture.back() = ti->second;
+	}
 
 	std::map<const FShape*, int> shapePrim;                               // emitting shape -> primitive index
 	for (size_t i = 0; i < scene.primitives.size(); i++)
@@ -281,7 +342,8 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 		if (it == shapeRef.end())
 		{
 			int kind = P.shape->Kind(), idx = 0;
-			if (kind == JP_SHAPE_TRIANGLE) { const FTriangle* t = static_cast<const FTriangle*>(P.shape); idx = (int)out.tri_p0.size() / 3; push3(out.tri_p0, t->p0); push3(out.tri_p1, t->p1); push3(out.tri_p2, t->p2); push3(out.tri_n, t->normal); }
+			if (kind == JP_SHAPE_TRIANGLE) { const FTriangle* t = static_cast<const FTriangle*>(P.shape); idx = (int)out.tri_p0.size() / 3; push3(out.tri_p0, t->p0); push3(out.tri_p1, t->p1); push3(out.tri_p2, t->p2); push3(out.tri_n, t->normal);
+			                                   const float uv[6] = { t->uv0.x, t->uv0.y, t->uv1.x, t->uv1.y, t->uv2.x, t->uv2.y }; out.tri_uv.insert(out.tri_uv.end(), uv, uv + 6); }
 			else if (kind == JP_SHAPE_RECTANGLE) { const FRectangle* r = static_cast<const FRectangle*>(P.shape); idx = (int)out.rect_p0.size() / 3; push3(out.rect_p0, r->p0); push3(out.rect_p1, r->p1); push3(out.rect_p2, r->p2); push3(out.rect_p3, r->p3); push3(out.rect_n, r->normal); }
 			else if (kind == JP_SHAPE_DISK) { const FDisk* k = static_cast<const FDisk*>(P.shape); idx = (int)out.disk_radius.size(); push3(out.disk_center, k->position); push3(out.disk_normal, k->normal); out.disk_radius.push_back(k->radius); }
 			else { const FSphere* s = static_cast<const FSphere*>(P.shape); idx = (int)out.sph_radius.size(); push3(out.sph_center, s->center); out.sph_radius.push_back(s->radius); }
@@ -336,6 +398,14 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 	v.n_bvh_nodes = (int)out.bvh.left.size();                    // 0: hierarchy to be built on the device
 	v.bvh_bounds = out.bvh.bounds.data(); v.bvh_left = out.bvh.left.data(); v.bvh_right = out.bvh.right.data();
 	v.n_bvh_prim_indices = (int)out.bvh.prim_index.size(); v.bvh_prim_index = out.bvh.prim_index.data();
+
+	JpTextures& t = out.textures; std::memset(&t, 0, sizeof(t));
+	t.struct_bytes = (int32_t)sizeof(JpTextures);
+	t.n_textures = (int)out.tex_type.size();                    // 0: no textured material (the view is then unused)
+	t.tex_type = out.tex_type.data(); t.tex_color = out.tex_color.data(); t.tex_width = out.tex_width.data(); t.tex_height = out.tex_height.data();
+	t.tex_offset = out.tex_offset.data(); t.n_texel_bytes = (int64_t)out.texels.size(); t.texels = out.texels.data();
+	t.n_materials = v.n_materials; t.mat_texture = out.mat_texture.data();
+	t.n_triangles = v.n_triangles; t.tri_uv = out.tri_uv.data();
 	return true;
 }
 

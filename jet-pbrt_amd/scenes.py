@@ -31,12 +31,16 @@ def asset_dir():
     return d
 
 
-def write_obj(path, verts, faces):
-    """verts (n,3) float32, faces (m,3) int 0-based -> triangulated single-mesh OBJ."""
+def write_obj(path, verts, faces, uvs=None):
+    """verts (n,3) float32, faces (m,3) int 0-based -> triangulated single-mesh OBJ; uvs (n,2): `vt` per vertex, faces v/vt."""
     verts = np.asarray(verts, np.float32)
     lines = ["o mesh"]
     lines += ["v %.9g %.9g %.9g" % (float(v[0]), float(v[1]), float(v[2])) for v in verts]
-    lines += ["f %d %d %d" % (f[0] + 1, f[1] + 1, f[2] + 1) for f in np.asarray(faces)]
+    if uvs is None:
+        lines += ["f %d %d %d" % (f[0] + 1, f[1] + 1, f[2] + 1) for f in np.asarray(faces)]
+    else:
+        lines += ["vt %.9g %.9g" % (float(t[0]), float(t[1])) for t in np.asarray(uvs, np.float32)]
+        lines += ["f %d/%d %d/%d %d/%d" % (f[0] + 1, f[0] + 1, f[1] + 1, f[1] + 1, f[2] + 1, f[2] + 1) for f in np.asarray(faces)]
     txt = "\n".join(lines) + "\n"
     tmp = path + ".tmp%d" % os.getpid()
     with open(tmp, "w") as fh:
@@ -45,14 +49,15 @@ def write_obj(path, verts, faces):
     return path
 
 
-def quads_to_obj(path, quads):
-    """each quad (v0,v1,v2,v3) -> triangles (v0,v1,v2),(v0,v2,v3)."""
+def quads_to_obj(path, quads, uv=False):
+    """each quad (v0,v1,v2,v3) -> triangles (v0,v1,v2),(v0,v2,v3); uv: vertices at uv (0,0) (1,0) (1,1) (0,1)."""
     verts, faces = [], []
     for q in quads:
         b = len(verts)
         verts += [q[0], q[1], q[2], q[3]]
         faces += [(b, b + 1, b + 2), (b, b + 2, b + 3)]
-    return write_obj(path, np.array(verts, np.float32), np.array(faces))
+    uvs = np.tile(np.array([(0, 0), (1, 0), (1, 1), (0, 1)], np.float32), (len(quads), 1)) if uv else None
+    return write_obj(path, np.array(verts, np.float32), np.array(faces), uvs)
 
 
 # ---- canonical Cornell box geometry (SURVEY.md section 8d) ---------------------------------------------------
@@ -194,17 +199,50 @@ class HostBackend:
     def dirlight(self, direction, irradiance):
         a, _a = _fa(direction); b, _b = _fa(irradiance); return self._f("scene_dirlight")(self.h, a, b)
 
-    def mat_matte(self, rgb):
+    def mat_matte(self, rgb=None, tex=None):
+        if tex is not None:
+            return self._f("mat_matte_tex")(self.h, tex)
         a, _a = _fa(rgb); return self._f("mat_matte")(self.h, a)
 
-    def mat_mirror(self, rgb):
+    def mat_mirror(self, rgb=None, tex=None):
+        if tex is not None:
+            return self._f("mat_mirror_tex")(self.h, tex)
         a, _a = _fa(rgb); return self._f("mat_mirror")(self.h, a)
+
+    # textures (host backend only): handles for the tex= argument of mat_matte / mat_mirror / mat_plastic
+    def texture_solid(self, rgb):
+        a, _a = _fa(rgb); return self._f("texture_solid")(self.h, a)
+
+    def texture_checker(self, odd, even):
+        a, _a = _fa(odd); b, _b = _fa(even); return self._f("texture_checker")(self.h, a, b)
+
+    def texture_image(self, rgb8):
+        """rgb8: (H, W, 3) uint8, top row first"""
+        img = np.ascontiguousarray(rgb8, np.uint8)
+        return self._f("texture_image")(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0])
+
+    def texture_image_file(self, path):
+        """FImageTexture(filename): binary PPM or uncompressed BMP; anything else is the reference's solid cyan"""
+        return self._f("texture_image_file")(self.h, path.encode())
+
+    def mat_set_texture(self, mat, tex):
+        """FMaterial::texture of any material (flatten refuses one on glass / metal)"""
+        return self._f("mat_set_texture")(self.h, mat, tex)
+
+    def flatten_textures(self):
+        p = self.L.jp_host_flatten_textures(self.h)
+        if not p:
+            raise RuntimeError("flatten failed: %s" % self.L.jp_host_last_error(self.h).decode())
+        return p
 
     def mat_glass(self, eta, kr, kt):
         a, _a = _fa(kr); b, _b = _fa(kt); return self._f("mat_glass")(self.h, C.c_float(eta), a, b)
 
-    def mat_plastic(self, kd, ks, rough, remap=False):
-        a, _a = _fa(kd); b, _b = _fa(ks); return self._f("mat_plastic")(self.h, a, b, C.c_float(rough), int(remap))
+    def mat_plastic(self, kd, ks, rough, remap=False, tex=None):
+        b, _b = _fa(ks)
+        if tex is not None:
+            return self._f("mat_plastic_tex")(self.h, tex, b, C.c_float(rough), int(remap))
+        a, _a = _fa(kd); return self._f("mat_plastic")(self.h, a, b, C.c_float(rough), int(remap))
 
     def mat_metal(self, eta, k, ur, vr, remap=False):
         a, _a = _fa(eta); b, _b = _fa(k); return self._f("mat_metal")(self.h, a, b, C.c_float(ur), C.c_float(vr), int(remap))
@@ -290,6 +328,56 @@ def build_cornell(be, width, height, lambert_only=False, extras=None, env=(0.0, 
     be.mesh(A["right"], True, True, mat=green)
     if extras:
         extras(be, dict(red=red, green=green, white=white, golden=golden))
+    be.preprocess()
+    return be
+
+
+def cornell_textured_assets():
+    """the Cornell box with the floor / ceiling / back wall as three meshes, each with uv (0,0) (1,0) (1,1) (0,1) at its corners"""
+    d = asset_dir()
+    out = {}
+    for name, quads in (("floor_only", CORNELL["floor"][:1]), ("ceiling", CORNELL["floor"][1:2]), ("back", CORNELL["floor"][2:3])):
+        p = os.path.join(d, "cornell_uv_%s.obj" % name)
+        if not os.path.exists(p):
+            quads_to_obj(p, quads, uv=True)
+        out[name] = p
+    return out
+
+
+def build_textured_cornell(be, width, height, back=None, left=None, right=None, floor=None, full_materials=True, mirror=None, plastic=None):
+    """The Cornell box of build_cornell with texture-mapped materials (HostBackend only).  back / left / right / floor: a callable
+    be -> texture handle for the matte back wall, red wall, green wall, floor; an rgb triple (a constant colour instead of the usual one);
+    None (the usual colour).  full_materials adds the metal tall box and a mirror and a plastic sphere, whose specularColor / Kd take
+    `mirror` / `plastic` the same way."""
+    lookfrom = np.array([278, 273, 960], np.float32); lookat = np.array([278, 273, 0], np.float32)
+    be.camera(lookfrom, _normalize(lookat - lookfrom), (0, 1, 0), 60.0, width, height)
+    be.envlight((0.0, 0.0, 0.0))
+    def matte(rgb, tex):
+        if callable(tex):
+            return be.mat_matte(tex=tex(be))
+        return be.mat_matte(rgb if tex is None else tex)
+    red = matte((0.63, 0.065, 0.05), left)
+    green = matte((0.14, 0.45, 0.091), right)
+    white = be.mat_matte((0.725, 0.71, 0.68))
+    wall = matte((0.725, 0.71, 0.68), back)
+    ground = matte((0.725, 0.71, 0.68), floor)
+    golden = be.mat_metal((0.18, 0.15, 0.81), (0.11, 0.11, 0.11), 0.2, 0.2, False)
+    mat_light = be.mat_matte((0.65, 0.65, 0.65))
+    A = cornell_assets(); T = cornell_textured_assets()
+    be.mesh(A["light"], True, True, mat=mat_light, radiance=light_radiance())
+    be.mesh(T["floor_only"], True, True, mat=ground)
+    be.mesh(T["ceiling"], True, True, mat=white)
+    be.mesh(T["back"], True, True, mat=wall)
+    be.mesh(A["shortbox"], True, True, mat=white)
+    be.mesh(A["tallbox"], True, True, mat=(golden if full_materials else white))
+    be.mesh(A["left"], True, True, mat=red)
+    be.mesh(A["right"], True, True, mat=green)
+    if full_materials:
+        mm = be.mat_mirror(tex=mirror(be)) if callable(mirror) else be.mat_mirror((0.9, 0.9, 0.9) if mirror is None else mirror)
+        ks = (0.3, 0.25, 0.2)
+        pm = be.mat_plastic(None, ks, 0.3, True, tex=plastic(be)) if callable(plastic) else be.mat_plastic((0.35, 0.12, 0.48) if plastic is None else plastic, ks, 0.3, True)
+        be.sphere((120, 330, -300), 40.0, mm, None)
+        be.sphere((420, 90, -120), 50.0, pm, None)
     be.preprocess()
     return be
 
