@@ -5,21 +5,28 @@
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
   python bench.py --gpus 8 --scene bunny --width 1920 --height 1080 --spp 4096 --scaling strong      (configs[4] as written)
   python bench.py ... --dump-outputs DIR                                  (also write the films the timed path returned)
+  python bench.py --full ...                                              (also sub-records, CPU baseline, parity, roofline.alone)
 
 A "step" is one full pass of the hot path over the workload: one frame rendered through the C ABI (jp_render), scene
 already resident in HBM, film download included.  The HEADLINE workload is BASELINE.json
 configs[2] -- the reference's own Cornell scene (main.cc:27-33: metal tall box) at 512x512, 1024 spp -- timed over EXACTLY
---steps frames after --warmup untimed ones.  At N = 1 the line also carries a `configs` object with one full sub-record per
-single-GPU configuration of BASELINE.json (configs[1] Lambertian-only Cornell, configs[2] full materials, configs[3] the
-bunny scene of main.cc:64-111 at 800x600, 2048 spp) and -- round 4 -- configs[4]'s frame (1920x1080, 4096 spp) rendered WHOLE on the
-one GPU: the N = 1 figure an 8-GPU run of that frame divides by; each is timed over its own region of >= --min-seconds (default 10 s);
-their figures are summarised in `config.sub` of the one stdout line, the full sub-records (roofline, cpu_baseline,
-l2_vs_cpu_ref) are written to stderr as one `configs_detail {...}` line.
+--steps frames after --warmup untimed ones.  A plain run does only that: it sets up, warms up, times the steps, writes
+--dump-outputs if asked, and prints the line (roofline from the last timed step's events, no CPU or parity legs).
+
+--full adds everything else the benchmark measures or checks.  At N = 1 the line then also carries a `configs` object with one
+full sub-record per single-GPU configuration of BASELINE.json (configs[1] Lambertian-only Cornell, configs[2] full materials,
+configs[3] the bunny scene of main.cc:64-111 at 800x600, 2048 spp) and configs[4]'s frame (1920x1080, 4096 spp) rendered WHOLE
+on the one GPU: the N = 1 figure an 8-GPU run of that frame divides by; each is timed over its own region of >= --min-seconds
+(default 10 s); their figures are summarised in `config.sub` of the one stdout line, the full sub-records (roofline,
+cpu_baseline, l2_vs_cpu_ref) are written to stderr as one `configs_detail {...}` line.  --configs, --min-seconds, --no-cpu,
+--no-exclusive and --cpu-bands shape a --full run and change nothing in a plain one.
 
 --dump-outputs DIR: after the timed steps, rank 0 writes the film (H, W, 3 float32) that the last timed step of each workload
-returned: DIR/film.npy for the headline, DIR/configs<i>_film.npy for each sub-record.  Scenes, seeds and sample counts depend on
-the arguments alone, so two builds run with the same arguments can be compared film for film.  The files stay under 64 MB in
-all; a film larger than its share is written as a fixed, seeded sample of its pixels ((n, 3), in pixel order).
+returned: DIR/film.npy for the headline, DIR/configs<i>_film.npy for each sub-record.  A plain run writes the same files: after
+the headline it renders each of those configs once, untimed (every frame of a workload returns the same film).  Scenes, seeds
+and sample counts depend on the arguments alone, so two builds run with the same arguments can be compared film for film.  The
+files stay under 64 MB in all; a film larger than its share is written as a fixed, seeded sample of its pixels ((n, 3), in
+pixel order).
 
 At N > 1 the row bands of the film (the reference's FRenderTask unit, integrator.cc:53: 20 rows; here the largest height
 <= 20 that deals evenly) are dealt round-robin to the ranks, each rank renders its bands into a device film that is zero
@@ -33,8 +40,10 @@ Rank 0 prints one JSON line.  Besides the contract fields:
   roofline     : dominant kernel class, algorithmic bytes per launch / HIP-event launch duration (events on the kernel
                  stream, taken on the last step of the timed region) vs 8 TB/s HBM; `traffic` = rocprofv3 PMC bytes per unit
                  (profiles/traffic_r04.json, named once in `notes`) x this run's units per launch; `attributed` = the same launch by
-                 the bytes that kernel class itself moves; `alone` = every class with the GPU to itself: contract / attributed HBM
+                 the bytes that kernel class itself moves; `per_class` = every class in the timed configuration, or with --full
+                 `alone` = every class with the GPU to itself (one extra step on one stream lane): contract / attributed HBM
                  fraction and the vector-instruction issue fraction (instructions per unit from the SQ counter passes under profiles/)
+  (--full)
   config.sub   : one compact summary per single-GPU BASELINE.json config (value, ms, whole-path fraction, parity, CPU reference);
                  the full sub-records follow under `configs`
   cpu_baseline : the unmodified reference (oracle/_ref) -- or the oracle port where that library is absent -- timed on this
@@ -196,7 +205,8 @@ def main():
     ap.add_argument("--spp", type=int, default=0, help="samples per pixel (weak scaling: per GPU share, total spp = spp * gpus)")
     ap.add_argument("--full-materials", action="store_true", help="kept for round-1 command lines: same as --scene cornell")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
-    ap.add_argument("--configs", default="1,2,3,4", help="sub-records at N = 1: comma list of BASELINE.json config indices, '' for none")
+    ap.add_argument("--full", action="store_true", help="also the sub-records, the CPU baseline and parity legs and the single-lane roofline step")
+    ap.add_argument("--configs", default="1,2,3,4", help="sub-records at N = 1 (--full; a plain run renders them only for --dump-outputs): comma list of BASELINE.json config indices, '' for none")
     ap.add_argument("--min-seconds", type=float, default=10.0, help="length of each sub-record's timed region")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline / parity samples")
     ap.add_argument("--no-exclusive", action="store_true", help="skip the extra single-lane step behind roofline.alone (profiling runs: keeps rocprofv3's per-kernel averages to the timed configuration)")
@@ -238,7 +248,8 @@ def main():
     avail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     ctx = jp.Context(dev)
     Hn = None
-    if rank == 0 and not args.no_cpu:
+    with_cpu_legs = args.full and not args.no_cpu
+    if rank == 0 and with_cpu_legs:
         sys.path.insert(0, os.path.join(REPO, "tests"))
         import harness as Hn                                # oracle/ bindings: the checker and the CPU baseline, never the thing measured
 
@@ -249,8 +260,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_workload(scene_key, W, H, spp, steps, warmup, min_seconds=None, with_cpu=True, tag="", parity_fn=None):
-        """upload, warm up, time `steps` frames (or as many as fill min_seconds), profile the last one; returns the record"""
+    def prepare(scene_key, W, H, spp):
+        """build and upload the scene; returns (host scene, flat scene, band rows, total spp, step) -- step() renders one frame.
+        The flat scene lives in the host scene's memory: keep the host scene while either is used"""
         spp_total = spp * n if args.scaling == "weak" else spp
         be = build_scene(scenes, scenes.HostBackend("bench"), scene_key, W, H)
         scene = be.flatten()
@@ -268,7 +280,11 @@ def main():
                 return full.cpu().numpy() if rank == 0 else None
             full = jp.distributed.assemble_bands(film_dev.cpu(), H, band_rows, dist)   # rehearsal backend: the same on host tensors
             return full.numpy() if rank == 0 else None
+        return be, scene, band_rows, spp_total, step
 
+    def run_workload(scene_key, W, H, spp, steps, warmup, min_seconds=None, with_cpu=True, tag="", parity_fn=None):
+        """upload, warm up, time `steps` frames (or as many as fill min_seconds), profile the last one; returns the record"""
+        be, scene, band_rows, spp_total, step = prepare(scene_key, W, H, spp)
         ctx.set_profiling(False)
         for _ in range(warmup):
             step()
@@ -327,7 +343,7 @@ def main():
         # figure the contract asks for) reflects that sharing.  One extra, untimed step on ONE lane gives the same kernels' figures
         # when each has the GPU to itself -- reported next to the contract figure as roofline.alone.
         c1 = None
-        if lanes > 1 and ctx.get_options().lanes == 0 and not args.no_exclusive:
+        if lanes > 1 and ctx.get_options().lanes == 0 and args.full and not args.no_exclusive:
             ctx.set_options(lanes=1)                           # JpOptions (ABI 7): schedule fields apply to the next render
             try:
                 step()
@@ -345,7 +361,7 @@ def main():
                    "roofline": roofline_record(c, c1, value, spp_total, n, lanes, scene_key, prof)}
             if shard_check is not None:
                 rec["shard_check"] = shard_check
-            if parity_fn is not None and n == 1 and not args.no_cpu:
+            if parity_fn is not None and n == 1 and with_cpu_legs:
                 rec["cpu_baseline"], rec["l2_vs_cpu_ref"] = parity_fn(scene_key, scene, film, W, H, spp_total)
             elif with_cpu and Hn is not None and (n == 1 or os.environ.get("JETPBRT_BENCH_PARITY_ALL")):
                 rec["cpu_baseline"], rec["l2_vs_cpu_ref"] = cpu_and_parity(scene_key, scene, film, W, H, spp_total)
@@ -516,17 +532,23 @@ def main():
     custom = bool(args.scene or args.width or args.height or args.spp or args.full_materials or args.config != 2)
     if custom:
         sub_ids = [] if args.configs == "1,2,3,4" else sub_ids          # a custom headline runs alone unless sub-records are asked for
-    head_in_sub = (not custom) and 2 in sub_ids
+    head_in_sub = args.full and (not custom) and 2 in sub_ids
     head, band_rows, lanes, film = run_workload(hk, hw, hh, hspp, args.steps, args.warmup, with_cpu=not head_in_sub)
     films = {"film": film}
     subs = {}
     for i in sub_ids:
         k, w, h, s = CONFIGS[i]
-        rec, _, _, film = run_workload(k, w, h, s, 0, 1, min_seconds=args.min_seconds, parity_fn=(parity_config4 if i == 4 else None))
-        if rank == 0:
-            subs["configs[%d]" % i] = rec
-            if args.dump_outputs:
-                films["configs%d_film" % i] = film
+        if args.full:
+            rec, _, _, film = run_workload(k, w, h, s, 0, 1, min_seconds=args.min_seconds, parity_fn=(parity_config4 if i == 4 else None))
+            if rank == 0:
+                subs["configs[%d]" % i] = rec
+        elif args.dump_outputs:
+            be, _, _, _, step = prepare(k, w, h, s)          # (be holds the scene's host memory: kept through the frame)
+            film = step()                                     # plain run: one untimed frame, the film a --full sub-record returns
+        else:
+            continue
+        if rank == 0 and args.dump_outputs:
+            films["configs%d_film" % i] = film
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, films)
     if rank == 0:

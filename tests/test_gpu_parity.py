@@ -1131,7 +1131,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu(H, gpu_ctx, tmp_path):
     env = dict(os.environ, JETPBRT_DIST_BACKEND="gloo", JETPBRT_BENCH_PARITY_ALL="1", MASTER_ADDR="127.0.0.1")
     port = 29700 + (os.getpid() % 200)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(H.REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--spp", "32", "--width", "256", "--height", "256", "--cpu-bands", "1"]
+           os.path.join(H.REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--spp", "32", "--width", "256", "--height", "256", "--cpu-bands", "1"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln][-1]
