@@ -1,4 +1,4 @@
-// jet-pbrt_amd/csrc/jp_render.h -- host runtime, part 3 of 3: jp_render* -- queue budget, the per-bounce launch sequence, stream lanes, the fused schedule,
+// jet-pbrt_amd/csrc/jp_render.h -- host runtime, part 3 of 3: jp_render* -- the shard helper, the kernel selectors, queue budget, the per-bounce launch sequence, stream lanes, the fused schedule,
 // and the rest of the C ABI (counters, build info, jp_trace, jp_bsdf, tone map).  Included by jp_kernels.hip after jp_upload.h.
 #pragma once
 // ---- render ---------------------------------------------------------------------------------------------------------------
@@ -24,41 +24,124 @@ int ensure_queues(JpContext* c, unsigned int cap, int planes, unsigned int nbloc
 
 struct Stamper
 {
-	JpContext* c; int cls; size_t a; hipStream_t st;
-	Stamper(JpContext* c, int cls, hipStream_t st_ = nullptr) : c(c), cls(cls), a(0), st(st_ ? st_ : c->stream)
+	JpContext* c; int cls; size_t a;
+	Stamper(JpContext* c, int cls) : c(c), cls(cls), a(0)
 	{
 		if (!c->profiling) return;
 		if (c->evused + 2 > c->evpool.size()) { size_t old = c->evpool.size(); c->evpool.resize(old + 64); for (size_t i = old; i < c->evpool.size(); i++) hipEventCreate(&c->evpool[i]); }
 		a = c->evused; c->evused += 2;
-		hipEventRecord(c->evpool[a], st);
+		hipEventRecord(c->evpool[a], c->stream);
 	}
-	~Stamper() { if (!c->profiling) return; hipEventRecord(c->evpool[a + 1], st); JpContext::Stamp s = { cls, a, a + 1 }; c->stamps.push_back(s); }
+	~Stamper() { if (!c->profiling) return; hipEventRecord(c->evpool[a + 1], c->stream); JpContext::Stamp s = { cls, a, a + 1 }; c->stamps.push_back(s); }
 };
 
-int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync, int lane_index = 0, int lane_count = 1, int lane_group = 4, bool ev0_recorded = false)
+// ---- the shard: JpRenderParams checked, its bands' rows counted, a lane's share of them ----------------------------------
+struct Shard { int band, count, index, local_rows, lane_rows; };     // local_rows: rows of the shard's bands; lane_rows: the ones this lane renders
+int shard_of(const JpRenderParams* rp, Shard& s, int lane_index = 0, int lane_count = 1, int lane_group = 4)
 {
-	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
-	if (!c->have_scene) return fail(JP_ERR_NO_SCENE, "jp_render: no scene uploaded");
 	if (rp->width <= 0 || rp->height <= 0 || rp->spp <= 0 || rp->max_depth < 0 || rp->max_depth > 200) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: bad width/height/spp/max_depth");
 	if (rp->integrator < JP_INTEGRATOR_PATH || rp->integrator > JP_INTEGRATOR_DEBUG_NORMAL) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: unknown integrator");
 	if (rp->integrator == JP_INTEGRATOR_WHITTED && rp->max_depth > JP_WHITTED_MAX_DEPTH) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator supports max_depth <= 16");
 	if (rp->sampler_mode != JP_SAMPLER_COUNTER && rp->sampler_mode != JP_SAMPLER_DEBUG) return fail(JP_ERR_UNSUPPORTED, "jp_render: the device path implements the counter sampler only (the sequential mt19937_64 stream is not reproducible in parallel)");
-	const int band = rp->band_rows > 0 ? rp->band_rows : 20;
-	const int scount = rp->shard_count > 1 ? rp->shard_count : 1;
-	const int sidx = scount > 1 ? rp->shard_index : 0;
-	if (sidx < 0 || sidx >= scount) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: shard_index out of range");
-	HIP_TRY(hipSetDevice(c->device));
+	s.band = rp->band_rows > 0 ? rp->band_rows : 20;
+	s.count = rp->shard_count > 1 ? rp->shard_count : 1;
+	s.index = s.count > 1 ? rp->shard_index : 0;
+	if (s.index < 0 || s.index >= s.count) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: shard_index out of range");
+	const int nbands = (rp->height + s.band - 1) / s.band;
+	s.local_rows = 0;
+	for (int b = s.index; b < nbands; b += s.count) s.local_rows += std::min(s.band, rp->height - b * s.band);
+	s.lane_rows = 0;      // this lane's share of the shard's rows: groups of lane_group rows dealt round-robin (only the shard's last group can be short; one lane: all of them)
+	for (int g0 = lane_index * lane_group; g0 < s.local_rows; g0 += lane_count * lane_group) s.lane_rows += std::min(lane_group, s.local_rows - g0);
+	return JP_OK;
+}
 
-	const int nbands = (rp->height + band - 1) / band;
-	int local_rows = 0;
-	for (int b = sidx; b < nbands; b += scount) local_rows += std::min(band, rp->height - b * band);
-	if (lane_count > 1)
-	{   // this lane's share of the shard's rows: groups of lane_group rows dealt round-robin (only the shard's last group can be short)
-		int mine = 0;
-		for (int g0 = lane_index * lane_group; g0 < local_rows; g0 += lane_count * lane_group) mine += std::min(lane_group, local_rows - g0);
-		local_rows = mine;
-	}
-	const long long npix = (long long)local_rows * rp->width;
+// ---- kernel selectors: one function per kernel family (path_kernel below is k_path's), the only place of the host code that names the family's instantiations.
+// Each returns the kernel with the dynamic LDS and the stack words it is launched with: a pure function of the plan (shadow: and the region size), called once per render.
+inline bool refill_walks(const ScenePlan& p) { return p.persist && (p.trav_mode == 0 || p.trav_mode == 3 || p.trav_mode == 5); }   // the lane refill kernels exist for these walks
+inline int refill_row(const ScenePlan& p) { return p.persist >= 32 ? 2 : (p.persist >= 16 ? 1 : 0); }   // refill threshold 8 / 16 / 32: the row of a walk's table
+// stack words a thread's walk may need: closest-hit rays, shadow rays, and the deepest walk of all (the spill area's size)
+inline int extend_depth(const ScenePlan& p) { return (p.trav_mode == 5 ? p.cert : p.use_q4) ? p.stack_depth_q4 : p.stack_depth; }
+inline int shadow_depth(const ScenePlan& p) { return (p.trav_mode == 5 ? p.cert : p.q4_shadow) ? p.stack_depth_q4 : (p.trav_mode == 3 ? (int)(p.lds_bytes_shadow / (JP_BLOCK * sizeof(int))) : p.stack_depth); }
+inline int deepest_walk(const ScenePlan& p) { return std::max(std::max(p.stack_depth, p.stack_depth_q4), p.trav_mode == 3 ? (int)(p.lds_bytes_shadow / (JP_BLOCK * sizeof(int))) : 0); }
+// spill area of the walkers' stacks: the words G workgroups' threads may need beyond the ones kept in LDS (+1: Walker<4> keeps one LDS word as a dump slot)
+inline size_t spill_need(const ScenePlan& p, int deep, unsigned int G) { return deep >= p.stack_lds_words ? (size_t)(deep - p.stack_lds_words + 1) * G * JP_BLOCK : 1; }
+
+typedef void (*ExtendKernel)(SceneView, Queues, int, int, DevCounters*);
+typedef void (*ExtendRefillKernel)(SceneView, Queues, int, int, int*, DevCounters*);
+struct ExtendLaunch { ExtendRefillKernel refill; ExtendKernel plain; size_t lds; int words; };   // one of the two kernels; words: of the stack, kept in LDS (refill) / in all (plain)
+template <int M> ExtendRefillKernel extend_refill(const ScenePlan& p)
+{
+	static const ExtendRefillKernel k[3][2] = { { k_extend_persist<M, 8, false>, k_extend_persist<M, 8, true> }, { k_extend_persist<M, 16, false>, k_extend_persist<M, 16, true> }, { k_extend_persist<M, 32, false>, k_extend_persist<M, 32, true> } };
+	return k[refill_row(p)][p.vote];
+}
+ExtendLaunch extend_kernel(const ScenePlan& p)
+{
+	if (!refill_walks(p)) return { nullptr, p.trav_mode == 5 ? k_extend<5> : (p.trav_mode == 2 ? k_extend<2> : (p.trav_mode == 1 ? k_extend<1> : k_extend<0>)), p.lds_bytes, p.stack_depth };
+	const int words = std::min(extend_depth(p), p.stack_lds_words);
+	const ExtendRefillKernel k = p.trav_mode == 5 ? (p.cert ? extend_refill<6>(p) : extend_refill<5>(p)) : (p.use_q4 ? extend_refill<4>(p) : extend_refill<0>(p));
+	return { k, nullptr, (size_t)words * JP_BLOCK * sizeof(int), words };
+}
+
+typedef void (*ShadowKernel)(SceneView, Queues, RenderConst, int, DevCounters*);
+typedef void (*ShadowRefillKernel)(SceneView, Queues, RenderConst, int, int*, DevCounters*);
+struct ShadowLaunch { ShadowRefillKernel refill; ShadowKernel plain; size_t lds; int words; bool cert_fell_back; };   // cert_fell_back: a certified scene whose shadow rays do not get the certified walk
+template <int M> ShadowRefillKernel shadow_refill(const ScenePlan& p)
+{
+	static const ShadowRefillKernel k[3][2] = { { k_shadow_persist<M, 8, false>, k_shadow_persist<M, 8, true> }, { k_shadow_persist<M, 16, false>, k_shadow_persist<M, 16, true> }, { k_shadow_persist<M, 32, false>, k_shadow_persist<M, 32, true> } };
+	return k[refill_row(p)][p.vote];
+}
+ShadowLaunch shadow_kernel(const ScenePlan& p, unsigned int R)         // R: slots per region (Queues::R), whose shadow bitmap shares the refill kernel's LDS with the stacks
+{
+	const int words = std::min(shadow_depth(p), p.stack_lds_words);
+	const size_t plds = (size_t)words * JP_BLOCK * sizeof(int) + (((size_t)R * p.n_planes + 31) / 32) * 4 * (p.cert ? 2 : 1);   // (certified walk: a second bitmap, the rays without a certificate)
+	if (!refill_walks(p) || plds > 64 * 1024)                         // one ray per lane: these kernels walk a certified scene's caller's tree verbatim
+		return { nullptr, p.trav_mode == 3 ? k_shadow<3> : (p.trav_mode == 5 ? k_shadow<5> : (p.trav_mode == 2 ? k_shadow<2> : (p.trav_mode == 1 ? k_shadow<1> : k_shadow<0>))), p.trav_mode == 3 ? p.lds_bytes_shadow : p.lds_bytes, p.stack_depth, p.cert };
+	const ShadowRefillKernel k = p.trav_mode == 5 ? (p.cert ? shadow_refill<6>(p) : shadow_refill<5>(p)) : (p.q4_shadow ? shadow_refill<4>(p) : (p.trav_mode == 3 ? shadow_refill<3>(p) : shadow_refill<0>(p)));
+	return { k, nullptr, plds, words, false };
+}
+
+typedef void (*ShadeKernel)(SceneView, Queues, RenderConst, int, DevCounters*);
+typedef void (*ShadeTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView);
+struct ShadeKernels { ShadeKernel plain; ShadeTexKernel tex; };        // k_shade and its textured twin (after k_texel); both take plan.shade_lds_bytes
+template <bool kTab, bool kPrims, bool kStage> ShadeKernels shade_row(bool sort)
+{
+	ShadeKernels k = { sort ? k_shade<kTab, kPrims, kStage, true> : k_shade<kTab, kPrims, kStage, false>, sort ? k_shade_tex<kTab, kPrims, kStage, true> : k_shade_tex<kTab, kPrims, kStage, false> };
+	return k;
+}
+ShadeKernels shade_kernels(const ScenePlan& p)
+{
+	if (p.shade_prims_in_lds) return p.stage_nee ? shade_row<true, true, true>(p.shade_sort) : shade_row<true, true, false>(p.shade_sort);
+	if (p.tables_in_lds) return p.stage_nee ? shade_row<true, false, true>(p.shade_sort) : shade_row<true, false, false>(p.shade_sort);
+	return shade_row<false, false, false>(p.shade_sort);
+}
+
+// the other two integrators' megakernel: one ray per lane, launched like the plain k_extend (plan.lds_bytes, plan.stack_depth)
+typedef void (*OtherKernel)(SceneView, Queues, RenderConst, int, int, DevCounters*);
+OtherKernel other_kernel(const ScenePlan& p) { return p.trav_mode == 5 ? k_other<5> : (p.trav_mode == 2 ? k_other<2> : (p.trav_mode == 1 ? k_other<1> : k_other<0>)); }
+
+// jp_trace / jp_surface.  JpOptions::trace_walk (tests; jp_surface passes 0): 1 the binary tree, 2 the 8-wide tree, 3 the caller's tree verbatim; else what the
+// render's closest-hit rays walk.  The one-ray-per-lane kernels keep the whole stack in LDS: a 4-wide tree deeper than 64 KB of stack falls back to the binary / verbatim walk
+typedef void (*TraceKernel)(SceneView, int, int, const float*, const float*, const float*, const float*, int*, float*, int*, float*);
+typedef void (*SurfaceKernel)(SceneView, TexView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*);
+struct TraceLaunch { TraceKernel trace; SurfaceKernel surface; size_t lds; int depth; };     // (surface: null for the 8-wide walk, which only trace_walk = 2 selects)
+template <int M> TraceLaunch trace_row(size_t lds, int depth) { TraceLaunch t = { k_trace<M>, k_surface<M>, lds, depth }; return t; }
+TraceLaunch trace_kernel(const ScenePlan& p, int tw)
+{
+	const size_t q4lds = (size_t)p.stack_depth_q4 * JP_BLOCK * sizeof(int);
+	if (p.trav_mode == 3 && tw == 2) { TraceLaunch t = { k_trace<3>, nullptr, p.lds_bytes_shadow, p.stack_depth }; return t; }
+	if (p.trav_mode == 5 && p.cert && q4lds <= 64 * 1024 && tw != 3) return trace_row<6>(q4lds, p.stack_depth_q4);
+	if (p.trav_mode == 5) return trace_row<5>(p.lds_bytes, p.stack_depth);
+	if (p.use_q4 && q4lds <= 64 * 1024 && tw != 1) return trace_row<4>(q4lds, p.stack_depth_q4);
+	return p.trav_mode == 2 ? trace_row<2>(p.lds_bytes, p.stack_depth) : (p.trav_mode == 1 ? trace_row<1>(p.lds_bytes, p.stack_depth) : trace_row<0>(p.lds_bytes, p.stack_depth));
+}
+
+int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync, int lane_index = 0, int lane_count = 1, int lane_group = 4, bool ev0_recorded = false)
+{
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_render: no scene uploaded");
+	const ScenePlan& p = c->plan; Shard sh;
+	if (const int e = shard_of(rp, sh, lane_index, lane_count, lane_group); e != JP_OK) return e;
+	HIP_TRY(hipSetDevice(c->device));
+	const long long npix = (long long)sh.lane_rows * rp->width;
 
 	if (!ev0_recorded) HIP_TRY(hipEventRecord(c->ev0, c->stream));          // (with several lanes render_impl records it before the first lane is enqueued)
 	HIP_TRY(hipMemsetAsync(film_dev, 0, sizeof(float) * 3 * (size_t)rp->width * rp->height, c->stream));
@@ -71,13 +154,13 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		// a shadow entry's header packs (slot, ray count) in 32 bits: 27 + 5 as a rule; batches of up to 2^26 slots (regions of <= 8192
 		// slots: up to 8192 workgroups a launch, whose tail -- the last workgroups finishing on an emptying GPU -- weighs a quarter of
 		// what it does with 2^24)
-		const int slot_bits = c->n_planes <= 31 ? 27 : 24;
+		const int slot_bits = p.n_planes <= 31 ? 27 : 24;
 		const unsigned int PMAX = slot_bits == 27 ? (1u << 26) : (1u << 24);
 		// memory budget for the queues: ~ (136 + 32 * planes) bytes per slot.  ONE budget -- half of what is free, at most 24 GB per lane --
 		// shared by the lanes that render concurrently (each lane sizes its own queue set from its share), and when the allocation still
 		// fails (another process took the memory in between) the batch is halved and tried again before the call gives up
 		size_t freeB = 0, totalB = 0; hipMemGetInfo(&freeB, &totalB);
-		const size_t per = 136 + 32 * (size_t)c->n_planes;
+		const size_t per = 136 + 32 * (size_t)p.n_planes;
 		size_t budget = std::min<size_t>((size_t)24 << 30, (freeB / (size_t)std::max(1, lane_count) + (c->cap ? (size_t)c->cap * (136 + 32 * (size_t)c->planes_alloc) : 0)) / 2);
 		if (c->opt.max_slots > 0) budget = std::min<size_t>(budget, (size_t)c->opt.max_slots * per);
 		int sbatch = 1; unsigned int P = 0, G = 1, R = JP_BLOCK, cap = 0;
@@ -97,29 +180,26 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 			G = std::max(G, (nchunks + JP_SHADE_TILE / JP_BLOCK - 1) / (JP_SHADE_TILE / JP_BLOCK));   // R <= JP_SHADE_TILE: k_shade partitions a whole region in LDS and counts its fills in 16 bits
 			R = ((nchunks + G - 1) / G) * JP_BLOCK;
 			cap = G * R;
-			const int st = ensure_queues(c, cap, c->n_planes, G);
+			const int st = ensure_queues(c, cap, p.n_planes, G);
 			if (st == JP_OK) break;
 			if (sbatch <= 1 || attempt >= 6) return st;                 // one sample per pixel does not fit either: out of device memory
 			budget = (size_t)sbatch / 2 * (size_t)npix * per;              // half the batch
 		}
 		c->q.cap = cap; c->q.R = R;
-		const bool tex = c->textured && rp->integrator == JP_INTEGRATOR_PATH;
+		const bool tex = p.textured && rp->integrator == JP_INTEGRATOR_PATH;
 		if (tex && c->side_n < cap)
 		{   // the side words of k_texel: one per queue position, allocated for textured scenes only
 			if (c->d_side) { HIP_TRY(hipStreamSynchronize(c->stream)); hipFree(c->d_side); } c->d_side = nullptr; c->side_n = 0;
 			HIP_TRY(hipMalloc((void**)&c->d_side, (size_t)cap * sizeof(unsigned int))); c->side_n = cap;
 		}
-		TexView tv = c->tv; tv.side = c->d_side;
-		{   // spill area of the walkers' stacks: the words a thread may need beyond the ones kept in LDS
-			const int deep = std::max(std::max(c->stack_depth, c->stack_depth_q4), c->trav_mode == 3 ? (int)(c->lds_bytes_shadow / (JP_BLOCK * sizeof(int))) : 0);
-			const size_t need = c->persist && deep >= c->stack_lds_words ? (size_t)(deep - c->stack_lds_words + 1) * G * JP_BLOCK : 1;   // (+1: Walker<4> keeps one LDS word as a dump slot)
-			if (c->spill_words < need) { if (c->d_spill) hipFree(c->d_spill); c->d_spill = nullptr; HIP_TRY(hipMalloc((void**)&c->d_spill, need * sizeof(int))); c->spill_words = need; }
-		}
+		TexView tv = p.tv; tv.side = c->d_side;
+		const size_t need = spill_need(p, p.persist ? deepest_walk(p) : 0, G);
+		if (c->spill_words < need) { if (c->d_spill) hipFree(c->d_spill); c->d_spill = nullptr; HIP_TRY(hipMalloc((void**)&c->d_spill, need * sizeof(int))); c->spill_words = need; }
 		if (c->pix_acc_n < (size_t)npix) { if (c->d_pix_acc) hipFree(c->d_pix_acc); c->d_pix_acc = nullptr; HIP_TRY(hipMalloc((void**)&c->d_pix_acc, (size_t)npix * 16)); c->pix_acc_n = (size_t)npix; }
 
 		RenderConst rc; rc.width = rp->width; rc.height = rp->height; rc.spp = rp->spp; rc.max_depth = rp->max_depth; rc.seed = rp->seed;
-		rc.band_rows = band; rc.shard_index = sidx; rc.shard_count = scount; rc.npix = (int)npix; rc.local_rows = local_rows; rc.n_planes = c->n_planes;
-		rc.lane_index = lane_index; rc.lane_count = lane_count; rc.lane_rows = lane_group; rc.class_mask = c->class_mask; rc.sampler_debug = rp->sampler_mode == JP_SAMPLER_DEBUG ? 1 : 0;
+		rc.band_rows = sh.band; rc.shard_index = sh.index; rc.shard_count = sh.count; rc.npix = (int)npix; rc.local_rows = sh.lane_rows; rc.n_planes = p.n_planes;
+		rc.lane_index = lane_index; rc.lane_count = lane_count; rc.lane_rows = lane_group; rc.class_mask = p.class_mask; rc.sampler_debug = rp->sampler_mode == JP_SAMPLER_DEBUG ? 1 : 0;
 		// measured: +6 % on the 280k-triangle scene (cache reuse), -8 % on the LDS-resident Cornell box (coherent waves finish
 		// together or not at all, which unbalances the workgroups) -> tiles only when traversal goes through global memory
 		rc.slot_bits = slot_bits;
@@ -127,23 +207,19 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		// compact regions (k_raygen): scenes walked through global memory -- one lane on the 280k-triangle scene: k_extend 64.1 -> 55.8 ms,
 		// k_shadow 47.1 -> 40.5 ms per 512 spp (the workgroups in flight share an image area, hence tree nodes: L2), three lanes +1.2 %;
 		// films bit-identical.  JETPBRT_COMPACT_REGIONS=0 / 1 forces it.
-		rc.compact = (c->trav_mode != 2 && c->trav_mode != 1 && npix % JP_BLOCK == 0) ? 1 : 0;
+		rc.compact = (p.trav_mode != 2 && p.trav_mode != 1 && npix % JP_BLOCK == 0) ? 1 : 0;
 		if (c->opt.compact_regions != 0) rc.compact = (c->opt.compact_regions > 0 && npix % JP_BLOCK == 0) ? 1 : 0;
 		const int grid = (int)G;
-		const size_t lds = c->lds_bytes;
+		const ExtendLaunch ek = extend_kernel(p); const ShadowLaunch sk = shadow_kernel(p, R); const ShadeKernels hk = shade_kernels(p); const OtherKernel ok = other_kernel(p);
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
-			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(JP_BLOCK), 0, c->stream, c->sv, c->q, rc, c->d_cnt); }
+			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, c->d_cnt); }
 			if (rp->integrator != JP_INTEGRATOR_PATH)
 			{   // the other two integrators: one megakernel launch per batch (k_other), then the same per-pixel sum
 				Stamper t(c, CLS_OTHER);
 				const int ogrid = (int)std::min<unsigned int>((P + JP_BLOCK - 1) / JP_BLOCK, (unsigned int)(c->n_cus * 16));
-				const size_t stack_lds = (size_t)c->stack_depth * JP_BLOCK * sizeof(int);
-				if (c->trav_mode == 5) hipLaunchKernelGGL(k_other<5>, dim3(ogrid), dim3(JP_BLOCK), stack_lds, c->stream, c->sv, c->q, rc, rp->integrator, c->stack_depth, c->d_cnt);
-				else if (c->trav_mode == 2) hipLaunchKernelGGL(k_other<2>, dim3(ogrid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, rc, rp->integrator, c->stack_depth, c->d_cnt);
-				else if (c->trav_mode == 1) hipLaunchKernelGGL(k_other<1>, dim3(ogrid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, rc, rp->integrator, c->stack_depth, c->d_cnt);
-				else hipLaunchKernelGGL(k_other<0>, dim3(ogrid), dim3(JP_BLOCK), stack_lds, c->stream, c->sv, c->q, rc, rp->integrator, c->stack_depth, c->d_cnt);
+				hipLaunchKernelGGL(ok, dim3(ogrid), dim3(JP_BLOCK), p.lds_bytes, c->stream, p.sv, c->q, rc, rp->integrator, p.stack_depth, c->d_cnt);
 			}
 			int cur = 0;
 			int iters = rp->integrator != JP_INTEGRATOR_PATH ? 0 : rp->max_depth + 1;
@@ -151,76 +227,32 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 			{
 				if (it >= iters)
 				{
-					if (rp->integrator != JP_INTEGRATOR_PATH || !c->has_null_material || it > iters + 64) break;
+					if (rp->integrator != JP_INTEGRATOR_PATH || !p.has_null_material || it > iters + 64) break;
 					// null-material primitives re-queue a path without consuming a bounce (integrator.cc:349-353): ask the device
 					DevCounters h; HIP_TRY(hipMemcpyAsync(&h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
 					if (h.n_queue[cur] == 0) break;
 				}
 				{
 					Stamper t(c, CLS_EXTEND);
-					if (c->persist && (c->trav_mode == 0 || c->trav_mode == 3 || c->trav_mode == 5))
-					{
-						const int edepth = (c->trav_mode == 5 ? c->cert : c->use_q4) ? c->stack_depth_q4 : c->stack_depth;
-						const int ecap = std::min(edepth, c->stack_lds_words); const size_t elds = (size_t)ecap * JP_BLOCK * sizeof(int);
-						#define JP_LAUNCH_EP(M, R) do { if (c->vote) hipLaunchKernelGGL((k_extend_persist<M, R, true>), dim3(grid), dim3(JP_BLOCK), elds, c->stream, c->sv, c->q, cur, ecap, c->d_spill, c->d_cnt); else hipLaunchKernelGGL((k_extend_persist<M, R, false>), dim3(grid), dim3(JP_BLOCK), elds, c->stream, c->sv, c->q, cur, ecap, c->d_spill, c->d_cnt); } while (0)
-						if (c->trav_mode == 5 && c->cert) { if (c->persist >= 32) JP_LAUNCH_EP(6, 32); else if (c->persist >= 16) JP_LAUNCH_EP(6, 16); else JP_LAUNCH_EP(6, 8); }
-						else if (c->trav_mode == 5) { if (c->persist >= 32) JP_LAUNCH_EP(5, 32); else if (c->persist >= 16) JP_LAUNCH_EP(5, 16); else JP_LAUNCH_EP(5, 8); }
-						else if (c->use_q4) { if (c->persist >= 32) JP_LAUNCH_EP(4, 32); else if (c->persist >= 16) JP_LAUNCH_EP(4, 16); else JP_LAUNCH_EP(4, 8); }
-						else { if (c->persist >= 32) JP_LAUNCH_EP(0, 32); else if (c->persist >= 16) JP_LAUNCH_EP(0, 16); else JP_LAUNCH_EP(0, 8); }
-						#undef JP_LAUNCH_EP
-					}
-					else if (c->trav_mode == 5) hipLaunchKernelGGL(k_extend<5>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, cur, c->stack_depth, c->d_cnt);
-					else if (c->trav_mode == 2) hipLaunchKernelGGL(k_extend<2>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, cur, c->stack_depth, c->d_cnt);
-					else if (c->trav_mode == 1) hipLaunchKernelGGL(k_extend<1>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, cur, c->stack_depth, c->d_cnt);
-					else hipLaunchKernelGGL(k_extend<0>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, cur, c->stack_depth, c->d_cnt);
+					if (ek.refill) hipLaunchKernelGGL(ek.refill, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, c->d_spill, c->d_cnt);
+					else hipLaunchKernelGGL(ek.plain, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, c->d_cnt);
 				}
-				if (tex)
-				{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
-					Stamper t(c, CLS_SHADE);
-					hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, c->sv, c->q, cur, tv);
-					const bool st = c->stage_nee;
-					#define JP_LAUNCH_SHADE(A, B, C) do { if (c->shade_sort) hipLaunchKernelGGL((k_shade_tex<A, B, C, true>), dim3(grid), dim3(JP_BLOCK), c->shade_lds_bytes, c->stream, c->sv, c->q, rc, cur, c->d_cnt, tv); \
-					                                   else hipLaunchKernelGGL((k_shade_tex<A, B, C, false>), dim3(grid), dim3(JP_BLOCK), c->shade_lds_bytes, c->stream, c->sv, c->q, rc, cur, c->d_cnt, tv); } while (0)
-					if (c->shade_prims_in_lds) { if (st) JP_LAUNCH_SHADE(true, true, true); else JP_LAUNCH_SHADE(true, true, false); }
-					else if (c->tables_in_lds) { if (st) JP_LAUNCH_SHADE(true, false, true); else JP_LAUNCH_SHADE(true, false, false); }
-					else JP_LAUNCH_SHADE(false, false, false);
-					#undef JP_LAUNCH_SHADE
-				}
-				else
 				{
 					Stamper t(c, CLS_SHADE);
-					const bool st = c->stage_nee;
-					#define JP_LAUNCH_SHADE(A, B, C) do { if (c->shade_sort) hipLaunchKernelGGL((k_shade<A, B, C, true>), dim3(grid), dim3(JP_BLOCK), c->shade_lds_bytes, c->stream, c->sv, c->q, rc, cur, c->d_cnt); \
-					                                   else hipLaunchKernelGGL((k_shade<A, B, C, false>), dim3(grid), dim3(JP_BLOCK), c->shade_lds_bytes, c->stream, c->sv, c->q, rc, cur, c->d_cnt); } while (0)
-					if (c->shade_prims_in_lds) { if (st) JP_LAUNCH_SHADE(true, true, true); else JP_LAUNCH_SHADE(true, true, false); }
-					else if (c->tables_in_lds) { if (st) JP_LAUNCH_SHADE(true, false, true); else JP_LAUNCH_SHADE(true, false, false); }
-					else JP_LAUNCH_SHADE(false, false, false);
-					#undef JP_LAUNCH_SHADE
+					if (tex)
+					{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
+						hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
+						hipLaunchKernelGGL(hk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt, tv);
+					}
+					else hipLaunchKernelGGL(hk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt);
 				}
 				HIP_TRY(hipGetLastError());                               // a failed launch (k_extend / k_shade) is reported where it happens, not at the end of the frame
-				if (it < rp->max_depth || c->has_null_material)                 // at bounce == maxDepth Li() breaks before the NEE (integrator.cc:340-343)
+				if (it < rp->max_depth || p.has_null_material)                 // at bounce == maxDepth Li() breaks before the NEE (integrator.cc:340-343)
 				{
-					hipStream_t sstream = c->stream; int* sspill = c->d_spill;
-					Stamper t(c, CLS_SHADOW, sstream);
-					const size_t slds = ((c->trav_mode == 5 && c->cert) || (c->trav_mode != 5 && c->q4_shadow)) ? (size_t)c->stack_depth_q4 * JP_BLOCK * sizeof(int) : (c->trav_mode == 3 ? c->lds_bytes_shadow : lds);
-					const int scap = std::min((int)(slds / (JP_BLOCK * sizeof(int))), c->stack_lds_words);     // stack words per thread kept in LDS
-					const size_t plds = (size_t)scap * JP_BLOCK * sizeof(int) + (((size_t)c->q.R * c->n_planes + 31) / 32) * 4 * (c->cert ? 2 : 1);   // (certified walk: a second bitmap, the rays without a certificate)
-					if (c->cert && !(c->persist && plds <= 64 * 1024)) c->cert_fell_back = true;   // the one-ray-per-lane kernels below walk the caller's tree verbatim
-					if (c->persist && (c->trav_mode == 0 || c->trav_mode == 3 || c->trav_mode == 5) && plds <= 64 * 1024)
-					{
-						#define JP_LAUNCH_SP(M, R) do { if (c->vote) hipLaunchKernelGGL((k_shadow_persist<M, R, true>), dim3(grid), dim3(JP_BLOCK), plds, sstream, c->sv, c->q, rc, scap, sspill, c->d_cnt); else hipLaunchKernelGGL((k_shadow_persist<M, R, false>), dim3(grid), dim3(JP_BLOCK), plds, sstream, c->sv, c->q, rc, scap, sspill, c->d_cnt); } while (0)
-						if (c->trav_mode == 5 && c->cert) { if (c->persist >= 32) JP_LAUNCH_SP(6, 32); else if (c->persist >= 16) JP_LAUNCH_SP(6, 16); else JP_LAUNCH_SP(6, 8); }
-						else if (c->trav_mode == 5) { if (c->persist >= 32) JP_LAUNCH_SP(5, 32); else if (c->persist >= 16) JP_LAUNCH_SP(5, 16); else JP_LAUNCH_SP(5, 8); }
-						else if (c->q4_shadow) { if (c->persist >= 32) JP_LAUNCH_SP(4, 32); else if (c->persist >= 16) JP_LAUNCH_SP(4, 16); else JP_LAUNCH_SP(4, 8); }
-						else if (c->trav_mode == 3) { if (c->persist >= 32) JP_LAUNCH_SP(3, 32); else if (c->persist >= 16) JP_LAUNCH_SP(3, 16); else JP_LAUNCH_SP(3, 8); }
-						else { if (c->persist >= 32) JP_LAUNCH_SP(0, 32); else if (c->persist >= 16) JP_LAUNCH_SP(0, 16); else JP_LAUNCH_SP(0, 8); }
-						#undef JP_LAUNCH_SP
-					}
-					else if (c->trav_mode == 3) hipLaunchKernelGGL(k_shadow<3>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes_shadow, c->stream, c->sv, c->q, rc, c->stack_depth, c->d_cnt);
-					else if (c->trav_mode == 5) hipLaunchKernelGGL(k_shadow<5>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, rc, c->stack_depth, c->d_cnt);
-					else if (c->trav_mode == 2) hipLaunchKernelGGL(k_shadow<2>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, rc, c->stack_depth, c->d_cnt);
-					else if (c->trav_mode == 1) hipLaunchKernelGGL(k_shadow<1>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, rc, c->stack_depth, c->d_cnt);
-					else hipLaunchKernelGGL(k_shadow<0>, dim3(grid), dim3(JP_BLOCK), lds, c->stream, c->sv, c->q, rc, c->stack_depth, c->d_cnt);
+					Stamper t(c, CLS_SHADOW);
+					if (sk.cert_fell_back) c->cert_fell_back = true;         // the one-ray-per-lane kernels walk the caller's tree verbatim
+					if (sk.refill) hipLaunchKernelGGL(sk.refill, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, c->d_spill, c->d_cnt);
+					else hipLaunchKernelGGL(sk.plain, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, c->d_cnt);
 					HIP_TRY(hipGetLastError());
 				}
 				cur ^= 1;
@@ -232,10 +264,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 	}
 	HIP_TRY(hipEventRecord(c->ev1, c->stream));
 	c->own_samples = samples;
-	if (sync)
-	{
-		HIP_TRY(hipStreamSynchronize(c->stream));
-	}
+	if (sync) HIP_TRY(hipStreamSynchronize(c->stream));
 	return JP_OK;
 }
 
@@ -262,21 +291,13 @@ int make_lanes(JpContext* c, int extra)
 	return JP_OK;
 }
 
-// a lane walks the same device tables as its parent (it owns none of them)
+// a lane walks the same device tables as its parent (it owns none of them): the plan, plus what really is per lane
 void sync_lane_scene(JpContext* c, JpContext* l)
 {
-	l->have_scene = c->have_scene; l->sv = c->sv; l->stack_depth = c->stack_depth; l->stack_depth_q4 = c->stack_depth_q4; l->scene_in_lds = c->scene_in_lds; l->shade_prims_in_lds = c->shade_prims_in_lds;
-	l->lds_bytes = c->lds_bytes; l->lds_bytes_shadow = c->lds_bytes_shadow; l->trav_mode = c->trav_mode; l->n_planes = c->n_planes;
-	l->stack_lds_words = c->stack_lds_words;
-	l->use_q4 = c->use_q4; l->q4_shadow = c->q4_shadow; l->cert = c->cert;
-	l->persist = c->persist; l->vote = c->vote; l->shade_sort = c->shade_sort; l->class_mask = c->class_mask;
-	l->has_null_material = c->has_null_material; l->tables_in_lds = c->tables_in_lds; l->stage_nee = c->stage_nee; l->shade_lds_bytes = c->shade_lds_bytes;
-	l->profiling = c->profiling;
-	l->tv = c->tv; l->textured = c->textured;                        // (the lane's side array is its own, allocated with its queues)
-	if (!l->textured && l->d_side) { hipStreamSynchronize(l->stream); hipFree(l->d_side); l->d_side = nullptr; l->side_n = 0; }   // untextured scene: not kept
-	l->opt = c->opt;                                                 // render_one(lane) reads max_slots / compact_regions from its own context
+	l->plan = c->plan;                                               // (the lane's side array is its own, allocated with its queues)
+	if (!l->plan.textured && l->d_side) { hipStreamSynchronize(l->stream); hipFree(l->d_side); l->d_side = nullptr; l->side_n = 0; }   // untextured scene: not kept
+	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
 }
-
 
 // ---- fused schedule: one k_path launch per batch (jp_path.h) --------------------------------------------------------------
 // OPT-IN (JETPBRT_FUSED=1; FScene / CLI: --fused).  Measured in round 3 (profiles/r03a_fused_ab.txt): films bit-identical to the
@@ -289,44 +310,37 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 bool fused_eligible(const JpContext* c, const JpRenderParams* rp)
 {
 	if (c->opt.fused <= 0) return false;                             // JpOptions::fused
-	if (c->is_lane || !c->have_scene || rp->integrator != JP_INTEGRATOR_PATH) return false;
-	if (!c->tables_in_lds || c->n_planes > 4) return false;          // (its own LDS budget: render_fused shrinks the region until the layout fits)
-	if (c->cert) return false;                                       // the certified walk lives in the per-bounce traversal kernels
-	if (c->textured) return false;                                   // textures: k_texel + k_shade_tex live in the per-bounce launches
-	if (c->trav_mode == 2) return c->shade_prims_in_lds;
-	return c->trav_mode == 0 || c->trav_mode == 3 || c->trav_mode == 5;
+	if (c->is_lane || !c->plan.have_scene || rp->integrator != JP_INTEGRATOR_PATH) return false;
+	if (!c->plan.tables_in_lds || c->plan.n_planes > 4) return false;          // (its own LDS budget: render_fused shrinks the region until the layout fits)
+	if (c->plan.cert) return false;                                       // the certified walk lives in the per-bounce traversal kernels
+	if (c->plan.textured) return false;                                   // textures: k_texel + k_shade_tex live in the per-bounce launches
+	if (c->plan.trav_mode == 2) return c->plan.shade_prims_in_lds;
+	return c->plan.trav_mode == 0 || c->plan.trav_mode == 3 || c->plan.trav_mode == 5;
 }
 
 typedef void (*PathKernel)(SceneView, Queues, RenderConst, PathConst, int*, DevCounters*);
-PathKernel path_kernel(const JpContext* c)
+PathKernel path_kernel(const ScenePlan& p)
 {
-	const bool so = c->shade_sort;
-	switch (c->trav_mode)
+	const bool so = p.shade_sort;
+	switch (p.trav_mode)
 	{
 	case 2: return so ? k_path<2, 2, true, true, true> : k_path<2, 2, true, false, true>;
 	case 3:
-		if (c->use_q4) return c->q4_shadow ? (so ? k_path<4, 4, false, true, true> : k_path<4, 4, false, false, true>) : (so ? k_path<4, 3, false, true, true> : k_path<4, 3, false, false, true>);
+		if (p.use_q4) return p.q4_shadow ? (so ? k_path<4, 4, false, true, true> : k_path<4, 4, false, false, true>) : (so ? k_path<4, 3, false, true, true> : k_path<4, 3, false, false, true>);
 		return so ? k_path<0, 3, false, true, true> : k_path<0, 3, false, false, true>;
 	case 5: return so ? k_path<5, 5, false, true, false> : k_path<5, 5, false, false, false>;
 	default:
-		if (c->use_q4) return so ? k_path<4, 4, false, true, true> : k_path<4, 4, false, false, true>;
+		if (p.use_q4) return so ? k_path<4, 4, false, true, true> : k_path<4, 4, false, false, true>;
 		return so ? k_path<0, 0, false, true, true> : k_path<0, 0, false, false, true>;
 	}
 }
 
 int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
-	if (rp->width <= 0 || rp->height <= 0 || rp->spp <= 0 || rp->max_depth < 0 || rp->max_depth > 200) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: bad width/height/spp/max_depth");
-	if (rp->sampler_mode != JP_SAMPLER_COUNTER && rp->sampler_mode != JP_SAMPLER_DEBUG) return fail(JP_ERR_UNSUPPORTED, "jp_render: the device path implements the counter sampler only (the sequential mt19937_64 stream is not reproducible in parallel)");
-	const int band = rp->band_rows > 0 ? rp->band_rows : 20;
-	const int scount = rp->shard_count > 1 ? rp->shard_count : 1;
-	const int sidx = scount > 1 ? rp->shard_index : 0;
-	if (sidx < 0 || sidx >= scount) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: shard_index out of range");
+	const ScenePlan& p = c->plan; Shard sh;
+	if (const int e = shard_of(rp, sh); e != JP_OK) return e;         // (fused_eligible: the path integrator, so the integrator checks cannot fire)
 	HIP_TRY(hipSetDevice(c->device));
-	const int nbands = (rp->height + band - 1) / band;
-	int local_rows = 0;
-	for (int b = sidx; b < nbands; b += scount) local_rows += std::min(band, rp->height - b * band);
-	const long long npix = (long long)local_rows * rp->width;
+	const long long npix = (long long)sh.local_rows * rp->width;
 
 	HIP_TRY(hipEventRecord(c->ev0, c->stream));
 	HIP_TRY(hipMemsetAsync(film_dev, 0, sizeof(float) * 3 * (size_t)rp->width * rp->height, c->stream));
@@ -337,9 +351,9 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 	if (npix > 0)
 	{
 		if (npix > (1 << 24)) return fail(JP_ERR_UNSUPPORTED, "jp_render: more than 2^24 pixels per shard");
-		const PathKernel kern = path_kernel(c);
-		const bool flat = c->trav_mode == 2;
-		const int modeE = flat ? 2 : (c->trav_mode == 5 ? 5 : 0);
+		const PathKernel kern = path_kernel(p);
+		const bool flat = p.trav_mode == 2;
+		const int modeE = flat ? 2 : (p.trav_mode == 5 ? 5 : 0);
 		// ---- batch: the radiance array holds one float4 per path of the batch (the only per-path array that outlives a job) ----
 		size_t freeB = 0, totalB = 0; hipMemGetInfo(&freeB, &totalB);
 		size_t budget = std::min<size_t>((size_t)4 << 30, (freeB + c->flacc_n * 16) / 4);
@@ -353,11 +367,11 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 		{ const int v = c->opt.fused_region; if (v >= JP_BLOCK && v <= 8192) R = (unsigned int)(v / JP_BLOCK) * JP_BLOCK; }
 		int S = 16;
 		{ const int v = c->opt.fused_job_spp; if (v >= 1 && v <= 128) S = v; }
-		const int n_tab = 2 * c->sv.n_lights + 4 * c->sv.n_mats + (c->sv.n_mats + 3) / 4, n_tab_all = n_tab + (flat ? 8 * c->sv.n_prims : 0);
-		const int deepE = (c->trav_mode != 5 && c->use_q4) ? c->stack_depth_q4 : c->stack_depth, deepS = (c->trav_mode != 5 && c->q4_shadow) ? c->stack_depth_q4 : (c->trav_mode == 3 ? (int)(c->lds_bytes_shadow / (JP_BLOCK * sizeof(int))) : c->stack_depth);
-		const int ecap = flat ? 0 : std::min(deepE, c->stack_lds_words), scap = flat ? 0 : std::min(deepS, c->stack_lds_words);
-		PathLds L = path_lds_layout(modeE, n_tab_all, c->sv.n_prims, R, c->n_planes, ecap, scap, c->shade_sort);
-		while (L.total > 64 * 1024 && R > JP_BLOCK) { R -= JP_BLOCK; L = path_lds_layout(modeE, n_tab_all, c->sv.n_prims, R, c->n_planes, ecap, scap, c->shade_sort); }
+		const int n_tab = 2 * p.sv.n_lights + 4 * p.sv.n_mats + (p.sv.n_mats + 3) / 4, n_tab_all = n_tab + (flat ? 8 * p.sv.n_prims : 0);
+		const int deepE = extend_depth(p), deepS = shadow_depth(p);
+		const int ecap = flat ? 0 : std::min(deepE, p.stack_lds_words), scap = flat ? 0 : std::min(deepS, p.stack_lds_words);
+		PathLds L = path_lds_layout(modeE, n_tab_all, p.sv.n_prims, R, p.n_planes, ecap, scap, p.shade_sort);
+		while (L.total > 64 * 1024 && R > JP_BLOCK) { R -= JP_BLOCK; L = path_lds_layout(modeE, n_tab_all, p.sv.n_prims, R, p.n_planes, ecap, scap, p.shade_sort); }
 		if (L.total > 64 * 1024) return fail(JP_ERR_UNSUPPORTED, "jp_render: the fused schedule's LDS layout does not fit this scene (JETPBRT_FUSED=0 selects the per-bounce launches)");
 		S = std::max(1, std::min(S, std::min(sbatch, (int)(R / 64))));
 		int PG = (int)(R / (unsigned int)S); if (PG >= 64) PG &= ~63;
@@ -373,10 +387,10 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 		{ const int v = c->opt.fused_workgroups; if (v >= 1 && v <= 16) per_cu = v; }
 		const unsigned int G = (unsigned int)std::min<unsigned long long>(njobs, (unsigned long long)c->n_cus * per_cu);
 		const unsigned int cap = G * R;
-		if (c->fcap < cap || c->fplanes < c->n_planes)
+		if (c->fcap < cap || c->fplanes < p.n_planes)
 		{
 			HIP_TRY(hipStreamSynchronize(c->stream));
-			const unsigned int ncap = std::max(cap, c->fcap); const int npl = std::max(c->n_planes, c->fplanes);
+			const unsigned int ncap = std::max(cap, c->fcap); const int npl = std::max(p.n_planes, c->fplanes);
 			const size_t keep_lacc = c->flacc_n; float4* keep = c->fq.lacc;
 			for (void* p : c->fbufs) if (p != (void*)keep) hipFree(p);
 			c->fbufs.clear(); if (keep) c->fbufs.push_back(keep);
@@ -401,30 +415,27 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 		const int nbatches = (rp->spp + sbatch - 1) / sbatch;
 		if (c->jobs_n < (size_t)nbatches) { HIP_TRY(hipStreamSynchronize(c->stream)); if (c->d_jobs) hipFree(c->d_jobs); c->d_jobs = nullptr; c->jobs_n = 0; HIP_TRY(hipMalloc((void**)&c->d_jobs, (size_t)nbatches * 4)); c->jobs_n = (size_t)nbatches; }
 		HIP_TRY(hipMemsetAsync(c->d_jobs, 0, (size_t)nbatches * 4, c->stream));
-		{   // spill area of the walkers' stacks beyond the words kept in LDS
-			const int deep = std::max(deepE, deepS);
-			const size_t need = !flat && deep >= c->stack_lds_words ? (size_t)(deep - c->stack_lds_words + 1) * G * JP_BLOCK : 1;   // (+1: Walker<4>'s dump slot)
-			if (c->spill_words < need) { HIP_TRY(hipStreamSynchronize(c->stream)); if (c->d_spill) hipFree(c->d_spill); c->d_spill = nullptr; c->spill_words = 0; HIP_TRY(hipMalloc((void**)&c->d_spill, need * sizeof(int))); c->spill_words = need; }
-		}
+		const size_t need = spill_need(p, flat ? 0 : std::max(deepE, deepS), G);
+		if (c->spill_words < need) { HIP_TRY(hipStreamSynchronize(c->stream)); if (c->d_spill) hipFree(c->d_spill); c->d_spill = nullptr; c->spill_words = 0; HIP_TRY(hipMalloc((void**)&c->d_spill, need * sizeof(int))); c->spill_words = need; }
 		if (c->pix_acc_n < (size_t)npix) { HIP_TRY(hipStreamSynchronize(c->stream)); if (c->d_pix_acc) hipFree(c->d_pix_acc); c->d_pix_acc = nullptr; HIP_TRY(hipMalloc((void**)&c->d_pix_acc, (size_t)npix * 16)); c->pix_acc_n = (size_t)npix; }
 
 		RenderConst rc; std::memset(&rc, 0, sizeof(rc));
 		rc.width = rp->width; rc.height = rp->height; rc.spp = rp->spp; rc.max_depth = rp->max_depth; rc.seed = rp->seed;
-		rc.band_rows = band; rc.shard_index = sidx; rc.shard_count = scount; rc.npix = (int)npix; rc.local_rows = local_rows; rc.n_planes = c->n_planes;
-		rc.lane_index = 0; rc.lane_count = 1; rc.lane_rows = 4; rc.class_mask = c->class_mask; rc.sampler_debug = rp->sampler_mode == JP_SAMPLER_DEBUG ? 1 : 0;
+		rc.band_rows = sh.band; rc.shard_index = sh.index; rc.shard_count = sh.count; rc.npix = (int)npix; rc.local_rows = sh.local_rows; rc.n_planes = p.n_planes;
+		rc.lane_index = 0; rc.lane_count = 1; rc.lane_rows = 4; rc.class_mask = p.class_mask; rc.sampler_debug = rp->sampler_mode == JP_SAMPLER_DEBUG ? 1 : 0;
 		rc.slot_bits = JP_PATH_LI_BITS;
 		// 16 x 4 pixel tiles: a job's 64-pixel groups are patches of the image, so the lanes of a wave start as neighbours (camera
 		// rays and first shadow rays of large scenes share nodes).  JETPBRT_NO_TILES=1: row-major groups.
-		rc.tiled = (rp->width % 16 == 0 && local_rows % 4 == 0 && PG % 64 == 0 && c->trav_mode != 2) ? 1 : 0;
+		rc.tiled = (rp->width % 16 == 0 && sh.local_rows % 4 == 0 && PG % 64 == 0 && p.trav_mode != 2) ? 1 : 0;
 		PathConst pc; pc.R = R; pc.PG = PG; pc.S = S; pc.npg = npg; pc.nsb = nsb; pc.ecap = ecap; pc.scap = scap;
-		pc.max_iters = rp->max_depth + 1 + (c->has_null_material ? 64 : 0);
+		pc.max_iters = rp->max_depth + 1 + (p.has_null_material ? 64 : 0);
 		c->last_region = (int)R; c->last_wgs = (int)G;
 		for (int s0 = 0, bi = 0; s0 < rp->spp; s0 += sbatch, bi++)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
 			pc.nsb = (rc.sbatch + S - 1) / S; pc.job = c->d_jobs + bi;
 			const unsigned int g = (unsigned int)std::min<unsigned long long>((unsigned long long)npg * pc.nsb, (unsigned long long)G);
-			{ Stamper t(c, CLS_PATH); hipLaunchKernelGGL(kern, dim3(g), dim3(JP_BLOCK), L.total, c->stream, c->sv, c->fq, rc, pc, c->d_spill, c->d_cnt); }
+			{ Stamper t(c, CLS_PATH); hipLaunchKernelGGL(kern, dim3(g), dim3(JP_BLOCK), L.total, c->stream, p.sv, c->fq, rc, pc, c->d_spill, c->d_cnt); }
 			HIP_TRY(hipGetLastError());
 			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_resolve, dim3((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, c->fq, rc, c->d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
 			HIP_TRY(hipGetLastError());
@@ -441,25 +452,19 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
 	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0;
-	if (c->textured && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample textures (scene uploaded by jp_upload_scene_textured)");
+	if (c->plan.textured && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample textures (scene uploaded by jp_upload_scene_textured)");
 	if (fused_eligible(c, rp)) return render_fused(c, rp, film_dev, sync);
-	c->last_textured = c->textured && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_textured = c->plan.textured && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
 	// Gsamples/s).  JETPBRT_LANES = 1 .. 4 forces a count, JETPBRT_LANE_ROWS the group height.
 	int forcedL = 0, group = 4;
 	if (c->opt.lanes >= 1 && c->opt.lanes <= 4) forcedL = c->opt.lanes;
 	if (c->opt.lane_rows >= 1 && c->opt.lane_rows <= 64) group = c->opt.lane_rows;
-	int L = 1;
-	const int band = rp->band_rows > 0 ? rp->band_rows : 20;
-	const int scount = rp->shard_count > 1 ? rp->shard_count : 1;
-	const int sidx = scount > 1 ? rp->shard_index : 0;
-	if (!c->is_lane && c->have_scene && !c->has_null_material && rp->width > 0 && rp->height > 0 && rp->integrator == JP_INTEGRATOR_PATH && sidx >= 0 && sidx < scount)
+	int L = 1; Shard sh;
+	if (!c->is_lane && c->plan.have_scene && !c->plan.has_null_material && rp->integrator == JP_INTEGRATOR_PATH && shard_of(rp, sh) == JP_OK)   // (bad parameters: render_one reports them)
 	{
-		const int nbands = (rp->height + band - 1) / band;
-		long long rows = 0;
-		for (int b = sidx; b < nbands; b += scount) rows += std::min(band, rp->height - b * band);
-		const long long groups = (rows + group - 1) / group;
+		const long long rows = sh.local_rows, groups = (rows + group - 1) / group;
 		if (forcedL) L = (int)std::min<long long>(forcedL, std::max<long long>(1, groups));
 		else
 		{
@@ -589,13 +594,13 @@ int jp_get_counters(JpContext* c, JpCounters* out)
 int jp_get_build_info(JpContext* c, JpBuildInfo* out)
 {
 	if (!c || !out) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_build_info: null argument");
-	if (!c->have_scene) return fail(JP_ERR_NO_SCENE, "jp_get_build_info: no scene uploaded");
-	out->built_on_device = c->build_on_device ? 1 : 0; out->traversal_mode = c->trav_mode; out->bvh_nodes = c->bvh_nodes; out->bvh_height = c->bvh_height;
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_get_build_info: no scene uploaded");
+	out->built_on_device = c->build_on_device ? 1 : 0; out->traversal_mode = c->plan.trav_mode; out->bvh_nodes = c->bvh_nodes; out->bvh_height = c->bvh_height;
 	out->device_build_ms = c->build_ms; out->libm_sincosf = c->sincosf_mode; out->lanes_last_render = c->last_lanes;
 	out->fused_last_render = c->last_fused; out->fused_region = c->last_region; out->fused_workgroups = c->last_wgs;
-	out->q4_nodes = c->use_q4 ? c->sv.n_q4 : 0; out->libm_xbsdf = c->libm_mode;
-	out->certified_walk = (c->cert && c->persist != 0 && !c->cert_fell_back) ? 1 : 0;   // (what the refill kernels of the last render actually walked: the certified structures exist AND were used)
-	out->certified_nodes = c->cert ? c->sv.n_q4 : 0; out->certified_eye_leaves = c->cert ? c->cert_eye_leaves : 0;
+	out->q4_nodes = c->plan.use_q4 ? c->plan.sv.n_q4 : 0; out->libm_xbsdf = c->libm_mode;
+	out->certified_walk = (c->plan.cert && c->plan.persist != 0 && !c->cert_fell_back) ? 1 : 0;   // (what the refill kernels of the last render actually walked: the certified structures exist AND were used)
+	out->certified_nodes = c->plan.cert ? c->plan.sv.n_q4 : 0; out->certified_eye_leaves = c->plan.cert ? c->cert_eye_leaves : 0;
 	return JP_OK;
 }
 
@@ -639,7 +644,7 @@ int jp_bsdf(JpContext* c, const JpBsdfDesc* d, int32_t n, const float* normal, c
 int jp_trace(JpContext* c, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, int32_t* hit, float* t, int32_t* prim, float* normal)
 {
 	if (!c || n < 0 || !origin || !dir || !tmin || !tmax || !hit || !t || !prim || !normal) return fail(JP_ERR_INVALID_ARGUMENT, "jp_trace: null argument");
-	if (!c->have_scene) return fail(JP_ERR_NO_SCENE, "jp_trace: no scene uploaded");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_trace: no scene uploaded");
 	if (n == 0) return JP_OK;
 	HIP_TRY(hipSetDevice(c->device));
 	float *d_o = nullptr, *d_d = nullptr, *d_t0 = nullptr, *d_t1 = nullptr, *d_t = nullptr, *d_n = nullptr; int *d_hit = nullptr, *d_prim = nullptr;
@@ -652,16 +657,8 @@ int jp_trace(JpContext* c, int32_t n, const float* origin, const float* dir, con
 		hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
 		hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
 		int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-		// JpOptions::trace_walk (tests): 1 the binary tree, 2 the 8-wide tree, 3 the caller's tree verbatim; else what the render's closest-hit rays walk.  The one-ray-per-lane
-		// kernels keep the whole stack in LDS: a 4-wide tree deeper than 64 KB of stack falls back to the binary / verbatim walk
-		const size_t q4lds = (size_t)c->stack_depth_q4 * JP_BLOCK * sizeof(int); const int tw = c->opt.trace_walk;
-		if (c->trav_mode == 3 && tw == 2) hipLaunchKernelGGL(k_trace<3>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes_shadow, c->stream, c->sv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
-		else if (c->trav_mode == 5 && c->cert && q4lds <= 64 * 1024 && tw != 3) hipLaunchKernelGGL(k_trace<6>, dim3(grid), dim3(JP_BLOCK), q4lds, c->stream, c->sv, c->stack_depth_q4, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
-		else if (c->trav_mode == 5) hipLaunchKernelGGL(k_trace<5>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
-		else if (c->use_q4 && q4lds <= 64 * 1024 && tw != 1) hipLaunchKernelGGL(k_trace<4>, dim3(grid), dim3(JP_BLOCK), q4lds, c->stream, c->sv, c->stack_depth_q4, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
-		else if (c->trav_mode == 2) hipLaunchKernelGGL(k_trace<2>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
-		else if (c->trav_mode == 1) hipLaunchKernelGGL(k_trace<1>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
-		else hipLaunchKernelGGL(k_trace<0>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
+		const TraceLaunch tk = trace_kernel(c->plan, c->opt.trace_walk);
+		hipLaunchKernelGGL(tk.trace, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
 		hipMemcpyAsync(hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream); hipMemcpyAsync(t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
 		hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream); hipMemcpyAsync(normal, d_n, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream);
 		hipError_t e = hipStreamSynchronize(c->stream);
@@ -676,7 +673,7 @@ int jp_get_texture_info(JpContext* c, JpTextureInfo* out)
 	if (!c || !out) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_texture_info: null argument");
 	if (out->struct_bytes < (int32_t)sizeof(int32_t)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_texture_info: set JpTextureInfo.struct_bytes to sizeof(JpTextureInfo)");
 	JpTextureInfo i; std::memset(&i, 0, sizeof(i));
-	i.n_textures = c->textured ? c->n_textures : 0; i.n_textured_materials = c->n_tex_mats; i.texel_bytes_device = c->texel_bytes; i.textured_last_render = c->last_textured;
+	i.n_textures = c->plan.textured ? c->n_textures : 0; i.n_textured_materials = c->n_tex_mats; i.texel_bytes_device = c->texel_bytes; i.textured_last_render = c->last_textured;
 	const size_t n = std::min((size_t)out->struct_bytes, sizeof(i));
 	i.struct_bytes = (int32_t)n;
 	std::memcpy(out, &i, n);                                                   // (a shorter struct of the caller is truncated)
@@ -686,7 +683,7 @@ int jp_get_texture_info(JpContext* c, JpTextureInfo* out)
 int jp_surface(JpContext* c, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, int32_t* prim, float* uv, float* albedo)
 {
 	if (!c || n < 0 || !origin || !dir || !tmin || !tmax || !prim || !uv || !albedo) return fail(JP_ERR_INVALID_ARGUMENT, "jp_surface: null argument");
-	if (!c->have_scene) return fail(JP_ERR_NO_SCENE, "jp_surface: no scene uploaded");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_surface: no scene uploaded");
 	if (n == 0) return JP_OK;
 	HIP_TRY(hipSetDevice(c->device));
 	float *d_in = nullptr, *d_uv = nullptr, *d_a = nullptr; int* d_prim = nullptr;
@@ -699,15 +696,8 @@ int jp_surface(JpContext* c, int32_t n, const float* origin, const float* dir, c
 		hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
 		hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
 		const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-		const size_t q4lds = (size_t)c->stack_depth_q4 * JP_BLOCK * sizeof(int);
-		const TexView tv = c->tv;
-		// the walk jp_trace takes by default (what the render's closest-hit rays walk)
-		if (c->trav_mode == 5 && c->cert && q4lds <= 64 * 1024) hipLaunchKernelGGL(k_surface<6>, dim3(grid), dim3(JP_BLOCK), q4lds, c->stream, c->sv, tv, c->stack_depth_q4, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
-		else if (c->trav_mode == 5) hipLaunchKernelGGL(k_surface<5>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, tv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
-		else if (c->use_q4 && q4lds <= 64 * 1024) hipLaunchKernelGGL(k_surface<4>, dim3(grid), dim3(JP_BLOCK), q4lds, c->stream, c->sv, tv, c->stack_depth_q4, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
-		else if (c->trav_mode == 2) hipLaunchKernelGGL(k_surface<2>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, tv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
-		else if (c->trav_mode == 1) hipLaunchKernelGGL(k_surface<1>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, tv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
-		else hipLaunchKernelGGL(k_surface<0>, dim3(grid), dim3(JP_BLOCK), c->lds_bytes, c->stream, c->sv, tv, c->stack_depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+		const TraceLaunch tk = trace_kernel(c->plan, 0);                // the walk jp_trace takes by default (what the render's closest-hit rays walk)
+		hipLaunchKernelGGL(tk.surface, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.tv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
 		hipError_t e = hipGetLastError();
 		if (e == hipSuccess)
 		{

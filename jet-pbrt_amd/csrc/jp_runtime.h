@@ -1,4 +1,4 @@
-// jet-pbrt_amd/csrc/jp_runtime.h -- host runtime, part 1 of 3: the context behind the C ABI (include/jetpbrt_amd.h), the options (JpOptions, ABI 7),
+// jet-pbrt_amd/csrc/jp_runtime.h -- host runtime, part 1 of 3: the context behind the C ABI (include/jetpbrt_amd.h) and its ScenePlan, the options (JpOptions, ABI 7),
 // the probes of the host libm the device reproduces, the gamma-threshold table, jp_create_context / jp_destroy_context / jp_set_options.
 // Included by jp_kernels.hip (one translation unit: the kernels above, then this host code that launches them).
 #pragma once
@@ -48,31 +48,40 @@ static void options_from_environment(JpOptions& o)
 	}
 }
 
+// Everything jp_upload_scene* derives from the scene and the options that later launches read: the ONE thing a lane context takes from its
+// parent (sync_lane_scene: one assignment), and the only input of the kernel selectors of jp_render.h besides the render's region size.
+struct ScenePlan
+{
+	bool have_scene = false;
+	SceneView sv; TexView tv = {}; bool textured = false;
+	int trav_mode = 0, stack_depth = 1, stack_depth_q4 = 0; bool scene_in_lds = false, shade_prims_in_lds = false; size_t lds_bytes = 0, lds_bytes_shadow = 0;
+	bool cert = false;                                                                 // reference semantics, certified walk (Walker<6>)
+	bool use_q4 = false, q4_shadow = false;                                            // closest-hit (and, as an experiment, shadow) rays walk the 4-wide quantised tree (Walker<4>)
+	bool vote = false; int persist = 0;                                             // lane refill in the closest-hit traversal of large scenes (k_extend_persist): refill threshold, 0 = off
+	int n_planes = 1; bool has_null_material = false;
+	bool tables_in_lds = false, stage_nee = false; size_t shade_lds_bytes = 0;
+	int class_mask = 0x3f; bool shade_sort = false;                                     // k_shade partitions its tiles by material class (scenes with more than one material kind)
+	// lane refill kernels: traversal-stack words per thread kept in LDS, the rest spills to global memory (WalkStack).  Measured on the
+	// 280k-triangle scene (tree height 24): 8 / 12 / 16 words 1922 / 1926 / 1922 Msamples/s, 20 words or the whole stack 1634 / 1692.
+	int stack_lds_words = 12;
+};
+
 struct JpContext
 {
 	int device = 0;
 	JpOptions opt{}, opt_env{};                                    // the options in force; their initial value (defaults + environment, jp_create_context)
 	hipStream_t stream = nullptr;
 	int n_cus = 256;
-	// scene
-	bool have_scene = false;
-	SceneView sv; int stack_depth = 1, stack_depth_q4 = 0; bool scene_in_lds = false, shade_prims_in_lds = false; size_t lds_bytes = 0, lds_bytes_shadow = 0;
-	void *d_flat = nullptr, *d_wide = nullptr, *d_q4 = nullptr; int trav_mode = 0;
-	void* d_refbox = nullptr; bool cert_fell_back = false; bool cert = false; int cert_eye_leaves = 0;                                       // reference semantics, certified walk (Walker<6>): leaf boxes per primitive
-	bool use_q4 = false, q4_shadow = false;                                            // closest-hit (and, as an experiment, shadow) rays walk the 4-wide quantised tree (Walker<4>)
-	bool vote = false; int persist = 0;                                             // lane refill in the closest-hit traversal of large scenes (k_extend_persist): refill threshold, 0 = off
+	ScenePlan plan;                                                // scene: what the upload decided, then the device tables behind it (owned by the context that uploaded them)
+	void *d_flat = nullptr, *d_wide = nullptr, *d_q4 = nullptr;
+	void* d_refbox = nullptr; bool cert_fell_back = false; int cert_eye_leaves = 0;       // certified walk: leaf boxes per primitive; did the last renders leave it (a result of rendering, cleared at upload)
 	void *d_nodes = nullptr, *d_prims = nullptr, *d_meta = nullptr, *d_mats = nullptr, *d_mat_type = nullptr, *d_lights = nullptr, *d_shade_tab = nullptr;
-	int n_planes = 1; bool has_null_material = false; int sincosf_mode = 0, libm_mode = 0;
+	int sincosf_mode = 0, libm_mode = 0;
 	bool build_on_device = false; float build_ms = 0.f; int bvh_height = 0, bvh_nodes = 0;
-	bool tables_in_lds = false, stage_nee = false; size_t shade_lds_bytes = 0;
-	int class_mask = 0x3f; bool shade_sort = false;                                     // k_shade partitions its tiles by material class (scenes with more than one material kind)
 	// queues
 	Queues q = {}; unsigned int cap = 0; int planes_alloc = 0; unsigned int blk_alloc = 0; int blocks_per_cu = 16;
 	std::vector<void*> qbufs;
 	float4* d_pix_acc = nullptr; size_t pix_acc_n = 0;
-	// lane refill kernels: traversal-stack words per thread kept in LDS, the rest spills to global memory (WalkStack).  Measured on the
-	// 280k-triangle scene (tree height 24): 8 / 12 / 16 words 1922 / 1926 / 1922 Msamples/s, 20 words or the whole stack 1634 / 1692.
-	int stack_lds_words = 12;
 	int* d_spill = nullptr; size_t spill_words = 0;
 	float* d_film = nullptr; size_t film_n = 0;
 	float *d_bsdf_in = nullptr, *d_bsdf_out = nullptr; int* d_bsdf_fl = nullptr; size_t bsdf_cap = 0;   // jp_bsdf scratch
@@ -96,9 +105,9 @@ struct JpContext
 	Queues fq = {}; std::vector<void*> fbufs; unsigned int fcap = 0; int fplanes = 0; size_t flacc_n = 0;
 	unsigned int* d_jobs = nullptr; size_t jobs_n = 0;
 	int last_fused = 0, last_region = 0, last_wgs = 0;
-	// textures (jp_upload_scene_textured): the tables belong to the parent context and reach the lanes through `tv` (its side pointer is
+	// textures (jp_upload_scene_textured): the tables belong to the parent context and reach the lanes through `plan.tv` (its side pointer is
 	// set per launch); every context owns the side array of its own queue set (k_texel -> k_shade_tex, one word per queue position)
-	TexView tv = {}; bool textured = false; int n_textures = 0, n_tex_mats = 0; long long texel_bytes = 0; int last_textured = 0;
+	int n_textures = 0, n_tex_mats = 0; long long texel_bytes = 0; int last_textured = 0;
 	void *d_tex_desc = nullptr, *d_tex_col = nullptr, *d_texels = nullptr, *d_mat_tex = nullptr, *d_prim_uv = nullptr;
 	unsigned int* d_side = nullptr; size_t side_n = 0;
 };
@@ -108,8 +117,8 @@ static void free_scene(JpContext* c)
 	void** ps[] = { &c->d_flat, &c->d_wide, &c->d_q4, &c->d_refbox, &c->d_nodes, &c->d_prims, &c->d_meta, &c->d_mats, &c->d_mat_type, &c->d_lights, &c->d_shade_tab,
 	                &c->d_tex_desc, &c->d_tex_col, &c->d_texels, &c->d_mat_tex, &c->d_prim_uv };
 	for (void** p : ps) { if (*p) hipFree(*p); *p = nullptr; }
-	c->have_scene = false;
-	c->tv = TexView(); c->textured = false; c->n_textures = c->n_tex_mats = 0; c->texel_bytes = 0;   // (jp_upload_scene drops the textures of an earlier textured upload)
+	c->plan.have_scene = false;
+	c->plan.tv = TexView(); c->plan.textured = false; c->n_textures = c->n_tex_mats = 0; c->texel_bytes = 0;   // (jp_upload_scene drops the textures of an earlier textured upload)
 	if (c->d_side) hipFree(c->d_side);                             // ... and the side array only textured frames use (callers synchronise first)
 	c->d_side = nullptr; c->side_n = 0;
 }
@@ -334,7 +343,7 @@ int jp_destroy_context(JpContext* c)
 	if (!c) return JP_OK;
 	hipSetDevice(c->device);
 	if (c->stream) hipStreamSynchronize(c->stream);
-	for (JpContext* l : c->lanes) { std::memset(&l->sv, 0, sizeof(l->sv)); jp_destroy_context(l); }
+	for (JpContext* l : c->lanes) { std::memset(&l->plan.sv, 0, sizeof(l->plan.sv)); jp_destroy_context(l); }
 	c->lanes.clear();
 	if (c->ev_added) hipEventDestroy(c->ev_added);
 	if (!c->is_lane) free_scene(c);

@@ -1,5 +1,5 @@
 // jet-pbrt_amd/csrc/jp_upload.h -- host runtime, part 2 of 3: jp_upload_scene -- validation of every index on the host, the device tables (primitive records in
-// leaf order, binary / 8-wide / 4-wide trees, the certified walk's tree over the caller's leaves), the device-side hierarchy build (jp_lbvh.h, jp_ploc.h).
+// leaf order, binary / 8-wide / 4-wide trees, the certified walk's tree over the caller's leaves), the device-side hierarchy build (jp_lbvh.h, jp_ploc.h), the ScenePlan.
 // Included by jp_kernels.hip after jp_runtime.h.
 #pragma once
 // ---- scene validation + upload ----------------------------------------------------------------------------------------
@@ -658,7 +658,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	if (use_cert) HIP_TRY(up(&c->d_refbox, refbox.data(), refbox.size() * sizeof(float4)));
 	if (!flat.empty()) HIP_TRY(up(&c->d_flat, flat.data(), flat.size() * sizeof(float4)));
 
-	SceneView& v = c->sv;
+	ScenePlan& p = c->plan; SceneView& v = p.sv;                    // from here on: the plan every later launch reads (jp_runtime.h)
 	v.nodes = (const float4*)c->d_nodes; v.n_nodes = (int)(n4nodes / 4);
 	v.prims = (const float4*)c->d_prims; v.meta = (const int4*)c->d_meta; v.n_prims = (int)nmeta;
 	v.mats = (const float4*)c->d_mats; v.mat_type = (const int*)c->d_mat_type; v.n_mats = s->n_materials;
@@ -668,59 +668,56 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	v.flat = (const float4*)c->d_flat; v.n_flat = (int)(flat.size() / 2);
 	v.wide = (const uint4*)c->d_wide; v.n_wide = dev_wide ? dev_n_wide : (int)(wide.size() / 20);
 	v.q4 = (const uint4*)c->d_q4; v.n_q4 = dev_q4 ? dev_n_q4 : (int)(q4.size() / 16);
-	v.refbox = (const float4*)c->d_refbox; v.cert_pad = cert_pad; v.cert_pad_eye = cert_pad_eye; c->cert = use_cert;
-	c->use_q4 = use_q4; c->q4_shadow = use_q4;                       // shadow rays too (measured against the 8-wide tree: k_shadow 53.8 -> 52.7 ms per 512 spp, frame +4 %)
-	c->q4_shadow = use_q4 && opt_flag(op.q4_shadow, true);
-	c->stack_depth = std::max(2, height + 2);                         // binary / 8-wide / verbatim walks: the tree's height
-	c->stack_depth_q4 = (use_q4 || use_cert) ? 3 * q4_height + 2 : 0;   // 4-wide walks (Walker<4> / <6>): a node pushes up to three children
+	v.refbox = (const float4*)c->d_refbox; v.cert_pad = cert_pad; v.cert_pad_eye = cert_pad_eye; p.cert = use_cert;
+	p.use_q4 = use_q4; p.q4_shadow = use_q4 && opt_flag(op.q4_shadow, true);   // shadow rays too (measured against the 8-wide tree: k_shadow 53.8 -> 52.7 ms per 512 spp, frame +4 %)
+	p.stack_depth = std::max(2, height + 2);                         // binary / 8-wide / verbatim walks: the tree's height
+	p.stack_depth_q4 = (use_q4 || use_cert) ? 3 * q4_height + 2 : 0;   // 4-wide walks (Walker<4> / <6>): a node pushes up to three children
 	size_t scene_bytes = (n4nodes + n4prims) / 4 * 5 * sizeof(float4);   // 80-byte LDS record stride
 	size_t prim_bytes = n4prims / 4 * 5 * sizeof(float4);
-	size_t stack_bytes = (size_t)c->stack_depth * JP_BLOCK * sizeof(int);
-	c->scene_in_lds = !device_build && scene_bytes + stack_bytes <= 40 * 1024;   // device-built trees are indexed sparsely (Karras numbering): global memory only
-	c->trav_mode = use_wide ? 3 : ((!flat.empty() && prim_bytes <= 40 * 1024) ? 2 : (c->scene_in_lds ? 1 : 0));
-	if (!use_wide && op.traversal > 0) { const int m = op.traversal - 1; if (m == 0 || (m == 1 && c->scene_in_lds)) c->trav_mode = m; }   // experiments: force a lower mode
-	if (use_wide) c->scene_in_lds = false;
-	if (ref_sem) c->trav_mode = 5;
+	size_t stack_bytes = (size_t)p.stack_depth * JP_BLOCK * sizeof(int);
+	p.scene_in_lds = !device_build && scene_bytes + stack_bytes <= 40 * 1024;   // device-built trees are indexed sparsely (Karras numbering): global memory only
+	p.trav_mode = use_wide ? 3 : ((!flat.empty() && prim_bytes <= 40 * 1024) ? 2 : (p.scene_in_lds ? 1 : 0));
+	if (!use_wide && op.traversal > 0) { const int m = op.traversal - 1; if (m == 0 || (m == 1 && p.scene_in_lds)) p.trav_mode = m; }   // experiments: force a lower mode
+	if (use_wide) p.scene_in_lds = false;
+	if (ref_sem) p.trav_mode = 5;
 	// large scenes: closest-hit rays walk the binary tree (exact near-to-far order, early out), any-hit shadow rays the
 	// 8-wide quantised tree (fewest node fetches; order irrelevant).  Measured on the 280k-triangle scene:
 	// k_extend 10.3 ms binary vs 13.8 ms wide, k_shadow 10.6 ms binary vs 8.6 ms wide.
-	c->lds_bytes_shadow = c->trav_mode == 3 ? (size_t)2 * (wide_height + 2) * JP_BLOCK * sizeof(int) : 0;
-	c->lds_bytes = c->trav_mode == 2 ? prim_bytes : (c->trav_mode == 1 ? stack_bytes + scene_bytes : stack_bytes);
-	if (c->trav_mode != 3) c->lds_bytes_shadow = c->lds_bytes;
+	p.lds_bytes = p.trav_mode == 2 ? prim_bytes : (p.trav_mode == 1 ? stack_bytes + scene_bytes : stack_bytes);
+	p.lds_bytes_shadow = p.trav_mode == 3 ? (size_t)2 * (wide_height + 2) * JP_BLOCK * sizeof(int) : p.lds_bytes;
 	{
 		size_t tab = ((size_t)2 * s->n_lights + (size_t)4 * s->n_materials) * sizeof(float4) + (size_t)s->n_materials * sizeof(int) + 16;
-		c->tables_in_lds = tab <= 16 * 1024;
+		p.tables_in_lds = tab <= 16 * 1024;
 		// k_shade's static LDS (tile index, keys, counters of the material sort) + tables + staging must stay within 64 KB a workgroup;
 		// beyond 24 KB of tables the kernel's three workgroups per CU would not fit the CU's LDS either
 		const size_t shade_static = (size_t)JP_SHADE_TILE * 3 + (size_t)JP_SHADE_CLASSES * (JP_SHADE_TILE / JP_BLOCK) * (JP_BLOCK / 64) * 4 + 128;
 		const size_t prim_part = n4prims * sizeof(float4) + nmeta * sizeof(int4) + 3 * nmeta * sizeof(float4);     // records, meta, shading frames
-		c->shade_prims_in_lds = c->tables_in_lds && c->scene_in_lds && tab + prim_part <= 24 * 1024;
-		c->shade_lds_bytes = c->tables_in_lds ? tab + (c->shade_prims_in_lds ? prim_part : 0) : 0;
+		p.shade_prims_in_lds = p.tables_in_lds && p.scene_in_lds && tab + prim_part <= 24 * 1024;
+		p.shade_lds_bytes = p.tables_in_lds ? tab + (p.shade_prims_in_lds ? prim_part : 0) : 0;
 		const size_t stage_bytes = 16 + (size_t)std::max(1, planes) * 2 * JP_BLOCK * sizeof(float4);
-		c->stage_nee = c->tables_in_lds && std::max(1, planes) <= 4 && shade_static + c->shade_lds_bytes + stage_bytes <= 64 * 1024;
-		if (c->stage_nee) c->shade_lds_bytes += stage_bytes;
+		p.stage_nee = p.tables_in_lds && std::max(1, planes) <= 4 && shade_static + p.shade_lds_bytes + stage_bytes <= 64 * 1024;
+		if (p.stage_nee) p.shade_lds_bytes += stage_bytes;
 	}
-	c->n_planes = std::max(1, planes);
+	p.n_planes = std::max(1, planes);
 	{   // material sort in k_shade: pays when the primitives carry more than one material kind (JETPBRT_SHADE_SORT = 0 / 1 forces it)
 		bool kinds[8] = { false, false, false, false, false, false, false, false }; int nk = 0;
 		for (int i = 0; i < s->n_primitives; i++) { const int m = s->prim_material[i]; const int k = m < 0 ? 7 : s->mat_type[m]; if (!kinds[k]) { kinds[k] = true; nk++; } }
-		c->stack_lds_words = op.stack_lds_words >= 2 ? (op.stack_lds_words & ~1) : 12;   // even: the wide tree's entries are word pairs
+		p.stack_lds_words = op.stack_lds_words >= 2 ? (op.stack_lds_words & ~1) : 12;   // even: the wide tree's entries are word pairs
 		// lane refill in the traversal kernels (k_extend_persist / k_shadow_persist): on by default for scenes walked through global
 		// memory (measured on the 280k-triangle scene: k_extend 39.1 -> 28.4 ms, k_shadow 28.8 -> 18.9 ms per 128 spp; reference-tree
 		// mode 154 -> 227 Msamples/s); the LDS-resident Cornell box loses with it (reference-tree mode 1109 -> 965), so small scenes keep
 		// the one-ray-per-lane kernels.  JETPBRT_PERSIST = 0 (off) or the refill threshold (8 / 16 / 32 idle lanes).
-		c->persist = ((c->trav_mode == 0 || c->trav_mode == 3 || c->trav_mode == 5) && s->n_primitives > 1024) ? 16 : 0;
-		if (op.persist != 0) c->persist = op.persist < 0 ? 0 : op.persist;
+		p.persist = ((p.trav_mode == 0 || p.trav_mode == 3 || p.trav_mode == 5) && s->n_primitives > 1024) ? 16 : 0;
+		if (op.persist != 0) p.persist = op.persist < 0 ? 0 : op.persist;
 		// each iteration the lanes of a wave vote on the kind of step it runs (node / leaf); measured on the 280k-triangle scene: k_extend
 		// 28.3 -> 21.9 ms, k_shadow 18.9 -> 16.5 ms per 128 spp.  The reference-tree walk (one node per step, leaf objects as their own
 		// steps) is faster without it: 310 vs 286 Msamples/s.
-		c->vote = opt_flag(op.vote, c->trav_mode != 5 || c->cert);
-		c->shade_sort = nk > 1;
-		c->class_mask = 1; for (int k = 0; k < 5; k++) if (kinds[k]) c->class_mask |= 2 << k;
-		c->shade_sort = opt_flag(op.shade_sort, c->shade_sort);
+		p.vote = opt_flag(op.vote, p.trav_mode != 5 || p.cert);
+		p.class_mask = 1; for (int k = 0; k < 5; k++) if (kinds[k]) p.class_mask |= 2 << k;
+		p.shade_sort = opt_flag(op.shade_sort, nk > 1);
 	}
-	c->has_null_material = hasNull; c->cert_fell_back = false;
-	c->have_scene = true;
+	p.has_null_material = hasNull; c->cert_fell_back = false;
+	p.have_scene = true;
 	return JP_OK;
 }
 
@@ -816,9 +813,9 @@ extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const Jp
 		free_scene(c);
 		return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: out of device memory for the texture tables");
 	}
-	c->tv = TexView();
-	c->tv.desc = (const int4*)c->d_tex_desc; c->tv.col = (const float4*)c->d_tex_col; c->tv.texels = (const unsigned int*)c->d_texels;
-	c->tv.mat_tex = (const int*)c->d_mat_tex; c->tv.prim_uv = (const float2*)c->d_prim_uv;
-	c->textured = true; c->n_textures = nt; c->n_tex_mats = ntm; c->texel_bytes = (long long)texels.size() * 4;
+	TexView& tv = c->plan.tv; tv = TexView();
+	tv.desc = (const int4*)c->d_tex_desc; tv.col = (const float4*)c->d_tex_col; tv.texels = (const unsigned int*)c->d_texels;
+	tv.mat_tex = (const int*)c->d_mat_tex; tv.prim_uv = (const float2*)c->d_prim_uv;
+	c->plan.textured = true; c->n_textures = nt; c->n_tex_mats = ntm; c->texel_bytes = (long long)texels.size() * 4;
 	return JP_OK;
 }
