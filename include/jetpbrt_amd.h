@@ -332,6 +332,58 @@ int  jp_get_texture_info(JpContext* ctx, JpTextureInfo* out);
 int  jp_surface(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax,
                 int32_t* prim, float* uv, float* albedo);
 
+/* Guides and denoising (additive to ABI 7; INTEGRATION.md "Guides and denoising").  A low-spp film is noisy; the first-hit feature buffers
+ * ("guides": albedo, normal, depth) are not, and an edge-avoiding a-trous wavelet filter steered by them removes most of the noise.
+ *
+ * jp_render_guides: first-hit feature buffers of the frame `params` describes (width, height, seed, sampler_mode, band shard fields; spp,
+ * max_depth and integrator are ignored).  guide_spp camera samples per pixel (1 .. 1024), sample indices 0 .. guide_spp-1 of the SAME counter
+ * stream the render uses (so sample s here is the camera ray of sample s of jp_render; JP_SAMPLER_DEBUG: the pixel centre; the stock sampler:
+ * JP_ERR_UNSUPPORTED as for jp_render).  The closest hit comes from the walk jp_surface uses.  Per sample:
+ *              hit                                                                                        miss
+ *   albedo     the colour jp_surface reports; where it reports 0 by definition (glass, metal, no         (1,1,1)
+ *              material): (1,1,1)
+ *   normal     FIntersection::normal as jp_trace returns it                                              (0,0,0)
+ *   depth      the hit distance t                                                                        0
+ * Per pixel and channel: acc = 0; for s in 0 .. guide_spp-1: acc += v_s; out = acc * (1.0f / guide_spp) -- fp32, in sample order, one thread per
+ * pixel: deterministic and independent of the schedule options.  Pixels outside the band shard are 0 in all three buffers, so shards sum to the
+ * full buffers like films do.  albedo 3*W*H, normal 3*W*H, depth W*H floats, row-major, top row first; any of the three may be NULL. */
+int  jp_render_guides(JpContext* ctx, const JpRenderParams* params, int32_t guide_spp, float* albedo, float* normal, float* depth);
+int  jp_render_guides_device(JpContext* ctx, const JpRenderParams* params, int32_t guide_spp, void* albedo_dev, void* normal_dev, void* depth_dev, int sync);
+
+/* jp_denoise: needs no scene -- a film and guides from anywhere will do (rank 0 after a multi-GPU reduce).  All fp32, no contraction, operations
+ * in the order written; only + - * / max min, so the device result is bit-identical to a restatement on any IEEE host:
+ *   a = max(albedo, 0.001f) per channel if demodulating, else 1.  c0 = film / a.
+ *   kn = 1/(sn*sn), kz = 1/(sz*sz), kc_i = 4^i / (sc*sc), computed in fp32 on the host.
+ *   iteration i = 0 .. n-1, step s = 2^i, taps (dy, dx) in {-2..2}^2, dy outer, dx inner, tap pixel q = p + s*(dx, dy); taps outside the image are
+ *   skipped.  h = {1/16, 1/4, 3/8, 1/4, 1/16}, hh = h[dy+2] * h[dx+2].
+ *     dc = ((dr*dr + dg*dg) + db*db) of c_p - c_q; dn likewise of n_p - n_q; m = max(max(z_p, z_q), 1e-20f), rz = (z_p - z_q) / m, dz = rz*rz
+ *     w = hh / (((1 + dc*kc_i) * (1 + dn*kn)) * (1 + dz*kz));  num += w * c_q (per channel), den += w
+ *   c_next_p = num / den;  out = Clamp01(c_n * a).
+ * Defaults (fields left 0): iterations 5, sigma_color 1.0, sigma_normal 0.1, sigma_depth 0.03, demodulation on (DESIGN.md "Denoiser": the grid
+ * they were chosen from).  film / albedo / normal / depth / out laid out as jp_render and jp_render_guides lay them out; albedo may be NULL only
+ * with demodulate = -1; out may not overlap an input (JP_ERR_INVALID_ARGUMENT).  Working buffers belong to the context and are reused. */
+typedef struct JpDenoiseParams {
+    int32_t struct_bytes, width, height;
+    int32_t iterations;                                  /* 1..6; 0: 5                                                       */
+    float   sigma_color, sigma_normal, sigma_depth;      /* > 0 and finite; 0: the library's default                         */
+    int32_t demodulate;                                  /* 0 default (on), 1 on, -1 off                                     */
+} JpDenoiseParams;
+int  jp_denoise(JpContext* ctx, const JpDenoiseParams* params, const float* film_rgb, const float* albedo, const float* normal, const float* depth, float* out_rgb);
+int  jp_denoise_device(JpContext* ctx, const JpDenoiseParams* params, const void* film_dev, const void* albedo_dev, const void* normal_dev, const void* depth_dev, void* out_dev, int sync);
+/* jp_render, jp_render_guides, jp_denoise (params NULL: guides only, the film as rendered; its width / height are taken from `render`) and, with
+ * rgb8_host, the tone map of jp_render_rgb8 on the result, in one call: the film stays on the device between the stages.  film_host or rgb8_host
+ * may be NULL (not both); albedo / normal / depth may be NULL.  The bytes are those of the separate calls. */
+int  jp_render_denoised(JpContext* ctx, const JpRenderParams* render, int32_t guide_spp, const JpDenoiseParams* params, float* film_host, uint8_t* rgb8_host,
+                        float* albedo, float* normal, float* depth);
+/* what the last jp_render_guides* / jp_denoise* of the context did (HIP-event times on the context stream, kernels only; synchronises the stream) */
+typedef struct JpDenoiseInfo {
+    int32_t struct_bytes, iterations;                    /* iterations of the last jp_denoise*                                */
+    float   sigma_color, sigma_normal, sigma_depth;      /* the values in force in it                                         */
+    int32_t demodulated, guide_spp;
+    double  denoise_ms, guides_ms;
+} JpDenoiseInfo;
+int  jp_get_denoise_info(JpContext* ctx, JpDenoiseInfo* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,21 @@ class JpTextureInfo(C.Structure):
                 ("texel_bytes_device", C.c_int64), ("textured_last_render", C.c_int32)]
 
 
+class JpDenoiseParams(C.Structure):
+    """include/jetpbrt_amd.h: JpDenoiseParams (jp_denoise); struct_bytes = sizeof(JpDenoiseParams); fields left 0 take the library's defaults"""
+    _fields_ = [("struct_bytes", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("demodulate", C.c_int32)]
+
+
+class JpDenoiseInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("demodulated", C.c_int32), ("guide_spp", C.c_int32), ("denoise_ms", C.c_double), ("guides_ms", C.c_double)]
+
+
+def denoise_params(width, height, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, demodulate=0):
+    return JpDenoiseParams(C.sizeof(JpDenoiseParams), width, height, iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
+
+
 def textures(tex_type, tex_color, mat_texture, n_triangles=0, tri_uv=None, images=()):
     """A JpTextures over numpy arrays (kept alive on the returned object as ._keep).  tex_type / tex_color (n, 6) / mat_texture as in the
     header; images: {texture index: (H, W, 3) uint8 array} -- their texels are packed one after another."""
@@ -206,6 +221,7 @@ def host_lib():
         L.jp_host_flatten_textures.restype = C.POINTER(JpTextures)
         L.jp_host_flatten_textures.argtypes = [C.c_void_p]
         L.jp_host_render_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.jp_host_render_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
         _host = L
     return _host
 
@@ -238,6 +254,11 @@ def hip_lib():
         L.jp_upload_scene_textured.argtypes = [C.c_void_p, C.POINTER(JpScene), C.POINTER(JpTextures)]
         L.jp_get_texture_info.argtypes = [C.c_void_p, C.POINTER(JpTextureInfo)]
         L.jp_surface.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+        L.jp_render_guides.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32] + [C.c_void_p] * 3
+        L.jp_render_guides_device.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32] + [C.c_void_p] * 3 + [C.c_int]
+        L.jp_denoise.argtypes = [C.c_void_p, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 5
+        L.jp_denoise_device.argtypes = [C.c_void_p, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 5 + [C.c_int]
+        L.jp_get_denoise_info.argtypes = [C.c_void_p, C.POINTER(JpDenoiseInfo)]
         _hip = L
     return _hip
 
@@ -313,6 +334,44 @@ class Context:
 
     def render_device(self, params, device_ptr, sync=False):
         self._check(self.lib.jp_render_device(self.h, C.byref(params), C.c_void_p(device_ptr), 1 if sync else 0))
+
+    def render_guides(self, params, guide_spp=8):
+        """jp_render_guides: the first-hit feature buffers of the frame -> (albedo (H, W, 3), normal (H, W, 3), depth (H, W))"""
+        import numpy as np
+        alb = np.zeros((params.height, params.width, 3), np.float32); nrm = np.zeros((params.height, params.width, 3), np.float32)
+        dep = np.zeros((params.height, params.width), np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_render_guides(self.h, C.byref(params), guide_spp, p(alb), p(nrm), p(dep)))
+        return alb, nrm, dep
+
+    def render_guides_device(self, params, guide_spp, albedo_ptr, normal_ptr, depth_ptr, sync=False):
+        """jp_render_guides_device: device pointers (any may be 0 / None), as render_device takes its film"""
+        self._check(self.lib.jp_render_guides_device(self.h, C.byref(params), guide_spp, C.c_void_p(albedo_ptr or None), C.c_void_p(normal_ptr or None),
+                                                     C.c_void_p(depth_ptr or None), 1 if sync else 0))
+
+    def denoise(self, film, albedo, normal, depth, **kw):
+        """jp_denoise: the edge-avoiding a-trous filter on a (H, W, 3) film with its guides -> the denoised (H, W, 3) film.
+        kw: iterations, sigma_color, sigma_normal, sigma_depth, demodulate (JpDenoiseParams; 0 = the library's default)"""
+        import numpy as np
+        h, w = film.shape[:2]
+        a = [None if x is None else np.ascontiguousarray(x, np.float32) for x in (film, albedo, normal, depth)]
+        out = np.zeros((h, w, 3), np.float32)
+        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        dp = denoise_params(w, h, **kw)
+        self._check(self.lib.jp_denoise(self.h, C.byref(dp), p(a[0]), p(a[1]), p(a[2]), p(a[3]), p(out)))
+        return out
+
+    def denoise_device(self, width, height, film_ptr, albedo_ptr, normal_ptr, depth_ptr, out_ptr, sync=False, **kw):
+        """jp_denoise_device: device pointers in the layouts jp_render_device / jp_render_guides_device write"""
+        dp = denoise_params(width, height, **kw)
+        self._check(self.lib.jp_denoise_device(self.h, C.byref(dp), C.c_void_p(film_ptr or None), C.c_void_p(albedo_ptr or None), C.c_void_p(normal_ptr or None),
+                                               C.c_void_p(depth_ptr or None), C.c_void_p(out_ptr or None), 1 if sync else 0))
+
+    def denoise_info(self):
+        i = JpDenoiseInfo()
+        i.struct_bytes = C.sizeof(JpDenoiseInfo)
+        self._check(self.lib.jp_get_denoise_info(self.h, C.byref(i)))
+        return i
 
     def synchronize(self):
         self._check(self.lib.jp_synchronize(self.h))

@@ -1203,3 +1203,4 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_runtime.h"          // context, options (JpOptions), libm probes, create / destroy
 #include "jp_upload.h"           // jp_upload_scene: validation, device tables, trees, device-side build
 #include "jp_render.h"           // jp_render*: queues, launch sequence, stream lanes, fused schedule; counters, jp_trace, jp_bsdf
+#include "jp_denoise.h"          // guides and denoising: k_guides, k_atrous and their entry points (additive: nothing above refers to it)

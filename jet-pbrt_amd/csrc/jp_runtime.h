@@ -110,6 +110,12 @@ struct JpContext
 	int n_textures = 0, n_tex_mats = 0; long long texel_bytes = 0; int last_textured = 0;
 	void *d_tex_desc = nullptr, *d_tex_col = nullptr, *d_texels = nullptr, *d_mat_tex = nullptr, *d_prim_uv = nullptr;
 	unsigned int* d_side = nullptr; size_t side_n = 0;
+	// guides and denoising (jp_denoise.h): the filter's per-pixel records (two colour buffers, the normals), the staging area of the host
+	// variants, event pairs around the kernels, what the last calls did (jp_get_denoise_info)
+	float4 *d_dn_cz[2] = { nullptr, nullptr }, *d_dn_nr = nullptr; size_t dn_n = 0;
+	float* d_dn_stage = nullptr; size_t dn_stage_n = 0;
+	hipEvent_t dn_ev[2] = { nullptr, nullptr }, gd_ev[2] = { nullptr, nullptr }; bool dn_timed = false, gd_timed = false;
+	int last_dn = 0, last_dn_demod = 0, last_guide_spp = 0; float last_dn_sigma[3] = { 0.f, 0.f, 0.f };
 };
 
 static void free_scene(JpContext* c)
@@ -359,6 +365,8 @@ int jp_destroy_context(JpContext* c)
 	if (c->d_rgb8) hipFree(c->d_rgb8);
 	if (c->h_rgb8) hipHostFree(c->h_rgb8);
 	if (c->d_cnt) hipFree(c->d_cnt);
+	for (void* p : { (void*)c->d_dn_cz[0], (void*)c->d_dn_cz[1], (void*)c->d_dn_nr, (void*)c->d_dn_stage }) if (p) hipFree(p);
+	for (hipEvent_t e : { c->dn_ev[0], c->dn_ev[1], c->gd_ev[0], c->gd_ev[1] }) if (e) hipEventDestroy(e);
 	for (hipEvent_t e : c->evpool) hipEventDestroy(e);
 	if (c->ev0) hipEventDestroy(c->ev0);
 	if (c->ev1) hipEventDestroy(c->ev1);

@@ -163,6 +163,34 @@ int jp_host_render_ldr(void* h, int W, int H, int spp, int maxdepth, unsigned se
 	return JP_OK;
 }
 
+// FFilm::RequestGuides(guide_spp) (denoise 0) / RequestDenoise(guide_spp) (denoise 1) [+ RequestDeviceLDR(ldr == 2): ldr 0 none, 1 next to the fp32 film,
+// 2 instead of it] -> Render -> the film (denoised when asked for), the guides and the 8-bit pixels; any output may be null
+int jp_host_render_denoised(void* h, int W, int H, int spp, int maxdepth, unsigned seed, int device, int guide_spp, int denoise, int ldr,
+                            float* film_out, float* albedo_out, float* normal_out, float* depth_out, unsigned char* rgb8_out)
+{
+	HostScene* hs = (HostScene*)h;
+	if (ldr == 2 && film_out) return JP_ERR_INVALID_ARGUMENT;
+	if (!hs->integ || hs->integDepth != maxdepth) { hs->integ.reset(new FGpuPathIntegrator(maxdepth, device)); hs->integDepth = maxdepth; }
+	hs->integ->SetShard(0, 1);
+	FFilm film(W, H);
+	if (denoise) film.RequestDenoise(guide_spp); else film.RequestGuides(guide_spp);
+	if (ldr) film.RequestDeviceLDR(ldr == 2);
+	FCounterSampler sampler(spp, seed);
+	hs->integ->Render(hs->scene.get(), &sampler, &film, 16);
+	if (hs->integ->LastStatus() != JP_OK) return hs->integ->LastStatus();
+	const size_t n = (size_t)W * H;
+	if (film.Albedo().size() != n || film.Normal().size() != n || film.Depth().size() != n || (ldr && !film.HasLDR())) return JP_ERR_DEVICE;
+	if (film_out) for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) { const FColor& c = static_cast<const FFilm&>(film)(x, y); float* o = film_out + 3 * ((size_t)y * W + x); o[0] = c.r; o[1] = c.g; o[2] = c.b; }
+	for (size_t i = 0; i < n; i++)
+	{
+		if (albedo_out) { albedo_out[3 * i] = film.Albedo()[i].r; albedo_out[3 * i + 1] = film.Albedo()[i].g; albedo_out[3 * i + 2] = film.Albedo()[i].b; }
+		if (normal_out) { normal_out[3 * i] = film.Normal()[i].x; normal_out[3 * i + 1] = film.Normal()[i].y; normal_out[3 * i + 2] = film.Normal()[i].z; }
+		if (depth_out) depth_out[i] = film.Depth()[i];
+	}
+	if (rgb8_out && ldr) std::memcpy(rgb8_out, film.ldr8.data(), film.ldr8.size());
+	return JP_OK;
+}
+
 // The reference's reflection classes by name (jetpbrt.h "reflection API"): builds the named class the way reference code would and
 // calls Evalf / Pdf / Sample once.  which: 0 FPhongSpecularReflection(Ks, exponent), 1 FMicrofacetReflection(R, Beckmann(ax, ay, vis),
 // FresnelNoOp), 2 FMicrofacetTransmission(T, TrowbridgeReitz(ax, ay, vis), etaA, etaB).  out: f[3], pdf, sample f[3], wi[3], pdf, flags

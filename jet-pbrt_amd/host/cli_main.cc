@@ -1,5 +1,8 @@
 // jet-pbrt_amd/host/cli_main.cc -- the reference's command line (main.cc:113-163) on the GPU integrator:
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
+//             [--denoise] [--guide-spp N] [--aov PREFIX]
+// --denoise: the edge-avoiding filter on the rendered film (FFilm::RequestDenoise); --guide-spp: camera samples per pixel of its guides (default 8,
+// 1 .. 1024); --aov: the guides as images PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5), PREFIX_depth (t / max t) in the chosen format.
 // sceneid 0 = Cornell box, 1 = bunny scene; spp defaults to 50, the film to 1024 x 1024, the output to
 // <scene name>_<spp>.bmp, as in the reference.  The scene scripts are the calls of main.cc:13-111; the meshes are
 // read from DIR/cornellbox/{light,floor,shortbox,tallbox,left,right}.obj and DIR/bunny/bunny.obj (the reference
@@ -71,7 +74,9 @@ int main(int argc, char* argv[])
 {
 	int width = 1024, height = 1024, samples_per_pixel = 50;     // main.cc:115,119
 	std::string assets = "scene", out, format = "bmp", integratorName = "path";
+	bool denoise = false; int guideSpp = 8; std::string aov;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
+	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -82,6 +87,9 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--integrator") && i + 1 < argc) integratorName = argv[++i];
 		else if (!strcmp(argv[i], "--reference-tree")) setenv("JETPBRT_REFERENCE_TREE", "1", 1);   // FScene::referenceTree: the reference's own BVH and traversal semantics
 		else if (!strcmp(argv[i], "--reference-tree=certified")) setenv("JETPBRT_REFERENCE_TREE", "2", 1);   // ... with the certified walk (FScene::certifiedWalk)
+		else if (!strcmp(argv[i], "--denoise")) denoise = true;
+		else if (!strcmp(argv[i], "--guide-spp") && i + 1 < argc) { guideSpp = atoi(argv[++i]); if (guideSpp < 1 || guideSpp > 1024) { fprintf(stderr, "--guide-spp must be 1 .. 1024\n"); return 5; } }
+		else if (!strcmp(argv[i], "--aov") && i + 1 < argc) aov = argv[++i];
 		else pos.push_back(argv[i]);
 	}
 	if (pos.empty()) return 0;                                    // main.cc:122-125
@@ -106,11 +114,26 @@ int main(int argc, char* argv[])
 	else if (integratorName == "recursive") integrator.reset(new FPathIntegratorRecursive(5));
 	else integrator.reset(new FPathIntegratorIteration(5));
 	if (format != "hdr") film.RequestDeviceLDR(true);             // BMP / PPM: gamma_encoding runs on the GPU, 3 bytes per pixel come back
+	if (denoise) film.RequestDenoise(guideSpp); else if (!aov.empty()) film.RequestGuides(guideSpp);
 	integrator->Render(scene.get(), sampler.get(), &film, 16);    // main.cc:156
 	if (integrator->LastStatus() != JP_OK) return 3;              // no GPU / no library: fail loudly, nothing is written
 	char fullname[512];
 	snprintf(fullname, sizeof(fullname), "%s_%d", scene->NameStr(), samples_per_pixel);
 	const std::string name = out.empty() ? fullname : out;
 	const EImageType t = format == "ppm" ? EImageType::PPM : (format == "hdr" ? EImageType::HDR : EImageType::BMP);
+	if (!aov.empty())
+	{   // the guides through SaveAsImage: albedo as it is, normal n * 0.5 + 0.5, depth t / max t
+		const size_t n = (size_t)width * height;
+		Float zmax = 0; for (Float z : film.Depth()) zmax = z > zmax ? z : zmax;
+		FFilm fa(width, height), fn(width, height), fz(width, height);
+		for (size_t i = 0; i < n; i++)
+		{
+			const int x = (int)(i % width), y = (int)(i / width);
+			fa(x, y) = film.Albedo()[i];
+			const FVector3& v = film.Normal()[i]; fn(x, y) = FColor(v.x * 0.5f + 0.5f, v.y * 0.5f + 0.5f, v.z * 0.5f + 0.5f);
+			const Float z = zmax > 0 ? film.Depth()[i] / zmax : 0; fz(x, y) = FColor(z, z, z);
+		}
+		if (!fa.SaveAsImage(aov + "_albedo", t) || !fn.SaveAsImage(aov + "_normal", t) || !fz.SaveAsImage(aov + "_depth", t)) return 4;
+	}
 	return film.SaveAsImage(name, t) ? 0 : 4;                     // main.cc:160
 }

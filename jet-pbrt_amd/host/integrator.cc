@@ -27,6 +27,7 @@ struct HipApi
 	int (*abi_version)() = nullptr;
 	int (*set_options)(JpContext*, const JpOptions*) = nullptr;
 	int (*upload_scene_textured)(JpContext*, const JpScene*, const JpTextures*) = nullptr;   // (looked up, needed by textured scenes only)
+	int (*render_denoised)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*) = nullptr;   // (looked up, needed by FFilm::RequestGuides / RequestDenoise only)
 	std::string error;
 };
 
@@ -53,6 +54,7 @@ HipApi& Api()
 		api.abi_version = (int (*)())dlsym(api.lib, "jp_abi_version");
 		api.set_options = (int (*)(JpContext*, const JpOptions*))dlsym(api.lib, "jp_set_options");
 		api.upload_scene_textured = (int (*)(JpContext*, const JpScene*, const JpTextures*))dlsym(api.lib, "jp_upload_scene_textured");
+		api.render_denoised = (decltype(api.render_denoised))dlsym(api.lib, "jp_render_denoised");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
 		else if (api.abi_version() != JP_ABI_VERSION)            // a stale build would be handed structs of another size (JpCounters, JpBuildInfo, JpOptions)
@@ -143,7 +145,19 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 	const bool floatFilm = !(film->wantLDR && film->ldrOnly);
 	std::vector<float> rgb(floatFilm ? (size_t)rp.width * rp.height * 3 : 0);
 	std::vector<uint8_t> ldr;
-	if (film->wantLDR)
+	std::vector<float> galb, gnrm, gdep;
+	if (film->wantGuides)
+	{   // FFilm::RequestGuides / RequestDenoise: render, guides, filter and tone map in one call -- the film stays on the device in between
+		if (!api.render_denoised) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_render_denoised\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+		const size_t n = (size_t)rp.width * rp.height;
+		galb.assign(3 * n, 0.f); gnrm.assign(3 * n, 0.f); gdep.assign(n, 0.f);
+		if (film->wantLDR) ldr.assign(3 * n, 0);
+		JpDenoiseParams dp; std::memset(&dp, 0, sizeof(dp));
+		dp.struct_bytes = (int32_t)sizeof(dp); dp.width = rp.width; dp.height = rp.height; dp.iterations = film->denoise.iterations;
+		dp.sigma_color = film->denoise.sigmaColor; dp.sigma_normal = film->denoise.sigmaNormal; dp.sigma_depth = film->denoise.sigmaDepth; dp.demodulate = film->denoise.demodulate ? 1 : -1;
+		lastStatus = api.render_denoised(ctx, &rp, film->guideSpp_, film->wantDenoise ? &dp : nullptr, floatFilm ? rgb.data() : nullptr, film->wantLDR ? ldr.data() : nullptr, galb.data(), gnrm.data(), gdep.data());
+	}
+	else if (film->wantLDR)
 	{   // FFilm::RequestDeviceLDR: gamma_encoding (film.h:24) runs on the GPU, the film comes back as 3 bytes per pixel
 		ldr.assign((size_t)rp.width * rp.height * 3, 0);
 		lastStatus = api.render_rgb8(ctx, &rp, ldr.data(), floatFilm ? rgb.data() : nullptr);
@@ -156,6 +170,12 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			const float* p = &rgb[3 * ((size_t)y * rp.width + x)];
 			film->AddColor(x, y, FColor(p[0], p[1], p[2]));               // integrator.cc:108 / film.h:64-68
 		}
+	if (film->wantGuides)
+	{
+		const size_t n = (size_t)rp.width * rp.height;
+		film->albedo.resize(n); film->normal.resize(n); film->depth.swap(gdep);
+		for (size_t i = 0; i < n; i++) { film->albedo[i] = FColor(galb[3 * i], galb[3 * i + 1], galb[3 * i + 2]); film->normal[i] = FVector3(gnrm[3 * i], gnrm[3 * i + 1], gnrm[3 * i + 2]); }
+	}
 	if (film->wantLDR) { film->ldr8.swap(ldr); film->floatValid = floatFilm; }   // (after AddColor: any later change of a pixel drops the bytes again)
 	api.get_counters(ctx, &counters);
 	fprintf(stderr, "finish rendering ...\n");

@@ -272,6 +272,9 @@ enum class EImageType { PPM, BMP, HDR };                         // film.h:15-20
 inline Float Clamp01(Float x) { return x < 0 ? 0 : (x > 1 ? 1 : x); }                                   // film.h:22
 inline uint8_t gamma_encoding(Float x) { return (uint8_t)(std::pow(Clamp01(x), (Float)(1 / 2.2)) * 255.0); }   // film.h:24
 
+// FFilm::RequestDenoise: the fields of JpDenoiseParams (0: the library's default; INTEGRATION.md "Guides and denoising")
+struct FDenoiseOptions { int iterations = 0; Float sigmaColor = 0, sigmaNormal = 0, sigmaDepth = 0; bool demodulate = true; };
+
 class FFilm                                                      // film.h:27-94
 {
 public:
@@ -291,6 +294,16 @@ public:
 	// BMP / PPM then costs a 3-bytes-per-pixel download instead of 12.  SaveAsImage writes ldr8 when it is present.
 	void RequestDeviceLDR(bool only = true) { wantLDR = true; ldrOnly = only; }
 	bool HasLDR() const { return ldr8.size() == (size_t)width * height * 3; }
+	// Guides and denoising: ask the integrator for the first-hit feature buffers of the frame (guideSpp camera samples per pixel) and, with
+	// RequestDenoise, for the edge-avoiding filter they steer: after Render the film holds the DENOISED image (added onto the film like every
+	// render result; with RequestDeviceLDR the bytes are its tone map) and Albedo() / Normal() / Depth() hold the guides, row-major, top row first.
+	void RequestDenoise(int guideSpp = 8, const FDenoiseOptions& options = FDenoiseOptions()) { wantGuides = wantDenoise = true; guideSpp_ = guideSpp; denoise = options; }
+	void RequestGuides(int guideSpp = 8) { wantGuides = true; guideSpp_ = guideSpp; }
+	const std::vector<FColor>& Albedo() const { return albedo; }
+	const std::vector<FVector3>& Normal() const { return normal; }
+	const std::vector<Float>& Depth() const { return depth; }
+	bool wantGuides = false, wantDenoise = false; int guideSpp_ = 8; FDenoiseOptions denoise;
+	std::vector<FColor> albedo; std::vector<FVector3> normal; std::vector<Float> depth;
 	int width, height; std::vector<FColor> pixels;
 	bool wantLDR = false, ldrOnly = false; std::vector<uint8_t> ldr8;   // R G B per pixel, top row first
 	bool floatValid = true;                                            // false after an LDR-only render: the fp32 pixels were not downloaded
