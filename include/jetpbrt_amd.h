@@ -384,6 +384,35 @@ typedef struct JpDenoiseInfo {
 } JpDenoiseInfo;
 int  jp_get_denoise_info(JpContext* ctx, JpDenoiseInfo* out);
 
+/* Light selection (additive to ABI 7; INTEGRATION.md "Light selection").  JP_LIGHTS_ALL: the reference's estimator, every light sampled at every
+ * non-delta bounce (at most 255 lights).  JP_LIGHTS_POWER_ONE: one light per bounce, picked with probability proportional to its power from an alias
+ * table, its contribution divided by that probability: one shadow ray and one shadow plane per bounce for up to 2^24 lights (emissive meshes).
+ *   weight (double, from the fp32 scene values, s = (double)r + g + b):  AREA (s * area) * pi, area = the fp32 FShape::Area() of the upload;
+ *     POINT s * (4 * pi);  DIRECTION, ENVIRONMENT (s * pi) * ((double)world_radius * world_radius).  W = the weights summed in light order;
+ *     pmf_i = (float)(w_i / W), all 0 when W == 0 (then no light is sampled).
+ *   table: Vose's alias method in double; bin i holds the fp32 threshold q[i] and alias[i]; a light of weight 0 is in no bin's reach.
+ *   pick from two draws: i = min((int)(u0 * (float)n), n - 1);  j = u1 < q[i] ? i : alias[i].
+ *   a non-delta bounce draws: [the plastic closure draw], u0, u1, the two draws of FLight::Sample_Li for light j (consumed even when the sample is
+ *     rejected), then the BSDF sample.  Contribution: (cmul(cmul(beta, f), Li) * absdot / pdf) / pmf_j.
+ * Path integrator only (Whitted: JP_ERR_UNSUPPORTED; the debug integrator ignores the mode); JpOptions.fused falls back to the per-bounce launches. */
+enum { JP_LIGHTS_ALL = 0, JP_LIGHTS_POWER_ONE = 1 };
+typedef struct JpLightSampling { int32_t struct_bytes; int32_t mode; } JpLightSampling;
+/* takes effect with the next jp_upload_scene*; NULL: back to JP_LIGHTS_ALL */
+int  jp_set_light_sampling(JpContext* ctx, const JpLightSampling* sampling);
+typedef struct JpLightInfo {
+    int32_t struct_bytes, mode, n_lights;    /* mode and light count of the uploaded scene                                   */
+    int32_t n_selectable;                    /* lights of weight > 0 (POWER_ONE; ALL: the non-black lights)                   */
+    double  total_weight;                    /* W (0 in ALL mode)                                                            */
+    int32_t picked_last_render;              /* the last jp_render* ran the pick kernels (k_shade_pick / k_shade_pick_tex)   */
+} JpLightInfo;
+int  jp_get_light_info(JpContext* ctx, JpLightInfo* out);
+/* the table in force, downloaded from the device: n_lights entries each (any pointer may be NULL); JP_ERR_UNSUPPORTED for a scene uploaded in ALL mode */
+int  jp_get_light_table(JpContext* ctx, float* q, int32_t* alias, float* pmf);
+/* test hook like jp_trace: the device's selection (the function the render calls) for n pairs of draws -> index (-1 for a scene without lights), pmf */
+int  jp_light_pick(JpContext* ctx, int32_t n, const float* u0, const float* u1, int32_t* index, float* pmf);
+/* the table builder of the upload; pure host code, no GPU needed.  weights: n finite values >= 0 (else JP_ERR_INVALID_ARGUMENT); n == 0 is JP_OK */
+int  jp_build_light_table(int32_t n, const double* weight, float* q, int32_t* alias, float* pmf);
+
 #ifdef __cplusplus
 }
 #endif

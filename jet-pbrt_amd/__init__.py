@@ -114,6 +114,33 @@ class JpDenoiseInfo(C.Structure):
                 ("demodulated", C.c_int32), ("guide_spp", C.c_int32), ("denoise_ms", C.c_double), ("guides_ms", C.c_double)]
 
 
+JP_LIGHTS_ALL, JP_LIGHTS_POWER_ONE = 0, 1
+LIGHT_SAMPLING_MODES = {None: JP_LIGHTS_ALL, "all": JP_LIGHTS_ALL, "power": JP_LIGHTS_POWER_ONE, JP_LIGHTS_ALL: JP_LIGHTS_ALL, JP_LIGHTS_POWER_ONE: JP_LIGHTS_POWER_ONE}
+
+
+class JpLightSampling(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("mode", C.c_int32)]
+
+
+class JpLightInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("mode", C.c_int32), ("n_lights", C.c_int32), ("n_selectable", C.c_int32),
+                ("total_weight", C.c_double), ("picked_last_render", C.c_int32)]
+
+
+def build_light_table(weights):
+    """jp_build_light_table: the alias table of the upload for `weights` (pure host code, no GPU) -> (q float32, alias int32, pmf float32)"""
+    import numpy as np
+    w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    n = w.shape[0]
+    q = np.zeros(n, np.float32); alias = np.zeros(n, np.int32); pmf = np.zeros(n, np.float32)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    st = L.jp_build_light_table(n, p(w), p(q), p(alias), p(pmf))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    return q, alias, pmf
+
+
 def denoise_params(width, height, iterations=0, sigma_color=0.0, sigma_normal=0.0, sigma_depth=0.0, demodulate=0):
     return JpDenoiseParams(C.sizeof(JpDenoiseParams), width, height, iterations, sigma_color, sigma_normal, sigma_depth, demodulate)
 
@@ -222,6 +249,7 @@ def host_lib():
         L.jp_host_flatten_textures.argtypes = [C.c_void_p]
         L.jp_host_render_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.jp_host_render_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.jp_host_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         _host = L
     return _host
 
@@ -259,6 +287,11 @@ def hip_lib():
         L.jp_denoise.argtypes = [C.c_void_p, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 5
         L.jp_denoise_device.argtypes = [C.c_void_p, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 5 + [C.c_int]
         L.jp_get_denoise_info.argtypes = [C.c_void_p, C.POINTER(JpDenoiseInfo)]
+        L.jp_set_light_sampling.argtypes = [C.c_void_p, C.POINTER(JpLightSampling)]
+        L.jp_get_light_info.argtypes = [C.c_void_p, C.POINTER(JpLightInfo)]
+        L.jp_get_light_table.argtypes = [C.c_void_p] * 4
+        L.jp_light_pick.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4
+        L.jp_build_light_table.argtypes = [C.c_int32] + [C.c_void_p] * 4
         _hip = L
     return _hip
 
@@ -372,6 +405,41 @@ class Context:
         i.struct_bytes = C.sizeof(JpDenoiseInfo)
         self._check(self.lib.jp_get_denoise_info(self.h, C.byref(i)))
         return i
+
+    def set_light_sampling(self, mode):
+        """jp_set_light_sampling for the next upload: None / "all" / JP_LIGHTS_ALL, or "power" / JP_LIGHTS_POWER_ONE (one light per bounce by power)"""
+        if mode not in LIGHT_SAMPLING_MODES:
+            raise JetPbrtError("unknown light sampling mode %r" % (mode,))
+        if mode is None:
+            self._check(self.lib.jp_set_light_sampling(self.h, None))
+            return
+        ls = JpLightSampling(C.sizeof(JpLightSampling), LIGHT_SAMPLING_MODES[mode])
+        self._check(self.lib.jp_set_light_sampling(self.h, C.byref(ls)))
+
+    def light_info(self):
+        i = JpLightInfo()
+        i.struct_bytes = C.sizeof(JpLightInfo)
+        self._check(self.lib.jp_get_light_info(self.h, C.byref(i)))
+        return i
+
+    def light_table(self):
+        """jp_get_light_table: the alias table on the device -> (q float32, alias int32, pmf float32), n_lights entries each"""
+        import numpy as np
+        n = self.light_info().n_lights
+        q = np.zeros(n, np.float32); alias = np.zeros(n, np.int32); pmf = np.zeros(n, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_get_light_table(self.h, p(q), p(alias), p(pmf)))
+        return q, alias, pmf
+
+    def light_pick(self, u0, u1):
+        """jp_light_pick: the device's selection for pairs of draws -> (index int32, pmf float32)"""
+        import numpy as np
+        a = np.ascontiguousarray(u0, np.float32).reshape(-1); b = np.ascontiguousarray(u1, np.float32).reshape(-1)
+        n = a.shape[0]
+        idx = np.zeros(n, np.int32); pmf = np.zeros(n, np.float32)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_light_pick(self.h, n, p(a), p(b), p(idx), p(pmf)))
+        return idx, pmf
 
     def synchronize(self):
         self._check(self.lib.jp_synchronize(self.h))

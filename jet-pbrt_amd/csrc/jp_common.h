@@ -99,3 +99,22 @@ struct TexView
 	const float2* prim_uv;       // three per primitive of the caller's order (uv0 uv1 uv2 of a triangle; 0 for other shapes)
 	unsigned int* side;          // one word per queue position (cap entries of the context's queue set)
 };
+
+// ---- light selection (k_shade_pick, k_shade_pick_tex, jp_light_pick; jp_pick.h) ----------------------------------------
+// A separate kernel argument like TexView: the kernels of a context that never switches JP_LIGHTS_POWER_ONE on do not change.
+struct PickView
+{
+	const float2* bins;          // alias table, one 8-byte record per light: (threshold q, alias as int bits)
+	const float* pmf;            // per light: (float)(w / W)
+	const float4* env;           // radiance of the non-black environment lights, in light order (the miss branch's short list)
+	int n, n_env;                // lights of the table (SceneView::n_lights), entries of env
+};
+// the pick: bin i from u0, then the bin's own light or its alias by u1 against the bin's threshold
+__device__ __forceinline__ int light_pick(const PickView& pv, float u0, float u1, float& pmf)
+{
+	int i = (int)(u0 * (float)pv.n); i = i < pv.n - 1 ? i : pv.n - 1;
+	const float2 b = pv.bins[i];
+	const int j = u1 < b.x ? i : __float_as_int(b.y);
+	pmf = pv.pmf[j];
+	return j;
+}

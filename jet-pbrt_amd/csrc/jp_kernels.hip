@@ -221,8 +221,12 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 #define JP_SHADE_TILE 8192
 #endif
 // kTex (k_shade_tex, textured scenes): the textured slot of a material's closure comes from the word k_texel left for the queue position.
-template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex>
-__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv)
+// kPick (k_shade_pick / k_shade_pick_tex, JP_LIGHTS_POWER_ONE; jp_pick.h): ONE light per non-delta bounce, picked from the alias table of pv with two
+// draws, its contribution divided by its pmf.  The light records stay in global memory (the LDS tables start at the materials: an emissive mesh of
+// 70k triangles has 2.2 MB of them), the one picked light's two float4 come from HBM / L2, and the miss branch walks pv.env, the short list of
+// non-black environment lights, instead of every light.
+template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick>
+__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv)
 {
 	static_assert(kTab || !kPrims, "k_shade: primitive records in LDS only together with the tables");
 	constexpr int kWaves = JP_BLOCK / 64, kMaxSeg = (JP_SHADE_TILE / JP_BLOCK) * kWaves;  // (pass, wave) segments of a tile, in queue order
@@ -234,9 +238,10 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 	__shared__ unsigned int s_ctr[3];      // [0] next 64-path chunk of the tile; [1], [2] fill of this block's ray / shadow output regions
 	const unsigned int lane = threadIdx.x & 63u;
 	// LDS tables in the order of sc.shade_tab: lights | mats | mat_type (padded to 16 B) | prims | meta | frames
-	const int n_tab = 2 * sc.n_lights + 4 * sc.n_mats + (sc.n_mats + 3) / 4, n_tab_all = n_tab + (kPrims ? 8 * sc.n_prims : 0);
+	const int n_tab_l = kPick ? 0 : 2 * sc.n_lights;              // (kPick: no light records in LDS, and none in the shade_tab the upload made)
+	const int n_tab = n_tab_l + 4 * sc.n_mats + (sc.n_mats + 3) / 4, n_tab_all = n_tab + (kPrims ? 8 * sc.n_prims : 0);
 	float4* s_lights = s_dyn;
-	float4* s_mats = s_lights + 2 * sc.n_lights;
+	float4* s_mats = s_lights + n_tab_l;
 	int* s_mtype = (int*)(s_mats + 4 * sc.n_mats);
 	float4* s_prims = s_dyn + n_tab;
 	int4* s_meta = (int4*)(s_prims + 4 * sc.n_prims);
@@ -264,7 +269,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 	if (n == 0) { if (threadIdx.x == 0) { q.blk_q[nxt][b] = 0; q.blk_sh[b] = 0; } return; }
 	if (threadIdx.x == 0) { s_ctr[0] = 0; s_ctr[1] = 0; s_ctr[2] = 0; }
 	__syncthreads();
-	const float4* lights = kTab ? (const float4*)s_lights : sc.lights;
+	const float4* lights = (kTab && !kPick) ? (const float4*)s_lights : sc.lights;
 	const float4* mats = kTab ? (const float4*)s_mats : sc.mats;
 	const int* mat_type = kTab ? (const int*)s_mtype : sc.mat_type;
 	const float4* prims = kPrims ? (const float4*)s_prims : sc.prims;
@@ -420,7 +425,16 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 			else if (bounce == 0 || spec)                                             // integrator.cc:334-336, light.h:300-303
 			{
 				// L += beta * Le for each infinite light in order; folded on the host only when there is at most one
-				for (int li = 0; li < sc.n_lights; li++)
+				if (kPick)
+				{
+					for (int e = 0; e < pv.n_env; e++)
+					{
+						float4 L = q.lacc[slot];
+						V3 a = mk(L.x, L.y, L.z) + cmul(beta, xyz(pv.env[e]));
+						q.lacc[slot] = make_float4(a.x, a.y, a.z, 0.f);
+					}
+				}
+				else for (int li = 0; li < sc.n_lights; li++)
 				{
 					const float4 l0 = lights[2 * li];
 					if (__float_as_int(l0.w) == JP_LIGHT_ENVIRONMENT && !isblack(xyz(l0)))
@@ -485,9 +499,17 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 			closure_set_wo(c, wo);
 			if (wantNee)
 			{
-				for (int li = 0; li < sc.n_lights; li++)
+				const int nl = kPick ? (sc.n_lights > 0 ? 1 : 0) : sc.n_lights;        // kPick: one iteration, the picked light
+				for (int it = 0; it < nl; it++)
 				{
+					int li = it; float pmf = 1.f;
+					if (kPick)
+					{   // u0, u1 pick the light, then its two draws: four draws a bounce, whatever becomes of the sample
+						const float u0 = rngf(rc, key, dim), u1 = rngf(rc, key, dim + 1); dim += 2;
+						li = light_pick(pv, u0, u1, pmf);
+					}
 					const unsigned int d0 = dim; dim += 2;                              // the two draws are consumed even when the sample is rejected
+					if (kPick && !(pmf > 0.f)) continue;                                // no light of weight > 0 (W == 0): no next-event estimation
 					const float4 lrad = lights[2 * li];
 					if (isblack(xyz(lrad))) continue;                                   // Li would be black (integrator.cc:362): skip the evaluation, keep the draws
 					const float ux = rngf(rc, key, d0), uy = rngf(rc, key, d0 + 1);
@@ -499,7 +521,8 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					// (for an area light Normalize(target - position) is the very expression that produced ls.wi)
 					const V3 sdir = __float_as_int(lrad.w) == JP_LIGHT_AREA ? ls.wi : normalize(ls.pos - p);
 					const float dist = ls.dist >= 0.f ? ls.dist : len(p - ls.pos);
-					const V3 contrib = cmul(cmul(beta, f), ls.Li) * absdot(ls.wi, N) / ls.pdf;   // integrator.cc:369
+					V3 contrib = cmul(cmul(beta, f), ls.Li) * absdot(ls.wi, N) / ls.pdf;   // integrator.cc:369
+					if (kPick) contrib = contrib / pmf;                                 // the one-light estimator: a pmf of 1 changes no bit
 					if (k < rc.n_planes)
 					{
 						if (kStage)
@@ -607,8 +630,8 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt)
 {
-	const TexView tv = {};
-	shade_body<kTab, kPrims, kStage, kSort, false>(sc, q, rc, cur, cnt, tv);
+	const TexView tv = {}; const PickView pv = {};
+	shade_body<kTab, kPrims, kStage, kSort, false, false>(sc, q, rc, cur, cnt, tv, pv);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1160,7 +1183,8 @@ __global__ void __launch_bounds__(JP_BLOCK, 8) k_texel(SceneView sc, Queues q, i
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_tex(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, TexView tv)
 {
-	shade_body<kTab, kPrims, kStage, kSort, true>(sc, q, rc, cur, cnt, tv);
+	const PickView pv = {};
+	shade_body<kTab, kPrims, kStage, kSort, true, false>(sc, q, rc, cur, cnt, tv, pv);
 }
 
 // k_surface (jp_surface): the closest hit of k_trace's walk, then the uv k_texel computes and the colour k_shade_tex puts in the textured
@@ -1204,3 +1228,4 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_upload.h"           // jp_upload_scene: validation, device tables, trees, device-side build
 #include "jp_render.h"           // jp_render*: queues, launch sequence, stream lanes, fused schedule; counters, jp_trace, jp_bsdf
 #include "jp_denoise.h"          // guides and denoising: k_guides, k_atrous and their entry points (additive: nothing above refers to it)
+#include "jp_pick.h"             // light selection: the alias table, k_shade_pick / k_shade_pick_tex, k_light_pick and their entry points (jp_render.h declares its two hooks)

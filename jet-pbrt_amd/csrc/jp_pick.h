@@ -1,0 +1,209 @@
+// jet-pbrt_amd/csrc/jp_pick.h -- light selection (JP_LIGHTS_POWER_ONE; INTEGRATION.md "Light selection", DESIGN.md "Light selection"): the alias table
+// builder, the upload's table step, k_shade_pick / k_shade_pick_tex (shade_body<..., kPick>), the test hook k_light_pick and the entry points
+// jp_set_light_sampling / jp_get_light_info / jp_get_light_table / jp_light_pick / jp_build_light_table.  Included last by jp_kernels.hip: a context that
+// never switches the mode on runs nothing of this file.
+#pragma once
+
+// ---- kernels ----------------------------------------------------------------------------------------------------------------
+// k_shade with ONE next-event light per bounce: the light from the alias table (light_pick, jp_common.h), its records from global memory
+template <bool kTab, bool kPrims, bool kStage, bool kSort>
+__global__ void __launch_bounds__(JP_BLOCK) k_shade_pick(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, PickView pv)
+{
+	const TexView tv = {};
+	shade_body<kTab, kPrims, kStage, kSort, false, true>(sc, q, rc, cur, cnt, tv, pv);
+}
+template <bool kTab, bool kPrims, bool kStage, bool kSort>
+__global__ void __launch_bounds__(JP_BLOCK) k_shade_pick_tex(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, TexView tv, PickView pv)
+{
+	shade_body<kTab, kPrims, kStage, kSort, true, true>(sc, q, rc, cur, cnt, tv, pv);
+}
+// jp_light_pick: the render's selection for n pairs of draws
+__global__ void __launch_bounds__(JP_BLOCK) k_light_pick(PickView pv, int n, const float* __restrict__ u0, const float* __restrict__ u1, int* __restrict__ index, float* __restrict__ pmf)
+{
+	for (int i = blockIdx.x * JP_BLOCK + threadIdx.x; i < n; i += gridDim.x * JP_BLOCK)
+	{
+		float pm = 0.f; int j = -1;
+		if (pv.n > 0) j = light_pick(pv, u0[i], u1[i], pm);
+		index[i] = j; pmf[i] = pm;
+	}
+}
+
+namespace
+{
+template <bool kTab, bool kPrims, bool kStage> ShadePickKernels shade_pick_row(bool sort)
+{
+	ShadePickKernels k = { sort ? k_shade_pick<kTab, kPrims, kStage, true> : k_shade_pick<kTab, kPrims, kStage, false>, sort ? k_shade_pick_tex<kTab, kPrims, kStage, true> : k_shade_pick_tex<kTab, kPrims, kStage, false> };
+	return k;
+}
+ShadePickKernels shade_pick_kernels(const ScenePlan& p)               // the rows of shade_kernels
+{
+	if (p.shade_prims_in_lds) return p.stage_nee ? shade_pick_row<true, true, true>(p.shade_sort) : shade_pick_row<true, true, false>(p.shade_sort);
+	if (p.tables_in_lds) return p.stage_nee ? shade_pick_row<true, false, true>(p.shade_sort) : shade_pick_row<true, false, false>(p.shade_sort);
+	return shade_pick_row<false, false, false>(p.shade_sort);
+}
+
+// Vose's alias method in double.  Bins of weight 0 are paired first, while the bins above average still hold all of their excess, so rounding
+// can never leave one of them to the closing "threshold 1" step: a light of weight 0 is in no bin's reach.  W: the weights summed in index order.
+int build_light_table(int n, const double* w, float* q, int32_t* alias, float* pmf, double* W_out, int* n_sel_out)
+{
+	double W = 0.0; int nsel = 0;
+	for (int i = 0; i < n; i++)
+	{
+		if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: a weight is negative or not finite");
+		W += w[i]; if (w[i] > 0.0) nsel++;
+	}
+	if (W_out) *W_out = std::isfinite(W) ? W : 0.0;
+	if (n_sel_out) *n_sel_out = nsel;
+	if (!std::isfinite(W)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: the weights' sum is not finite");
+	if (!(W > 0.0))
+	{
+		for (int i = 0; i < n; i++) { if (q) q[i] = 0.f; if (alias) alias[i] = i; if (pmf) pmf[i] = 0.f; }
+		return JP_OK;
+	}
+	std::vector<double> p((size_t)n); std::vector<int> small, large, al((size_t)n); std::vector<float> th((size_t)n);
+	small.reserve((size_t)n); large.reserve((size_t)n);
+	for (int i = 0; i < n; i++) { p[i] = w[i] * (double)n / W; al[i] = i; th[i] = 1.f; }
+	for (int i = n - 1; i >= 0; i--) if (w[i] > 0.0 && p[i] < 1.0) small.push_back(i);
+	for (int i = n - 1; i >= 0; i--) if (w[i] == 0.0) small.push_back(i);          // on top of the stack: taken first
+	for (int i = n - 1; i >= 0; i--) if (p[i] >= 1.0) large.push_back(i);
+	while (!small.empty() && !large.empty())
+	{
+		const int s = small.back(); small.pop_back();
+		const int l = large.back();
+		th[s] = (float)p[s]; al[s] = l;
+		p[l] = (p[l] + p[s]) - 1.0;
+		if (p[l] < 1.0) { large.pop_back(); small.push_back(l); }
+	}
+	// what is left has its whole bin (threshold 1): bins above average, and bins that rounding left a hair below it.  A bin of weight 0 left
+	// here would mean every positive weight was used up first, which the order above excludes; refused rather than made selectable.
+	for (int s : small) if (w[s] == 0.0) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: weights too extreme for the table");
+	for (int i = 0; i < n; i++)
+	{
+		if (q) q[i] = th[i];
+		if (alias) alias[i] = al[i];
+		if (pmf) pmf[i] = (float)(w[i] / W);
+	}
+	return JP_OK;
+}
+}
+
+// the upload's table step (jp_upload_scene, mode JP_LIGHTS_POWER_ONE): weights, table, the environment list, the device copies, plan.pv
+static int upload_light_table(JpContext* c, const JpScene* s, const std::vector<float>& area)
+{
+	const int n = s->n_lights;
+	const double kPi = 3.14159265358979323846;
+	std::vector<double> w((size_t)n); std::vector<float4> env;
+	for (int i = 0; i < n; i++)
+	{
+		const float* rad = s->light_radiance + 3 * (size_t)i;
+		const double sum = ((double)rad[0] + (double)rad[1]) + (double)rad[2];
+		const int ty = s->light_type[i];
+		if (ty == JP_LIGHT_AREA) w[i] = (sum * (double)area[i]) * kPi;
+		else if (ty == JP_LIGHT_POINT) w[i] = sum * (4.0 * kPi);
+		else w[i] = (sum * kPi) * ((double)s->world_radius * (double)s->world_radius);          // light.cc:17-33
+		if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene: a light's power is negative or not finite (JP_LIGHTS_POWER_ONE)");
+		if (ty == JP_LIGHT_ENVIRONMENT && !(rad[0] == 0.f && rad[1] == 0.f && rad[2] == 0.f)) env.push_back(make_float4(rad[0], rad[1], rad[2], 0.f));
+	}
+	std::vector<float> q((size_t)std::max(1, n), 0.f), pmf((size_t)std::max(1, n), 0.f); std::vector<int32_t> alias((size_t)std::max(1, n), 0);
+	double W = 0.0; int nsel = 0;
+	if (const int st = build_light_table(n, w.data(), q.data(), alias.data(), pmf.data(), &W, &nsel); st != JP_OK) return st;
+	std::vector<float2> bins((size_t)std::max(1, n), make_float2(0.f, 0.f));
+	for (int i = 0; i < n; i++) { float af; std::memcpy(&af, &alias[i], 4); bins[i] = make_float2(q[i], af); }
+	const int n_env = (int)env.size();
+	if (env.empty()) env.push_back(make_float4(0, 0, 0, 0));         // (never read: n_env is 0)
+	auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
+		hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16)); if (e != hipSuccess) return e;
+		return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
+	};
+	HIP_TRY(up(&c->d_pick_bins, bins.data(), bins.size() * sizeof(float2)));
+	HIP_TRY(up(&c->d_pick_pmf, pmf.data(), pmf.size() * sizeof(float)));
+	HIP_TRY(up(&c->d_pick_env, env.data(), env.size() * sizeof(float4)));
+	PickView& pv = c->plan.pv;
+	pv.bins = (const float2*)c->d_pick_bins; pv.pmf = (const float*)c->d_pick_pmf; pv.env = (const float4*)c->d_pick_env; pv.n = n; pv.n_env = n_env;
+	c->plan.pick = true; c->n_selectable = nsel; c->total_weight = W;
+	return JP_OK;
+}
+
+extern "C" {
+
+int jp_build_light_table(int32_t n, const double* weight, float* q, int32_t* alias, float* pmf)
+{
+	if (n < 0 || (n > 0 && !weight)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: bad count or null weights");
+	return build_light_table(n, weight, q, alias, pmf, nullptr, nullptr);
+}
+
+int jp_set_light_sampling(JpContext* c, const JpLightSampling* ls)
+{
+	if (!c) return fail(JP_ERR_INVALID_ARGUMENT, "jp_set_light_sampling: null context");
+	int mode = JP_LIGHTS_ALL;
+	if (ls)
+	{
+		if (ls->struct_bytes < (int32_t)sizeof(JpLightSampling)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_set_light_sampling: set JpLightSampling.struct_bytes to sizeof(JpLightSampling)");
+		if (ls->mode != JP_LIGHTS_ALL && ls->mode != JP_LIGHTS_POWER_ONE) return fail(JP_ERR_INVALID_ARGUMENT, "jp_set_light_sampling: unknown mode");
+		mode = ls->mode;
+	}
+	c->light_mode = mode;                                              // read by the next jp_upload_scene*
+	return JP_OK;
+}
+
+int jp_get_light_info(JpContext* c, JpLightInfo* out)
+{
+	if (!c || !out) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_light_info: null argument");
+	if (out->struct_bytes < (int32_t)sizeof(int32_t)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_light_info: set JpLightInfo.struct_bytes to sizeof(JpLightInfo)");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_get_light_info: no scene uploaded");
+	JpLightInfo i; std::memset(&i, 0, sizeof(i));
+	i.mode = c->plan.pick ? JP_LIGHTS_POWER_ONE : JP_LIGHTS_ALL; i.n_lights = c->plan.sv.n_lights;
+	i.n_selectable = c->plan.pick ? c->n_selectable : (c->plan.sv.n_lights > 0 ? c->plan.n_planes : 0);
+	i.total_weight = c->plan.pick ? c->total_weight : 0.0; i.picked_last_render = c->last_picked;
+	const size_t n = std::min((size_t)out->struct_bytes, sizeof(i));
+	i.struct_bytes = (int32_t)n;
+	std::memcpy(out, &i, n);
+	return JP_OK;
+}
+
+int jp_get_light_table(JpContext* c, float* q, int32_t* alias, float* pmf)
+{
+	if (!c) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_light_table: null context");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_get_light_table: no scene uploaded");
+	if (!c->plan.pick) return fail(JP_ERR_UNSUPPORTED, "jp_get_light_table: the scene was uploaded with JP_LIGHTS_ALL (no table)");
+	const int n = c->plan.pv.n;
+	if (n == 0) return JP_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	std::vector<float2> bins((size_t)n);
+	HIP_TRY(hipMemcpy(bins.data(), c->d_pick_bins, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
+	for (int i = 0; i < n; i++) { if (q) q[i] = bins[i].x; if (alias) std::memcpy(&alias[i], &bins[i].y, 4); }
+	if (pmf) HIP_TRY(hipMemcpy(pmf, c->d_pick_pmf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+	return JP_OK;
+}
+
+int jp_light_pick(JpContext* c, int32_t n, const float* u0, const float* u1, int32_t* index, float* pmf)
+{
+	if (!c || n < 0 || !u0 || !u1 || !index || !pmf) return fail(JP_ERR_INVALID_ARGUMENT, "jp_light_pick: null argument");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_light_pick: no scene uploaded");
+	if (!c->plan.pick) return fail(JP_ERR_UNSUPPORTED, "jp_light_pick: the scene was uploaded with JP_LIGHTS_ALL (no table)");
+	if (n == 0) return JP_OK;
+	for (int i = 0; i < n; i++) if (!(u0[i] >= 0.f && u0[i] < 1.f) || !(u1[i] >= 0.f && u1[i] < 1.f)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_light_pick: a draw outside [0, 1)");   // (what the samplers deliver; the bin index is not clamped from below)
+	HIP_TRY(hipSetDevice(c->device));
+	float* d_u = nullptr; int* d_i = nullptr; float* d_p = nullptr;
+	int rc = JP_OK;
+	do
+	{
+		if (hipMalloc((void**)&d_u, (size_t)n * 8) != hipSuccess || hipMalloc((void**)&d_i, (size_t)n * 4) != hipSuccess || hipMalloc((void**)&d_p, (size_t)n * 4) != hipSuccess)
+		{ rc = fail(JP_ERR_DEVICE, "jp_light_pick: out of device memory"); break; }
+		hipMemcpyAsync(d_u, u0, (size_t)n * 4, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_u + n, u1, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
+		const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
+		hipLaunchKernelGGL(k_light_pick, dim3(grid), dim3(JP_BLOCK), 0, c->stream, c->plan.pv, n, (const float*)d_u, (const float*)(d_u + n), d_i, d_p);
+		hipError_t e = hipGetLastError();
+		if (e == hipSuccess)
+		{
+			hipMemcpyAsync(index, d_i, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream); hipMemcpyAsync(pmf, d_p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
+			e = hipStreamSynchronize(c->stream);
+		}
+		if (e != hipSuccess) rc = fail(JP_ERR_DEVICE, std::string("jp_light_pick: ") + hipGetErrorString(e));
+	} while (0);
+	hipFree(d_u); hipFree(d_i); hipFree(d_p);
+	return rc;
+}
+
+} // extern "C"

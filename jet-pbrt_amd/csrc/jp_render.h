@@ -115,6 +115,12 @@ ShadeKernels shade_kernels(const ScenePlan& p)
 	return shade_row<false, false, false>(p.shade_sort);
 }
 
+// JP_LIGHTS_POWER_ONE: k_shade_pick and its textured twin, same rows (selector in jp_pick.h, next to the kernels)
+typedef void (*ShadePickKernel)(SceneView, Queues, RenderConst, int, DevCounters*, PickView);
+typedef void (*ShadePickTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView);
+struct ShadePickKernels { ShadePickKernel plain; ShadePickTexKernel tex; };
+ShadePickKernels shade_pick_kernels(const ScenePlan& p);
+
 // the other two integrators' megakernel: one ray per lane, launched like the plain k_extend (plan.lds_bytes, plan.stack_depth)
 typedef void (*OtherKernel)(SceneView, Queues, RenderConst, int, int, DevCounters*);
 OtherKernel other_kernel(const ScenePlan& p) { return p.trav_mode == 5 ? k_other<5> : (p.trav_mode == 2 ? k_other<2> : (p.trav_mode == 1 ? k_other<1> : k_other<0>)); }
@@ -211,6 +217,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		if (c->opt.compact_regions != 0) rc.compact = (c->opt.compact_regions > 0 && npix % JP_BLOCK == 0) ? 1 : 0;
 		const int grid = (int)G;
 		const ExtendLaunch ek = extend_kernel(p); const ShadowLaunch sk = shadow_kernel(p, R); const ShadeKernels hk = shade_kernels(p); const OtherKernel ok = other_kernel(p);
+		const ShadePickKernels pk = p.pick ? shade_pick_kernels(p) : ShadePickKernels{ nullptr, nullptr };
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
@@ -242,8 +249,10 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 					if (tex)
 					{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
 						hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
-						hipLaunchKernelGGL(hk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt, tv);
+						if (p.pick) hipLaunchKernelGGL(pk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt, tv, p.pv);
+						else hipLaunchKernelGGL(hk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt, tv);
 					}
+					else if (p.pick) hipLaunchKernelGGL(pk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt, p.pv);
 					else hipLaunchKernelGGL(hk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt);
 				}
 				HIP_TRY(hipGetLastError());                               // a failed launch (k_extend / k_shade) is reported where it happens, not at the end of the frame
@@ -314,6 +323,7 @@ bool fused_eligible(const JpContext* c, const JpRenderParams* rp)
 	if (!c->plan.tables_in_lds || c->plan.n_planes > 4) return false;          // (its own LDS budget: render_fused shrinks the region until the layout fits)
 	if (c->plan.cert) return false;                                       // the certified walk lives in the per-bounce traversal kernels
 	if (c->plan.textured) return false;                                   // textures: k_texel + k_shade_tex live in the per-bounce launches
+	if (c->plan.pick) return false;                                       // JP_LIGHTS_POWER_ONE: k_shade_pick lives there too
 	if (c->plan.trav_mode == 2) return c->plan.shade_prims_in_lds;
 	return c->plan.trav_mode == 0 || c->plan.trav_mode == 3 || c->plan.trav_mode == 5;
 }
@@ -451,10 +461,12 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0;
+	if (c->plan.pick && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator samples every light (scene uploaded with JP_LIGHTS_POWER_ONE)");
 	if (c->plan.textured && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample textures (scene uploaded by jp_upload_scene_textured)");
 	if (fused_eligible(c, rp)) return render_fused(c, rp, film_dev, sync);
 	c->last_textured = c->plan.textured && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_picked = c->plan.pick && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
 	// Gsamples/s).  JETPBRT_LANES = 1 .. 4 forces a count, JETPBRT_LANE_ROWS the group height.

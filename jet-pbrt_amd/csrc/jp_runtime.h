@@ -54,6 +54,7 @@ struct ScenePlan
 {
 	bool have_scene = false;
 	SceneView sv; TexView tv = {}; bool textured = false;
+	PickView pv = {}; bool pick = false;                                               // JP_LIGHTS_POWER_ONE (jp_pick.h): the alias table; one shadow plane, no light records in k_shade's LDS tables
 	int trav_mode = 0, stack_depth = 1, stack_depth_q4 = 0; bool scene_in_lds = false, shade_prims_in_lds = false; size_t lds_bytes = 0, lds_bytes_shadow = 0;
 	bool cert = false;                                                                 // reference semantics, certified walk (Walker<6>)
 	bool use_q4 = false, q4_shadow = false;                                            // closest-hit (and, as an experiment, shadow) rays walk the 4-wide quantised tree (Walker<4>)
@@ -116,14 +117,21 @@ struct JpContext
 	float* d_dn_stage = nullptr; size_t dn_stage_n = 0;
 	hipEvent_t dn_ev[2] = { nullptr, nullptr }, gd_ev[2] = { nullptr, nullptr }; bool dn_timed = false, gd_timed = false;
 	int last_dn = 0, last_dn_demod = 0, last_guide_spp = 0; float last_dn_sigma[3] = { 0.f, 0.f, 0.f };
+	// light selection (jp_pick.h): the mode the next upload takes (jp_set_light_sampling), the uploaded scene's table (owned by the parent context,
+	// reaches the lanes through `plan.pv`) and what jp_get_light_info reports
+	int light_mode = JP_LIGHTS_ALL; void *d_pick_bins = nullptr, *d_pick_pmf = nullptr, *d_pick_env = nullptr;
+	int n_selectable = 0; double total_weight = 0.0; int last_picked = 0;
 };
+// jp_pick.h (included last) defines the upload's table step
+static int upload_light_table(JpContext* c, const JpScene* s, const std::vector<float>& area);
 
 static void free_scene(JpContext* c)
 {
 	void** ps[] = { &c->d_flat, &c->d_wide, &c->d_q4, &c->d_refbox, &c->d_nodes, &c->d_prims, &c->d_meta, &c->d_mats, &c->d_mat_type, &c->d_lights, &c->d_shade_tab,
-	                &c->d_tex_desc, &c->d_tex_col, &c->d_texels, &c->d_mat_tex, &c->d_prim_uv };
+	                &c->d_tex_desc, &c->d_tex_col, &c->d_texels, &c->d_mat_tex, &c->d_prim_uv, &c->d_pick_bins, &c->d_pick_pmf, &c->d_pick_env };
 	for (void** p : ps) { if (*p) hipFree(*p); *p = nullptr; }
 	c->plan.have_scene = false;
+	c->plan.pv = PickView(); c->plan.pick = false; c->n_selectable = 0; c->total_weight = 0.0;
 	c->plan.tv = TexView(); c->plan.textured = false; c->n_textures = c->n_tex_mats = 0; c->texel_bytes = 0;   // (jp_upload_scene drops the textures of an earlier textured upload)
 	if (c->d_side) hipFree(c->d_side);                             // ... and the side array only textured frames use (callers synchronise first)
 	c->d_side = nullptr; c->side_n = 0;

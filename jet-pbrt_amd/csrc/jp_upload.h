@@ -95,7 +95,9 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	if ((s->n_triangles && (!s->tri_p0 || !s->tri_p1 || !s->tri_p2 || !s->tri_n)) || (s->n_rectangles && (!s->rect_p0 || !s->rect_p1 || !s->rect_p2 || !s->rect_p3 || !s->rect_n))
 	    || (s->n_spheres && (!s->sph_center || !s->sph_radius)) || (s->n_disks && (!s->disk_center || !s->disk_normal || !s->disk_radius)) || (s->n_materials && (!s->mat_type || !s->mat_params)) || (s->n_lights && (!s->light_type || !s->light_radiance || !s->light_prim)))
 		return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene: null array for a non-zero count");
-	if (s->n_lights > 255) return fail(JP_ERR_UNSUPPORTED, "jp_upload_scene: more than 255 lights are not supported by the shadow-entry packing");
+	const bool pick = c->light_mode == JP_LIGHTS_POWER_ONE;     // one light per bounce from the alias table (jp_pick.h): one shadow plane whatever the light count
+	if (!pick && s->n_lights > 255) return fail(JP_ERR_UNSUPPORTED, "jp_upload_scene: more than 255 lights are not supported by the shadow-entry packing");
+	if (pick && s->n_lights > (1 << 24)) return fail(JP_ERR_UNSUPPORTED, "jp_upload_scene: more than 2^24 lights (JP_LIGHTS_POWER_ONE)");
 	bool hasNull = false;
 	for (int i = 0; i < s->n_primitives; i++)
 	{
@@ -588,6 +590,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	for (int i = 0; i < s->n_materials; i++) { std::memcpy(&mats[4 * i], s->mat_params + (size_t)i * JP_MAT_PARAM_STRIDE, 16 * sizeof(float)); mtype[i] = s->mat_type[i]; }
 	// lights: (radiance, type) (device prim, 1/Area(), -, -); areas with the reference's expressions (shape.h:351, 457, 546)
 	std::vector<float4> lights(2 * std::max(1, s->n_lights)); int planes = 0, nenv = 0; float envsum[3] = { 0, 0, 0 };
+	std::vector<float> light_area(pick ? (size_t)s->n_lights : 0, 0.f);       // FShape::Area() per area light: the weights of the alias table
 	for (int i = 0; i < s->n_lights; i++)
 	{
 		int ty = s->light_type[i]; float tf; std::memcpy(&tf, &ty, 4);
@@ -605,6 +608,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 			else if (t == JP_SHAPE_DISK) { const float kPi = (float)3.14159265358979323846; area = kPi * s->disk_radius[k] * s->disk_radius[k]; }   // shape.h:253
 			else { const float kPi = (float)3.14159265358979323846; float r2 = s->sph_radius[k] * s->sph_radius[k]; area = 4 * kPi * r2; }
 			inv_area = 1 / area;
+			if (pick) light_area[i] = area;
 		}
 		else if (ty == JP_LIGHT_ENVIRONMENT) { nenv++; envsum[0] += rad[0]; envsum[1] += rad[1]; envsum[2] += rad[2]; }
 		float df; std::memcpy(&df, &dp, 4);
@@ -628,7 +632,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	HIP_TRY(up(&c->d_lights, lights.data(), lights.size() * sizeof(float4)));
 	{   // k_shade's LDS tables as one array (SceneView::shade_tab); the primitive part only when the host has the records
 		std::vector<float4> tabv;
-		tabv.insert(tabv.end(), lights.begin(), lights.begin() + 2 * (size_t)s->n_lights);          // exactly the counts the kernel indexes with
+		if (!pick) tabv.insert(tabv.end(), lights.begin(), lights.begin() + 2 * (size_t)s->n_lights);          // exactly the counts the kernel indexes with (the pick kernels: no light records)
 		tabv.insert(tabv.end(), mats.begin(), mats.begin() + 4 * (size_t)s->n_materials);
 		const size_t at = tabv.size(); tabv.resize(at + ((size_t)s->n_materials + 3) / 4, make_float4(0, 0, 0, 0));
 		if (s->n_materials > 0) std::memcpy(&tabv[at], mtype.data(), (size_t)s->n_materials * sizeof(int));
@@ -686,7 +690,8 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	p.lds_bytes = p.trav_mode == 2 ? prim_bytes : (p.trav_mode == 1 ? stack_bytes + scene_bytes : stack_bytes);
 	p.lds_bytes_shadow = p.trav_mode == 3 ? (size_t)2 * (wide_height + 2) * JP_BLOCK * sizeof(int) : p.lds_bytes;
 	{
-		size_t tab = ((size_t)2 * s->n_lights + (size_t)4 * s->n_materials) * sizeof(float4) + (size_t)s->n_materials * sizeof(int) + 16;
+		if (pick) planes = std::min(planes, 1);
+		size_t tab = ((pick ? (size_t)0 : (size_t)2 * s->n_lights) + (size_t)4 * s->n_materials) * sizeof(float4) + (size_t)s->n_materials * sizeof(int) + 16;
 		p.tables_in_lds = tab <= 16 * 1024;
 		// k_shade's static LDS (tile index, keys, counters of the material sort) + tables + staging must stay within 64 KB a workgroup;
 		// beyond 24 KB of tables the kernel's three workgroups per CU would not fit the CU's LDS either
@@ -717,6 +722,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 		p.shade_sort = opt_flag(op.shade_sort, nk > 1);
 	}
 	p.has_null_material = hasNull; c->cert_fell_back = false;
+	if (pick) { const int st = upload_light_table(c, s, light_area); if (st != JP_OK) { free_scene(c); return st; } }
 	p.have_scene = true;
 	return JP_OK;
 }

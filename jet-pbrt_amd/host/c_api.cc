@@ -94,6 +94,7 @@ void jp_host_scene_disk(void* h, const float* pos, const float* normal, float ra
 
 void jp_host_scene_set_reference_tree(void* h, int on) { ((HostScene*)h)->scene->referenceTree = on != 0; ((HostScene*)h)->scene->certifiedWalk = on == 2; }   // 1: verbatim walk, 2: certified walk
 void jp_host_scene_set_device_build(void* h, int on) { ((HostScene*)h)->scene->deviceBuild = on != 0; ((HostScene*)h)->scene->hostBuild = on == 0; }   // explicit either way
+void jp_host_scene_set_light_sampling(void* h, int mode) { ((HostScene*)h)->scene->SetLightSampling(mode); }   // FScene::SetLightSampling (JP_LIGHTS_*)
 void jp_host_scene_preprocess(void* h) { HostScene* hs = (HostScene*)h; hs->scene->Preprocess(); hs->flattened = false; }
 int  jp_host_num_primitives(void* h) { return (int)((HostScene*)h)->scene->primitives.size(); }
 int  jp_host_num_lights(void* h) { return ((HostScene*)h)->scene->LightNum(); }

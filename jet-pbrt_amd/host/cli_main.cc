@@ -1,6 +1,7 @@
 // jet-pbrt_amd/host/cli_main.cc -- the reference's command line (main.cc:113-163) on the GPU integrator:
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
-//             [--denoise] [--guide-spp N] [--aov PREFIX]
+//             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power]
+// --light-sampling power: one light per bounce, picked by power (FScene::SetLightSampling(JP_LIGHTS_POWER_ONE)); all (default): every light at every bounce.
 // --denoise: the edge-avoiding filter on the rendered film (FFilm::RequestDenoise); --guide-spp: camera samples per pixel of its guides (default 8,
 // 1 .. 1024); --aov: the guides as images PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5), PREFIX_depth (t / max t) in the chosen format.
 // sceneid 0 = Cornell box, 1 = bunny scene; spp defaults to 50, the film to 1024 x 1024, the output to
@@ -74,9 +75,9 @@ int main(int argc, char* argv[])
 {
 	int width = 1024, height = 1024, samples_per_pixel = 50;     // main.cc:115,119
 	std::string assets = "scene", out, format = "bmp", integratorName = "path";
-	bool denoise = false; int guideSpp = 8; std::string aov;
+	bool denoise = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
-	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX]\n");
+	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -90,6 +91,12 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--denoise")) denoise = true;
 		else if (!strcmp(argv[i], "--guide-spp") && i + 1 < argc) { guideSpp = atoi(argv[++i]); if (guideSpp < 1 || guideSpp > 1024) { fprintf(stderr, "--guide-spp must be 1 .. 1024\n"); return 5; } }
 		else if (!strcmp(argv[i], "--aov") && i + 1 < argc) aov = argv[++i];
+		else if (!strcmp(argv[i], "--light-sampling") && i + 1 < argc)
+		{
+			const char* m = argv[++i];
+			if (!strcmp(m, "power")) lightSampling = JP_LIGHTS_POWER_ONE; else if (!strcmp(m, "all")) lightSampling = JP_LIGHTS_ALL;
+			else { fprintf(stderr, "--light-sampling must be all or power\n"); return 5; }
+		}
 		else pos.push_back(argv[i]);
 	}
 	if (pos.empty()) return 0;                                    // main.cc:122-125
@@ -105,6 +112,7 @@ int main(int argc, char* argv[])
 	default: return 0;
 	}
 	fprintf(stderr, "current scene: %s\n", scene->NameStr());
+	scene->SetLightSampling(lightSampling);
 	if (scene->primitives.empty()) { fprintf(stderr, "no geometry loaded from %s\n", assets.c_str()); return 2; }
 	std::shared_ptr<FSampler> sampler = std::make_shared<FRandomSampler>(samples_per_pixel);
 	// main.cc:154 constructs FPathIntegratorIteration(5); the commented-out alternatives of main.cc:150-153 are selectable here

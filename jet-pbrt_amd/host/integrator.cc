@@ -28,6 +28,7 @@ struct HipApi
 	int (*set_options)(JpContext*, const JpOptions*) = nullptr;
 	int (*upload_scene_textured)(JpContext*, const JpScene*, const JpTextures*) = nullptr;   // (looked up, needed by textured scenes only)
 	int (*render_denoised)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*) = nullptr;   // (looked up, needed by FFilm::RequestGuides / RequestDenoise only)
+	int (*set_light_sampling)(JpContext*, const JpLightSampling*) = nullptr;                 // (looked up, needed by FScene::SetLightSampling only)
 	std::string error;
 };
 
@@ -55,6 +56,7 @@ HipApi& Api()
 		api.set_options = (int (*)(JpContext*, const JpOptions*))dlsym(api.lib, "jp_set_options");
 		api.upload_scene_textured = (int (*)(JpContext*, const JpScene*, const JpTextures*))dlsym(api.lib, "jp_upload_scene_textured");
 		api.render_denoised = (decltype(api.render_denoised))dlsym(api.lib, "jp_render_denoised");
+		api.set_light_sampling = (decltype(api.set_light_sampling))dlsym(api.lib, "jp_set_light_sampling");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
 		else if (api.abi_version() != JP_ABI_VERSION)            // a stale build would be handed structs of another size (JpCounters, JpBuildInfo, JpOptions)
@@ -114,8 +116,16 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 	if (!scene || !sampler || !film) { fprintf(stderr, "FGpuPathIntegrator::Render: null argument\n"); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
 	if (!ctx) { lastStatus = api.create_context(deviceId, &ctx); if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); ctx = nullptr; return; } }
 	if (optionsDirty) { lastStatus = api.set_options(ctx, &options); if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; } optionsDirty = false; }
-	if (uploaded != scene)
+	if (uploaded != scene || uploadedLights != scene->lightSampling)
 	{
+		if (ctxLights != scene->lightSampling)
+		{   // FScene::SetLightSampling: the mode goes to the context before the upload it is to affect; a scene that never set one makes no such call
+			if (!api.set_light_sampling) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_light_sampling\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			JpLightSampling ls; ls.struct_bytes = (int32_t)sizeof(ls); ls.mode = scene->lightSampling;
+			lastStatus = api.set_light_sampling(ctx, &ls);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxLights = scene->lightSampling; uploaded = nullptr;
+		}
 		FlatScene flat; std::string err;
 		if (!FlattenScene(*scene, flat, &err)) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", err.c_str()); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
 		// a scene with a textured material goes through jp_upload_scene_textured; any other makes exactly the calls it always made
@@ -135,7 +145,7 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			lastStatus = upload();
 		}
 		if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
-		uploaded = scene;
+		uploaded = scene; uploadedLights = scene->lightSampling;
 	}
 	JpRenderParams rp; std::memset(&rp, 0, sizeof(rp));
 	rp.width = film->Width(); rp.height = film->Height();

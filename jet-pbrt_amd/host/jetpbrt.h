@@ -416,6 +416,11 @@ public:
 	// triangle's plane is decided in the reference by the signs of rounding errors wherever that triangle is; camera rays are covered by flags on the
 	// leaves edge-on to the camera, secondary rays only by measurement (the 280k-triangle frame is bit-identical).  Default from env JETPBRT_REFERENCE_TREE=2.
 	bool certifiedWalk = false;
+	// Light selection of the path integrator (include/jetpbrt_amd.h, INTEGRATION.md "Light selection"): JP_LIGHTS_ALL samples every light at every
+	// bounce, the reference's estimator (at most 255 lights); JP_LIGHTS_POWER_ONE picks one light per bounce with probability proportional to its
+	// power -- what a scene lit by CreateAreaLights(mesh) needs.  Read by FGpuPathIntegrator::Render at its next upload of this scene.
+	int lightSampling = JP_LIGHTS_ALL;
+	void SetLightSampling(int mode) { lightSampling = mode; }
 };
 
 // binned-SAH BVH over primitive bounds -> the flat node arrays of JpScene (own topology)
@@ -476,6 +481,7 @@ protected:
 	int shardIndex = 0, shardCount = 1, bandRows = 20;
 	mutable JpContext* ctx = nullptr;
 	mutable const FScene* uploaded = nullptr;
+	mutable int uploadedLights = JP_LIGHTS_ALL, ctxLights = JP_LIGHTS_ALL;   // FScene::lightSampling of the uploaded scene; the mode the context was last told
 	mutable int lastStatus = 0;
 	mutable JpCounters counters;
 protected:

@@ -276,6 +276,12 @@ class HostBackend:
         by ray except for secondary rays within fp32 noise of a triangle's plane (about one in 10^9; a generous cull slack reaches those seen: the 280k-triangle frames measured are bit-identical)."""
         self._f("scene_set_reference_tree")(self.h, (2 if certified else 1) if on else 0)
 
+    def set_light_sampling(self, mode="power"):
+        """FScene::SetLightSampling: "power" = one light per bounce picked by power (JP_LIGHTS_POWER_ONE, emissive meshes of any size),
+        None / "all" = every light at every bounce (host backend only; takes effect with the integrator's next upload)"""
+        from . import LIGHT_SAMPLING_MODES
+        self._f("scene_set_light_sampling")(self.h, LIGHT_SAMPLING_MODES[mode])
+
     def set_device_build(self, on=True):
         """FScene::deviceBuild: leave the hierarchy to jp_upload_scene's device LBVH pass (host backend only)."""
         self._f("scene_set_device_build")(self.h, 1 if on else 0)
@@ -380,6 +386,74 @@ def build_textured_cornell(be, width, height, back=None, left=None, right=None, 
         be.sphere((420, 90, -120), 50.0, pm, None)
     be.preprocess()
     return be
+
+
+# ---- mesh lights (INTEGRATION.md "Light selection") ----------------------------------------------------------------
+LAMP_RECT = (213.0, 343.0, 227.0, 332.0, 548.7)      # the Cornell box's ceiling light: x0, x1, z0, z1 (OBJ handedness), y
+
+
+def lamp_grid_asset(nx, nz, rect=LAMP_RECT, warp=0.0, name=None):
+    """A rectangle of the ceiling plane as nx x nz quads (2 nx nz triangles, wound like cornellbox/light.obj: facing down when loaded with
+    flip_normal and flip_handedness).  warp 0: a regular grid (equal triangles, the tessellated rectangle light); warp > 0: the grid lines are
+    spaced unevenly (triangle areas differ by up to (1 + warp)^2 : (1 - warp)^2 and more)."""
+    x0, x1, z0, z1, y = rect
+    def cuts(a, b, n, phase):
+        t = np.arange(n + 1, dtype=np.float64) / n
+        t = t + warp * np.sin(np.pi * t) * np.cos(2.5 * np.pi * t + phase) / 2.0 if warp else t
+        t = np.sort(np.clip(t, 0.0, 1.0)); t[0], t[-1] = 0.0, 1.0
+        return (a + (b - a) * t).astype(np.float32)
+    xs, zs = cuts(x0, x1, nx, 0.3), cuts(z0, z1, nz, 1.1)
+    quads = [[(xs[i + 1], y, zs[j]), (xs[i + 1], y, zs[j + 1]), (xs[i], y, zs[j + 1]), (xs[i], y, zs[j])] for i in range(nx) for j in range(nz)]
+    p = os.path.join(asset_dir(), name or "lamp_%dx%d_%g_%s.obj" % (nx, nz, warp, hashlib.sha1(repr(rect).encode()).hexdigest()[:8]))
+    if not os.path.exists(p):
+        quads_to_obj(p, quads)
+    return p
+
+
+def build_lamp_box(be, width, height, lamp, floor=None, full_materials=False):
+    """The Cornell box WITHOUT its light and without an environment light: `lamp(be, mats)` creates every light of the scene, in its own order
+    (mats: white / light material indices).  floor: as build_textured_cornell takes it (a texture on the floor)."""
+    lookfrom = np.array([278, 273, 960], np.float32); lookat = np.array([278, 273, 0], np.float32)
+    be.camera(lookfrom, _normalize(lookat - lookfrom), (0, 1, 0), 60.0, width, height)
+    red = be.mat_matte((0.63, 0.065, 0.05))
+    green = be.mat_matte((0.14, 0.45, 0.091))
+    white = be.mat_matte((0.725, 0.71, 0.68))
+    ground = be.mat_matte(tex=floor(be)) if callable(floor) else be.mat_matte((0.725, 0.71, 0.68) if floor is None else floor)
+    golden = be.mat_metal((0.18, 0.15, 0.81), (0.11, 0.11, 0.11), 0.2, 0.2, False)
+    mat_light = be.mat_matte((0.65, 0.65, 0.65))
+    A = cornell_assets(); T = cornell_textured_assets()
+    lamp(be, dict(white=white, light=mat_light))
+    be.mesh(T["floor_only"], True, True, mat=ground)
+    be.mesh(T["ceiling"], True, True, mat=white)
+    be.mesh(T["back"], True, True, mat=white)
+    be.mesh(A["shortbox"], True, True, mat=white)
+    be.mesh(A["tallbox"], True, True, mat=(golden if full_materials else white))
+    be.mesh(A["left"], True, True, mat=red)
+    be.mesh(A["right"], True, True, mat=green)
+    be.preprocess()
+    return be
+
+
+def lamp_rect(radiance=None, rect=LAMP_RECT):
+    """the ceiling light as ONE rectangle light (facing down)"""
+    def lamp(be, m):
+        x0, x1, z0, z1, y = rect
+        be.rect(AXIS_XZ, x0, x1, -z1, -z0, y, True, m["light"], light_radiance() if radiance is None else radiance)
+    return lamp
+
+
+def lamp_mesh(nx, nz, radiance=None, rect=LAMP_RECT, warp=0.0):
+    """the ceiling light as an emissive mesh of 2 nx nz triangles, every one an FAreaLight (FScene::CreateAreaLights)"""
+    def lamp(be, m):
+        be.mesh(lamp_grid_asset(nx, nz, rect, warp), True, True, mat=m["light"], radiance=light_radiance() if radiance is None else radiance)
+    return lamp
+
+
+def lamp_66(be, m):
+    """66 lights: two rectangle lights of different radiance and size, then a 64-triangle emissive mesh (8 x 4 quads) of unequal triangles"""
+    be.rect(AXIS_XZ, 60.0, 150.0, -180.0, -110.0, 548.7, True, m["light"], (30.0, 24.0, 18.0))
+    be.rect(AXIS_XZ, 420.0, 480.0, -460.0, -400.0, 548.7, True, m["light"], (8.0, 12.0, 20.0))
+    lamp_mesh(8, 4, (12.0, 11.0, 9.0), (200.0, 360.0, 240.0, 320.0, 548.7), warp=0.6)(be, m)
 
 
 def build_bunny(be, width, height, n_lon=187, n_lat=188, instances=4, obj_path=None):
