@@ -258,6 +258,9 @@ int  jp_gamma_thresholds(float* out255);
  * byte-identical for EVERY input; the table's binary search assumes the host's powf-based curve never steps down) */
 long long jp_gamma_sweep(int n_threads);
 int  jp_synchronize(JpContext* ctx);
+/* bytes of device memory the library holds in this process right now, over all contexts (every allocation goes through one owner type,
+ * which counts it): a destroyed context gives back exactly what it took, which is what tests/test_gpu_memory.py asserts.  No GPU call. */
+long long jp_device_bytes_in_use(void);
 
 /* per-kernel-class event timing (adds two events per launch); off by default */
 int  jp_set_profiling(JpContext* ctx, int enabled);

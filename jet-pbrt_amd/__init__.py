@@ -292,8 +292,14 @@ def hip_lib():
         L.jp_get_light_table.argtypes = [C.c_void_p] * 4
         L.jp_light_pick.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4
         L.jp_build_light_table.argtypes = [C.c_int32] + [C.c_void_p] * 4
+        L.jp_device_bytes_in_use.restype = C.c_longlong
         _hip = L
     return _hip
+
+
+def device_bytes_in_use():
+    """Bytes of device memory the library holds in this process, over all contexts (jp_device_bytes_in_use)."""
+    return int(hip_lib().jp_device_bytes_in_use())
 
 
 class Context:

@@ -228,28 +228,22 @@ int denoise_launch(JpContext* c, const DenoiseSetup& s, const float* film, const
 	HIP_TRY(hipSetDevice(c->device));
 	if (const int e = ensure_events(c); e != JP_OK) return e;
 	const size_t npix = (size_t)s.width * s.height;
-	if (c->dn_n < npix)
-	{   // the records: two colour buffers and the normals, 48 bytes per pixel
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		for (float4** p : { &c->d_dn_cz[0], &c->d_dn_cz[1], &c->d_dn_nr }) { if (*p) hipFree(*p); *p = nullptr; }
-		c->dn_n = 0;
-		if (hipMalloc((void**)&c->d_dn_cz[0], npix * 16) != hipSuccess || hipMalloc((void**)&c->d_dn_cz[1], npix * 16) != hipSuccess || hipMalloc((void**)&c->d_dn_nr, npix * 16) != hipSuccess)
-			return fail(JP_ERR_DEVICE, "jp_denoise: out of device memory");
-		c->dn_n = npix;
-	}
+	for (DevBuf* b : { &c->dn_cz[0], &c->dn_cz[1], &c->dn_nr })      // the records: two colour buffers and the normals, 48 bytes per pixel
+		if (const int e = reserve_idle(c, *b, npix * 16); e != JP_OK) return e;
+	float4* const cz[2] = { c->dn_cz[0].get<float4>(), c->dn_cz[1].get<float4>() }; float4* const nr = c->dn_nr.get<float4>();
 	const float kn = 1.0f / (s.sn * s.sn), kz = 1.0f / (s.sz * s.sz), sc2 = s.sc * s.sc;
 	const float* alb = s.demod ? albedo : nullptr;
 	HIP_TRY(hipEventRecord(c->dn_ev[0], c->stream));
 	hipLaunchKernelGGL(k_atrous_pack, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream,
-	                   (int)npix, film, alb, normal, dist, c->d_dn_cz[0], c->d_dn_nr);
+	                   (int)npix, film, alb, normal, dist, cz[0], nr);
 	const dim3 grid((s.width + JP_ATROUS_TW - 1) / JP_ATROUS_TW, (s.height + JP_ATROUS_TH - 1) / JP_ATROUS_TH);
 	float pow4 = 1.0f;
 	for (int i = 0; i < s.iterations; i++, pow4 *= 4.0f)
 	{
 		const AtrousConst ac = { s.width, s.height, 1 << i, pow4 / sc2, kn, kz };
-		const float4* src = c->d_dn_cz[i & 1]; float4* dst = c->d_dn_cz[(i & 1) ^ 1];
-		if (i + 1 < s.iterations) hipLaunchKernelGGL(k_atrous<false>, grid, dim3(JP_BLOCK), 0, c->stream, ac, src, (const float4*)c->d_dn_nr, dst, (const float*)nullptr, (float*)nullptr);
-		else hipLaunchKernelGGL(k_atrous<true>, grid, dim3(JP_BLOCK), 0, c->stream, ac, src, (const float4*)c->d_dn_nr, (float4*)nullptr, alb, out);
+		const float4* src = cz[i & 1]; float4* dst = cz[(i & 1) ^ 1];
+		if (i + 1 < s.iterations) hipLaunchKernelGGL(k_atrous<false>, grid, dim3(JP_BLOCK), 0, c->stream, ac, src, (const float4*)nr, dst, (const float*)nullptr, (float*)nullptr);
+		else hipLaunchKernelGGL(k_atrous<true>, grid, dim3(JP_BLOCK), 0, c->stream, ac, src, (const float4*)nr, (float4*)nullptr, alb, out);
 	}
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->dn_ev[1], c->stream));
@@ -258,16 +252,7 @@ int denoise_launch(JpContext* c, const DenoiseSetup& s, const float* film, const
 }
 
 // staging area of the host variants (floats)
-int ensure_stage(JpContext* c, size_t n)
-{
-	if (c->dn_stage_n >= n) return JP_OK;
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->d_dn_stage) hipFree(c->d_dn_stage);
-	c->d_dn_stage = nullptr; c->dn_stage_n = 0;
-	HIP_TRY(hipMalloc((void**)&c->d_dn_stage, n * sizeof(float)));
-	c->dn_stage_n = n;
-	return JP_OK;
-}
+int ensure_stage(JpContext* c, size_t n) { return reserve_idle(c, c->dn_stage, n * sizeof(float)); }
 }
 
 extern "C" {
@@ -289,7 +274,7 @@ int jp_render_guides(JpContext* c, const JpRenderParams* rp, int32_t guide_spp, 
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t n = (size_t)gc.width * gc.height;
 	if (const int e = ensure_stage(c, 7 * n); e != JP_OK) return e;
-	float *da = c->d_dn_stage, *dn = da + 3 * n, *dz = da + 6 * n;
+	float *da = c->dn_stage.get<float>(), *dn = da + 3 * n, *dz = da + 6 * n;
 	if (const int e = guides_launch(c, gc, albedo ? da : nullptr, normal ? dn : nullptr, depth ? dz : nullptr); e != JP_OK) return e;
 	if (albedo) HIP_TRY(hipMemcpyAsync(albedo, da, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	if (normal) HIP_TRY(hipMemcpyAsync(normal, dn, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -314,7 +299,7 @@ int jp_denoise(JpContext* c, const JpDenoiseParams* dp, const float* film, const
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t n = (size_t)s.width * s.height;
 	if (const int e = ensure_stage(c, 13 * n); e != JP_OK) return e;
-	float *df = c->d_dn_stage, *da = df + 3 * n, *dn = df + 6 * n, *dz = df + 9 * n, *dout = df + 10 * n;
+	float *df = c->dn_stage.get<float>(), *da = df + 3 * n, *dn = df + 6 * n, *dz = df + 9 * n, *dout = df + 10 * n;
 	HIP_TRY(hipMemcpyAsync(df, film, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
 	if (s.demod) HIP_TRY(hipMemcpyAsync(da, albedo, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipMemcpyAsync(dn, normal, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -334,24 +319,24 @@ int jp_render_denoised(JpContext* c, const JpRenderParams* rp, int32_t guide_spp
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t n = (size_t)gc.width * gc.height;
 	if (const int e = ensure_stage(c, 10 * n); e != JP_OK) return e;
-	float *da = c->d_dn_stage, *dn = da + 3 * n, *dz = da + 6 * n, *dout = da + 7 * n;
-	if (c->film_n < 3 * n) { if (c->d_film) hipFree(c->d_film); c->d_film = nullptr; c->film_n = 0; HIP_TRY(hipMalloc((void**)&c->d_film, 3 * n * sizeof(float))); c->film_n = 3 * n; }
+	float *da = c->dn_stage.get<float>(), *dn = da + 3 * n, *dz = da + 6 * n, *dout = da + 7 * n;
+	if (const int e = ensure_film(c, 3 * n); e != JP_OK) return e;
+	float* const film = c->film.get<float>();
 	DenoiseSetup s;
 	if (dp)
 	{
 		JpDenoiseParams d = *dp; d.width = gc.width; d.height = gc.height;
-		if (const int e = denoise_check(c, &d, c->d_film, da, dn, dz, dout, s); e != JP_OK) return e;
+		if (const int e = denoise_check(c, &d, film, da, dn, dz, dout, s); e != JP_OK) return e;
 	}
-	if (const int e = render_impl(c, rp, c->d_film, false); e != JP_OK) return e;
+	if (const int e = render_impl(c, rp, film, false); e != JP_OK) return e;
 	if (const int e = guides_launch(c, gc, da, dn, dz); e != JP_OK) return e;
-	const float* result = c->d_film;
-	if (dp) { if (const int e = denoise_launch(c, s, c->d_film, da, dn, dz, dout); e != JP_OK) return e; result = dout; }
+	const float* result = film;
+	if (dp) { if (const int e = denoise_launch(c, s, film, da, dn, dz, dout); e != JP_OK) return e; result = dout; }
 	if (rgb8_host)
 	{
-		if (c->rgb8_n < 3 * n) { if (c->d_rgb8) hipFree(c->d_rgb8); c->d_rgb8 = nullptr; c->rgb8_n = 0; HIP_TRY(hipMalloc((void**)&c->d_rgb8, 3 * n)); c->rgb8_n = 3 * n; }
-		if (!c->d_gamma) { HIP_TRY(hipMalloc((void**)&c->d_gamma, 255 * sizeof(float))); HIP_TRY(hipMemcpy(c->d_gamma, host_gamma_thresholds(), 255 * sizeof(float), hipMemcpyHostToDevice)); }
-		hipLaunchKernelGGL(k_tonemap8, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (3 * n + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, result, c->d_rgb8, (const float*)c->d_gamma, 3 * n);
-		HIP_TRY(hipMemcpyAsync(rgb8_host, c->d_rgb8, 3 * n, hipMemcpyDeviceToHost, c->stream));
+		if (const int e = ensure_rgb8(c, 3 * n); e != JP_OK) return e;
+		tonemap8(c, result, 3 * n);
+		HIP_TRY(hipMemcpyAsync(rgb8_host, c->rgb8.get<void>(), 3 * n, hipMemcpyDeviceToHost, c->stream));
 	}
 	if (film_host) HIP_TRY(hipMemcpyAsync(film_host, result, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	if (albedo) HIP_TRY(hipMemcpyAsync(albedo, da, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));

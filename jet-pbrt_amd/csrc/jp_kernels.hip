@@ -31,6 +31,7 @@
 #include <cmath>
 #include <mutex>
 #include <thread>
+#include "jp_devmem.h"           // DevBuf / PinnedBuf: who owns device memory
 #include "jp_lbvh.h"
 #include "jp_ploc.h"
 

@@ -228,7 +228,7 @@ __global__ void k_lbvh_single(const float4* __restrict__ lo, const float4* __res
 	nodes[2] = make_float4(1e30f, -1e30f, -1e30f, -1e30f); nodes[3] = make_float4(__int_as_float(ref), __int_as_float(ref), 0, 0);
 }
 
-struct LbvhResult { void* d_nodes = nullptr; void* d_prims = nullptr; void* d_meta = nullptr; int n_nodes = 0, height = 0; float build_ms = 0.f; };
+struct LbvhResult { DevBuf nodes, prims, meta; int n_nodes = 0, height = 0; float build_ms = 0.f; };   // the caller moves the tables into its context
 
 // ---- LSD radix sort of (64-bit code, primitive index) pairs: 8 passes of 8 bits, stable --------------------------------------
 // (round 1 called hipcub here; the sort is off the hot path -- 280k pairs once per scene upload -- but it is the step that
@@ -326,66 +326,62 @@ static void lbvh_sort(hipStream_t stream, unsigned long long* keys, unsigned lon
 	hipMemcpyAsync(vals2, vals, (size_t)n * 4, hipMemcpyDeviceToDevice, stream);
 }
 
-// prims0 / meta0: device arrays in creation order (4 x float4 and one int4 per primitive).  On success the caller
-// owns r.d_nodes / d_prims / d_meta and `order` holds, for each device (sorted) position, the creation-order index.
+// prims0 / meta0: device arrays in creation order (4 x float4 and one int4 per primitive).  On success r holds the tables and `order`, for
+// each device (sorted) position, the creation-order index; on failure r is untouched.  The temporaries are locals: every return frees them.
 static hipError_t lbvh_build(hipStream_t stream, const float4* prims0, const int4* meta0, int n, int maxLeaf, LbvhResult& r, std::vector<int>& order)
 {
 	hipError_t e = hipSuccess;
-	std::vector<void*> tmp;
-	auto dalloc = [&](void** p, size_t bytes, bool keep) -> bool { e = hipMalloc(p, std::max<size_t>(bytes, 16)); if (e != hipSuccess) return false; if (!keep) tmp.push_back(*p); return true; };
-	auto cleanup = [&]() { for (void* p : tmp) hipFree(p); };
-	auto bail = [&]() { cleanup(); if (r.d_nodes) hipFree(r.d_nodes); if (r.d_prims) hipFree(r.d_prims); if (r.d_meta) hipFree(r.d_meta); r = LbvhResult(); return e; };
-	float4 *lo0, *hi0, *lo, *hi, *nlo, *nhi; unsigned long long *keys, *keys2; int *vals, *vals2, *childL, *childR, *parentI, *parentL, *first, *last, *height;
-	unsigned int *scene6, *flag; void* sorttmp = nullptr; size_t sortbytes = 0;
+	DevBuf t[20]; LbvhResult out;                                  // the twenty temporaries and the tables: locals
+	float4 *lo0, *hi0, *lo, *hi, *nlo, *nhi, *r_nodes, *r_prims; int4* r_meta; unsigned long long *keys, *keys2; int *vals, *vals2, *childL, *childR, *parentI, *parentL, *first, *last, *height;
+	unsigned int *scene6, *flag, *sorttmp;
 	const size_t N = (size_t)n, NI = (size_t)std::max(1, n - 1);
-	if (!dalloc((void**)&lo0, N * 16, false) || !dalloc((void**)&hi0, N * 16, false) || !dalloc((void**)&lo, N * 16, false) || !dalloc((void**)&hi, N * 16, false)
-	    || !dalloc((void**)&nlo, NI * 16, false) || !dalloc((void**)&nhi, NI * 16, false) || !dalloc((void**)&keys, N * 8, false) || !dalloc((void**)&keys2, N * 8, false)
-	    || !dalloc((void**)&vals, N * 4, false) || !dalloc((void**)&vals2, N * 4, false) || !dalloc((void**)&childL, NI * 4, false) || !dalloc((void**)&childR, NI * 4, false)
-	    || !dalloc((void**)&parentI, NI * 4, false) || !dalloc((void**)&parentL, N * 4, false) || !dalloc((void**)&first, NI * 4, false) || !dalloc((void**)&last, NI * 4, false)
-	    || !dalloc((void**)&scene6, 32, false) || !dalloc((void**)&height, 16, false) || !dalloc((void**)&flag, NI * 4, false)
-	    || !dalloc(&r.d_nodes, NI * 64, true) || !dalloc(&r.d_prims, N * 64, true) || !dalloc(&r.d_meta, N * 16, true))
-		return bail();
-	sortbytes = (size_t)256 * ((N + 256 * JP_RS_ITEMS - 1) / (256 * JP_RS_ITEMS)) * sizeof(unsigned int);
-	if (!dalloc(&sorttmp, sortbytes, false)) return bail();
+	if ((e = reserve16(t[0], lo0, N * 16)) || (e = reserve16(t[1], hi0, N * 16)) || (e = reserve16(t[2], lo, N * 16)) || (e = reserve16(t[3], hi, N * 16))
+	    || (e = reserve16(t[4], nlo, NI * 16)) || (e = reserve16(t[5], nhi, NI * 16)) || (e = reserve16(t[6], keys, N * 8)) || (e = reserve16(t[7], keys2, N * 8))
+	    || (e = reserve16(t[8], vals, N * 4)) || (e = reserve16(t[9], vals2, N * 4)) || (e = reserve16(t[10], childL, NI * 4)) || (e = reserve16(t[11], childR, NI * 4))
+	    || (e = reserve16(t[12], parentI, NI * 4)) || (e = reserve16(t[13], parentL, N * 4)) || (e = reserve16(t[14], first, NI * 4)) || (e = reserve16(t[15], last, NI * 4))
+	    || (e = reserve16(t[16], scene6, 32)) || (e = reserve16(t[17], height, 16)) || (e = reserve16(t[18], flag, NI * 4))
+	    || (e = reserve16(out.nodes, r_nodes, NI * 64)) || (e = reserve16(out.prims, r_prims, N * 64)) || (e = reserve16(out.meta, r_meta, N * 16))
+	    || (e = reserve16(t[19], sorttmp, (size_t)256 * ((N + 256 * JP_RS_ITEMS - 1) / (256 * JP_RS_ITEMS)) * sizeof(unsigned int))))
+		return e;
 	hipEvent_t e0, e1;
-	if ((e = hipEventCreate(&e0)) != hipSuccess) return bail();
-	if ((e = hipEventCreate(&e1)) != hipSuccess) { hipEventDestroy(e0); return bail(); }
+	if ((e = hipEventCreate(&e0)) != hipSuccess) return e;
+	if ((e = hipEventCreate(&e1)) != hipSuccess) { hipEventDestroy(e0); return e; }
 	const int grid = (n + 255) / 256;
 	hipEventRecord(e0, stream);
 	hipLaunchKernelGGL(k_lbvh_init, dim3(1), dim3(64), 0, stream, scene6, height);
 	hipMemsetAsync(flag, 0, NI * 4, stream);
-	hipMemsetAsync(r.d_nodes, 0, NI * 64, stream);
+	hipMemsetAsync(r_nodes, 0, NI * 64, stream);
 	hipLaunchKernelGGL(k_lbvh_bounds, dim3(grid), dim3(256), 0, stream, prims0, n, lo0, hi0, scene6);
 	if (n == 1)
 	{
-		hipLaunchKernelGGL(k_lbvh_single, dim3(1), dim3(1), 0, stream, (const float4*)lo0, (const float4*)hi0, (float4*)r.d_nodes);
-		hipMemcpyAsync(r.d_prims, prims0, 64, hipMemcpyDeviceToDevice, stream); hipMemcpyAsync(r.d_meta, meta0, 16, hipMemcpyDeviceToDevice, stream);
-		order.assign(1, 0); r.n_nodes = 1; r.height = 1;
+		hipLaunchKernelGGL(k_lbvh_single, dim3(1), dim3(1), 0, stream, (const float4*)lo0, (const float4*)hi0, r_nodes);
+		hipMemcpyAsync(r_prims, prims0, 64, hipMemcpyDeviceToDevice, stream); hipMemcpyAsync(r_meta, meta0, 16, hipMemcpyDeviceToDevice, stream);
+		order.assign(1, 0); out.n_nodes = 1; out.height = 1;
 	}
 	else
 	{
 		hipLaunchKernelGGL(k_lbvh_morton, dim3(grid), dim3(256), 0, stream, (const float4*)lo0, (const float4*)hi0, n, (const unsigned int*)scene6, keys, vals);
-		lbvh_sort(stream, keys, keys2, vals, vals2, n, (unsigned int*)sorttmp);
-		hipLaunchKernelGGL(k_lbvh_gather, dim3(grid), dim3(256), 0, stream, (const int*)vals2, n, prims0, meta0, (const float4*)lo0, (const float4*)hi0, (float4*)r.d_prims, (int4*)r.d_meta, lo, hi);
+		lbvh_sort(stream, keys, keys2, vals, vals2, n, sorttmp);
+		hipLaunchKernelGGL(k_lbvh_gather, dim3(grid), dim3(256), 0, stream, (const int*)vals2, n, prims0, meta0, (const float4*)lo0, (const float4*)hi0, r_prims, r_meta, lo, hi);
 		hipLaunchKernelGGL(k_lbvh_hier, dim3(grid), dim3(256), 0, stream, (const unsigned long long*)keys2, n, childL, childR, parentI, parentL, first, last);
 		hipLaunchKernelGGL(k_lbvh_refit, dim3(grid), dim3(256), 0, stream, n, maxLeaf, (const int*)childL, (const int*)childR, (const int*)parentI, (const int*)parentL,
-		                   (const int*)first, (const int*)last, (const float4*)lo, (const float4*)hi, nlo, nhi, flag, (float4*)r.d_nodes);
+		                   (const int*)first, (const int*)last, (const float4*)lo, (const float4*)hi, nlo, nhi, flag, r_nodes);
 		hipLaunchKernelGGL(k_lbvh_depth, dim3(grid), dim3(256), 0, stream, n, maxLeaf, (const int*)parentI, (const int*)parentL, (const int*)first, (const int*)last, height);
-		r.n_nodes = n - 1;
+		out.n_nodes = n - 1;
 	}
 	hipEventRecord(e1, stream);
 	if (n > 1)
 	{
 		order.resize(N);
-		if ((e = hipMemcpyAsync(order.data(), vals2, N * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return bail(); }
-		if ((e = hipMemcpyAsync(&r.height, height, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return bail(); }
+		if ((e = hipMemcpyAsync(order.data(), vals2, N * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return e; }
+		if ((e = hipMemcpyAsync(&out.height, height, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return e; }
 	}
 	e = hipStreamSynchronize(stream);
 	if (e == hipSuccess) e = hipGetLastError();
-	if (e == hipSuccess) hipEventElapsedTime(&r.build_ms, e0, e1);
+	if (e == hipSuccess) hipEventElapsedTime(&out.build_ms, e0, e1);
 	hipEventDestroy(e0); hipEventDestroy(e1);
-	if (e != hipSuccess) return bail();
-	cleanup();
+	if (e != hipSuccess) return e;
+	r = std::move(out);
 	return hipSuccess;
 }
 
@@ -520,21 +516,21 @@ __global__ void __launch_bounds__(64) k_wide_level(const float4* __restrict__ no
 	w[16] = pack4(qh[1]); w[17] = pack4(qh[1] + 4); w[18] = pack4(qh[2]); w[19] = pack4(qh[2] + 4);
 }
 
-struct WideResult { void* d_wide = nullptr; int n_wide = 0, height = 0; float build_ms = 0.f; };
+struct WideResult { DevBuf wide; int n_wide = 0, height = 0; float build_ms = 0.f; };
 
 // nodes: the device binary tree of lbvh_build (root = node 0, which is always interior there).  On failure (a box that cannot
-// be quantised conservatively, index overflow) r.d_wide stays null and the caller keeps the binary tree for the shadow rays.
+// be quantised conservatively, index overflow) r.wide stays empty and the caller keeps the binary tree for the shadow rays.
 static hipError_t lbvh_build_wide(hipStream_t stream, const float4* nodes, int n_prims, WideResult& r)
 {
 	r = WideResult();
 	if (n_prims < 2) return hipSuccess;
 	hipError_t e;
 	const unsigned int max_wide = (unsigned int)std::max(16, 2 * n_prims);
-	uint32_t* wide = nullptr; WideItem *fa = nullptr, *fb = nullptr; unsigned int* ctr = nullptr; int* fail = nullptr;
-	auto bail = [&](hipError_t err) { if (wide) hipFree(wide); if (fa) hipFree(fa); if (fb) hipFree(fb); if (ctr) hipFree(ctr); if (fail) hipFree(fail); return err; };
-	if ((e = hipMalloc((void**)&wide, (size_t)max_wide * 80)) != hipSuccess || (e = hipMalloc((void**)&fa, (size_t)max_wide * sizeof(WideItem))) != hipSuccess
-	    || (e = hipMalloc((void**)&fb, (size_t)max_wide * sizeof(WideItem))) != hipSuccess || (e = hipMalloc((void**)&ctr, 16)) != hipSuccess || (e = hipMalloc((void**)&fail, 16)) != hipSuccess)
-		return bail(e);
+	uint32_t* wide; WideItem *fa, *fb; unsigned int* ctr; int* fail;
+	DevBuf b_wide, b_fa, b_fb, b_ctr, b_fail;
+	if ((e = reserve(b_wide, wide, (size_t)max_wide * 80)) != hipSuccess || (e = reserve(b_fa, fa, (size_t)max_wide * sizeof(WideItem))) != hipSuccess
+	    || (e = reserve(b_fb, fb, (size_t)max_wide * sizeof(WideItem))) != hipSuccess || (e = reserve(b_ctr, ctr, 16)) != hipSuccess || (e = reserve(b_fail, fail, 16)) != hipSuccess)
+		return e;
 	hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
 	hipEventRecord(e0, stream);
 	hipMemsetAsync(wide, 0, (size_t)max_wide * 80, stream);
@@ -550,7 +546,7 @@ static hipError_t lbvh_build_wide(hipStream_t stream, const float4* nodes, int n
 		hipLaunchKernelGGL(k_wide_level, dim3((n_items + 63) / 64), dim3(64), 0, stream, nodes, (const WideItem*)cur, n_items, wide, ctr, nxt, ctr + 1, max_wide, fail);
 		hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, stream);
 		hipMemcpyAsync(&h_fail, fail, 4, hipMemcpyDeviceToHost, stream);
-		if ((e = hipStreamSynchronize(stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return bail(e); }
+		if ((e = hipStreamSynchronize(stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return e; }
 		levels++;
 		if (h_fail) break;
 		n_items = (int)h_ctr[1]; h_ctr[1] = 0u;
@@ -558,9 +554,8 @@ static hipError_t lbvh_build_wide(hipStream_t stream, const float4* nodes, int n
 	}
 	hipEventRecord(e1, stream); hipStreamSynchronize(stream);
 	hipEventElapsedTime(&r.build_ms, e0, e1); hipEventDestroy(e0); hipEventDestroy(e1);
-	hipFree(fa); hipFree(fb); hipFree(ctr); hipFree(fail);
-	if (h_fail || levels >= 64) { hipFree(wide); return hipSuccess; }
-	r.d_wide = wide; r.n_wide = (int)h_ctr[0]; r.height = levels;
+	if (h_fail || levels >= 64) return hipSuccess;
+	r.wide = std::move(b_wide); r.n_wide = (int)h_ctr[0]; r.height = levels;
 	return hipSuccess;
 }
 // ---- [round 3] 4-wide quantised tree (Walker<4>, jp_device.h) collapsed on the device from the binary tree above --------------------
@@ -633,18 +628,18 @@ __global__ void __launch_bounds__(64) k_q4_level(const float4* __restrict__ node
 	w[12] = pack4(qh[1]); w[13] = pack4(qh[2]); w[14] = 0; w[15] = 0;
 }
 
-// nodes: the device binary tree (root = node 0, always interior).  On failure r.d_wide stays null and the caller keeps the binary tree.
+// nodes: the device binary tree (root = node 0, always interior).  On failure r.wide stays empty and the caller keeps the binary tree.
 static hipError_t lbvh_build_q4(hipStream_t stream, const float4* nodes, int n_prims, WideResult& r)
 {
 	r = WideResult();
 	if (n_prims < 2) return hipSuccess;
 	hipError_t e;
 	const unsigned int max_nodes = (unsigned int)std::max(16, n_prims);
-	uint32_t* q4 = nullptr; WideItem *fa = nullptr, *fb = nullptr; unsigned int* ctr = nullptr; int* fail = nullptr;
-	auto bail = [&](hipError_t err) { if (q4) hipFree(q4); if (fa) hipFree(fa); if (fb) hipFree(fb); if (ctr) hipFree(ctr); if (fail) hipFree(fail); return err; };
-	if ((e = hipMalloc((void**)&q4, (size_t)max_nodes * 64)) != hipSuccess || (e = hipMalloc((void**)&fa, (size_t)max_nodes * sizeof(WideItem))) != hipSuccess
-	    || (e = hipMalloc((void**)&fb, (size_t)max_nodes * sizeof(WideItem))) != hipSuccess || (e = hipMalloc((void**)&ctr, 16)) != hipSuccess || (e = hipMalloc((void**)&fail, 16)) != hipSuccess)
-		return bail(e);
+	uint32_t* q4; WideItem *fa, *fb; unsigned int* ctr; int* fail;
+	DevBuf b_q4, b_fa, b_fb, b_ctr, b_fail;
+	if ((e = reserve(b_q4, q4, (size_t)max_nodes * 64)) != hipSuccess || (e = reserve(b_fa, fa, (size_t)max_nodes * sizeof(WideItem))) != hipSuccess
+	    || (e = reserve(b_fb, fb, (size_t)max_nodes * sizeof(WideItem))) != hipSuccess || (e = reserve(b_ctr, ctr, 16)) != hipSuccess || (e = reserve(b_fail, fail, 16)) != hipSuccess)
+		return e;
 	hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
 	hipEventRecord(e0, stream);
 	hipMemsetAsync(q4, 0, (size_t)max_nodes * 64, stream);
@@ -660,7 +655,7 @@ static hipError_t lbvh_build_q4(hipStream_t stream, const float4* nodes, int n_p
 		hipLaunchKernelGGL(k_q4_level, dim3((n_items + 63) / 64), dim3(64), 0, stream, nodes, (const WideItem*)cur, n_items, q4, ctr, nxt, ctr + 1, max_nodes, fail);
 		hipMemcpyAsync(h_ctr, ctr, 8, hipMemcpyDeviceToHost, stream);
 		hipMemcpyAsync(&h_fail, fail, 4, hipMemcpyDeviceToHost, stream);
-		if ((e = hipStreamSynchronize(stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return bail(e); }
+		if ((e = hipStreamSynchronize(stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return e; }
 		levels++;
 		if (h_fail) break;
 		n_items = (int)h_ctr[1]; h_ctr[1] = 0u;
@@ -668,9 +663,8 @@ static hipError_t lbvh_build_q4(hipStream_t stream, const float4* nodes, int n_p
 	}
 	hipEventRecord(e1, stream); hipStreamSynchronize(stream);
 	hipEventElapsedTime(&r.build_ms, e0, e1); hipEventDestroy(e0); hipEventDestroy(e1);
-	hipFree(fa); hipFree(fb); hipFree(ctr); hipFree(fail);
-	if (h_fail || levels >= 64) { hipFree(q4); return hipSuccess; }
-	r.d_wide = q4; r.n_wide = (int)h_ctr[0]; r.height = levels;
+	if (h_fail || levels >= 64) return hipSuccess;
+	r.wide = std::move(b_q4); r.n_wide = (int)h_ctr[0]; r.height = levels;
 	return hipSuccess;
 }
 #endif

@@ -111,15 +111,12 @@ static int upload_light_table(JpContext* c, const JpScene* s, const std::vector<
 	for (int i = 0; i < n; i++) { float af; std::memcpy(&af, &alias[i], 4); bins[i] = make_float2(q[i], af); }
 	const int n_env = (int)env.size();
 	if (env.empty()) env.push_back(make_float4(0, 0, 0, 0));         // (never read: n_env is 0)
-	auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-		hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16)); if (e != hipSuccess) return e;
-		return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-	};
-	HIP_TRY(up(&c->d_pick_bins, bins.data(), bins.size() * sizeof(float2)));
-	HIP_TRY(up(&c->d_pick_pmf, pmf.data(), pmf.size() * sizeof(float)));
-	HIP_TRY(up(&c->d_pick_env, env.data(), env.size() * sizeof(float4)));
+	SceneTables& T = c->tab;
+	HIP_TRY(upload(T.pick_bins, bins.data(), bins.size() * sizeof(float2)));
+	HIP_TRY(upload(T.pick_pmf, pmf.data(), pmf.size() * sizeof(float)));
+	HIP_TRY(upload(T.pick_env, env.data(), env.size() * sizeof(float4)));
 	PickView& pv = c->plan.pv;
-	pv.bins = (const float2*)c->d_pick_bins; pv.pmf = (const float*)c->d_pick_pmf; pv.env = (const float4*)c->d_pick_env; pv.n = n; pv.n_env = n_env;
+	pv.bins = T.pick_bins.get<float2>(); pv.pmf = T.pick_pmf.get<float>(); pv.env = T.pick_env.get<float4>(); pv.n = n; pv.n_env = n_env;
 	c->plan.pick = true; c->n_selectable = nsel; c->total_weight = W;
 	return JP_OK;
 }
@@ -171,9 +168,9 @@ int jp_get_light_table(JpContext* c, float* q, int32_t* alias, float* pmf)
 	HIP_TRY(hipSetDevice(c->device));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	std::vector<float2> bins((size_t)n);
-	HIP_TRY(hipMemcpy(bins.data(), c->d_pick_bins, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(bins.data(), c->plan.pv.bins, (size_t)n * sizeof(float2), hipMemcpyDeviceToHost));
 	for (int i = 0; i < n; i++) { if (q) q[i] = bins[i].x; if (alias) std::memcpy(&alias[i], &bins[i].y, 4); }
-	if (pmf) HIP_TRY(hipMemcpy(pmf, c->d_pick_pmf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+	if (pmf) HIP_TRY(hipMemcpy(pmf, c->plan.pv.pmf, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
 	return JP_OK;
 }
 
@@ -185,25 +182,15 @@ int jp_light_pick(JpContext* c, int32_t n, const float* u0, const float* u1, int
 	if (n == 0) return JP_OK;
 	for (int i = 0; i < n; i++) if (!(u0[i] >= 0.f && u0[i] < 1.f) || !(u1[i] >= 0.f && u1[i] < 1.f)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_light_pick: a draw outside [0, 1)");   // (what the samplers deliver; the bin index is not clamped from below)
 	HIP_TRY(hipSetDevice(c->device));
-	float* d_u = nullptr; int* d_i = nullptr; float* d_p = nullptr;
-	int rc = JP_OK;
-	do
-	{
-		if (hipMalloc((void**)&d_u, (size_t)n * 8) != hipSuccess || hipMalloc((void**)&d_i, (size_t)n * 4) != hipSuccess || hipMalloc((void**)&d_p, (size_t)n * 4) != hipSuccess)
-		{ rc = fail(JP_ERR_DEVICE, "jp_light_pick: out of device memory"); break; }
-		hipMemcpyAsync(d_u, u0, (size_t)n * 4, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_u + n, u1, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-		const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-		hipLaunchKernelGGL(k_light_pick, dim3(grid), dim3(JP_BLOCK), 0, c->stream, c->plan.pv, n, (const float*)d_u, (const float*)(d_u + n), d_i, d_p);
-		hipError_t e = hipGetLastError();
-		if (e == hipSuccess)
-		{
-			hipMemcpyAsync(index, d_i, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream); hipMemcpyAsync(pmf, d_p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
-			e = hipStreamSynchronize(c->stream);
-		}
-		if (e != hipSuccess) rc = fail(JP_ERR_DEVICE, std::string("jp_light_pick: ") + hipGetErrorString(e));
-	} while (0);
-	hipFree(d_u); hipFree(d_i); hipFree(d_p);
-	return rc;
+	DevBuf b_u, b_i, b_p; float *d_u, *d_p; int* d_i;                // per-call scratch: freed on every return
+	HIP_TRY(reserve(b_u, d_u, (size_t)n * 8)); HIP_TRY(reserve(b_i, d_i, (size_t)n * 4)); HIP_TRY(reserve(b_p, d_p, (size_t)n * 4));
+	HIP_TRY(hipMemcpyAsync(d_u, u0, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_u + n, u1, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
+	hipLaunchKernelGGL(k_light_pick, dim3(grid), dim3(JP_BLOCK), 0, c->stream, c->plan.pv, n, (const float*)d_u, (const float*)(d_u + n), d_i, d_p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(index, d_i, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(pmf, d_p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return JP_OK;
 }
 
 } // extern "C"

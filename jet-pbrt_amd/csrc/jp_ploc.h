@@ -205,39 +205,36 @@ __global__ void __launch_bounds__(256) k_ploc_depth(const PlocNode* __restrict__
 }
 
 // Same contract as lbvh_build (jp_lbvh.h).  Returns hipErrorNotReady when the clustering does not finish within the round limit (the caller
-// falls back to the LBVH topology); r is then untouched.
+// falls back to the LBVH topology); r is untouched by any failure.
 static hipError_t ploc_build(hipStream_t stream, const float4* prims0, const int4* meta0, int n, int maxLeaf, int opt_radius, int opt_max_rounds, LbvhResult& r, std::vector<int>& order)
 {
 	if (n < 2) return lbvh_build(stream, prims0, meta0, n, maxLeaf, r, order);
 	hipError_t e = hipSuccess;
-	std::vector<void*> tmp;
-	auto dalloc = [&](void** p, size_t bytes, bool keep) -> bool { e = hipMalloc(p, std::max<size_t>(bytes, 16)); if (e != hipSuccess) return false; if (!keep) tmp.push_back(*p); return true; };
-	auto cleanup = [&]() { for (void* p : tmp) hipFree(p); };
-	auto bail = [&]() { cleanup(); if (r.d_nodes) hipFree(r.d_nodes); if (r.d_prims) hipFree(r.d_prims); if (r.d_meta) hipFree(r.d_meta); r = LbvhResult(); return e; };
+	DevBuf t[25]; LbvhResult out;                                  // locals: every return frees the twenty-five temporaries, and the tables unless they were moved into r
 	const size_t N = (size_t)n, NI = (size_t)(n - 1);
-	float4 *lo0, *hi0, *lo, *hi, *primsS; int4* metaS; unsigned long long *keys, *keys2; int *vals, *vals2, *nn, *parentLeaf, *firstNode, *posLeaf, *height, *dorder;
-	unsigned int* scene6; void* sorttmp = nullptr; PlocCluster *ca, *cb; PlocNode* nodes; uint2 *flags, *scan, *tops, *total;
+	float4 *lo0, *hi0, *lo, *hi, *primsS, *r_nodes, *r_prims; int4 *metaS, *r_meta; unsigned long long *keys, *keys2; int *vals, *vals2, *nn, *parentLeaf, *firstNode, *posLeaf, *height, *dorder;
+	unsigned int *scene6, *sorttmp; PlocCluster *ca, *cb; PlocNode* nodes; uint2 *flags, *scan, *tops, *total;
 	const size_t nblk = (N + 1023) / 1024;
-	if (!dalloc((void**)&lo0, N * 16, false) || !dalloc((void**)&hi0, N * 16, false) || !dalloc((void**)&lo, N * 16, false) || !dalloc((void**)&hi, N * 16, false)
-	    || !dalloc((void**)&primsS, N * 64, false) || !dalloc((void**)&metaS, N * 16, false) || !dalloc((void**)&keys, N * 8, false) || !dalloc((void**)&keys2, N * 8, false)
-	    || !dalloc((void**)&vals, N * 4, false) || !dalloc((void**)&vals2, N * 4, false) || !dalloc((void**)&nn, N * 4, false) || !dalloc((void**)&parentLeaf, N * 4, false)
-	    || !dalloc((void**)&firstNode, NI * 4, false) || !dalloc((void**)&posLeaf, N * 4, false) || !dalloc((void**)&height, 16, false) || !dalloc((void**)&dorder, N * 4, false)
-	    || !dalloc((void**)&scene6, 32, false) || !dalloc((void**)&ca, N * sizeof(PlocCluster), false) || !dalloc((void**)&cb, N * sizeof(PlocCluster), false)
-	    || !dalloc((void**)&nodes, NI * sizeof(PlocNode), false) || !dalloc((void**)&flags, N * 8, false) || !dalloc((void**)&scan, N * 8, false)
-	    || !dalloc((void**)&tops, nblk * 8, false) || !dalloc((void**)&total, 16, false)
-	    || !dalloc(&sorttmp, (size_t)256 * ((N + 256 * JP_RS_ITEMS - 1) / (256 * JP_RS_ITEMS)) * sizeof(unsigned int), false)
-	    || !dalloc(&r.d_nodes, NI * 64, true) || !dalloc(&r.d_prims, N * 64, true) || !dalloc(&r.d_meta, N * 16, true))
-		return bail();
+	if ((e = reserve16(t[0], lo0, N * 16)) || (e = reserve16(t[1], hi0, N * 16)) || (e = reserve16(t[2], lo, N * 16)) || (e = reserve16(t[3], hi, N * 16))
+	    || (e = reserve16(t[4], primsS, N * 64)) || (e = reserve16(t[5], metaS, N * 16)) || (e = reserve16(t[6], keys, N * 8)) || (e = reserve16(t[7], keys2, N * 8))
+	    || (e = reserve16(t[8], vals, N * 4)) || (e = reserve16(t[9], vals2, N * 4)) || (e = reserve16(t[10], nn, N * 4)) || (e = reserve16(t[11], parentLeaf, N * 4))
+	    || (e = reserve16(t[12], firstNode, NI * 4)) || (e = reserve16(t[13], posLeaf, N * 4)) || (e = reserve16(t[14], height, 16)) || (e = reserve16(t[15], dorder, N * 4))
+	    || (e = reserve16(t[16], scene6, 32)) || (e = reserve16(t[17], ca, N * sizeof(PlocCluster))) || (e = reserve16(t[18], cb, N * sizeof(PlocCluster)))
+	    || (e = reserve16(t[19], nodes, NI * sizeof(PlocNode))) || (e = reserve16(t[20], flags, N * 8)) || (e = reserve16(t[21], scan, N * 8))
+	    || (e = reserve16(t[22], tops, nblk * 8)) || (e = reserve16(t[23], total, 16))
+	    || (e = reserve16(t[24], sorttmp, (size_t)256 * ((N + 256 * JP_RS_ITEMS - 1) / (256 * JP_RS_ITEMS)) * sizeof(unsigned int)))
+	    || (e = reserve16(out.nodes, r_nodes, NI * 64)) || (e = reserve16(out.prims, r_prims, N * 64)) || (e = reserve16(out.meta, r_meta, N * 16)))
+		return e;
 	hipEvent_t e0, e1;
-	if ((e = hipEventCreate(&e0)) != hipSuccess) return bail();
-	if ((e = hipEventCreate(&e1)) != hipSuccess) { hipEventDestroy(e0); return bail(); }
+	if ((e = hipEventCreate(&e0)) != hipSuccess) return e;
+	if ((e = hipEventCreate(&e1)) != hipSuccess) { hipEventDestroy(e0); return e; }
 	const int grid = (n + 255) / 256;
 	hipEventRecord(e0, stream);
 	hipLaunchKernelGGL(k_lbvh_init, dim3(1), dim3(64), 0, stream, scene6, height);
-	hipMemsetAsync(r.d_nodes, 0, NI * 64, stream);
+	hipMemsetAsync(r_nodes, 0, NI * 64, stream);
 	hipLaunchKernelGGL(k_lbvh_bounds, dim3(grid), dim3(256), 0, stream, prims0, n, lo0, hi0, scene6);
 	hipLaunchKernelGGL(k_lbvh_morton, dim3(grid), dim3(256), 0, stream, (const float4*)lo0, (const float4*)hi0, n, (const unsigned int*)scene6, keys, vals);
-	lbvh_sort(stream, keys, keys2, vals, vals2, n, (unsigned int*)sorttmp);
+	lbvh_sort(stream, keys, keys2, vals, vals2, n, sorttmp);
 	hipLaunchKernelGGL(k_lbvh_gather, dim3(grid), dim3(256), 0, stream, (const int*)vals2, n, prims0, meta0, (const float4*)lo0, (const float4*)hi0, primsS, metaS, lo, hi);
 	hipLaunchKernelGGL(k_ploc_init, dim3(grid), dim3(256), 0, stream, (const float4*)lo, (const float4*)hi, n, ca);
 	int radius = JP_PLOC_RADIUS;                                   // measured on the 280k-triangle scene (profiles/r03g_ploc_ab.txt)
@@ -257,27 +254,27 @@ static hipError_t ploc_build(hipStream_t stream, const float4* prims0, const int
 		hipLaunchKernelGGL(k_scan2_add, dim3(nb), dim3(256), 0, stream, scan, m, (const uint2*)tops);
 		hipLaunchKernelGGL(k_ploc_merge, dim3(g), dim3(256), 0, stream, (const PlocCluster*)ca, (const int*)nn, (const uint2*)flags, (const uint2*)scan, m, next_id, cb, nodes, parentLeaf);
 		uint2 h_total;
-		if ((e = hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = hipStreamSynchronize(stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return bail(); }
+		if ((e = hipMemcpyAsync(&h_total, total, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = hipStreamSynchronize(stream)) != hipSuccess) { hipEventDestroy(e0); hipEventDestroy(e1); return e; }
 		if (h_total.y == 0) { stuck = true; break; }             // no mutual pair: cannot happen for m >= 2 (the global minimum is mutual), guards a hang
 		m = (int)h_total.x; next_id += (int)h_total.y;
 		std::swap(ca, cb);
 	}
-	if (stuck || next_id != n - 1) { hipEventDestroy(e0); hipEventDestroy(e1); e = hipErrorNotReady; hipError_t keep = e; bail(); return keep; }
+	if (stuck || next_id != n - 1) { hipEventDestroy(e0); hipEventDestroy(e1); return hipErrorNotReady; }
 	hipLaunchKernelGGL(k_ploc_first, dim3((2 * n - 1 + 255) / 256), dim3(256), 0, stream, (const PlocNode*)nodes, (const int*)parentLeaf, n, firstNode, posLeaf);
-	hipLaunchKernelGGL(k_ploc_permute, dim3(grid), dim3(256), 0, stream, (const int*)posLeaf, (const int*)vals2, n, (const float4*)primsS, (const int4*)metaS, (float4*)r.d_prims, (int4*)r.d_meta, dorder);
-	hipLaunchKernelGGL(k_ploc_emit, dim3(grid), dim3(256), 0, stream, (const PlocNode*)nodes, (const int*)firstNode, (const int*)posLeaf, n, maxLeaf, (float4*)r.d_nodes);
+	hipLaunchKernelGGL(k_ploc_permute, dim3(grid), dim3(256), 0, stream, (const int*)posLeaf, (const int*)vals2, n, (const float4*)primsS, (const int4*)metaS, r_prims, r_meta, dorder);
+	hipLaunchKernelGGL(k_ploc_emit, dim3(grid), dim3(256), 0, stream, (const PlocNode*)nodes, (const int*)firstNode, (const int*)posLeaf, n, maxLeaf, r_nodes);
 	hipLaunchKernelGGL(k_ploc_depth, dim3(grid), dim3(256), 0, stream, (const PlocNode*)nodes, (const int*)parentLeaf, n, maxLeaf, height);
 	hipEventRecord(e1, stream);
 	order.resize(N);
-	if ((e = hipMemcpyAsync(order.data(), dorder, N * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = hipMemcpyAsync(&r.height, height, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess)
-	{ hipEventDestroy(e0); hipEventDestroy(e1); return bail(); }
+	if ((e = hipMemcpyAsync(order.data(), dorder, N * 4, hipMemcpyDeviceToHost, stream)) != hipSuccess || (e = hipMemcpyAsync(&out.height, height, 4, hipMemcpyDeviceToHost, stream)) != hipSuccess)
+	{ hipEventDestroy(e0); hipEventDestroy(e1); return e; }
 	e = hipStreamSynchronize(stream);
 	if (e == hipSuccess) e = hipGetLastError();
-	if (e == hipSuccess) hipEventElapsedTime(&r.build_ms, e0, e1);
+	if (e == hipSuccess) hipEventElapsedTime(&out.build_ms, e0, e1);
 	hipEventDestroy(e0); hipEventDestroy(e1);
-	if (e != hipSuccess) return bail();
-	r.n_nodes = n - 1;
-	cleanup();
+	if (e != hipSuccess) return e;
+	out.n_nodes = n - 1;
+	r = std::move(out);
 	return hipSuccess;
 }
 #endif

@@ -1,25 +1,44 @@
 // jet-pbrt_amd/csrc/jp_render.h -- host runtime, part 3 of 3: jp_render* -- the shard helper, the kernel selectors, queue budget, the per-bounce launch sequence, stream lanes, the fused schedule,
-// and the rest of the C ABI (counters, build info, jp_trace, jp_bsdf, tone map).  Included by jp_kernels.hip after jp_upload.h.
+// and the rest of the C ABI (counters, build info, jp_trace, jp_bsdf, tone map).  Every buffer is a DevBuf of the context (grown through reserve_idle, jp_runtime.h, when
+// kernels in flight may use it) or a local DevBuf of the call; ensure_queues regrows a queue set as a whole.  Included by jp_kernels.hip after jp_upload.h.
 #pragma once
 // ---- render ---------------------------------------------------------------------------------------------------------------
 namespace
 {
 enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4 };
 
+void free_queues(JpContext* c) { c->qb = QueueBufs(); c->cap = 0; c->planes_alloc = 0; c->blk_alloc = 0; }
+
 int ensure_queues(JpContext* c, unsigned int cap, int planes, unsigned int nblocks)
 {
 	if (c->cap >= cap && c->planes_alloc >= planes && c->blk_alloc >= nblocks) return JP_OK;
 	cap = std::max(cap, c->cap); planes = std::max(planes, c->planes_alloc); nblocks = std::max(nblocks, c->blk_alloc);
-	free_queues(c); c->blk_alloc = 0;
-	auto alloc = [&](void** p, size_t bytes) -> bool { if (hipMalloc(p, bytes) != hipSuccess) return false; c->qbufs.push_back(*p); return true; };
-	Queues& q = c->q; bool ok = true;
-	for (int b = 0; b < 2 && ok; b++) ok = alloc((void**)&q.ray_o[b], (size_t)cap * 16) && alloc((void**)&q.ray_d[b], (size_t)cap * 16) && alloc((void**)&q.beta[b], (size_t)cap * 16)
-	                                       && alloc((void**)&q.blk_q[b], (size_t)nblocks * 4);
-	ok = ok && alloc((void**)&q.hit, (size_t)cap * 8) && alloc((void**)&q.lacc, (size_t)cap * 16) && alloc((void**)&q.sh_o, (size_t)cap * 16)
-	     && alloc((void**)&q.sh_d, (size_t)cap * 16 * planes) && alloc((void**)&q.sh_c, (size_t)cap * 16 * planes) && alloc((void**)&q.blk_sh, (size_t)nblocks * 4);
+	free_queues(c);                                                  // all or nothing: the whole set goes before the larger one is allocated
+	auto alloc = [](DevBuf& b, auto*& p, size_t bytes) { return reserve(b, p, bytes) == hipSuccess; };
+	Queues& q = c->q; QueueBufs& qb = c->qb; bool ok = true;
+	for (int b = 0; b < 2 && ok; b++) ok = alloc(qb.ray_o[b], q.ray_o[b], (size_t)cap * 16) && alloc(qb.ray_d[b], q.ray_d[b], (size_t)cap * 16) && alloc(qb.beta[b], q.beta[b], (size_t)cap * 16)
+	                                       && alloc(qb.blk_q[b], q.blk_q[b], (size_t)nblocks * 4);
+	ok = ok && alloc(qb.hit, q.hit, (size_t)cap * 8) && alloc(qb.lacc, q.lacc, (size_t)cap * 16) && alloc(qb.sh_o, q.sh_o, (size_t)cap * 16)
+	     && alloc(qb.sh_d, q.sh_d, (size_t)cap * 16 * planes) && alloc(qb.sh_c, q.sh_c, (size_t)cap * 16 * planes) && alloc(qb.blk_sh, q.blk_sh, (size_t)nblocks * 4);
 	if (!ok) { free_queues(c); return fail(JP_ERR_DEVICE, "jp_render: out of device memory for the path queues"); }
 	c->cap = cap; c->planes_alloc = planes; c->blk_alloc = nblocks;
 	return JP_OK;
+}
+
+int ensure_gamma(JpContext* c)
+{
+	if (!c->gamma) HIP_TRY(upload(c->gamma, host_gamma_thresholds(), 255 * sizeof(float)));
+	return JP_OK;
+}
+// the 8-bit film of n bytes and the gamma table, then k_tonemap8: n floats at src -> c->rgb8, on the context's stream
+int ensure_rgb8(JpContext* c, size_t n)
+{
+	if (const int e = reserve_idle(c, c->rgb8, n); e != JP_OK) return e;
+	return ensure_gamma(c);
+}
+void tonemap8(JpContext* c, const float* src, size_t n)
+{
+	hipLaunchKernelGGL(k_tonemap8, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, src, c->rgb8.get<unsigned char>(), c->gamma.get<const float>(), n);
 }
 
 struct Stamper
@@ -144,14 +163,14 @@ TraceLaunch trace_kernel(const ScenePlan& p, int tw)
 int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync, int lane_index = 0, int lane_count = 1, int lane_group = 4, bool ev0_recorded = false)
 {
 	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_render: no scene uploaded");
-	const ScenePlan& p = c->plan; Shard sh;
+	const ScenePlan& p = c->plan; Shard sh; DevCounters* const d_cnt = c->cnt.get<DevCounters>();
 	if (const int e = shard_of(rp, sh, lane_index, lane_count, lane_group); e != JP_OK) return e;
 	HIP_TRY(hipSetDevice(c->device));
 	const long long npix = (long long)sh.lane_rows * rp->width;
 
 	if (!ev0_recorded) HIP_TRY(hipEventRecord(c->ev0, c->stream));          // (with several lanes render_impl records it before the first lane is enqueued)
 	HIP_TRY(hipMemsetAsync(film_dev, 0, sizeof(float) * 3 * (size_t)rp->width * rp->height, c->stream));
-	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(DevCounters), c->stream));
+	HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(DevCounters), c->stream));
 	c->evused = 0; c->stamps.clear();
 	unsigned long long samples = 0;
 	if (npix > 0)
@@ -193,15 +212,12 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		}
 		c->q.cap = cap; c->q.R = R;
 		const bool tex = p.textured && rp->integrator == JP_INTEGRATOR_PATH;
-		if (tex && c->side_n < cap)
-		{   // the side words of k_texel: one per queue position, allocated for textured scenes only
-			if (c->d_side) { HIP_TRY(hipStreamSynchronize(c->stream)); hipFree(c->d_side); } c->d_side = nullptr; c->side_n = 0;
-			HIP_TRY(hipMalloc((void**)&c->d_side, (size_t)cap * sizeof(unsigned int))); c->side_n = cap;
-		}
-		TexView tv = p.tv; tv.side = c->d_side;
-		const size_t need = spill_need(p, p.persist ? deepest_walk(p) : 0, G);
-		if (c->spill_words < need) { if (c->d_spill) hipFree(c->d_spill); c->d_spill = nullptr; HIP_TRY(hipMalloc((void**)&c->d_spill, need * sizeof(int))); c->spill_words = need; }
-		if (c->pix_acc_n < (size_t)npix) { if (c->d_pix_acc) hipFree(c->d_pix_acc); c->d_pix_acc = nullptr; HIP_TRY(hipMalloc((void**)&c->d_pix_acc, (size_t)npix * 16)); c->pix_acc_n = (size_t)npix; }
+		// the side words of k_texel: one per queue position, allocated for textured scenes only
+		if (tex) if (const int e = reserve_idle(c, c->side, (size_t)cap * sizeof(unsigned int)); e != JP_OK) return e;
+		TexView tv = p.tv; tv.side = c->side.get<unsigned int>();
+		if (const int e = reserve_idle(c, c->spill, spill_need(p, p.persist ? deepest_walk(p) : 0, G) * sizeof(int)); e != JP_OK) return e;
+		if (const int e = reserve_idle(c, c->pix_acc, (size_t)npix * 16); e != JP_OK) return e;
+		int* const d_spill = c->spill.get<int>(); float4* const d_pix_acc = c->pix_acc.get<float4>();
 
 		RenderConst rc; rc.width = rp->width; rc.height = rp->height; rc.spp = rp->spp; rc.max_depth = rp->max_depth; rc.seed = rp->seed;
 		rc.band_rows = sh.band; rc.shard_index = sh.index; rc.shard_count = sh.count; rc.npix = (int)npix; rc.local_rows = sh.lane_rows; rc.n_planes = p.n_planes;
@@ -221,12 +237,12 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
-			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, c->d_cnt); }
+			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt); }
 			if (rp->integrator != JP_INTEGRATOR_PATH)
 			{   // the other two integrators: one megakernel launch per batch (k_other), then the same per-pixel sum
 				Stamper t(c, CLS_OTHER);
 				const int ogrid = (int)std::min<unsigned int>((P + JP_BLOCK - 1) / JP_BLOCK, (unsigned int)(c->n_cus * 16));
-				hipLaunchKernelGGL(ok, dim3(ogrid), dim3(JP_BLOCK), p.lds_bytes, c->stream, p.sv, c->q, rc, rp->integrator, p.stack_depth, c->d_cnt);
+				hipLaunchKernelGGL(ok, dim3(ogrid), dim3(JP_BLOCK), p.lds_bytes, c->stream, p.sv, c->q, rc, rp->integrator, p.stack_depth, d_cnt);
 			}
 			int cur = 0;
 			int iters = rp->integrator != JP_INTEGRATOR_PATH ? 0 : rp->max_depth + 1;
@@ -236,37 +252,37 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 				{
 					if (rp->integrator != JP_INTEGRATOR_PATH || !p.has_null_material || it > iters + 64) break;
 					// null-material primitives re-queue a path without consuming a bounce (integrator.cc:349-353): ask the device
-					DevCounters h; HIP_TRY(hipMemcpyAsync(&h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
+					DevCounters h; HIP_TRY(hipMemcpyAsync(&h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
 					if (h.n_queue[cur] == 0) break;
 				}
 				{
 					Stamper t(c, CLS_EXTEND);
-					if (ek.refill) hipLaunchKernelGGL(ek.refill, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, c->d_spill, c->d_cnt);
-					else hipLaunchKernelGGL(ek.plain, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, c->d_cnt);
+					if (ek.refill) hipLaunchKernelGGL(ek.refill, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, d_spill, d_cnt);
+					else hipLaunchKernelGGL(ek.plain, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, d_cnt);
 				}
 				{
 					Stamper t(c, CLS_SHADE);
 					if (tex)
 					{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
 						hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
-						if (p.pick) hipLaunchKernelGGL(pk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt, tv, p.pv);
-						else hipLaunchKernelGGL(hk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt, tv);
+						if (p.pick) hipLaunchKernelGGL(pk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv);
+						else hipLaunchKernelGGL(hk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv);
 					}
-					else if (p.pick) hipLaunchKernelGGL(pk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt, p.pv);
-					else hipLaunchKernelGGL(hk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, c->d_cnt);
+					else if (p.pick) hipLaunchKernelGGL(pk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv);
+					else hipLaunchKernelGGL(hk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt);
 				}
 				HIP_TRY(hipGetLastError());                               // a failed launch (k_extend / k_shade) is reported where it happens, not at the end of the frame
 				if (it < rp->max_depth || p.has_null_material)                 // at bounce == maxDepth Li() breaks before the NEE (integrator.cc:340-343)
 				{
 					Stamper t(c, CLS_SHADOW);
 					if (sk.cert_fell_back) c->cert_fell_back = true;         // the one-ray-per-lane kernels walk the caller's tree verbatim
-					if (sk.refill) hipLaunchKernelGGL(sk.refill, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, c->d_spill, c->d_cnt);
-					else hipLaunchKernelGGL(sk.plain, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, c->d_cnt);
+					if (sk.refill) hipLaunchKernelGGL(sk.refill, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, d_spill, d_cnt);
+					else hipLaunchKernelGGL(sk.plain, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, d_cnt);
 					HIP_TRY(hipGetLastError());
 				}
 				cur ^= 1;
 			}
-			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_resolve, dim3((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, c->q, rc, c->d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
+			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_resolve, dim3((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, c->q, rc, d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
 			samples += (unsigned long long)rc.sbatch * (unsigned long long)npix;
 		}
 		HIP_TRY(hipGetLastError());
@@ -293,7 +309,7 @@ int make_lanes(JpContext* c, int extra)
 		l->device = c->device; l->is_lane = true; l->n_cus = c->n_cus; l->blocks_per_cu = c->blocks_per_cu; l->opt = c->opt; l->opt_env = c->opt_env;
 		std::memset(&l->counters, 0, sizeof(l->counters)); std::memset(&l->q, 0, sizeof(l->q));
 		if (hipStreamCreateWithFlags(&l->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&l->ev0) != hipSuccess || hipEventCreate(&l->ev1) != hipSuccess
-		    || hipMalloc((void**)&l->d_cnt, sizeof(DevCounters)) != hipSuccess)
+		    || l->cnt.reserve(sizeof(DevCounters)) != hipSuccess)
 		{ jp_destroy_context(l); return fail(JP_ERR_DEVICE, "jp_render: stream/event allocation for an extra lane failed"); }
 		c->lanes.push_back(l);
 	}
@@ -304,7 +320,7 @@ int make_lanes(JpContext* c, int extra)
 void sync_lane_scene(JpContext* c, JpContext* l)
 {
 	l->plan = c->plan;                                               // (the lane's side array is its own, allocated with its queues)
-	if (!l->plan.textured && l->d_side) { hipStreamSynchronize(l->stream); hipFree(l->d_side); l->d_side = nullptr; l->side_n = 0; }   // untextured scene: not kept
+	if (!l->plan.textured && l->side) { hipStreamSynchronize(l->stream); l->side.reset(); }   // untextured scene: not kept
 	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
 }
 
@@ -347,14 +363,14 @@ PathKernel path_kernel(const ScenePlan& p)
 
 int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
-	const ScenePlan& p = c->plan; Shard sh;
+	const ScenePlan& p = c->plan; Shard sh; DevCounters* const d_cnt = c->cnt.get<DevCounters>();
 	if (const int e = shard_of(rp, sh); e != JP_OK) return e;         // (fused_eligible: the path integrator, so the integrator checks cannot fire)
 	HIP_TRY(hipSetDevice(c->device));
 	const long long npix = (long long)sh.local_rows * rp->width;
 
 	HIP_TRY(hipEventRecord(c->ev0, c->stream));
 	HIP_TRY(hipMemsetAsync(film_dev, 0, sizeof(float) * 3 * (size_t)rp->width * rp->height, c->stream));
-	HIP_TRY(hipMemsetAsync(c->d_cnt, 0, sizeof(DevCounters), c->stream));
+	HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(DevCounters), c->stream));
 	c->evused = 0; c->stamps.clear();
 	unsigned long long samples = 0;
 	c->last_fused = 1; c->last_lanes = 1;
@@ -366,7 +382,7 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 		const int modeE = flat ? 2 : (p.trav_mode == 5 ? 5 : 0);
 		// ---- batch: the radiance array holds one float4 per path of the batch (the only per-path array that outlives a job) ----
 		size_t freeB = 0, totalB = 0; hipMemGetInfo(&freeB, &totalB);
-		size_t budget = std::min<size_t>((size_t)4 << 30, (freeB + c->flacc_n * 16) / 4);
+		size_t budget = std::min<size_t>((size_t)4 << 30, (freeB + c->fqb.lacc.bytes()) / 4);
 		if (c->opt.max_slots > 0) budget = std::min<size_t>(budget, (size_t)c->opt.max_slots * 16);
 		const size_t PMAX = (size_t)1 << 26;
 		const size_t pcap = std::min<size_t>(PMAX, std::max<size_t>((size_t)npix, budget / 16));
@@ -401,33 +417,26 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 		{
 			HIP_TRY(hipStreamSynchronize(c->stream));
 			const unsigned int ncap = std::max(cap, c->fcap); const int npl = std::max(p.n_planes, c->fplanes);
-			const size_t keep_lacc = c->flacc_n; float4* keep = c->fq.lacc;
-			for (void* p : c->fbufs) if (p != (void*)keep) hipFree(p);
-			c->fbufs.clear(); if (keep) c->fbufs.push_back(keep);
-			c->fcap = 0; c->fplanes = 0;
-			Queues& q = c->fq; float4* lacc = keep; std::memset(&q, 0, sizeof(q)); q.lacc = lacc; c->flacc_n = keep_lacc;
-			auto alloc = [&](void** p, size_t bytes) -> bool { if (hipMalloc(p, bytes) != hipSuccess) return false; c->fbufs.push_back(*p); return true; };
+			QueueBufs& qb = c->fqb; Queues& q = c->fq;
+			{ DevBuf lacc = std::move(qb.lacc); qb = QueueBufs(); qb.lacc = std::move(lacc); }   // all or nothing, except the radiance array: it is sized by the batch (below) and stays
+			c->fcap = 0; c->fplanes = 0; q = Queues();
+			auto alloc = [](DevBuf& b, auto*& p, size_t bytes) { return reserve(b, p, bytes) == hipSuccess; };
 			bool ok = true;
-			for (int b = 0; b < 2 && ok; b++) ok = alloc((void**)&q.ray_o[b], (size_t)ncap * 16) && alloc((void**)&q.ray_d[b], (size_t)ncap * 16) && alloc((void**)&q.beta[b], (size_t)ncap * 16);
-			ok = ok && alloc((void**)&q.sh_o, (size_t)ncap * 16) && alloc((void**)&q.sh_d, (size_t)ncap * 16 * npl) && alloc((void**)&q.sh_c, (size_t)ncap * 16 * npl);
-			if (!ok) { free_fused(c); return fail(JP_ERR_DEVICE, "jp_render: out of device memory for the region queues"); }
+			for (int b = 0; b < 2 && ok; b++) ok = alloc(qb.ray_o[b], q.ray_o[b], (size_t)ncap * 16) && alloc(qb.ray_d[b], q.ray_d[b], (size_t)ncap * 16) && alloc(qb.beta[b], q.beta[b], (size_t)ncap * 16);
+			ok = ok && alloc(qb.sh_o, q.sh_o, (size_t)ncap * 16) && alloc(qb.sh_d, q.sh_d, (size_t)ncap * 16 * npl) && alloc(qb.sh_c, q.sh_c, (size_t)ncap * 16 * npl);
+			if (!ok) { qb = QueueBufs(); return fail(JP_ERR_DEVICE, "jp_render: out of device memory for the region queues"); }
 			c->fcap = ncap; c->fplanes = npl;
 		}
 		const size_t P = (size_t)sbatch * (size_t)npix;
-		if (c->flacc_n < P)
-		{
-			HIP_TRY(hipStreamSynchronize(c->stream));
-			if (c->fq.lacc) { c->fbufs.erase(std::remove(c->fbufs.begin(), c->fbufs.end(), (void*)c->fq.lacc), c->fbufs.end()); hipFree(c->fq.lacc); c->fq.lacc = nullptr; c->flacc_n = 0; }
-			void* pl = nullptr; if (hipMalloc(&pl, P * 16) != hipSuccess) return fail(JP_ERR_DEVICE, "jp_render: out of device memory for the batch's radiance array");
-			c->fq.lacc = (float4*)pl; c->fbufs.push_back(pl); c->flacc_n = P;
-		}
-		c->fq.cap = c->fcap; c->fq.R = R;
+		if (const int e = reserve_idle(c, c->fqb.lacc, P * 16); e != JP_OK) return e;      // the batch's radiance array
+		c->fq.lacc = c->fqb.lacc.get<float4>(); c->fq.cap = c->fcap; c->fq.R = R;
 		const int nbatches = (rp->spp + sbatch - 1) / sbatch;
-		if (c->jobs_n < (size_t)nbatches) { HIP_TRY(hipStreamSynchronize(c->stream)); if (c->d_jobs) hipFree(c->d_jobs); c->d_jobs = nullptr; c->jobs_n = 0; HIP_TRY(hipMalloc((void**)&c->d_jobs, (size_t)nbatches * 4)); c->jobs_n = (size_t)nbatches; }
-		HIP_TRY(hipMemsetAsync(c->d_jobs, 0, (size_t)nbatches * 4, c->stream));
-		const size_t need = spill_need(p, flat ? 0 : std::max(deepE, deepS), G);
-		if (c->spill_words < need) { HIP_TRY(hipStreamSynchronize(c->stream)); if (c->d_spill) hipFree(c->d_spill); c->d_spill = nullptr; c->spill_words = 0; HIP_TRY(hipMalloc((void**)&c->d_spill, need * sizeof(int))); c->spill_words = need; }
-		if (c->pix_acc_n < (size_t)npix) { HIP_TRY(hipStreamSynchronize(c->stream)); if (c->d_pix_acc) hipFree(c->d_pix_acc); c->d_pix_acc = nullptr; HIP_TRY(hipMalloc((void**)&c->d_pix_acc, (size_t)npix * 16)); c->pix_acc_n = (size_t)npix; }
+		if (const int e = reserve_idle(c, c->jobs, (size_t)nbatches * 4); e != JP_OK) return e;
+		unsigned int* const d_jobs = c->jobs.get<unsigned int>();
+		HIP_TRY(hipMemsetAsync(d_jobs, 0, (size_t)nbatches * 4, c->stream));
+		if (const int e = reserve_idle(c, c->spill, spill_need(p, flat ? 0 : std::max(deepE, deepS), G) * sizeof(int)); e != JP_OK) return e;
+		if (const int e = reserve_idle(c, c->pix_acc, (size_t)npix * 16); e != JP_OK) return e;
+		int* const d_spill = c->spill.get<int>(); float4* const d_pix_acc = c->pix_acc.get<float4>();
 
 		RenderConst rc; std::memset(&rc, 0, sizeof(rc));
 		rc.width = rp->width; rc.height = rp->height; rc.spp = rp->spp; rc.max_depth = rp->max_depth; rc.seed = rp->seed;
@@ -443,11 +452,11 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 		for (int s0 = 0, bi = 0; s0 < rp->spp; s0 += sbatch, bi++)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
-			pc.nsb = (rc.sbatch + S - 1) / S; pc.job = c->d_jobs + bi;
+			pc.nsb = (rc.sbatch + S - 1) / S; pc.job = d_jobs + bi;
 			const unsigned int g = (unsigned int)std::min<unsigned long long>((unsigned long long)npg * pc.nsb, (unsigned long long)G);
-			{ Stamper t(c, CLS_PATH); hipLaunchKernelGGL(kern, dim3(g), dim3(JP_BLOCK), L.total, c->stream, p.sv, c->fq, rc, pc, c->d_spill, c->d_cnt); }
+			{ Stamper t(c, CLS_PATH); hipLaunchKernelGGL(kern, dim3(g), dim3(JP_BLOCK), L.total, c->stream, p.sv, c->fq, rc, pc, d_spill, d_cnt); }
 			HIP_TRY(hipGetLastError());
-			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_resolve, dim3((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, c->fq, rc, c->d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
+			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_resolve, dim3((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, c->fq, rc, d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
 			HIP_TRY(hipGetLastError());
 			samples += (unsigned long long)rc.sbatch * (unsigned long long)npix;
 		}
@@ -503,10 +512,11 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	{
 		JpContext* l = c->lanes[k - 1];
 		sync_lane_scene(c, l);
-		if (l->film_n < n) { if (l->d_film) { HIP_TRY(hipStreamSynchronize(c->stream)); hipFree(l->d_film); } l->d_film = nullptr; l->film_n = 0; HIP_TRY(hipMalloc((void**)&l->d_film, n * sizeof(float))); l->film_n = n; c->added_valid = false; }
+		if (l->film.bytes() < n * sizeof(float)) c->added_valid = false;
+		if (const int e = reserve_idle(c, l->film, n * sizeof(float)); e != JP_OK) return e;   // (waits for the PARENT's stream: its merge of the previous frame reads the lane film)
 		if (c->added_valid) HIP_TRY(hipStreamWaitEvent(l->stream, c->ev_added, 0));   // the previous frame's merge still reads the lane film
 		l->blocks_per_cu = bpc_lane;
-		st = render_one(l, rp, l->d_film, false, k, L, group);
+		st = render_one(l, rp, l->film.get<float>(), false, k, L, group);
 	}
 	if (st == JP_OK) { c->blocks_per_cu = bpc_lane; st = render_one(c, rp, film_dev, false, 0, L, group, true); c->blocks_per_cu = bpc_single; }
 	if (st != JP_OK) return st;
@@ -514,7 +524,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	{
 		JpContext* l = c->lanes[k - 1];
 		HIP_TRY(hipStreamWaitEvent(c->stream, l->ev1, 0));                           // recorded at the end of the lane's render_one
-		hipLaunchKernelGGL(k_add_film, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, film_dev, (const float*)l->d_film, n);
+		hipLaunchKernelGGL(k_add_film, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, film_dev, l->film.get<const float>(), n);
 	}
 	HIP_TRY(hipEventRecord(c->ev_added, c->stream)); c->added_valid = true;
 	HIP_TRY(hipEventRecord(c->ev1, c->stream));                                       // render_ms: all lanes and the merge
@@ -526,7 +536,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 int finish_one(JpContext* c, JpCounters& o)
 {
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	DevCounters h; HIP_TRY(hipMemcpy(&h, c->d_cnt, sizeof(h), hipMemcpyDeviceToHost));
+	DevCounters h; HIP_TRY(hipMemcpy(&h, c->cnt.get<void>(), sizeof(h), hipMemcpyDeviceToHost));
 	o.closest_rays += h.closest; o.closest_hits += h.closest_hit; o.shadow_rays += h.shadow; o.shadow_occluded += h.shadow_occ; o.certified_fallback_rays += h.cert_fallback;
 	for (const JpContext::Stamp& s : c->stamps)
 	{
@@ -565,11 +575,11 @@ int jp_render(JpContext* c, const JpRenderParams* rp, float* film_host)
 	if (rp->width <= 0 || rp->height <= 0) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: bad width/height");
 	HIP_TRY(hipSetDevice(c->device));
 	size_t n = (size_t)rp->width * rp->height * 3;
-	if (c->film_n < n) { if (c->d_film) hipFree(c->d_film); c->d_film = nullptr; HIP_TRY(hipMalloc((void**)&c->d_film, n * sizeof(float))); c->film_n = n; }
-	if (c->h_film_n < n) { if (c->h_film) hipHostFree(c->h_film); c->h_film = nullptr; c->h_film_n = 0; if (hipHostMalloc((void**)&c->h_film, n * sizeof(float), hipHostMallocDefault) == hipSuccess) c->h_film_n = n; else c->h_film = nullptr; }
-	int st = render_impl(c, rp, c->d_film, false); if (st != JP_OK) return st;
-	float* stage = c->h_film ? c->h_film : film_host;
-	HIP_TRY(hipMemcpyAsync(stage, c->d_film, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	if (const int e = ensure_film(c, n); e != JP_OK) return e;
+	float* const d_film = c->film.get<float>();
+	float* stage = c->h_film.reserve(n * sizeof(float)) == hipSuccess ? c->h_film.get<float>() : film_host;   // (no pinned memory: the pageable copy)
+	int st = render_impl(c, rp, d_film, false); if (st != JP_OK) return st;
+	HIP_TRY(hipMemcpyAsync(stage, d_film, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	if (stage != film_host) std::memcpy(film_host, stage, n * sizeof(float));
 	return JP_OK;
@@ -581,15 +591,14 @@ int jp_render_rgb8(JpContext* c, const JpRenderParams* rp, uint8_t* rgb8_host, f
 	if (rp->width <= 0 || rp->height <= 0) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render_rgb8: bad width/height");
 	HIP_TRY(hipSetDevice(c->device));
 	const size_t n = (size_t)rp->width * rp->height * 3;
-	if (c->film_n < n) { if (c->d_film) hipFree(c->d_film); c->d_film = nullptr; HIP_TRY(hipMalloc((void**)&c->d_film, n * sizeof(float))); c->film_n = n; }
-	if (c->rgb8_n < n) { if (c->d_rgb8) hipFree(c->d_rgb8); c->d_rgb8 = nullptr; c->rgb8_n = 0; HIP_TRY(hipMalloc((void**)&c->d_rgb8, n)); c->rgb8_n = n; }
-	if (c->h_rgb8_n < n) { if (c->h_rgb8) hipHostFree(c->h_rgb8); c->h_rgb8 = nullptr; c->h_rgb8_n = 0; if (hipHostMalloc((void**)&c->h_rgb8, n, hipHostMallocDefault) == hipSuccess) c->h_rgb8_n = n; else c->h_rgb8 = nullptr; }
-	if (!c->d_gamma) { HIP_TRY(hipMalloc((void**)&c->d_gamma, 255 * sizeof(float))); HIP_TRY(hipMemcpy(c->d_gamma, host_gamma_thresholds(), 255 * sizeof(float), hipMemcpyHostToDevice)); }
-	int st = render_impl(c, rp, c->d_film, false); if (st != JP_OK) return st;
-	hipLaunchKernelGGL(k_tonemap8, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, (const float*)c->d_film, c->d_rgb8, (const float*)c->d_gamma, n);
-	unsigned char* stage = c->h_rgb8 ? c->h_rgb8 : rgb8_host;
-	HIP_TRY(hipMemcpyAsync(stage, c->d_rgb8, n, hipMemcpyDeviceToHost, c->stream));
-	if (film_host) HIP_TRY(hipMemcpyAsync(film_host, c->d_film, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+	if (const int e = ensure_film(c, n); e != JP_OK) return e;
+	float* const d_film = c->film.get<float>();
+	if (const int e = ensure_rgb8(c, n); e != JP_OK) return e;
+	unsigned char* stage = c->h_rgb8.reserve(n) == hipSuccess ? c->h_rgb8.get<unsigned char>() : rgb8_host;
+	int st = render_impl(c, rp, d_film, false); if (st != JP_OK) return st;
+	tonemap8(c, d_film, n);
+	HIP_TRY(hipMemcpyAsync(stage, c->rgb8.get<void>(), n, hipMemcpyDeviceToHost, c->stream));
+	if (film_host) HIP_TRY(hipMemcpyAsync(film_host, d_film, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	if (stage != rgb8_host) std::memcpy(rgb8_host, stage, n);
 	return JP_OK;
@@ -628,19 +637,13 @@ int jp_bsdf(JpContext* c, const JpBsdfDesc* d, int32_t n, const float* normal, c
 	if (n == 0) return JP_OK;
 	HIP_TRY(hipSetDevice(c->device));
 	// scratch buffers kept in the context (a host FBSDF::Evalf is one event per call: no allocation per event); every copy checked
-	if (c->bsdf_cap < (size_t)n)
-	{
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		if (c->d_bsdf_in) hipFree(c->d_bsdf_in); if (c->d_bsdf_out) hipFree(c->d_bsdf_out); if (c->d_bsdf_fl) hipFree(c->d_bsdf_fl);
-		c->d_bsdf_in = c->d_bsdf_out = nullptr; c->d_bsdf_fl = nullptr; c->bsdf_cap = 0;
-		const size_t cap = std::max<size_t>((size_t)n, 256);
-		if (hipMalloc((void**)&c->d_bsdf_in, cap * 11 * 4) != hipSuccess || hipMalloc((void**)&c->d_bsdf_out, cap * 11 * 4) != hipSuccess || hipMalloc((void**)&c->d_bsdf_fl, cap * 4) != hipSuccess)
-			return fail(JP_ERR_DEVICE, "jp_bsdf: out of device memory");
-		c->bsdf_cap = cap;
-	}
-	float *dn = c->d_bsdf_in, *dwo = dn + 3 * (size_t)n, *dwi = dn + 6 * (size_t)n, *du = dn + 9 * (size_t)n;
-	float *df = c->d_bsdf_out, *dpe = df + 3 * (size_t)n, *dsf = df + 4 * (size_t)n, *dswi = df + 7 * (size_t)n, *dsp = df + 10 * (size_t)n;
-	int* dfl = c->d_bsdf_fl;
+	const size_t cap = std::max<size_t>((size_t)n, 256);
+	if (const int e = reserve_idle(c, c->bsdf_in, cap * 11 * 4); e != JP_OK) return e;
+	if (const int e = reserve_idle(c, c->bsdf_out, cap * 11 * 4); e != JP_OK) return e;
+	if (const int e = reserve_idle(c, c->bsdf_fl, cap * 4); e != JP_OK) return e;
+	float *dn = c->bsdf_in.get<float>(), *dwo = dn + 3 * (size_t)n, *dwi = dn + 6 * (size_t)n, *du = dn + 9 * (size_t)n;
+	float *df = c->bsdf_out.get<float>(), *dpe = df + 3 * (size_t)n, *dsf = df + 4 * (size_t)n, *dswi = df + 7 * (size_t)n, *dsp = df + 10 * (size_t)n;
+	int* dfl = c->bsdf_fl.get<int>();
 	HIP_TRY(hipMemcpyAsync(dn, normal, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(dwo, wo, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipMemcpyAsync(dwi, wi, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(du, u, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
 	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
@@ -659,25 +662,19 @@ int jp_trace(JpContext* c, int32_t n, const float* origin, const float* dir, con
 	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_trace: no scene uploaded");
 	if (n == 0) return JP_OK;
 	HIP_TRY(hipSetDevice(c->device));
-	float *d_o = nullptr, *d_d = nullptr, *d_t0 = nullptr, *d_t1 = nullptr, *d_t = nullptr, *d_n = nullptr; int *d_hit = nullptr, *d_prim = nullptr;
-	int rc = JP_OK;
-	do
-	{
-		if (hipMalloc((void**)&d_o, (size_t)n * 12) != hipSuccess || hipMalloc((void**)&d_d, (size_t)n * 12) != hipSuccess || hipMalloc((void**)&d_t0, (size_t)n * 4) != hipSuccess
-		    || hipMalloc((void**)&d_t1, (size_t)n * 4) != hipSuccess || hipMalloc((void**)&d_t, (size_t)n * 4) != hipSuccess || hipMalloc((void**)&d_n, (size_t)n * 12) != hipSuccess
-		    || hipMalloc((void**)&d_hit, (size_t)n * 4) != hipSuccess || hipMalloc((void**)&d_prim, (size_t)n * 4) != hipSuccess) { rc = fail(JP_ERR_DEVICE, "jp_trace: out of device memory"); break; }
-		hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-		hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-		int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-		const TraceLaunch tk = trace_kernel(c->plan, c->opt.trace_walk);
-		hipLaunchKernelGGL(tk.trace, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
-		hipMemcpyAsync(hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream); hipMemcpyAsync(t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream);
-		hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream); hipMemcpyAsync(normal, d_n, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream);
-		hipError_t e = hipStreamSynchronize(c->stream);
-		if (e != hipSuccess) rc = fail(JP_ERR_DEVICE, std::string("jp_trace: ") + hipGetErrorString(e));
-	} while (0);
-	hipFree(d_o); hipFree(d_d); hipFree(d_t0); hipFree(d_t1); hipFree(d_t); hipFree(d_n); hipFree(d_hit); hipFree(d_prim);
-	return rc;
+	DevBuf b_o, b_d, b_t0, b_t1, b_t, b_n, b_hit, b_prim;           // per-call scratch: freed on every return
+	float *d_o, *d_d, *d_t0, *d_t1, *d_t, *d_n; int *d_hit, *d_prim;
+	HIP_TRY(reserve(b_o, d_o, (size_t)n * 12)); HIP_TRY(reserve(b_d, d_d, (size_t)n * 12)); HIP_TRY(reserve(b_t0, d_t0, (size_t)n * 4)); HIP_TRY(reserve(b_t1, d_t1, (size_t)n * 4));
+	HIP_TRY(reserve(b_t, d_t, (size_t)n * 4)); HIP_TRY(reserve(b_n, d_n, (size_t)n * 12)); HIP_TRY(reserve(b_hit, d_hit, (size_t)n * 4)); HIP_TRY(reserve(b_prim, d_prim, (size_t)n * 4));
+	HIP_TRY(hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
+	const TraceLaunch tk = trace_kernel(c->plan, c->opt.trace_walk);
+	hipLaunchKernelGGL(tk.trace, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
+	HIP_TRY(hipMemcpyAsync(hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(normal, d_n, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return JP_OK;
 }
 
 int jp_get_texture_info(JpContext* c, JpTextureInfo* out)
@@ -698,29 +695,19 @@ int jp_surface(JpContext* c, int32_t n, const float* origin, const float* dir, c
 	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_surface: no scene uploaded");
 	if (n == 0) return JP_OK;
 	HIP_TRY(hipSetDevice(c->device));
-	float *d_in = nullptr, *d_uv = nullptr, *d_a = nullptr; int* d_prim = nullptr;
-	int rc = JP_OK;
-	do
-	{
-		if (hipMalloc((void**)&d_in, (size_t)n * 32) != hipSuccess || hipMalloc((void**)&d_uv, (size_t)n * 8) != hipSuccess || hipMalloc((void**)&d_a, (size_t)n * 12) != hipSuccess
-		    || hipMalloc((void**)&d_prim, (size_t)n * 4) != hipSuccess) { rc = fail(JP_ERR_DEVICE, "jp_surface: out of device memory"); break; }
-		float *d_o = d_in, *d_d = d_in + 3 * (size_t)n, *d_t0 = d_in + 6 * (size_t)n, *d_t1 = d_in + 7 * (size_t)n;
-		hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream);
-		hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream); hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream);
-		const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-		const TraceLaunch tk = trace_kernel(c->plan, 0);                // the walk jp_trace takes by default (what the render's closest-hit rays walk)
-		hipLaunchKernelGGL(tk.surface, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.tv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
-		hipError_t e = hipGetLastError();
-		if (e == hipSuccess)
-		{
-			hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream); hipMemcpyAsync(uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream);
-			hipMemcpyAsync(albedo, d_a, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream);
-			e = hipStreamSynchronize(c->stream);
-		}
-		if (e != hipSuccess) rc = fail(JP_ERR_DEVICE, std::string("jp_surface: ") + hipGetErrorString(e));
-	} while (0);
-	hipFree(d_in); hipFree(d_uv); hipFree(d_a); hipFree(d_prim);
-	return rc;
+	DevBuf b_in, b_uv, b_a, b_prim; float *d_in, *d_uv, *d_a; int* d_prim;   // per-call scratch: freed on every return
+	HIP_TRY(reserve(b_in, d_in, (size_t)n * 32)); HIP_TRY(reserve(b_uv, d_uv, (size_t)n * 8)); HIP_TRY(reserve(b_a, d_a, (size_t)n * 12)); HIP_TRY(reserve(b_prim, d_prim, (size_t)n * 4));
+	float *d_o = d_in, *d_d = d_in + 3 * (size_t)n, *d_t0 = d_in + 6 * (size_t)n, *d_t1 = d_in + 7 * (size_t)n;
+	HIP_TRY(hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
+	const TraceLaunch tk = trace_kernel(c->plan, 0);                // the walk jp_trace takes by default (what the render's closest-hit rays walk)
+	hipLaunchKernelGGL(tk.surface, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.tv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(albedo, d_a, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return JP_OK;
 }
 
 } // extern "C"

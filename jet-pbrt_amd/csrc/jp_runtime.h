@@ -1,5 +1,6 @@
-// jet-pbrt_amd/csrc/jp_runtime.h -- host runtime, part 1 of 3: the context behind the C ABI (include/jetpbrt_amd.h) and its ScenePlan, the options (JpOptions, ABI 7),
-// the probes of the host libm the device reproduces, the gamma-threshold table, jp_create_context / jp_destroy_context / jp_set_options.
+// jet-pbrt_amd/csrc/jp_runtime.h -- host runtime, part 1 of 3: the context behind the C ABI (include/jetpbrt_amd.h), its ScenePlan and the device memory it owns
+// (SceneTables, QueueBufs and single DevBufs of jp_devmem.h: the context's destructor is what frees them), the options (JpOptions, ABI 7), the probes of the host
+// libm the device reproduces, the gamma-threshold table, jp_create_context / jp_destroy_context / jp_set_options.
 // Included by jp_kernels.hip (one translation unit: the kernels above, then this host code that launches them).
 #pragma once
 
@@ -67,28 +68,34 @@ struct ScenePlan
 	int stack_lds_words = 12;
 };
 
+// The device tables of an uploaded scene, owned by the context that uploaded them; the views of the plan (sv, tv, pv) point into them.
+// A lane context's stay empty: it reads its parent's through the plan.
+struct SceneTables
+{
+	DevBuf nodes, prims, meta, mats, mat_type, lights, shade_tab, flat, wide, q4, refbox;
+	DevBuf tex_desc, tex_col, texels, mat_tex, prim_uv;             // jp_upload_scene_textured
+	DevBuf pick_bins, pick_pmf, pick_env;                            // JP_LIGHTS_POWER_ONE (jp_pick.h)
+};
+// The arrays behind a Queues view (the fused schedule's region queues have no hit records and no per-block counts)
+struct QueueBufs { DevBuf ray_o[2], ray_d[2], beta[2], blk_q[2], hit, lacc, sh_o, sh_d, sh_c, blk_sh; };
+
 struct JpContext
 {
 	int device = 0;
 	JpOptions opt{}, opt_env{};                                    // the options in force; their initial value (defaults + environment, jp_create_context)
 	hipStream_t stream = nullptr;
 	int n_cus = 256;
-	ScenePlan plan;                                                // scene: what the upload decided, then the device tables behind it (owned by the context that uploaded them)
-	void *d_flat = nullptr, *d_wide = nullptr, *d_q4 = nullptr;
-	void* d_refbox = nullptr; bool cert_fell_back = false; int cert_eye_leaves = 0;       // certified walk: leaf boxes per primitive; did the last renders leave it (a result of rendering, cleared at upload)
-	void *d_nodes = nullptr, *d_prims = nullptr, *d_meta = nullptr, *d_mats = nullptr, *d_mat_type = nullptr, *d_lights = nullptr, *d_shade_tab = nullptr;
+	ScenePlan plan; SceneTables tab;                               // scene: what the upload decided, then the device tables behind it
+	bool cert_fell_back = false; int cert_eye_leaves = 0;          // certified walk: did the last renders leave it (a result of rendering, cleared at upload)
 	int sincosf_mode = 0, libm_mode = 0;
 	bool build_on_device = false; float build_ms = 0.f; int bvh_height = 0, bvh_nodes = 0;
 	// queues
-	Queues q = {}; unsigned int cap = 0; int planes_alloc = 0; unsigned int blk_alloc = 0; int blocks_per_cu = 16;
-	std::vector<void*> qbufs;
-	float4* d_pix_acc = nullptr; size_t pix_acc_n = 0;
-	int* d_spill = nullptr; size_t spill_words = 0;
-	float* d_film = nullptr; size_t film_n = 0;
-	float *d_bsdf_in = nullptr, *d_bsdf_out = nullptr; int* d_bsdf_fl = nullptr; size_t bsdf_cap = 0;   // jp_bsdf scratch
-	float* d_gamma = nullptr; unsigned char* d_rgb8 = nullptr; size_t rgb8_n = 0; unsigned char* h_rgb8 = nullptr; size_t h_rgb8_n = 0;   // jp_render_rgb8
-	float* h_film = nullptr; size_t h_film_n = 0;                // pinned staging buffer of jp_render (a pageable copy of the film costs ~2 ms)
-	DevCounters* d_cnt = nullptr;
+	Queues q = {}; QueueBufs qb; unsigned int cap = 0; int planes_alloc = 0; unsigned int blk_alloc = 0; int blocks_per_cu = 16;
+	DevBuf pix_acc, spill, film;
+	DevBuf bsdf_in, bsdf_out, bsdf_fl;                             // jp_bsdf scratch
+	DevBuf gamma, rgb8; PinnedBuf h_rgb8;                          // jp_render_rgb8
+	PinnedBuf h_film;                                              // pinned staging buffer of jp_render (a pageable copy of the film costs ~2 ms)
+	DevBuf cnt;                                                    // one DevCounters
 	// timing
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	bool profiling = false;
@@ -99,53 +106,47 @@ struct JpContext
 	// Extra "lanes": the shard's bands are dealt round-robin to L lanes (this context + L - 1 lane contexts) and rendered
 	// concurrently on L streams with L queue sets, so the tail and the launch gap of one lane's kernel are filled by another
 	// lane's and bandwidth-bound kernels overlap instruction-bound ones ("Stream lanes").  A lane shares
-	// the scene tables (not owned) and writes its bands into its own film; the films are merged at the end.
+	// the scene tables (its own `tab` stays empty) and writes its bands into its own film; the films are merged at the end.
 	std::vector<JpContext*> lanes; bool is_lane = false; unsigned long long own_samples = 0; bool bpc_from_env = false;
 	hipEvent_t ev_added = nullptr; bool added_valid = false; int last_lanes = 1;      // lanes used by the last render (1: this context alone)
 	// fused schedule (k_path, jp_path.h): region queues of the resident workgroups, the batch's radiance array, job counters
-	Queues fq = {}; std::vector<void*> fbufs; unsigned int fcap = 0; int fplanes = 0; size_t flacc_n = 0;
-	unsigned int* d_jobs = nullptr; size_t jobs_n = 0;
+	Queues fq = {}; QueueBufs fqb; unsigned int fcap = 0; int fplanes = 0;
+	DevBuf jobs;
 	int last_fused = 0, last_region = 0, last_wgs = 0;
 	// textures (jp_upload_scene_textured): the tables belong to the parent context and reach the lanes through `plan.tv` (its side pointer is
 	// set per launch); every context owns the side array of its own queue set (k_texel -> k_shade_tex, one word per queue position)
 	int n_textures = 0, n_tex_mats = 0; long long texel_bytes = 0; int last_textured = 0;
-	void *d_tex_desc = nullptr, *d_tex_col = nullptr, *d_texels = nullptr, *d_mat_tex = nullptr, *d_prim_uv = nullptr;
-	unsigned int* d_side = nullptr; size_t side_n = 0;
+	DevBuf side;
 	// guides and denoising (jp_denoise.h): the filter's per-pixel records (two colour buffers, the normals), the staging area of the host
 	// variants, event pairs around the kernels, what the last calls did (jp_get_denoise_info)
-	float4 *d_dn_cz[2] = { nullptr, nullptr }, *d_dn_nr = nullptr; size_t dn_n = 0;
-	float* d_dn_stage = nullptr; size_t dn_stage_n = 0;
+	DevBuf dn_cz[2], dn_nr, dn_stage;
 	hipEvent_t dn_ev[2] = { nullptr, nullptr }, gd_ev[2] = { nullptr, nullptr }; bool dn_timed = false, gd_timed = false;
 	int last_dn = 0, last_dn_demod = 0, last_guide_spp = 0; float last_dn_sigma[3] = { 0.f, 0.f, 0.f };
 	// light selection (jp_pick.h): the mode the next upload takes (jp_set_light_sampling), the uploaded scene's table (owned by the parent context,
 	// reaches the lanes through `plan.pv`) and what jp_get_light_info reports
-	int light_mode = JP_LIGHTS_ALL; void *d_pick_bins = nullptr, *d_pick_pmf = nullptr, *d_pick_env = nullptr;
+	int light_mode = JP_LIGHTS_ALL;
 	int n_selectable = 0; double total_weight = 0.0; int last_picked = 0;
 };
 // jp_pick.h (included last) defines the upload's table step
 static int upload_light_table(JpContext* c, const JpScene* s, const std::vector<float>& area);
 
+// a context buffer that kernels in flight may still use: grown only once the stream is idle (nothing happens when the capacity suffices)
+static int reserve_idle(JpContext* c, DevBuf& b, size_t bytes)
+{
+	if (b.bytes() >= bytes) return JP_OK;
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	HIP_TRY(b.reserve(bytes));
+	return JP_OK;
+}
+static int ensure_film(JpContext* c, size_t n_floats) { return reserve_idle(c, c->film, n_floats * sizeof(float)); }
+
 static void free_scene(JpContext* c)
 {
-	void** ps[] = { &c->d_flat, &c->d_wide, &c->d_q4, &c->d_refbox, &c->d_nodes, &c->d_prims, &c->d_meta, &c->d_mats, &c->d_mat_type, &c->d_lights, &c->d_shade_tab,
-	                &c->d_tex_desc, &c->d_tex_col, &c->d_texels, &c->d_mat_tex, &c->d_prim_uv, &c->d_pick_bins, &c->d_pick_pmf, &c->d_pick_env };
-	for (void** p : ps) { if (*p) hipFree(*p); *p = nullptr; }
+	c->tab = SceneTables();
 	c->plan.have_scene = false;
 	c->plan.pv = PickView(); c->plan.pick = false; c->n_selectable = 0; c->total_weight = 0.0;
 	c->plan.tv = TexView(); c->plan.textured = false; c->n_textures = c->n_tex_mats = 0; c->texel_bytes = 0;   // (jp_upload_scene drops the textures of an earlier textured upload)
-	if (c->d_side) hipFree(c->d_side);                             // ... and the side array only textured frames use (callers synchronise first)
-	c->d_side = nullptr; c->side_n = 0;
-}
-static void free_queues(JpContext* c)
-{
-	for (void* p : c->qbufs) hipFree(p);
-	c->qbufs.clear(); c->cap = 0; c->planes_alloc = 0;
-}
-static void free_fused(JpContext* c)
-{
-	for (void* p : c->fbufs) hipFree(p);
-	c->fbufs.clear(); c->fcap = 0; c->fplanes = 0; c->flacc_n = 0;
-	if (c->d_jobs) hipFree(c->d_jobs); c->d_jobs = nullptr; c->jobs_n = 0;
+	c->side.reset();                                               // ... and the side array only textured frames use (callers synchronise first)
 }
 
 // Which build of glibc's sinf / cosf / sincosf does this host run (jp_shading.h, sincosf_libm)?  The reference computes its
@@ -303,8 +304,8 @@ int jp_create_context(int device_id, JpContext** out)
 	hipDeviceProp_t prop;
 	if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) c->n_cus = prop.multiProcessorCount;
 	if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess
-	    || hipMalloc((void**)&c->d_cnt, sizeof(DevCounters)) != hipSuccess)
-	{ delete c; return fail(JP_ERR_DEVICE, "jp_create_context: stream/event/counter allocation failed"); }
+	    || c->cnt.reserve(sizeof(DevCounters)) != hipSuccess)
+	{ jp_destroy_context(c); return fail(JP_ERR_DEVICE, "jp_create_context: stream/event/counter allocation failed"); }
 	c->sincosf_mode = c->opt.libm_sincosf == 0 ? probe_host_sincosf() : (c->opt.libm_sincosf < 0 ? 0 : std::min(2, c->opt.libm_sincosf));
 	{ hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(jp::g_sincosf_mode), &c->sincosf_mode, sizeof(int)); if (e != hipSuccess) { jp_destroy_context(c); return fail(JP_ERR_DEVICE, std::string("jp_create_context: hipMemcpyToSymbol: ") + hipGetErrorString(e)); } }
 	c->libm_mode = c->opt.libm_xbsdf == 0 ? probe_host_libm() : (c->opt.libm_xbsdf < 0 ? 0 : (c->opt.libm_xbsdf & 3));
@@ -357,31 +358,15 @@ int jp_destroy_context(JpContext* c)
 	if (!c) return JP_OK;
 	hipSetDevice(c->device);
 	if (c->stream) hipStreamSynchronize(c->stream);
-	for (JpContext* l : c->lanes) { std::memset(&l->plan.sv, 0, sizeof(l->plan.sv)); jp_destroy_context(l); }
+	for (JpContext* l : c->lanes) jp_destroy_context(l);
 	c->lanes.clear();
-	if (c->ev_added) hipEventDestroy(c->ev_added);
-	if (!c->is_lane) free_scene(c);
-	free_queues(c);
-	free_fused(c);
-	if (c->d_pix_acc) hipFree(c->d_pix_acc);
-	if (c->d_side) hipFree(c->d_side);
-	if (c->d_spill) hipFree(c->d_spill);
-	if (c->d_film) hipFree(c->d_film);
-	if (c->h_film) hipHostFree(c->h_film);
-	if (c->d_bsdf_in) hipFree(c->d_bsdf_in); if (c->d_bsdf_out) hipFree(c->d_bsdf_out); if (c->d_bsdf_fl) hipFree(c->d_bsdf_fl);
-	if (c->d_gamma) hipFree(c->d_gamma);
-	if (c->d_rgb8) hipFree(c->d_rgb8);
-	if (c->h_rgb8) hipHostFree(c->h_rgb8);
-	if (c->d_cnt) hipFree(c->d_cnt);
-	for (void* p : { (void*)c->d_dn_cz[0], (void*)c->d_dn_cz[1], (void*)c->d_dn_nr, (void*)c->d_dn_stage }) if (p) hipFree(p);
-	for (hipEvent_t e : { c->dn_ev[0], c->dn_ev[1], c->gd_ev[0], c->gd_ev[1] }) if (e) hipEventDestroy(e);
+	for (hipEvent_t e : { c->ev_added, c->dn_ev[0], c->dn_ev[1], c->gd_ev[0], c->gd_ev[1], c->ev0, c->ev1 }) if (e) hipEventDestroy(e);
 	for (hipEvent_t e : c->evpool) hipEventDestroy(e);
-	if (c->ev0) hipEventDestroy(c->ev0);
-	if (c->ev1) hipEventDestroy(c->ev1);
 	if (c->stream) hipStreamDestroy(c->stream);
-	delete c;
+	delete c;                                                      // every DevBuf / PinnedBuf member frees its memory
 	return JP_OK;
 }
+long long jp_device_bytes_in_use(void) { return g_device_bytes.load(); }
 
 } // extern "C"
 

@@ -1,5 +1,6 @@
 // jet-pbrt_amd/csrc/jp_upload.h -- host runtime, part 2 of 3: jp_upload_scene -- validation of every index on the host, the device tables (primitive records in
 // leaf order, binary / 8-wide / 4-wide trees, the certified walk's tree over the caller's leaves), the device-side hierarchy build (jp_lbvh.h, jp_ploc.h), the ScenePlan.
+// The tables go into the context's SceneTables (jp_runtime.h) through upload() or are moved there out of the builders' results; nothing here frees by hand.
 // Included by jp_kernels.hip after jp_runtime.h.
 #pragma once
 // ---- scene validation + upload ----------------------------------------------------------------------------------------
@@ -519,8 +520,8 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	if (device_build)
 	{
 		for (int p = 0; p < s->n_primitives; p++) emit_prim(p);
-		void *d_p0 = nullptr, *d_m0 = nullptr;
-		hipError_t e = hipMalloc(&d_p0, prims.size() * sizeof(float4)); if (e == hipSuccess) e = hipMalloc(&d_m0, meta.size() * sizeof(int4));
+		DevBuf p0, m0; float4* d_p0; int4* d_m0;                    // the records in creation order: only the builders read them
+		hipError_t e = reserve(p0, d_p0, prims.size() * sizeof(float4)); if (e == hipSuccess) e = reserve(m0, d_m0, meta.size() * sizeof(int4));
 		if (e == hipSuccess) e = hipMemcpyAsync(d_p0, prims.data(), prims.size() * sizeof(float4), hipMemcpyHostToDevice, c->stream);
 		if (e == hipSuccess) e = hipMemcpyAsync(d_m0, meta.data(), meta.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream);
 		LbvhResult lr; std::vector<int> sorted;
@@ -531,16 +532,12 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 		if (op.bvh_max_leaf >= 1 && op.bvh_max_leaf <= 16) maxLeaf = op.bvh_max_leaf;
 		// [round 3] PLOC clustering (jp_ploc.h) instead of the Karras topology; JETPBRT_DEVICE_TREE=lbvh restores the latter, which also serves
 		// as the fallback should the clustering not finish within its round limit
-		if (e == hipSuccess && ploc) { e = ploc_build(c->stream, (const float4*)d_p0, (const int4*)d_m0, s->n_primitives, maxLeaf, op.ploc_radius, op.ploc_max_rounds, lr, sorted); if (e == hipErrorNotReady) { e = hipSuccess; ploc = false; } }
-		if (e == hipSuccess && !ploc) e = lbvh_build(c->stream, (const float4*)d_p0, (const int4*)d_m0, s->n_primitives, maxLeaf, lr, sorted);
-		if (d_p0) hipFree(d_p0); if (d_m0) hipFree(d_m0);
+		if (e == hipSuccess && ploc) { e = ploc_build(c->stream, d_p0, d_m0, s->n_primitives, maxLeaf, op.ploc_radius, op.ploc_max_rounds, lr, sorted); if (e == hipErrorNotReady) { e = hipSuccess; ploc = false; } }
+		if (e == hipSuccess && !ploc) e = lbvh_build(c->stream, d_p0, d_m0, s->n_primitives, maxLeaf, lr, sorted);
+		p0.reset(); m0.reset();
 		if (e != hipSuccess) return fail(JP_ERR_DEVICE, std::string("jp_upload_scene: device BVH build failed: ") + hipGetErrorString(e));
-		if (lr.height + 2 > 60)
-		{
-			hipFree(lr.d_nodes); hipFree(lr.d_prims); hipFree(lr.d_meta);
-			return fail(JP_ERR_UNSUPPORTED, "jp_upload_scene: device-built BVH is deeper than the 58-entry traversal stack; hand over a host-built hierarchy for this scene");
-		}
-		c->d_nodes = lr.d_nodes; c->d_prims = lr.d_prims; c->d_meta = lr.d_meta;
+		if (lr.height + 2 > 60) return fail(JP_ERR_UNSUPPORTED, "jp_upload_scene: device-built BVH is deeper than the 58-entry traversal stack; hand over a host-built hierarchy for this scene");
+		c->tab.nodes = std::move(lr.nodes); c->tab.prims = std::move(lr.prims); c->tab.meta = std::move(lr.meta);
 		for (int i = 0; i < s->n_primitives; i++) devPrimOf[sorted[i]] = i;
 		height = lr.height; c->build_ms = lr.build_ms;
 		n4nodes = (size_t)4 * lr.n_nodes; n4prims = (size_t)4 * s->n_primitives; nmeta = (size_t)s->n_primitives;
@@ -549,18 +546,18 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 		if (want_wide)
 		{
 			WideResult wr;
-			e = lbvh_build_wide(c->stream, (const float4*)c->d_nodes, s->n_primitives, wr);
+			e = lbvh_build_wide(c->stream, c->tab.nodes.get<float4>(), s->n_primitives, wr);
 			if (e != hipSuccess) return fail(JP_ERR_DEVICE, std::string("jp_upload_scene: device wide-tree build failed: ") + hipGetErrorString(e));
-			if (wr.d_wide) { c->d_wide = wr.d_wide; dev_wide = true; dev_n_wide = wr.n_wide; wide_height = wr.height; use_wide = true; c->build_ms += wr.build_ms; }
+			if (wr.wide) { c->tab.wide = std::move(wr.wide); dev_wide = true; dev_n_wide = wr.n_wide; wide_height = wr.height; use_wide = true; c->build_ms += wr.build_ms; }
 		}
 		// [round 3] ... and the 4-wide tree of Walker<4> for the closest-hit (and shadow) rays, as the host path has it
 		const bool want_q4 = s->n_primitives > 1024 && opt_flag(op.q4, true);
 		if (want_q4)
 		{
 			WideResult qr;
-			e = lbvh_build_q4(c->stream, (const float4*)c->d_nodes, s->n_primitives, qr);
+			e = lbvh_build_q4(c->stream, c->tab.nodes.get<float4>(), s->n_primitives, qr);
 			if (e != hipSuccess) return fail(JP_ERR_DEVICE, std::string("jp_upload_scene: device 4-wide tree build failed: ") + hipGetErrorString(e));
-			if (qr.d_wide) { c->d_q4 = qr.d_wide; dev_q4 = true; dev_n_q4 = qr.n_wide; c->build_ms += qr.build_ms; use_q4 = true; q4_height = qr.height; }
+			if (qr.wide) { c->tab.q4 = std::move(qr.wide); dev_q4 = true; dev_n_q4 = qr.n_wide; c->build_ms += qr.build_ms; use_q4 = true; q4_height = qr.height; }
 		}
 	}
 	c->bvh_height = height; c->bvh_nodes = ref_sem ? s->n_bvh_nodes : (int)(n4nodes / 4);
@@ -617,19 +614,16 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	}
 	// meta.z must index lights (already does); fix nothing else.
 
-	auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-		hipError_t e = hipMalloc(dst, std::max<size_t>(bytes, 16)); if (e != hipSuccess) return e;
-		return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-	};
+	SceneTables& T = c->tab;
 	if (!device_build)
 	{
-		HIP_TRY(up(&c->d_nodes, nodes.data(), nodes.size() * sizeof(float4)));
-		HIP_TRY(up(&c->d_prims, prims.data(), prims.size() * sizeof(float4)));
-		HIP_TRY(up(&c->d_meta, meta.data(), meta.size() * sizeof(int4)));
+		HIP_TRY(upload(T.nodes, nodes.data(), nodes.size() * sizeof(float4)));
+		HIP_TRY(upload(T.prims, prims.data(), prims.size() * sizeof(float4)));
+		HIP_TRY(upload(T.meta, meta.data(), meta.size() * sizeof(int4)));
 	}
-	HIP_TRY(up(&c->d_mats, mats.data(), mats.size() * sizeof(float4)));
-	HIP_TRY(up(&c->d_mat_type, mtype.data(), mtype.size() * sizeof(int)));
-	HIP_TRY(up(&c->d_lights, lights.data(), lights.size() * sizeof(float4)));
+	HIP_TRY(upload(T.mats, mats.data(), mats.size() * sizeof(float4)));
+	HIP_TRY(upload(T.mat_type, mtype.data(), mtype.size() * sizeof(int)));
+	HIP_TRY(upload(T.lights, lights.data(), lights.size() * sizeof(float4)));
 	{   // k_shade's LDS tables as one array (SceneView::shade_tab); the primitive part only when the host has the records
 		std::vector<float4> tabv;
 		if (!pick) tabv.insert(tabv.end(), lights.begin(), lights.begin() + 2 * (size_t)s->n_lights);          // exactly the counts the kernel indexes with (the pick kernels: no light records)
@@ -655,24 +649,24 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 				tabv.push_back(make_float4(n.x, n.y, n.z, 0)); tabv.push_back(make_float4(sv.x, sv.y, sv.z, 0)); tabv.push_back(make_float4(t.x, t.y, t.z, 0));
 			}
 		}
-		HIP_TRY(up(&c->d_shade_tab, tabv.data(), tabv.size() * sizeof(float4)));
+		HIP_TRY(upload(T.shade_tab, tabv.data(), tabv.size() * sizeof(float4)));
 	}
-	if (use_wide && !dev_wide) HIP_TRY(up(&c->d_wide, wide.data(), wide.size() * sizeof(uint32_t)));
-	if ((use_q4 && !dev_q4) || use_cert) HIP_TRY(up(&c->d_q4, q4.data(), q4.size() * sizeof(uint32_t)));
-	if (use_cert) HIP_TRY(up(&c->d_refbox, refbox.data(), refbox.size() * sizeof(float4)));
-	if (!flat.empty()) HIP_TRY(up(&c->d_flat, flat.data(), flat.size() * sizeof(float4)));
+	if (use_wide && !dev_wide) HIP_TRY(upload(T.wide, wide.data(), wide.size() * sizeof(uint32_t)));
+	if ((use_q4 && !dev_q4) || use_cert) HIP_TRY(upload(T.q4, q4.data(), q4.size() * sizeof(uint32_t)));
+	if (use_cert) HIP_TRY(upload(T.refbox, refbox.data(), refbox.size() * sizeof(float4)));
+	if (!flat.empty()) HIP_TRY(upload(T.flat, flat.data(), flat.size() * sizeof(float4)));
 
 	ScenePlan& p = c->plan; SceneView& v = p.sv;                    // from here on: the plan every later launch reads (jp_runtime.h)
-	v.nodes = (const float4*)c->d_nodes; v.n_nodes = (int)(n4nodes / 4);
-	v.prims = (const float4*)c->d_prims; v.meta = (const int4*)c->d_meta; v.n_prims = (int)nmeta;
-	v.mats = (const float4*)c->d_mats; v.mat_type = (const int*)c->d_mat_type; v.n_mats = s->n_materials;
-	v.lights = (const float4*)c->d_lights; v.n_lights = s->n_lights; v.shade_tab = (const float4*)c->d_shade_tab;
+	v.nodes = T.nodes.get<float4>(); v.n_nodes = (int)(n4nodes / 4);
+	v.prims = T.prims.get<float4>(); v.meta = T.meta.get<int4>(); v.n_prims = (int)nmeta;
+	v.mats = T.mats.get<float4>(); v.mat_type = T.mat_type.get<int>(); v.n_mats = s->n_materials;
+	v.lights = T.lights.get<float4>(); v.n_lights = s->n_lights; v.shade_tab = T.shade_tab.get<float4>();
 	v.env_sum = make_float3(envsum[0], envsum[1], envsum[2]); v.n_env = nenv;
 	v.world_radius = s->world_radius; v.cam = s->camera;
-	v.flat = (const float4*)c->d_flat; v.n_flat = (int)(flat.size() / 2);
-	v.wide = (const uint4*)c->d_wide; v.n_wide = dev_wide ? dev_n_wide : (int)(wide.size() / 20);
-	v.q4 = (const uint4*)c->d_q4; v.n_q4 = dev_q4 ? dev_n_q4 : (int)(q4.size() / 16);
-	v.refbox = (const float4*)c->d_refbox; v.cert_pad = cert_pad; v.cert_pad_eye = cert_pad_eye; p.cert = use_cert;
+	v.flat = T.flat.get<float4>(); v.n_flat = (int)(flat.size() / 2);
+	v.wide = T.wide.get<uint4>(); v.n_wide = dev_wide ? dev_n_wide : (int)(wide.size() / 20);
+	v.q4 = T.q4.get<uint4>(); v.n_q4 = dev_q4 ? dev_n_q4 : (int)(q4.size() / 16);
+	v.refbox = T.refbox.get<float4>(); v.cert_pad = cert_pad; v.cert_pad_eye = cert_pad_eye; p.cert = use_cert;
 	p.use_q4 = use_q4; p.q4_shadow = use_q4 && opt_flag(op.q4_shadow, true);   // shadow rays too (measured against the 8-wide tree: k_shadow 53.8 -> 52.7 ms per 512 spp, frame +4 %)
 	p.stack_depth = std::max(2, height + 2);                         // binary / 8-wide / verbatim walks: the tree's height
 	p.stack_depth_q4 = (use_q4 || use_cert) ? 3 * q4_height + 2 : 0;   // 4-wide walks (Walker<4> / <6>): a node pushes up to three children
@@ -807,21 +801,17 @@ extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const Jp
 				const float* u = t->tri_uv + 6 * (size_t)s->prim_shape_index[p];
 				for (int k = 0; k < 3; k++) puv[3 * (size_t)p + k] = make_float2(u[2 * k], u[2 * k + 1]);
 			}
-	auto put = [&](void** d, const void* src, size_t bytes) -> bool {
-		if (bytes == 0) return true;
-		if (hipMalloc(d, bytes) != hipSuccess) return false;
-		return hipMemcpy(*d, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-	};
-	if (!put(&c->d_tex_desc, desc.data(), desc.size() * sizeof(int4)) || !put(&c->d_tex_col, col.data(), col.size() * sizeof(float4))
-	    || !put(&c->d_texels, texels.data(), texels.size() * sizeof(unsigned int)) || !put(&c->d_mat_tex, mt.data(), mt.size() * sizeof(int))
-	    || !put(&c->d_prim_uv, puv.data(), puv.size() * sizeof(float2)))
+	SceneTables& T = c->tab;
+	if (upload(T.tex_desc, desc.data(), desc.size() * sizeof(int4)) != hipSuccess || upload(T.tex_col, col.data(), col.size() * sizeof(float4)) != hipSuccess
+	    || upload(T.texels, texels.data(), texels.size() * sizeof(unsigned int)) != hipSuccess || upload(T.mat_tex, mt.data(), mt.size() * sizeof(int)) != hipSuccess
+	    || upload(T.prim_uv, puv.data(), puv.size() * sizeof(float2)) != hipSuccess)
 	{
 		free_scene(c);
 		return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: out of device memory for the texture tables");
 	}
 	TexView& tv = c->plan.tv; tv = TexView();
-	tv.desc = (const int4*)c->d_tex_desc; tv.col = (const float4*)c->d_tex_col; tv.texels = (const unsigned int*)c->d_texels;
-	tv.mat_tex = (const int*)c->d_mat_tex; tv.prim_uv = (const float2*)c->d_prim_uv;
+	tv.desc = T.tex_desc.get<int4>(); tv.col = T.tex_col.get<float4>(); tv.texels = T.texels.get<unsigned int>();
+	tv.mat_tex = T.mat_tex.get<int>(); tv.prim_uv = T.prim_uv.get<float2>();
 	c->plan.textured = true; c->n_textures = nt; c->n_tex_mats = ntm; c->texel_bytes = (long long)texels.size() * 4;
 	return JP_OK;
 }
