@@ -214,7 +214,8 @@ typedef struct JpOptions {
     /* ---- diagnostics (tests, tools/) ---- */
     int32_t trace_walk;          /* jp_trace on a large scene walks: 0 what the render's closest-hit rays walk, 1 the binary tree, 2 the 8-wide tree, 3 the caller's tree verbatim */
     float   box_pad;             /* every box of a host-built tree grows by this many scene units (fringe census, tools/gpu_fringe_census.py)  */
-    int32_t reserved[8];
+    int32_t reserved[8];         /* [0] == 1: the next jp_render* uses the generic kernels (every shape, light and material alternative compiled in) even
+                                    where the uploaded scene's feature set allows a lean instance -- tests and A/B runs; same films either way.  [1..7]: 0 */
 } JpOptions;
 
 typedef struct JpContext JpContext;

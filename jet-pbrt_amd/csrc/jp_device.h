@@ -72,6 +72,20 @@ struct SceneView
 	const float4* refbox; float cert_pad, cert_pad_eye;   // (cert_pad_eye: the slack for rays from the camera position, which the edge-on flags cover)  // reference semantics, certified walk (Walker<6>): per device primitive the exact box of its leaf in the caller's tree (min, max); distance-cull slack c in tmax + c * tmax^2
 };
 
+// ---- feature sets ("Feature sets") ----------------------------------------------------------------------------
+// What a scene can contain, as a compile-time parameter of the tiny-scene kernels (k_extend<2>, k_shadow<2>, k_shade with the tables in
+// LDS): an absent alternative is compiled out with `if constexpr`, every remaining one is the same code in the same order, so a lean
+// instance computes bit for bit what the generic one does on the scenes it is selected for.  The upload records what the scene holds
+// (ScenePlan::shape_mask / light_mask / light_shape_mask / class_mask), the selectors of jp_render.h pick the instance.
+//   kCurved      spheres or disks among the primitives (false: triangles and rectangles only)
+//   kOtherLights environment, point or direction lights, or area lights on spheres / disks (false: area lights on flat shapes only)
+//   kDelta       mirror, glass or plastic materials (false: matte and metal only -- no delta closure, no plastic draw)
+template <bool kCurved, bool kOtherLights, bool kDelta>
+struct Feat { static constexpr bool curved = kCurved, other_lights = kOtherLights, delta = kDelta; };
+typedef Feat<true, true, true> FeatAll;                 // today's kernels: the fallback for every scene outside the lean sets
+typedef Feat<false, true, true> FeatFlat;               // the traversal kernels only look at the shapes
+typedef Feat<false, false, false> FeatLean;             // flat shapes, area lights on them, matte / metal
+
 // ---- shape intersection: exact restatements ---------------------------------------------------------------------
 // FTriangle::Intersect shape.h:291-327.  On acceptance `tmax` shrinks (ray.SetMaxT).
 __device__ __forceinline__ bool tri_hit(V3 p0, V3 p1, V3 p2, V3 n, V3 o, V3 d, float tmin, float& tmax)
@@ -144,7 +158,7 @@ __device__ __forceinline__ bool disk_hit(V3 c, float r, V3 n, V3 o, V3 d, float 
 // One primitive record against the ray; FPrimitive::Intersect primitive.h:39-48.  kS = record stride in float4
 // units: 4 in global memory, 5 in LDS (the 80-byte stride spreads randomly indexed 64-byte records over all
 // bank groups instead of four).
-template <int kS, typename PrimPtr>
+template <int kS, typename F = FeatAll, typename PrimPtr>
 __device__ __forceinline__ bool prim_hit(PrimPtr prims, int pi, V3 o, V3 d, float tmin, float& tmax)
 {
 	// all four quads of the record are requested together (no load waits on the shape type): one memory latency per
@@ -152,8 +166,11 @@ __device__ __forceinline__ bool prim_hit(PrimPtr prims, int pi, V3 o, V3 d, floa
 	const float4 g0 = prims[kS * pi + 0], g1 = prims[kS * pi + 1], g2 = prims[kS * pi + 2], g3 = prims[kS * pi + 3];
 	const int type = __float_as_int(g3.w);
 	if (type == JP_SHAPE_TRIANGLE) return tri_hit(xyz(g0), xyz(g1), xyz(g2), xyz(g3), o, d, tmin, tmax);
-	if (type == JP_SHAPE_SPHERE) return sph_hit(xyz(g0), g0.w, o, d, tmin, tmax);
-	if (type == JP_SHAPE_DISK) return disk_hit(xyz(g0), g0.w, xyz(g1), o, d, tmin, tmax);
+	if constexpr (F::curved)
+	{
+		if (type == JP_SHAPE_SPHERE) return sph_hit(xyz(g0), g0.w, o, d, tmin, tmax);
+		if (type == JP_SHAPE_DISK) return disk_hit(xyz(g0), g0.w, xyz(g1), o, d, tmin, tmax);
+	}
 	return rect_hit(xyz(g0), xyz(g1), xyz(g2), mk(g0.w, g1.w, g2.w), xyz(g3), o, d, tmin, tmax);
 }
 
@@ -329,7 +346,7 @@ __device__ __forceinline__ typename FlatMask<k64>::type flat_boxes(const float4*
 	return mask;
 }
 
-template <bool kAnyHit, bool k64, int kS, typename PrimPtr>
+template <bool kAnyHit, bool k64, int kS, typename F = FeatAll, typename PrimPtr>
 __device__ __forceinline__ int flat_prims(typename FlatMask<k64>::type mask, PrimPtr prims, V3 o, V3 d, float tmin, float& tmax)
 {
 	int hit = -1;
@@ -340,16 +357,16 @@ __device__ __forceinline__ int flat_prims(typename FlatMask<k64>::type mask, Pri
 	{
 		const int p = (k64 ? __ffsll((unsigned long long)mask) : __ffs((int)mask)) - 1;
 		mask &= mask - 1;
-		if (prim_hit<kS>(prims, p, o, d, tmin, tmax)) { hit = p; if (kAnyHit) return hit; }
+		if (prim_hit<kS, F>(prims, p, o, d, tmin, tmax)) { hit = p; if (kAnyHit) return hit; }
 	}
 	return hit;
 }
 
-template <bool kAnyHit, int kS, typename PrimPtr>
+template <bool kAnyHit, int kS, typename F = FeatAll, typename PrimPtr>
 __device__ __forceinline__ int traverse_flat(const float4* flat_g, int n_flat, int n_prims, PrimPtr prims, V3 o, V3 d, float tmin, float& tmax)
 {
-	if (n_prims > 32) return flat_prims<kAnyHit, true, kS>(flat_boxes<true>(flat_g, n_flat, o, d, tmin, tmax), prims, o, d, tmin, tmax);   // wave-uniform branch
-	return flat_prims<kAnyHit, false, kS>(flat_boxes<false>(flat_g, n_flat, o, d, tmin, tmax), prims, o, d, tmin, tmax);
+	if (n_prims > 32) return flat_prims<kAnyHit, true, kS, F>(flat_boxes<true>(flat_g, n_flat, o, d, tmin, tmax), prims, o, d, tmin, tmax);   // wave-uniform branch
+	return flat_prims<kAnyHit, false, kS, F>(flat_boxes<false>(flat_g, n_flat, o, d, tmin, tmax), prims, o, d, tmin, tmax);
 }
 
 // Large scenes: 8-wide BVH with quantised child boxes (after Ylitie, Karras, Laine: "Efficient Incoherent Ray Traversal

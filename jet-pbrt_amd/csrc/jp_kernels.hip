@@ -107,7 +107,7 @@ __device__ unsigned long long g_shade_t[16];
 #else
 #define JP_TT(i) do { } while (0)
 #endif
-template <int kMode>
+template <int kMode, typename F = FeatAll>                       // F: the scene's feature set (jp_device.h); only the tiny-scene access looks at it
 struct SceneAccess;
 template <> struct SceneAccess<0>
 {
@@ -131,7 +131,7 @@ template <> struct SceneAccess<1>
 	template <bool kAnyHit> __device__ __forceinline__ int trace(const SceneView&, V3 o, V3 d, float tmin, float& tmax) const
 	{ return traverse<kAnyHit, 5>(nodes, prims, o, d, tmin, tmax, stack); }
 };
-template <> struct SceneAccess<2>
+template <typename F> struct SceneAccess<2, F>
 {
 	float4* prims;
 	__device__ __forceinline__ SceneAccess(const SceneView& sc, int)
@@ -141,7 +141,7 @@ template <> struct SceneAccess<2>
 		__syncthreads();
 	}
 	template <bool kAnyHit> __device__ __forceinline__ int trace(const SceneView& sc, V3 o, V3 d, float tmin, float& tmax) const
-	{ return traverse_flat<kAnyHit, 5>(sc.flat, sc.n_flat, sc.n_prims, prims, o, d, tmin, tmax); }
+	{ return traverse_flat<kAnyHit, 5, F>(sc.flat, sc.n_flat, sc.n_prims, prims, o, d, tmin, tmax); }
 };
 
 template <> struct SceneAccess<3>
@@ -179,10 +179,10 @@ template <> struct SceneAccess<5>
 // ---------------------------------------------------------------------------------------------------------------------
 // k_extend: FScene::Intersect (scene.cc:25-33) for every ray of this block's region
 // ---------------------------------------------------------------------------------------------------------------------
-template <int kMode>
+template <int kMode, typename F = FeatAll>
 __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int cur, int depth, DevCounters* cnt)
 {
-	SceneAccess<kMode> acc(sc, depth);
+	SceneAccess<kMode, F> acc(sc, depth);
 	const unsigned int b = blockIdx.x, n = q.blk_q[cur][b], rbase = b * q.R;
 	if (b == 0 && threadIdx.x == 0) { cnt->closest += cnt->n_queue[cur]; cnt->n_queue[cur ^ 1] = 0; cnt->n_shadow = 0; }
 	unsigned int h = 0;
@@ -226,7 +226,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 // draws, its contribution divided by its pmf.  The light records stay in global memory (the LDS tables start at the materials: an emissive mesh of
 // 70k triangles has 2.2 MB of them), the one picked light's two float4 come from HBM / L2, and the miss branch walks pv.env, the short list of
 // non-black environment lights, instead of every light.
-template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick>
+// F: the scene's feature set (jp_device.h, DESIGN.md "Feature sets"); the lean instances exist for k_shade<true, true, true, kSort> only.
+template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, typename F = FeatAll>
 __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv)
 {
 	static_assert(kTab || !kPrims, "k_shade: primitive records in LDS only together with the tables");
@@ -412,7 +413,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 				const int type = __float_as_int(g3.w);
 				p = o + h.x * d;                                                      // ray(distance) geometry.h:412-416
 				if (type == JP_SHAPE_TRIANGLE) N = xyz(g3);
-				else if (type == JP_SHAPE_RECTANGLE) { nflip = !(dot(xyz(g3), d) <= 0); N = nflip ? -xyz(g3) : xyz(g3); }   // shape.h:427
+				else if (!F::curved || type == JP_SHAPE_RECTANGLE) { nflip = !(dot(xyz(g3), d) <= 0); N = nflip ? -xyz(g3) : xyz(g3); }   // shape.h:427
 				else if (type == JP_SHAPE_DISK) N = xyz(prims[4 * pi + 1]);                           // shape.h:214
 				else { const float4 g0 = prims[4 * pi]; N = normalize(p - xyz(g0)); tabframe = false; }   // shape.h:521
 				hitprim = pi;
@@ -423,7 +424,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					if (dot(N, wo) > 0.f) Le = xyz(lights[2 * meta.z]);
 				}
 			}
-			else if (bounce == 0 || spec)                                             // integrator.cc:334-336, light.h:300-303
+			else if (F::other_lights && (bounce == 0 || spec))                        // integrator.cc:334-336, light.h:300-303
 			{
 				// L += beta * Le for each infinite light in order; folded on the host only when there is at most one
 				if (kPick)
@@ -459,13 +460,13 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 				{
 					float up = 0.f;
 					const int mtype = mat_type[mat];
-					if (mtype == JP_MAT_PLASTIC) up = rngf(rc, key, dim++);   // material.cc:14
+					if (F::delta && mtype == JP_MAT_PLASTIC) up = rngf(rc, key, dim++);   // material.cc:14
 					if (kTex && sw != 0u) make_closure_tex(mats, mtype, mat, up, tex_color(tv, sw), c);
-					else make_closure(mats, mtype, mat, up, c);
+					else make_closure<F>(mats, mtype, mat, up, c);
 #ifdef JP_DBG_SKIP_FRAME
 					fr.n = N; fr.s = mk(N.y, N.z, N.x); fr.t = mk(N.z, N.x, N.y);
 #else
-					if (kPrims && tabframe)
+					if (kPrims && (!F::curved || tabframe))
 					{   // FFrame(normal) geometry.h:345-349 from the table the host computed with the same operations in the same order;
 						// for the far side of a rectangle n and t change sign and s does not (every product and quotient keeps its
 						// magnitude; |n.x| > 0.99 picks the same helper axis)
@@ -475,7 +476,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					else fr = frame_from_z(N);
 #endif
 					shaded = true;
-					wantNee = !is_delta(c);
+					wantNee = !is_delta<F>(c);
 #ifdef JP_DBG_SKIP_NEE
 					wantNee = false;
 #endif
@@ -514,14 +515,15 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					const float4 lrad = lights[2 * li];
 					if (isblack(xyz(lrad))) continue;                                   // Li would be black (integrator.cc:362): skip the evaluation, keep the draws
 					const float ux = rngf(rc, key, d0), uy = rngf(rc, key, d0 + 1);
-					LightSample ls = sample_li(sc, prims, lights, li, p, N, ux, uy);
+					LightSample ls = sample_li<F>(sc, prims, lights, li, p, N, ux, uy);
 					if (isblack(ls.Li) || ls.pdf == 0.f) continue;
-					const V3 f = eval_local(c, wo, to_local(fr, ls.wi));               // FBSDF::Evalf bsdf.h:284-287
+					const V3 f = eval_local<F>(c, wo, to_local(fr, ls.wi));            // FBSDF::Evalf bsdf.h:284-287
 					if (isblack(f)) continue;
 					// FScene::Occluded scene.h:36-47: dir and distance recomputed from the sampled position
 					// (for an area light Normalize(target - position) is the very expression that produced ls.wi)
-					const V3 sdir = __float_as_int(lrad.w) == JP_LIGHT_AREA ? ls.wi : normalize(ls.pos - p);
-					const float dist = ls.dist >= 0.f ? ls.dist : len(p - ls.pos);
+					// (area lights on flat shapes only: the sampler kept the length of every sample that gets here -- pdf != 0 means dist2 != 0)
+					const V3 sdir = (!F::other_lights || __float_as_int(lrad.w) == JP_LIGHT_AREA) ? ls.wi : normalize(ls.pos - p);
+					const float dist = (!F::other_lights || ls.dist >= 0.f) ? ls.dist : len(p - ls.pos);
 					V3 contrib = cmul(cmul(beta, f), ls.Li) * absdot(ls.wi, N) / ls.pdf;   // integrator.cc:369
 					if (kPick) contrib = contrib / pmf;                                 // the one-light estimator: a pmf of 1 changes no bit
 					if (k < rc.n_planes)
@@ -551,7 +553,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 		{
 			// ---- BSDF sample (integrator.cc:375-379) ----
 			const float ux = rngf(rc, key, dim), uy = rngf(rc, key, dim + 1); dim += 2;
-			BsdfSample bs = sample_local(c, wo, ux, uy);
+			BsdfSample bs = sample_local<F>(c, wo, ux, uy);
 			bs.wi = to_world(fr, bs.wi);                                              // bsdf.h:295-301
 			if (!(isblack(bs.f) || bs.pdf == 0.f))
 			{
@@ -628,11 +630,11 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 		if (run_sh) atomicAdd(&cnt->n_shadow, run_sh);
 	}
 }
-template <bool kTab, bool kPrims, bool kStage, bool kSort>
+template <bool kTab, bool kPrims, bool kStage, bool kSort, typename F = FeatAll>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt)
 {
 	const TexView tv = {}; const PickView pv = {};
-	shade_body<kTab, kPrims, kStage, kSort, false, false>(sc, q, rc, cur, cnt, tv, pv);
+	shade_body<kTab, kPrims, kStage, kSort, false, false, F>(sc, q, rc, cur, cnt, tv, pv);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -640,13 +642,13 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, Rend
 // (integrator.cc:367-370).  One lane owns a path's entry, so the path's radiance is summed in exactly the
 // reference's order and the film is run-to-run deterministic (no float atomics).
 // ---------------------------------------------------------------------------------------------------------------------
-template <int kMode>
+template <int kMode, typename F = FeatAll>
 __global__ void __launch_bounds__(JP_BLOCK, 4) k_shadow(SceneView sc, Queues q, RenderConst rc, int depth, DevCounters* cnt)
 {
 #ifdef JP_TRAV_TIMING
 	unsigned long long t_acc[10] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 }, t_last = __builtin_amdgcn_s_memtime();
 #endif
-	SceneAccess<kMode> acc(sc, depth);
+	SceneAccess<kMode, F> acc(sc, depth);
 	const unsigned int b = blockIdx.x, E = q.blk_sh[b], rbase = b * q.R;
 	JP_TT(0);                                                      // [0] primitive records to LDS, region fill
 	unsigned int rays = 0, occ = 0;
@@ -682,7 +684,7 @@ __global__ void __launch_bounds__(JP_BLOCK, 4) k_shadow(SceneView sc, Queues q, 
 			{
 				const unsigned int m = flat_boxes<false>(sc.flat, sc.n_flat, xyz(so), dir, 0.001f, tmax);
 				JP_TT(4);                                          // [4] box phase
-				hit = flat_prims<true, false, 5>(m, acc.prims, xyz(so), dir, 0.001f, tmax);
+				hit = flat_prims<true, false, 5, F>(m, acc.prims, xyz(so), dir, 0.001f, tmax);
 				JP_TT(5);                                          // [5] primitive phase
 			}
 			else hit = acc.template trace<true>(sc, xyz(so), dir, 0.001f, tmax);

@@ -85,6 +85,18 @@ inline int deepest_walk(const ScenePlan& p) { return std::max(std::max(p.stack_d
 // spill area of the walkers' stacks: the words G workgroups' threads may need beyond the ones kept in LDS (+1: Walker<4> keeps one LDS word as a dump slot)
 inline size_t spill_need(const ScenePlan& p, int deep, unsigned int G) { return deep >= p.stack_lds_words ? (size_t)(deep - p.stack_lds_words + 1) * G * JP_BLOCK : 1; }
 
+// Feature sets (jp_device.h): the tiny-scene kernels exist a second time without the code a scene of flat shapes (FeatFlat: k_extend<2>,
+// k_shadow<2>) lit by area lights on them and made of matte / metal only (FeatLean: k_shade<true, true, true, kSort>) cannot reach.  The plan says what the
+// scene holds; `generic` (JpOptions::reserved[0] == 1: tests, A/B runs) keeps the instances with everything in them, which every other scene gets anyway.
+inline bool flat_shapes_only(int shape_mask) { return (shape_mask & ~((1 << JP_SHAPE_TRIANGLE) | (1 << JP_SHAPE_RECTANGLE))) == 0; }
+inline bool lean_traversal(const ScenePlan& p, bool generic) { return !generic && p.trav_mode == 2 && flat_shapes_only(p.shape_mask); }
+inline bool lean_shading(const ScenePlan& p, bool generic)
+{
+	const int delta_classes = (2 << JP_MAT_MIRROR) | (2 << JP_MAT_GLASS) | (2 << JP_MAT_PLASTIC);      // class_mask: bit 0 none, bit 1 + JP_MAT_*
+	return !generic && p.shade_prims_in_lds && p.stage_nee && flat_shapes_only(p.shape_mask) && (p.light_mask & ~(1 << JP_LIGHT_AREA)) == 0
+	    && flat_shapes_only(p.light_shape_mask) && (p.class_mask & delta_classes) == 0;
+}
+
 typedef void (*ExtendKernel)(SceneView, Queues, int, int, DevCounters*);
 typedef void (*ExtendRefillKernel)(SceneView, Queues, int, int, int*, DevCounters*);
 struct ExtendLaunch { ExtendRefillKernel refill; ExtendKernel plain; size_t lds; int words; };   // one of the two kernels; words: of the stack, kept in LDS (refill) / in all (plain)
@@ -93,8 +105,9 @@ template <int M> ExtendRefillKernel extend_refill(const ScenePlan& p)
 	static const ExtendRefillKernel k[3][2] = { { k_extend_persist<M, 8, false>, k_extend_persist<M, 8, true> }, { k_extend_persist<M, 16, false>, k_extend_persist<M, 16, true> }, { k_extend_persist<M, 32, false>, k_extend_persist<M, 32, true> } };
 	return k[refill_row(p)][p.vote];
 }
-ExtendLaunch extend_kernel(const ScenePlan& p)
+ExtendLaunch extend_kernel(const ScenePlan& p, bool generic)
 {
+	if (lean_traversal(p, generic)) return { nullptr, k_extend<2, FeatFlat>, p.lds_bytes, p.stack_depth };
 	if (!refill_walks(p)) return { nullptr, p.trav_mode == 5 ? k_extend<5> : (p.trav_mode == 2 ? k_extend<2> : (p.trav_mode == 1 ? k_extend<1> : k_extend<0>)), p.lds_bytes, p.stack_depth };
 	const int words = std::min(extend_depth(p), p.stack_lds_words);
 	const ExtendRefillKernel k = p.trav_mode == 5 ? (p.cert ? extend_refill<6>(p) : extend_refill<5>(p)) : (p.use_q4 ? extend_refill<4>(p) : extend_refill<0>(p));
@@ -109,10 +122,11 @@ template <int M> ShadowRefillKernel shadow_refill(const ScenePlan& p)
 	static const ShadowRefillKernel k[3][2] = { { k_shadow_persist<M, 8, false>, k_shadow_persist<M, 8, true> }, { k_shadow_persist<M, 16, false>, k_shadow_persist<M, 16, true> }, { k_shadow_persist<M, 32, false>, k_shadow_persist<M, 32, true> } };
 	return k[refill_row(p)][p.vote];
 }
-ShadowLaunch shadow_kernel(const ScenePlan& p, unsigned int R)         // R: slots per region (Queues::R), whose shadow bitmap shares the refill kernel's LDS with the stacks
+ShadowLaunch shadow_kernel(const ScenePlan& p, unsigned int R, bool generic)   // R: slots per region (Queues::R), whose shadow bitmap shares the refill kernel's LDS with the stacks
 {
 	const int words = std::min(shadow_depth(p), p.stack_lds_words);
 	const size_t plds = (size_t)words * JP_BLOCK * sizeof(int) + (((size_t)R * p.n_planes + 31) / 32) * 4 * (p.cert ? 2 : 1);   // (certified walk: a second bitmap, the rays without a certificate)
+	if (lean_traversal(p, generic)) return { nullptr, k_shadow<2, FeatFlat>, p.lds_bytes, p.stack_depth, p.cert };
 	if (!refill_walks(p) || plds > 64 * 1024)                         // one ray per lane: these kernels walk a certified scene's caller's tree verbatim
 		return { nullptr, p.trav_mode == 3 ? k_shadow<3> : (p.trav_mode == 5 ? k_shadow<5> : (p.trav_mode == 2 ? k_shadow<2> : (p.trav_mode == 1 ? k_shadow<1> : k_shadow<0>))), p.trav_mode == 3 ? p.lds_bytes_shadow : p.lds_bytes, p.stack_depth, p.cert };
 	const ShadowRefillKernel k = p.trav_mode == 5 ? (p.cert ? shadow_refill<6>(p) : shadow_refill<5>(p)) : (p.q4_shadow ? shadow_refill<4>(p) : (p.trav_mode == 3 ? shadow_refill<3>(p) : shadow_refill<0>(p)));
@@ -127,8 +141,14 @@ template <bool kTab, bool kPrims, bool kStage> ShadeKernels shade_row(bool sort)
 	ShadeKernels k = { sort ? k_shade<kTab, kPrims, kStage, true> : k_shade<kTab, kPrims, kStage, false>, sort ? k_shade_tex<kTab, kPrims, kStage, true> : k_shade_tex<kTab, kPrims, kStage, false> };
 	return k;
 }
-ShadeKernels shade_kernels(const ScenePlan& p)
+ShadeKernels shade_kernels(const ScenePlan& p, bool generic)
 {
+	if (lean_shading(p, generic))
+	{   // the textured twin stays generic (a textured scene is outside the lean sets' measurements)
+		ShadeKernels k = shade_row<true, true, true>(p.shade_sort);
+		k.plain = p.shade_sort ? k_shade<true, true, true, true, FeatLean> : k_shade<true, true, true, false, FeatLean>;
+		return k;
+	}
 	if (p.shade_prims_in_lds) return p.stage_nee ? shade_row<true, true, true>(p.shade_sort) : shade_row<true, true, false>(p.shade_sort);
 	if (p.tables_in_lds) return p.stage_nee ? shade_row<true, false, true>(p.shade_sort) : shade_row<true, false, false>(p.shade_sort);
 	return shade_row<false, false, false>(p.shade_sort);
@@ -232,7 +252,8 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		rc.compact = (p.trav_mode != 2 && p.trav_mode != 1 && npix % JP_BLOCK == 0) ? 1 : 0;
 		if (c->opt.compact_regions != 0) rc.compact = (c->opt.compact_regions > 0 && npix % JP_BLOCK == 0) ? 1 : 0;
 		const int grid = (int)G;
-		const ExtendLaunch ek = extend_kernel(p); const ShadowLaunch sk = shadow_kernel(p, R); const ShadeKernels hk = shade_kernels(p); const OtherKernel ok = other_kernel(p);
+		const bool generic = c->opt.reserved[0] == 1;                // JpOptions::reserved[0]: the kernels with every feature in them, whatever the scene holds
+		const ExtendLaunch ek = extend_kernel(p, generic); const ShadowLaunch sk = shadow_kernel(p, R, generic); const ShadeKernels hk = shade_kernels(p, generic); const OtherKernel ok = other_kernel(p);
 		const ShadePickKernels pk = p.pick ? shade_pick_kernels(p) : ShadePickKernels{ nullptr, nullptr };
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{

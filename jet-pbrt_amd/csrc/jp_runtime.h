@@ -63,6 +63,7 @@ struct ScenePlan
 	int n_planes = 1; bool has_null_material = false;
 	bool tables_in_lds = false, stage_nee = false; size_t shade_lds_bytes = 0;
 	int class_mask = 0x3f; bool shade_sort = false;                                     // k_shade partitions its tiles by material class (scenes with more than one material kind)
+	int shape_mask = 0xf, light_mask = 0xf, light_shape_mask = 0xf;                    // feature set: JP_SHAPE_* of the primitives, JP_LIGHT_* of the non-black lights, JP_SHAPE_* under the non-black area lights (bit = 1 << value); materials: class_mask
 	// lane refill kernels: traversal-stack words per thread kept in LDS, the rest spills to global memory (WalkStack).  Measured on the
 	// 280k-triangle scene (tree height 24): 8 / 12 / 16 words 1922 / 1926 / 1922 Msamples/s, 20 words or the whole stack 1634 / 1692.
 	int stack_lds_words = 12;

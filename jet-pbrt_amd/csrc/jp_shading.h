@@ -138,7 +138,9 @@ struct Closure
 	int fresnel; V3 feta, fk;
 	float lam_o;            // microfacet: Lambda(wo), the same value in every Evalf / Pdf of one shading event (closure_set_wo)
 };
-__device__ __forceinline__ bool is_delta(const Closure& c) { return c.kind == CL_MIRROR || c.kind == CL_FRESNEL_SPECULAR; }
+// F (here and below): the scene's feature set (jp_device.h); the default is "everything present"
+template <typename F = FeatAll>
+__device__ __forceinline__ bool is_delta(const Closure& c) { if constexpr (!F::delta) return false; else return c.kind == CL_MIRROR || c.kind == CL_FRESNEL_SPECULAR; }
 
 struct BsdfSample { V3 f, wi; float pdf; int flags; };
 
@@ -212,9 +214,10 @@ __device__ __forceinline__ V3 fresnel_conductor(float cosI, V3 etai, V3 etat, V3
 	return (Rp + Rs) * 0.5f;
 }
 
+template <typename F = FeatAll>
 __device__ __forceinline__ V3 fresnel_eval(const Closure& c, float cosI)                      // bsdf.cc:15-24
 {
-	if (c.fresnel == FR_CONDUCTOR) return fresnel_conductor(fabsf(cosI), splat(1.f), c.feta, c.fk);
+	if (!F::delta || c.fresnel == FR_CONDUCTOR) return fresnel_conductor(fabsf(cosI), splat(1.f), c.feta, c.fk);
 	return splat(fresnel_dielectric(cosI, 1.5f, 1.f));                                        // material.cc:21
 }
 
@@ -289,6 +292,7 @@ __device__ __forceinline__ V3 tr_sample_wh(const Closure& c, V3 wo, float u0, fl
 	return wh;
 }
 
+template <typename F = FeatAll>
 __device__ __forceinline__ V3 eval_local(const Closure& c, V3 wo, V3 wi)
 {
 	if (c.kind == CL_LAMBERT)                                                                 // bsdf.h:347-355
@@ -296,7 +300,7 @@ __device__ __forceinline__ V3 eval_local(const Closure& c, V3 wo, V3 wi)
 		if (!same_hemi(wo, wi)) return splat(0);
 		return c.c0 * JP_INV_PI;
 	}
-	if (c.kind == CL_MICROFACET)                                                              // bsdf.cc:35-51
+	if (!F::delta || c.kind == CL_MICROFACET)                                                 // bsdf.cc:35-51 (without delta materials: the only other kind)
 	{
 		float cosO = fabsf(wo.z), cosI = fabsf(wi.z);
 		V3 wh = wi + wo;
@@ -304,12 +308,13 @@ __device__ __forceinline__ V3 eval_local(const Closure& c, V3 wo, V3 wi)
 		if (wh.x == 0 && wh.y == 0 && wh.z == 0) return splat(0);
 		wh = normalize(wh);
 		V3 ff = (dot(wh, mk(0, 0, 1)) < 0) ? -wh : wh;
-		V3 F = fresnel_eval(c, dot(wi, ff));
-		return cmul(c.c0 * tr_D(c, wh) * tr_G(c, wi), F) / (4 * cosI * cosO);
+		V3 Fr = fresnel_eval<F>(c, dot(wi, ff));
+		return cmul(c.c0 * tr_D(c, wh) * tr_G(c, wi), Fr) / (4 * cosI * cosO);
 	}
 	return splat(0);                                                                          // delta BSDFs
 }
 
+template <typename FS = FeatAll>                            // (FS: the feature set; F is the Fresnel term below)
 __device__ __forceinline__ BsdfSample sample_local(const Closure& c, V3 wo, float ux, float uy)
 {
 	BsdfSample s; s.f = splat(0); s.wi = mk(0, 0, 1); s.pdf = 0; s.flags = 0;                // bsdf.h:252-265
@@ -317,18 +322,18 @@ __device__ __forceinline__ BsdfSample sample_local(const Closure& c, V3 wo, floa
 	{
 		s.wi = cosine_hemisphere(ux, uy);
 		if (wo.z < 0) s.wi.z *= -1;
-		s.f = eval_local(c, wo, s.wi);
+		s.f = eval_local<FS>(c, wo, s.wi);
 		s.pdf = same_hemi(wo, s.wi) ? fabsf(s.wi.z) * JP_INV_PI : 0;
 		s.flags = BS_REFLECTION | BS_DIFFUSE;
 	}
-	else if (c.kind == CL_MIRROR)                                                             // bsdf.h:415-429
+	else if (FS::delta && c.kind == CL_MIRROR)                                                 // bsdf.h:415-429
 	{
 		s.wi = mk(-wo.x, -wo.y, wo.z);
 		s.f = c.c0 / fabsf(s.wi.z);
 		s.pdf = 1;
 		s.flags = BS_REFLECTION | BS_SPECULAR;
 	}
-	else if (c.kind == CL_FRESNEL_SPECULAR)                                                   // bsdf.h:478-539
+	else if (FS::delta && c.kind == CL_FRESNEL_SPECULAR)                                       // bsdf.h:478-539
 	{
 		if (wo.z == 0.f) return s;
 		float F = fresnel_dielectric(wo.z, 1.f, c.eta_t);
@@ -372,7 +377,7 @@ __device__ __forceinline__ BsdfSample sample_local(const Closure& c, V3 wo, floa
 		V3 wi = -wo + 2 * owh * wh;                                                           // reflect bsdf.h:62-67
 		if (!same_hemi(wo, wi)) return s;
 		s.wi = wi;
-		s.f = eval_local(c, wo, wi);
+		s.f = eval_local<FS>(c, wo, wi);
 		s.pdf = tr_Pdf(c, wo, wh) / (4 * dot(wo, wh));
 		s.flags = BS_REFLECTION | BS_GLOSSY;
 	}
@@ -381,15 +386,15 @@ __device__ __forceinline__ BsdfSample sample_local(const Closure& c, V3 wo, floa
 
 // FMaterial::Scattering (material.h:34-37, 52-55, 72-75; material.cc:12-43).  `uplastic` is the draw
 // FPlasticMaterial consumes (material.cc:14); the caller draws it only for JP_MAT_PLASTIC.
-template <typename MatPtr>
+template <typename F = FeatAll, typename MatPtr>
 __device__ __forceinline__ void make_closure(MatPtr mats, int type, int mat, float uplastic, Closure& c)
 {
 	const float4 p0 = mats[4 * mat + 0], p1 = mats[4 * mat + 1];
 	c.c0 = splat(0); c.c1 = splat(0); c.eta_t = 1; c.ax = c.ay = 0; c.fresnel = FR_CONDUCTOR; c.feta = splat(0); c.fk = splat(0);
 	if (type == JP_MAT_MATTE) { c.kind = CL_LAMBERT; c.c0 = xyz(p0); }
-	else if (type == JP_MAT_MIRROR) { c.kind = CL_MIRROR; c.c0 = xyz(p0); }
-	else if (type == JP_MAT_GLASS) { c.kind = CL_FRESNEL_SPECULAR; c.eta_t = p0.x; c.c0 = mk(p0.y, p0.z, p0.w); c.c1 = mk(p1.x, p1.y, p1.z); }
-	else if (type == JP_MAT_PLASTIC)
+	else if (F::delta && type == JP_MAT_MIRROR) { c.kind = CL_MIRROR; c.c0 = xyz(p0); }
+	else if (F::delta && type == JP_MAT_GLASS) { c.kind = CL_FRESNEL_SPECULAR; c.eta_t = p0.x; c.c0 = mk(p0.y, p0.z, p0.w); c.c1 = mk(p1.x, p1.y, p1.z); }
+	else if (F::delta && type == JP_MAT_PLASTIC)
 	{
 		float Qd = p1.w;
 		if (uplastic < Qd) { c.kind = CL_LAMBERT; c.c0 = xyz(p0) / Qd; }
@@ -404,13 +409,13 @@ struct LightSample { V3 pos, wi; float pdf; V3 Li; float dist; };   // dist: |po
 // FLight::Sample_Li for light `li` from surface point p with normal n (isect.normal, used by the sphere's
 // inside branch only).  light.h:199-216 (area), :265-291 (environment); shape sampling shape.h:124-145, 353-363,
 // 459-467, 549-644.
-template <typename PrimPtr, typename LightPtr>
+template <typename F = FeatAll, typename PrimPtr, typename LightPtr>
 __device__ __forceinline__ LightSample sample_li(const SceneView& sc, PrimPtr prims, LightPtr lights, int li, V3 p, V3 n_isect, float ux, float uy)
 {
 	LightSample s; s.pos = mk(0, 0, 0); s.wi = mk(0, 0, 0); s.pdf = 0; s.Li = splat(0); s.dist = -1.f;
 	const float4 l0 = lights[2 * li], l1 = lights[2 * li + 1];
 	const V3 radiance = xyz(l0);
-	if (__float_as_int(l0.w) == JP_LIGHT_ENVIRONMENT)
+	if (F::other_lights && __float_as_int(l0.w) == JP_LIGHT_ENVIRONMENT)
 	{
 		float theta = uy * JP_PI, phi = ux * 2 * JP_PI;
 		float cosT, sinT, sinP, cosP; sincos_f(theta, &sinT, &cosT); sincos_f(phi, &sinP, &cosP);
@@ -420,7 +425,7 @@ __device__ __forceinline__ LightSample sample_li(const SceneView& sc, PrimPtr pr
 		s.Li = radiance;
 		return s;
 	}
-	if (__float_as_int(l0.w) == JP_LIGHT_POINT)                   // FPointLight::Sample_Li light.h:94-123; l1.xyz = worldPosition
+	if (F::other_lights && __float_as_int(l0.w) == JP_LIGHT_POINT)                 // FPointLight::Sample_Li light.h:94-123; l1.xyz = worldPosition
 	{
 		const V3 wp = xyz(l1);
 		s.pos = wp;
@@ -429,7 +434,7 @@ __device__ __forceinline__ LightSample sample_li(const SceneView& sc, PrimPtr pr
 		s.Li = radiance / len2(wp - p);
 		return s;
 	}
-	if (__float_as_int(l0.w) == JP_LIGHT_DIRECTION)               // FDirectionLight::Sample_Li light.h:155-164; l1.xyz = worldDir
+	if (F::other_lights && __float_as_int(l0.w) == JP_LIGHT_DIRECTION)             // FDirectionLight::Sample_Li light.h:155-164; l1.xyz = worldDir
 	{
 		s.wi = -xyz(l1);
 		s.pos = p + s.wi * 2 * sc.world_radius;
@@ -442,7 +447,7 @@ __device__ __forceinline__ LightSample sample_li(const SceneView& sc, PrimPtr pr
 	const float4 g0 = prims[4 * pi + 0], g3 = prims[4 * pi + 3];
 	const int type = __float_as_int(g3.w);
 	V3 lp, ln; float pdf;
-	if (type != JP_SHAPE_SPHERE)
+	if (!F::other_lights || type != JP_SHAPE_SPHERE)
 	{
 		const float4 g1 = prims[4 * pi + 1], g2 = prims[4 * pi + 2];
 		if (type == JP_SHAPE_TRIANGLE)                            // shape.h:353-363 + sampling.h:121-125
@@ -450,14 +455,14 @@ __device__ __forceinline__ LightSample sample_li(const SceneView& sc, PrimPtr pr
 			float su0 = sqrtf(ux); float bx = 1 - su0, by = uy * su0;
 			lp = bx * xyz(g0) + by * xyz(g1) + (1 - bx - by) * xyz(g2);
 		}
-		else if (type == JP_SHAPE_DISK)                           // FDisk::SamplePosition shape.h:256-268: g0 = (position, radius), g1 = normal
+		else if (F::other_lights && type == JP_SHAPE_DISK)        // FDisk::SamplePosition shape.h:256-268: g0 = (position, radius), g1 = normal
 		{
 			const Frame fr = frame_from_z(xyz(g1));
 			float px, py; concentric_disk(ux, uy, px, py);
 			lp = xyz(g0) + g0.w * (fr.s * px + fr.t * py);
 		}
 		else lp = xyz(g1) + (xyz(g0) - xyz(g1)) * ux + (xyz(g2) - xyz(g1)) * uy;   // shape.h:459-467
-		ln = type == JP_SHAPE_DISK ? xyz(g1) : xyz(g3);
+		ln = (F::other_lights && type == JP_SHAPE_DISK) ? xyz(g1) : xyz(g3);
 		pdf = inv_area;
 		V3 wi = lp - p;                                           // FShape::SampleDirection shape.h:124-145
 		float dist2 = len2(wi);

@@ -714,6 +714,17 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 		p.vote = opt_flag(op.vote, p.trav_mode != 5 || p.cert);
 		p.class_mask = 1; for (int k = 0; k < 5; k++) if (kinds[k]) p.class_mask |= 2 << k;
 		p.shade_sort = opt_flag(op.shade_sort, nk > 1);
+		// the rest of the feature set (jp_device.h "Feature sets"; the materials' part is class_mask): shape types of the primitives, light
+		// types, shape types under the area lights -- fixed for every frame rendered from this upload, read by the selectors of jp_render.h
+		p.shape_mask = 0; p.light_mask = 0; p.light_shape_mask = 0;
+		for (int i = 0; i < s->n_primitives; i++) p.shape_mask |= 1 << (s->prim_shape_type[i] & 3);
+		for (int i = 0; i < s->n_lights; i++)
+		{   // a black light is never sampled (k_shade skips it before sample_li, its two draws kept) and adds nothing on a miss: it is no feature
+			const float* rad = s->light_radiance + 3 * i;
+			if (rad[0] == 0.f && rad[1] == 0.f && rad[2] == 0.f) continue;
+			p.light_mask |= 1 << (s->light_type[i] & 3);
+			if (s->light_type[i] == JP_LIGHT_AREA) p.light_shape_mask |= 1 << (s->prim_shape_type[s->light_prim[i]] & 3);
+		}
 	}
 	p.has_null_material = hasNull; c->cert_fell_back = false;
 	if (pick) { const int st = upload_light_table(c, s, light_area); if (st != JP_OK) { free_scene(c); return st; } }
