@@ -417,6 +417,31 @@ int  jp_light_pick(JpContext* ctx, int32_t n, const float* u0, const float* u1, 
 /* the table builder of the upload; pure host code, no GPU needed.  weights: n finite values >= 0 (else JP_ERR_INVALID_ARGUMENT); n == 0 is JP_OK */
 int  jp_build_light_table(int32_t n, const double* weight, float* q, int32_t* alias, float* pmf);
 
+
+/* What jp_upload_scene would do with `scene` (additive to ABI 7; INTEGRATION.md "Describing an upload"): the scalars of the plan every later launch
+ * reads, and for each table the host builds the byte count and the 64-bit FNV-1a of exactly the bytes the upload copies to the device.  Pure host code, no GPU
+ * needed: the same validation (same status codes and jp_last_error texts), table builders and plan function the upload runs, nothing decided twice.
+ * options NULL: the defaults (no environment); light_mode: JP_LIGHTS_*.  A scene without a hierarchy (n_bvh_nodes == 0) gets its trees from the device
+ * builders: JP_ERR_UNSUPPORTED.  Set struct_bytes to sizeof(JpUploadInfo); a shorter struct is truncated. */
+#define JP_UPLOAD_TABLES 11
+typedef struct JpUploadTable { int64_t bytes; uint64_t fnv1a; } JpUploadTable;   /* both 0: the upload has no such table */
+typedef struct JpUploadInfo {
+    int32_t struct_bytes;
+    int32_t trav_mode;                       /* JpBuildInfo.traversal_mode; 5: reference semantics                              */
+    int32_t stack_depth, stack_depth_q4;     /* traversal stack entries of the binary / 8-wide / verbatim walks, of the 4-wide walks */
+    int64_t lds_bytes, lds_bytes_shadow, shade_lds_bytes;   /* dynamic LDS of k_extend, k_shadow, k_shade                          */
+    int32_t scene_in_lds, tables_in_lds, shade_prims_in_lds, stage_nee, n_planes;
+    int32_t persist, vote, shade_sort, use_q4, q4_shadow, cert;
+    int32_t class_mask, shape_mask, light_mask, light_shape_mask;   /* the feature set (DESIGN.md "Feature sets")                     */
+    int32_t has_null_material, stack_lds_words;
+    int32_t n_nodes, n_prims, n_flat, n_wide, n_q4;          /* entries of the binary tree, records, flat leaf list, 8-wide and 4-wide trees */
+    int32_t bvh_nodes, bvh_height;           /* as JpBuildInfo reports them                                                     */
+    int32_t wide_height, q4_height, cert_eye_leaves, n_env;
+    float   cert_pad, cert_pad_eye, env_sum[3];
+    JpUploadTable table[JP_UPLOAD_TABLES];   /* nodes, prims, meta, mats, mat_type, lights, shade_tab, wide, q4, refbox, flat   */
+} JpUploadInfo;
+int  jp_describe_upload(const JpOptions* options_or_null, int32_t light_mode, const JpScene* scene, JpUploadInfo* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,41 @@ class JpLightInfo(C.Structure):
                 ("total_weight", C.c_double), ("picked_last_render", C.c_int32)]
 
 
+UPLOAD_TABLES = ("nodes", "prims", "meta", "mats", "mat_type", "lights", "shade_tab", "wide", "q4", "refbox", "flat")
+
+
+class JpUploadTable(C.Structure):
+    _fields_ = [("bytes", C.c_int64), ("fnv1a", C.c_uint64)]
+
+
+class JpUploadInfo(C.Structure):
+    """include/jetpbrt_amd.h: JpUploadInfo (jp_describe_upload); table[i] belongs to UPLOAD_TABLES[i]"""
+    _fields_ = [("struct_bytes", C.c_int32), ("trav_mode", C.c_int32), ("stack_depth", C.c_int32), ("stack_depth_q4", C.c_int32),
+                ("lds_bytes", C.c_int64), ("lds_bytes_shadow", C.c_int64), ("shade_lds_bytes", C.c_int64),
+                ("scene_in_lds", C.c_int32), ("tables_in_lds", C.c_int32), ("shade_prims_in_lds", C.c_int32), ("stage_nee", C.c_int32), ("n_planes", C.c_int32),
+                ("persist", C.c_int32), ("vote", C.c_int32), ("shade_sort", C.c_int32), ("use_q4", C.c_int32), ("q4_shadow", C.c_int32), ("cert", C.c_int32),
+                ("class_mask", C.c_int32), ("shape_mask", C.c_int32), ("light_mask", C.c_int32), ("light_shape_mask", C.c_int32),
+                ("has_null_material", C.c_int32), ("stack_lds_words", C.c_int32),
+                ("n_nodes", C.c_int32), ("n_prims", C.c_int32), ("n_flat", C.c_int32), ("n_wide", C.c_int32), ("n_q4", C.c_int32),
+                ("bvh_nodes", C.c_int32), ("bvh_height", C.c_int32), ("wide_height", C.c_int32), ("q4_height", C.c_int32), ("cert_eye_leaves", C.c_int32), ("n_env", C.c_int32),
+                ("cert_pad", C.c_float), ("cert_pad_eye", C.c_float), ("env_sum", C.c_float * 3),
+                ("table", JpUploadTable * len(UPLOAD_TABLES))]
+
+
+def describe_upload(scene, options=None, light_mode=JP_LIGHTS_ALL):
+    """jp_describe_upload: what jp_upload_scene would decide for `scene` (a JpScene or a pointer to one) and the digests of the tables it would
+    copy to the device (pure host code, no GPU).  options: a JpOptions, or None for the defaults without the environment -> JpUploadInfo"""
+    L = hip_lib()
+    info = JpUploadInfo()
+    info.struct_bytes = C.sizeof(JpUploadInfo)
+    if options is not None:
+        options.struct_bytes = C.sizeof(JpOptions)
+    st = L.jp_describe_upload(None if options is None else C.byref(options), LIGHT_SAMPLING_MODES[light_mode], scene if isinstance(scene, C._Pointer) else C.byref(scene), C.byref(info))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    return info
+
+
 def build_light_table(weights):
     """jp_build_light_table: the alias table of the upload for `weights` (pure host code, no GPU) -> (q float32, alias int32, pmf float32)"""
     import numpy as np
@@ -293,6 +328,7 @@ def hip_lib():
         L.jp_light_pick.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4
         L.jp_build_light_table.argtypes = [C.c_int32] + [C.c_void_p] * 4
         L.jp_device_bytes_in_use.restype = C.c_longlong
+        L.jp_describe_upload.argtypes = [C.POINTER(JpOptions), C.c_int32, C.POINTER(JpScene), C.POINTER(JpUploadInfo)]
         _hip = L
     return _hip
 

@@ -1228,7 +1228,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 // host runtime (same translation unit: the code below launches the kernels above)
 // ---------------------------------------------------------------------------------------------------------------------
 #include "jp_runtime.h"          // context, options (JpOptions), libm probes, create / destroy
-#include "jp_upload.h"           // jp_upload_scene: validation, device tables, trees, device-side build
+#include "jp_scene_host.h"       // the upload's host half: check_scene, the table builders (HostTables), plan_scene -- no device, no context
+#include "jp_upload.h"           // jp_upload_scene: check -> tables (host builders or device-side build) -> uploads -> plan; jp_describe_upload
 #include "jp_render.h"           // jp_render*: queues, launch sequence, stream lanes, fused schedule; counters, jp_trace, jp_bsdf
 #include "jp_denoise.h"          // guides and denoising: k_guides, k_atrous and their entry points (additive: nothing above refers to it)
 #include "jp_pick.h"             // light selection: the alias table, k_shade_pick / k_shade_pick_tex, k_light_pick and their entry points (jp_render.h declares its two hooks)

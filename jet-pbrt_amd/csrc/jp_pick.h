@@ -87,8 +87,9 @@ int build_light_table(int n, const double* w, float* q, int32_t* alias, float* p
 }
 }
 
-// the upload's table step (jp_upload_scene, mode JP_LIGHTS_POWER_ONE): weights, table, the environment list, the device copies, plan.pv
-static int upload_light_table(JpContext* c, const JpScene* s, const std::vector<float>& area)
+// the upload's table step (jp_upload_scene, mode JP_LIGHTS_POWER_ONE): weights, table, the environment list, the device copies into the upload's
+// tables T, and its plan's pv
+static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area)
 {
 	const int n = s->n_lights;
 	const double kPi = 3.14159265358979323846;
@@ -111,13 +112,12 @@ static int upload_light_table(JpContext* c, const JpScene* s, const std::vector<
 	for (int i = 0; i < n; i++) { float af; std::memcpy(&af, &alias[i], 4); bins[i] = make_float2(q[i], af); }
 	const int n_env = (int)env.size();
 	if (env.empty()) env.push_back(make_float4(0, 0, 0, 0));         // (never read: n_env is 0)
-	SceneTables& T = c->tab;
 	HIP_TRY(upload(T.pick_bins, bins.data(), bins.size() * sizeof(float2)));
 	HIP_TRY(upload(T.pick_pmf, pmf.data(), pmf.size() * sizeof(float)));
 	HIP_TRY(upload(T.pick_env, env.data(), env.size() * sizeof(float4)));
-	PickView& pv = c->plan.pv;
+	PickView& pv = plan.pv;
 	pv.bins = T.pick_bins.get<float2>(); pv.pmf = T.pick_pmf.get<float>(); pv.env = T.pick_env.get<float4>(); pv.n = n; pv.n_env = n_env;
-	c->plan.pick = true; c->n_selectable = nsel; c->total_weight = W;
+	plan.pick = true; c->n_selectable = nsel; c->total_weight = W;
 	return JP_OK;
 }
 

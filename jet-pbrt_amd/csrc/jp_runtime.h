@@ -129,7 +129,7 @@ struct JpContext
 	int n_selectable = 0; double total_weight = 0.0; int last_picked = 0;
 };
 // jp_pick.h (included last) defines the upload's table step
-static int upload_light_table(JpContext* c, const JpScene* s, const std::vector<float>& area);
+static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area);
 
 // a context buffer that kernels in flight may still use: grown only once the stream is idle (nothing happens when the capacity suffices)
 static int reserve_idle(JpContext* c, DevBuf& b, size_t bytes)
@@ -277,6 +277,20 @@ static unsigned long long host_gamma_sweep(int n_threads)
 	return s2;
 }
 
+// a caller's JpOptions by value: a longer struct of a later ABI is truncated, a shorter one zero-extended; every field range-checked
+static int read_options(const char* who, const JpOptions* o, JpOptions& n)
+{
+	if (o->struct_bytes < (int32_t)sizeof(int32_t) || o->struct_bytes > 4096) return fail(JP_ERR_INVALID_ARGUMENT, std::string(who) + ": struct_bytes is not a struct size");
+	std::memset(&n, 0, sizeof(n));
+	std::memcpy(&n, o, std::min<size_t>(sizeof(n), (size_t)o->struct_bytes));
+	n.struct_bytes = (int32_t)sizeof(JpOptions);
+	if (n.lanes < 0 || n.lanes > 4 || n.lane_rows < 0 || n.lane_rows > 64 || n.blocks_per_cu < 0 || n.blocks_per_cu > 256 || n.max_slots < 0 || n.traversal < 0 || n.traversal > 4
+	    || n.stack_lds_words < 0 || n.bvh_max_leaf < 0 || n.bvh_max_leaf > 16 || n.trace_walk < 0 || n.trace_walk > 3 || n.device_tree < 0 || n.device_tree > 2
+	    || (n.persist > 0 && n.persist != 8 && n.persist != 16 && n.persist != 32))
+		return fail(JP_ERR_INVALID_ARGUMENT, std::string(who) + ": field out of range (see JpOptions in jetpbrt_amd.h)");
+	return JP_OK;
+}
+
 extern "C" {
 
 const char* jp_last_error(void) { return g_err.c_str(); }
@@ -321,17 +335,7 @@ int jp_set_options(JpContext* c, const JpOptions* o)
 {
 	if (!c) return fail(JP_ERR_INVALID_ARGUMENT, "jp_set_options: null context");
 	JpOptions n = c->opt_env;
-	if (o)
-	{
-		if (o->struct_bytes < (int32_t)sizeof(int32_t) || o->struct_bytes > 4096) return fail(JP_ERR_INVALID_ARGUMENT, "jp_set_options: struct_bytes is not a struct size");
-		std::memset(&n, 0, sizeof(n));
-		std::memcpy(&n, o, std::min<size_t>(sizeof(n), (size_t)o->struct_bytes));
-		n.struct_bytes = (int32_t)sizeof(JpOptions);
-		if (n.lanes < 0 || n.lanes > 4 || n.lane_rows < 0 || n.lane_rows > 64 || n.blocks_per_cu < 0 || n.blocks_per_cu > 256 || n.max_slots < 0 || n.traversal < 0 || n.traversal > 4
-		    || n.stack_lds_words < 0 || n.bvh_max_leaf < 0 || n.bvh_max_leaf > 16 || n.trace_walk < 0 || n.trace_walk > 3 || n.device_tree < 0 || n.device_tree > 2
-		    || (n.persist > 0 && n.persist != 8 && n.persist != 16 && n.persist != 32))
-			return fail(JP_ERR_INVALID_ARGUMENT, "jp_set_options: field out of range (see JpOptions in jetpbrt_amd.h)");
-	}
+	if (o) if (const int st = read_options("jp_set_options", o, n); st != JP_OK) return st;
 	const bool libm_changed = n.libm_sincosf != c->opt.libm_sincosf || n.libm_xbsdf != c->opt.libm_xbsdf;
 	c->opt = n;
 	c->blocks_per_cu = (n.blocks_per_cu >= 1) ? n.blocks_per_cu : 16; c->bpc_from_env = n.blocks_per_cu >= 1;
