@@ -417,6 +417,43 @@ int  jp_light_pick(JpContext* ctx, int32_t n, const float* u0, const float* u1, 
 /* the table builder of the upload; pure host code, no GPU needed.  weights: n finite values >= 0 (else JP_ERR_INVALID_ARGUMENT); n == 0 is JP_OK */
 int  jp_build_light_table(int32_t n, const double* weight, float* q, int32_t* alias, float* pmf);
 
+/* Environment maps (additive to ABI 7; INTEGRATION.md "Environment maps" has the definition).  A lat-long fp32 RGB image, width x height texels, row-major,
+ * top row first, 1 <= width, height <= 4096, every value finite and >= 0.  Row r covers the polar angle [pi r / H, pi (r + 1) / H] from the map's up axis,
+ * column c the azimuth [2 pi c / W, 2 pi (c + 1) / W].  JP_ENV_UP_Z: map space is world space (the reference's SphericalTheta / SphericalPhi);
+ * JP_ENV_UP_Y: map (x, y, z) = world (z, x, y).  The map is context state like the light sampling mode: the next jp_upload_scene* reads it.  That scene
+ * must hold exactly one JP_LIGHT_ENVIRONMENT light (else JP_ERR_INVALID_ARGUMENT), whose light_radiance tints the map (device texel = tint * texel in fp32),
+ * and be uploaded with JP_LIGHTS_POWER_ONE (else JP_ERR_UNSUPPORTED): the map light is one entry of the light table, weight (mean_sum * pi) * R^2.
+ * A miss at bounce 0 or after a specular bounce adds beta * the nearest texel; when the light table returns the map light, five draws a0 a1 a2 b0 b1
+ * follow u0 u1 in place of the light's two: the texel from an alias table over the texels (weight: (r + g + b) * solid angle of the row's texels;
+ * importance = -1: the solid angle alone), then a place inside it uniform in (cos theta, phi).  Path integrator only (Whitted: JP_ERR_UNSUPPORTED; the
+ * debug integrator and jp_render_guides ignore the map); JpOptions.fused falls back to the per-bounce launches. */
+enum { JP_ENV_UP_Z = 0, JP_ENV_UP_Y = 1 };
+typedef struct JpEnvMap {
+    int32_t struct_bytes;                    /* sizeof(JpEnvMap)                                                              */
+    int32_t width, height, up_axis;          /* up_axis: JP_ENV_UP_*                                                          */
+    int32_t importance;                      /* 0: sample by radiance x solid angle; -1: by solid angle alone (A/B, tests)    */
+    const float* rgb;                        /* 3 * width * height values; copied by jp_set_environment_map                   */
+} JpEnvMap;
+/* validates and copies the map; takes effect with the next jp_upload_scene*; NULL: no map */
+int  jp_set_environment_map(JpContext* ctx, const JpEnvMap* map);
+typedef struct JpEnvInfo {
+    int32_t struct_bytes, width, height, up_axis, importance;   /* the uploaded scene's map (all 0: none)                     */
+    int32_t n_selectable;                    /* texels of weight > 0                                                          */
+    double  total_weight;                    /* W_env: the texel weights summed in row-major order                            */
+    double  mean_sum;                        /* sum over texels of (r + g + b) * solid angle / (4 pi): the map light's "radiance sum" */
+    int32_t mapped_last_render;              /* the last jp_render* ran the map kernels (k_shade_env / k_shade_env_tex)       */
+    int64_t table_bytes_device;              /* device bytes of the texel, bin and row tables                                 */
+} JpEnvInfo;
+int  jp_get_env_info(JpContext* ctx, JpEnvInfo* out);
+/* test hooks like jp_trace: the device functions the render calls.  lookup: n directions (3 floats each, world space, finite) -> texel index, tinted rgb.
+ * sample: n times five draws in [0, 1) (a0 a1 a2 b0 b1) -> texel index, world-space wi, Li, pdf.  Any output pointer may be NULL.
+ * JP_ERR_UNSUPPORTED for a scene uploaded without a map. */
+int  jp_env_lookup(JpContext* ctx, int32_t n, const float* dir, int32_t* texel_index, float* rgb);
+int  jp_env_sample(JpContext* ctx, int32_t n, const float* u, int32_t* texel_index, float* wi, float* Li, float* pdf);
+/* the table builder of the upload; pure host code, no GPU needed.  tint: 3 floats (NULL: 1 1 1).  Outputs (any may be NULL): weight, q, alias: W * H each;
+ * texel: 4 floats per texel (tinted r g b, pdf); row_cos: 2 floats per row; total: W_env; mean_sum: as JpEnvInfo. */
+int  jp_build_environment_table(const JpEnvMap* map, const float* tint, double* weight, float* q, int32_t* alias, float* texel, float* row_cos, double* total, double* mean_sum);
+
 
 /* What jp_upload_scene would do with `scene` (additive to ABI 7; INTEGRATION.md "Describing an upload"): the scalars of the plan every later launch
  * reads, and for each table the host builds the byte count and the 64-bit FNV-1a of exactly the bytes the upload copies to the device.  Pure host code, no GPU

@@ -127,6 +127,52 @@ class JpLightInfo(C.Structure):
                 ("total_weight", C.c_double), ("picked_last_render", C.c_int32)]
 
 
+JP_ENV_UP_Z, JP_ENV_UP_Y = 0, 1
+ENV_UP_AXES = {"z": JP_ENV_UP_Z, "y": JP_ENV_UP_Y, JP_ENV_UP_Z: JP_ENV_UP_Z, JP_ENV_UP_Y: JP_ENV_UP_Y}
+
+
+class JpEnvMap(C.Structure):
+    """include/jetpbrt_amd.h: JpEnvMap (jp_set_environment_map); struct_bytes = sizeof(JpEnvMap)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("up_axis", C.c_int32), ("importance", C.c_int32), ("rgb", _fp)]
+
+
+class JpEnvInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("up_axis", C.c_int32), ("importance", C.c_int32),
+                ("n_selectable", C.c_int32), ("total_weight", C.c_double), ("mean_sum", C.c_double), ("mapped_last_render", C.c_int32),
+                ("table_bytes_device", C.c_int64)]
+
+
+def env_map(rgb, up_axis=JP_ENV_UP_Z, importance=0):
+    """A JpEnvMap over an (H, W, 3) float32 array, top row first (kept alive on the returned object as ._keep)"""
+    import numpy as np
+    a = np.ascontiguousarray(rgb, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise JetPbrtError("an environment map is an (H, W, 3) array")
+    m = JpEnvMap(C.sizeof(JpEnvMap), a.shape[1], a.shape[0], ENV_UP_AXES[up_axis], importance, a.ctypes.data_as(_fp))
+    m._keep = a
+    return m
+
+
+def build_environment_table(rgb, tint=(1.0, 1.0, 1.0), up_axis=JP_ENV_UP_Z, importance=0):
+    """jp_build_environment_table: the tables the upload makes of an (H, W, 3) map and a tint (pure host code, no GPU) ->
+    dict(weight float64 (H*W), q float32, alias int32, texel float32 (H*W, 4), row_cos float32 (H, 2), total, mean_sum).
+    rgb may also be a ready JpEnvMap (refusal tests)."""
+    import numpy as np
+    m = rgb if isinstance(rgb, JpEnvMap) else env_map(rgb, up_axis, importance)
+    n = max(0, m.width) * max(0, m.height) if 0 < m.width <= 4096 and 0 < m.height <= 4096 else 0
+    out = dict(weight=np.zeros(n, np.float64), q=np.zeros(n, np.float32), alias=np.zeros(n, np.int32), texel=np.zeros((n, 4), np.float32),
+               row_cos=np.zeros((m.height if n else 0, 2), np.float32))
+    t = np.ascontiguousarray(tint, np.float32)
+    tot, mean = C.c_double(0.0), C.c_double(0.0)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    st = L.jp_build_environment_table(C.byref(m), p(t), p(out["weight"]), p(out["q"]), p(out["alias"]), p(out["texel"]), p(out["row_cos"]), C.byref(tot), C.byref(mean))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    out["total"], out["mean_sum"] = tot.value, mean.value
+    return out
+
+
 UPLOAD_TABLES = ("nodes", "prims", "meta", "mats", "mat_type", "lights", "shade_tab", "wide", "q4", "refbox", "flat")
 
 
@@ -285,6 +331,10 @@ def host_lib():
         L.jp_host_render_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.jp_host_render_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.jp_host_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
+        L.jp_host_scene_envmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.jp_host_scene_envmap_file.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        L.jp_host_flatten_envmap.restype = C.POINTER(JpEnvMap)
+        L.jp_host_flatten_envmap.argtypes = [C.c_void_p]
         _host = L
     return _host
 
@@ -328,6 +378,11 @@ def hip_lib():
         L.jp_light_pick.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4
         L.jp_build_light_table.argtypes = [C.c_int32] + [C.c_void_p] * 4
         L.jp_device_bytes_in_use.restype = C.c_longlong
+        L.jp_set_environment_map.argtypes = [C.c_void_p, C.POINTER(JpEnvMap)]
+        L.jp_get_env_info.argtypes = [C.c_void_p, C.POINTER(JpEnvInfo)]
+        L.jp_env_lookup.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 3
+        L.jp_env_sample.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+        L.jp_build_environment_table.argtypes = [C.POINTER(JpEnvMap)] + [C.c_void_p] * 6 + [C.POINTER(C.c_double)] * 2
         L.jp_describe_upload.argtypes = [C.POINTER(JpOptions), C.c_int32, C.POINTER(JpScene), C.POINTER(JpUploadInfo)]
         _hip = L
     return _hip
@@ -482,6 +537,42 @@ class Context:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         self._check(self.lib.jp_light_pick(self.h, n, p(a), p(b), p(idx), p(pmf)))
         return idx, pmf
+
+    def set_environment_map(self, rgb, up_axis=JP_ENV_UP_Z, importance=0):
+        """jp_set_environment_map for the next upload: an (H, W, 3) float32 array top row first, a JpEnvMap, or None for no map.
+        up_axis: "z" / JP_ENV_UP_Z (map space = world space) or "y" / JP_ENV_UP_Y; importance -1: sample by solid angle alone"""
+        if rgb is None:
+            self._check(self.lib.jp_set_environment_map(self.h, None))
+            return
+        m = rgb if isinstance(rgb, JpEnvMap) else env_map(rgb, up_axis, importance)
+        self._check(self.lib.jp_set_environment_map(self.h, C.byref(m)))
+
+    def env_info(self):
+        i = JpEnvInfo()
+        i.struct_bytes = C.sizeof(JpEnvInfo)
+        self._check(self.lib.jp_get_env_info(self.h, C.byref(i)))
+        return i
+
+    def env_lookup(self, direction):
+        """jp_env_lookup: the texel a world-space direction sees -> (texel index int32 (n,), tinted rgb float32 (n, 3))"""
+        import numpy as np
+        d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        n = d.shape[0]
+        idx = np.zeros(n, np.int32); rgb = np.zeros((n, 3), np.float32)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_env_lookup(self.h, n, p(d), p(idx), p(rgb)))
+        return idx, rgb
+
+    def env_sample(self, u):
+        """jp_env_sample: the device's next-event sample of the map for (n, 5) draws a0 a1 a2 b0 b1 ->
+        (texel index int32 (n,), wi float32 (n, 3), Li float32 (n, 3), pdf float32 (n,))"""
+        import numpy as np
+        a = np.ascontiguousarray(u, np.float32).reshape(-1, 5)
+        n = a.shape[0]
+        idx = np.zeros(n, np.int32); wi = np.zeros((n, 3), np.float32); Li = np.zeros((n, 3), np.float32); pdf = np.zeros(n, np.float32)
+        p = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_env_sample(self.h, n, p(a), p(idx), p(wi), p(Li), p(pdf)))
+        return idx, wi, Li, pdf
 
     def synchronize(self):
         self._check(self.lib.jp_synchronize(self.h))

@@ -21,6 +21,7 @@
 // layout is deterministic.  Launches are asynchronous on one stream, no host round trip inside a batch.
 #include "jp_common.h"
 #include "jp_tex.h"
+#include "jp_env.h"              // part 1: EnvView, env_lookup, env_sample (the kernels and entry points: part 2, at the end)
 #include "jp_xbsdf.h"
 
 #include <cstdio>
@@ -227,10 +228,11 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 // 70k triangles has 2.2 MB of them), the one picked light's two float4 come from HBM / L2, and the miss branch walks pv.env, the short list of
 // non-black environment lights, instead of every light.
 // F: the scene's feature set (jp_device.h, DESIGN.md "Feature sets"); the lean instances exist for k_shade<true, true, true, kSort> only.
-template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, typename F = FeatAll>
-__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv)
+template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, bool kEnv, typename F = FeatAll>
+__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv, const EnvView& ev)
 {
 	static_assert(kTab || !kPrims, "k_shade: primitive records in LDS only together with the tables");
+	static_assert(kPick || !kEnv, "k_shade: the map light is an entry of the light table");
 	constexpr int kWaves = JP_BLOCK / 64, kMaxSeg = (JP_SHADE_TILE / JP_BLOCK) * kWaves;  // (pass, wave) segments of a tile, in queue order
 	static_assert(JP_SHADE_TILE % JP_BLOCK == 0 && JP_SHADE_TILE <= 65536, "k_shade: tile positions are 16-bit");
 	__shared__ unsigned short s_idx[kSort ? JP_SHADE_TILE : 1];
@@ -427,7 +429,14 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 			else if (F::other_lights && (bounce == 0 || spec))                        // integrator.cc:334-336, light.h:300-303
 			{
 				// L += beta * Le for each infinite light in order; folded on the host only when there is at most one
-				if (kPick)
+				if (kEnv)
+				{   // the map: the texel the ray sees (the scene's one environment light; its radiance is in the texels as the tint)
+					const float4 t = ev.texel[env_lookup(ev, d)];
+					float4 L = q.lacc[slot];
+					V3 a = mk(L.x, L.y, L.z) + cmul(beta, xyz(t));
+					q.lacc[slot] = make_float4(a.x, a.y, a.z, 0.f);
+				}
+				else if (kPick)
 				{
 					for (int e = 0; e < pv.n_env; e++)
 					{
@@ -510,12 +519,23 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 						const float u0 = rngf(rc, key, dim), u1 = rngf(rc, key, dim + 1); dim += 2;
 						li = light_pick(pv, u0, u1, pmf);
 					}
-					const unsigned int d0 = dim; dim += 2;                              // the two draws are consumed even when the sample is rejected
+					const bool mapped = kEnv && li == ev.light;                         // the map light: five draws in place of the light's two (jp_env.h)
+					const unsigned int d0 = dim; dim += mapped ? 5 : 2;                 // the draws are consumed even when the sample is rejected
 					if (kPick && !(pmf > 0.f)) continue;                                // no light of weight > 0 (W == 0): no next-event estimation
-					const float4 lrad = lights[2 * li];
-					if (isblack(xyz(lrad))) continue;                                   // Li would be black (integrator.cc:362): skip the evaluation, keep the draws
-					const float ux = rngf(rc, key, d0), uy = rngf(rc, key, d0 + 1);
-					LightSample ls = sample_li<F>(sc, prims, lights, li, p, N, ux, uy);
+					float4 lrad; LightSample ls;
+					if (mapped)
+					{
+						lrad = make_float4(0.f, 0.f, 0.f, __int_as_float(JP_LIGHT_ENVIRONMENT));
+						env_sample(ev, rngf(rc, key, d0), rngf(rc, key, d0 + 1), rngf(rc, key, d0 + 2), rngf(rc, key, d0 + 3), rngf(rc, key, d0 + 4), ls.wi, ls.Li, ls.pdf);
+						ls.pos = p + ls.wi * 2 * sc.world_radius; ls.dist = -1.f;
+					}
+					else
+					{
+						lrad = lights[2 * li];
+						if (isblack(xyz(lrad))) continue;                               // Li would be black (integrator.cc:362): skip the evaluation, keep the draws
+						const float ux = rngf(rc, key, d0), uy = rngf(rc, key, d0 + 1);
+						ls = sample_li<F>(sc, prims, lights, li, p, N, ux, uy);
+					}
 					if (isblack(ls.Li) || ls.pdf == 0.f) continue;
 					const V3 f = eval_local<F>(c, wo, to_local(fr, ls.wi));            // FBSDF::Evalf bsdf.h:284-287
 					if (isblack(f)) continue;
@@ -633,8 +653,8 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 template <bool kTab, bool kPrims, bool kStage, bool kSort, typename F = FeatAll>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt)
 {
-	const TexView tv = {}; const PickView pv = {};
-	shade_body<kTab, kPrims, kStage, kSort, false, false, F>(sc, q, rc, cur, cnt, tv, pv);
+	const TexView tv = {}; const PickView pv = {}; const EnvView ev = {};
+	shade_body<kTab, kPrims, kStage, kSort, false, false, false, F>(sc, q, rc, cur, cnt, tv, pv, ev);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1186,8 +1206,8 @@ __global__ void __launch_bounds__(JP_BLOCK, 8) k_texel(SceneView sc, Queues q, i
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_tex(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, TexView tv)
 {
-	const PickView pv = {};
-	shade_body<kTab, kPrims, kStage, kSort, true, false>(sc, q, rc, cur, cnt, tv, pv);
+	const PickView pv = {}; const EnvView ev = {};
+	shade_body<kTab, kPrims, kStage, kSort, true, false, false>(sc, q, rc, cur, cnt, tv, pv, ev);
 }
 
 // k_surface (jp_surface): the closest hit of k_trace's walk, then the uv k_texel computes and the colour k_shade_tex puts in the textured
@@ -1232,4 +1252,6 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_upload.h"           // jp_upload_scene: check -> tables (host builders or device-side build) -> uploads -> plan; jp_describe_upload
 #include "jp_render.h"           // jp_render*: queues, launch sequence, stream lanes, fused schedule; counters, jp_trace, jp_bsdf
 #include "jp_denoise.h"          // guides and denoising: k_guides, k_atrous and their entry points (additive: nothing above refers to it)
+#define JP_ENV_RUNTIME
+#include "jp_env.h"              // environment maps, part 2: k_shade_env / k_shade_env_tex, k_env_probe and their entry points (jp_render.h declares the selector)
 #include "jp_pick.h"             // light selection: the alias table, k_shade_pick / k_shade_pick_tex, k_light_pick and their entry points (jp_render.h declares its two hooks)

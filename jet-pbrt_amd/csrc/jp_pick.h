@@ -1,5 +1,5 @@
 // jet-pbrt_amd/csrc/jp_pick.h -- light selection (JP_LIGHTS_POWER_ONE; INTEGRATION.md "Light selection", DESIGN.md "Light selection"): the alias table
-// builder, the upload's table step, k_shade_pick / k_shade_pick_tex (shade_body<..., kPick>), the test hook k_light_pick and the entry points
+// builder's entry point (the builder itself: build_light_table, jp_scene_host.h), the upload's table step, k_shade_pick / k_shade_pick_tex (shade_body<..., kPick>), the test hook k_light_pick and the entry points
 // jp_set_light_sampling / jp_get_light_info / jp_get_light_table / jp_light_pick / jp_build_light_table.  Included last by jp_kernels.hip: a context that
 // never switches the mode on runs nothing of this file.
 #pragma once
@@ -9,13 +9,14 @@
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_pick(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, PickView pv)
 {
-	const TexView tv = {};
-	shade_body<kTab, kPrims, kStage, kSort, false, true>(sc, q, rc, cur, cnt, tv, pv);
+	const TexView tv = {}; const EnvView ev = {};
+	shade_body<kTab, kPrims, kStage, kSort, false, true, false>(sc, q, rc, cur, cnt, tv, pv, ev);
 }
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_pick_tex(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, TexView tv, PickView pv)
 {
-	shade_body<kTab, kPrims, kStage, kSort, true, true>(sc, q, rc, cur, cnt, tv, pv);
+	const EnvView ev = {};
+	shade_body<kTab, kPrims, kStage, kSort, true, true, false>(sc, q, rc, cur, cnt, tv, pv, ev);
 }
 // jp_light_pick: the render's selection for n pairs of draws
 __global__ void __launch_bounds__(JP_BLOCK) k_light_pick(PickView pv, int n, const float* __restrict__ u0, const float* __restrict__ u1, int* __restrict__ index, float* __restrict__ pmf)
@@ -42,49 +43,6 @@ ShadePickKernels shade_pick_kernels(const ScenePlan& p)               // the row
 	return shade_pick_row<false, false, false>(p.shade_sort);
 }
 
-// Vose's alias method in double.  Bins of weight 0 are paired first, while the bins above average still hold all of their excess, so rounding
-// can never leave one of them to the closing "threshold 1" step: a light of weight 0 is in no bin's reach.  W: the weights summed in index order.
-int build_light_table(int n, const double* w, float* q, int32_t* alias, float* pmf, double* W_out, int* n_sel_out)
-{
-	double W = 0.0; int nsel = 0;
-	for (int i = 0; i < n; i++)
-	{
-		if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: a weight is negative or not finite");
-		W += w[i]; if (w[i] > 0.0) nsel++;
-	}
-	if (W_out) *W_out = std::isfinite(W) ? W : 0.0;
-	if (n_sel_out) *n_sel_out = nsel;
-	if (!std::isfinite(W)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: the weights' sum is not finite");
-	if (!(W > 0.0))
-	{
-		for (int i = 0; i < n; i++) { if (q) q[i] = 0.f; if (alias) alias[i] = i; if (pmf) pmf[i] = 0.f; }
-		return JP_OK;
-	}
-	std::vector<double> p((size_t)n); std::vector<int> small, large, al((size_t)n); std::vector<float> th((size_t)n);
-	small.reserve((size_t)n); large.reserve((size_t)n);
-	for (int i = 0; i < n; i++) { p[i] = w[i] * (double)n / W; al[i] = i; th[i] = 1.f; }
-	for (int i = n - 1; i >= 0; i--) if (w[i] > 0.0 && p[i] < 1.0) small.push_back(i);
-	for (int i = n - 1; i >= 0; i--) if (w[i] == 0.0) small.push_back(i);          // on top of the stack: taken first
-	for (int i = n - 1; i >= 0; i--) if (p[i] >= 1.0) large.push_back(i);
-	while (!small.empty() && !large.empty())
-	{
-		const int s = small.back(); small.pop_back();
-		const int l = large.back();
-		th[s] = (float)p[s]; al[s] = l;
-		p[l] = (p[l] + p[s]) - 1.0;
-		if (p[l] < 1.0) { large.pop_back(); small.push_back(l); }
-	}
-	// what is left has its whole bin (threshold 1): bins above average, and bins that rounding left a hair below it.  A bin of weight 0 left
-	// here would mean every positive weight was used up first, which the order above excludes; refused rather than made selectable.
-	for (int s : small) if (w[s] == 0.0) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: weights too extreme for the table");
-	for (int i = 0; i < n; i++)
-	{
-		if (q) q[i] = th[i];
-		if (alias) alias[i] = al[i];
-		if (pmf) pmf[i] = (float)(w[i] / W);
-	}
-	return JP_OK;
-}
 }
 
 // the upload's table step (jp_upload_scene, mode JP_LIGHTS_POWER_ONE): weights, table, the environment list, the device copies into the upload's
@@ -101,6 +59,7 @@ static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, con
 		const int ty = s->light_type[i];
 		if (ty == JP_LIGHT_AREA) w[i] = (sum * (double)area[i]) * kPi;
 		else if (ty == JP_LIGHT_POINT) w[i] = sum * (4.0 * kPi);
+		else if (plan.env && ty == JP_LIGHT_ENVIRONMENT) w[i] = (plan.env_mean_sum * kPi) * ((double)s->world_radius * (double)s->world_radius);   // the map light (jp_env.h): the map's mean in place of the sum
 		else w[i] = (sum * kPi) * ((double)s->world_radius * (double)s->world_radius);          // light.cc:17-33
 		if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene: a light's power is negative or not finite (JP_LIGHTS_POWER_ONE)");
 		if (ty == JP_LIGHT_ENVIRONMENT && !(rad[0] == 0.f && rad[1] == 0.f && rad[2] == 0.f)) env.push_back(make_float4(rad[0], rad[1], rad[2], 0.f));

@@ -159,6 +159,11 @@ typedef void (*ShadePickKernel)(SceneView, Queues, RenderConst, int, DevCounters
 typedef void (*ShadePickTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView);
 struct ShadePickKernels { ShadePickKernel plain; ShadePickTexKernel tex; };
 ShadePickKernels shade_pick_kernels(const ScenePlan& p);
+// ... with an environment map: k_shade_env and its textured twin, same rows again (selector in jp_env.h)
+typedef void (*ShadeEnvKernel)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, EnvView);
+typedef void (*ShadeEnvTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView);
+struct ShadeEnvKernels { ShadeEnvKernel plain; ShadeEnvTexKernel tex; };
+ShadeEnvKernels shade_env_kernels(const ScenePlan& p);
 
 // the other two integrators' megakernel: one ray per lane, launched like the plain k_extend (plan.lds_bytes, plan.stack_depth)
 typedef void (*OtherKernel)(SceneView, Queues, RenderConst, int, int, DevCounters*);
@@ -255,6 +260,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		const bool generic = c->opt.reserved[0] == 1;                // JpOptions::reserved[0]: the kernels with every feature in them, whatever the scene holds
 		const ExtendLaunch ek = extend_kernel(p, generic); const ShadowLaunch sk = shadow_kernel(p, R, generic); const ShadeKernels hk = shade_kernels(p, generic); const OtherKernel ok = other_kernel(p);
 		const ShadePickKernels pk = p.pick ? shade_pick_kernels(p) : ShadePickKernels{ nullptr, nullptr };
+		const ShadeEnvKernels vk = p.env ? shade_env_kernels(p) : ShadeEnvKernels{ nullptr, nullptr };
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
@@ -286,9 +292,11 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 					if (tex)
 					{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
 						hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
-						if (p.pick) hipLaunchKernelGGL(pk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv);
+						if (p.env) hipLaunchKernelGGL(vk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev);
+						else if (p.pick) hipLaunchKernelGGL(pk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv);
 						else hipLaunchKernelGGL(hk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv);
 					}
+					else if (p.env) hipLaunchKernelGGL(vk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev);
 					else if (p.pick) hipLaunchKernelGGL(pk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv);
 					else hipLaunchKernelGGL(hk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt);
 				}
@@ -491,12 +499,14 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0;
+	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
 	if (c->plan.pick && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator samples every light (scene uploaded with JP_LIGHTS_POWER_ONE)");
 	if (c->plan.textured && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample textures (scene uploaded by jp_upload_scene_textured)");
 	if (fused_eligible(c, rp)) return render_fused(c, rp, film_dev, sync);
 	c->last_textured = c->plan.textured && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_picked = c->plan.pick && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_mapped = c->plan.env && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
 	// Gsamples/s).  JETPBRT_LANES = 1 .. 4 forces a count, JETPBRT_LANE_ROWS the group height.

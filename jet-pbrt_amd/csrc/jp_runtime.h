@@ -56,6 +56,7 @@ struct ScenePlan
 	bool have_scene = false;
 	SceneView sv; TexView tv = {}; bool textured = false;
 	PickView pv = {}; bool pick = false;                                               // JP_LIGHTS_POWER_ONE (jp_pick.h): the alias table; one shadow plane, no light records in k_shade's LDS tables
+	EnvView ev = {}; bool env = false; double env_mean_sum = 0.0;                      // environment map (jp_env.h): the texel tables; the map light's weight in the light table is (env_mean_sum * pi) * R^2
 	int trav_mode = 0, stack_depth = 1, stack_depth_q4 = 0; bool scene_in_lds = false, shade_prims_in_lds = false; size_t lds_bytes = 0, lds_bytes_shadow = 0;
 	bool cert = false;                                                                 // reference semantics, certified walk (Walker<6>)
 	bool use_q4 = false, q4_shadow = false;                                            // closest-hit (and, as an experiment, shadow) rays walk the 4-wide quantised tree (Walker<4>)
@@ -76,9 +77,13 @@ struct SceneTables
 	DevBuf nodes, prims, meta, mats, mat_type, lights, shade_tab, flat, wide, q4, refbox;
 	DevBuf tex_desc, tex_col, texels, mat_tex, prim_uv;             // jp_upload_scene_textured
 	DevBuf pick_bins, pick_pmf, pick_env;                            // JP_LIGHTS_POWER_ONE (jp_pick.h)
+	DevBuf env_texel, env_bins, env_rows;                            // environment map (jp_env.h)
 };
 // The arrays behind a Queues view (the fused schedule's region queues have no hit records and no per-block counts)
 struct QueueBufs { DevBuf ray_o[2], ray_d[2], beta[2], blk_q[2], hit, lacc, sh_o, sh_d, sh_c, blk_sh; };
+
+// the map jp_set_environment_map copied, waiting for the next upload (W == 0: none)
+struct EnvMapHost { int W = 0, H = 0, up = 0, importance = 0; std::vector<float> rgb; };
 
 struct JpContext
 {
@@ -127,9 +132,13 @@ struct JpContext
 	// reaches the lanes through `plan.pv`) and what jp_get_light_info reports
 	int light_mode = JP_LIGHTS_ALL;
 	int n_selectable = 0; double total_weight = 0.0; int last_picked = 0;
+	// environment map (jp_env.h): the map the next upload takes (jp_set_environment_map), and what jp_get_env_info reports of the uploaded scene's
+	EnvMapHost env_map;
+	int env_importance = 0, env_n_selectable = 0; double env_total_weight = 0.0; long long env_table_bytes = 0; int last_mapped = 0;
 };
-// jp_pick.h (included last) defines the upload's table step
+// jp_pick.h / jp_env.h (included last) define the upload's table steps
 static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area);
+static int upload_environment_map(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, bool pick);
 
 // a context buffer that kernels in flight may still use: grown only once the stream is idle (nothing happens when the capacity suffices)
 static int reserve_idle(JpContext* c, DevBuf& b, size_t bytes)
@@ -146,6 +155,7 @@ static void free_scene(JpContext* c)
 	c->tab = SceneTables();
 	c->plan.have_scene = false;
 	c->plan.pv = PickView(); c->plan.pick = false; c->n_selectable = 0; c->total_weight = 0.0;
+	c->plan.ev = EnvView(); c->plan.env = false; c->plan.env_mean_sum = 0.0; c->env_n_selectable = 0; c->env_total_weight = 0.0; c->env_table_bytes = 0;
 	c->plan.tv = TexView(); c->plan.textured = false; c->n_textures = c->n_tex_mats = 0; c->texel_bytes = 0;   // (jp_upload_scene drops the textures of an earlier textured upload)
 	c->side.reset();                                               // ... and the side array only textured frames use (callers synchronise first)
 }

@@ -641,6 +641,101 @@ int build_host_tables(const JpScene* s, const JpOptions& op, bool pick, const Sc
 	return JP_OK;
 }
 
+// ---- the alias table of JP_LIGHTS_POWER_ONE (jp_pick.h) and of the environment map's texels (jp_env.h) ----------------------------------
+// Vose's alias method in double.  Bins of weight 0 are paired first, while the bins above average still hold all of their excess, so rounding
+// can never leave one of them to the closing "threshold 1" step: a light of weight 0 is in no bin's reach.  W: the weights summed in index order.
+int build_light_table(int n, const double* w, float* q, int32_t* alias, float* pmf, double* W_out, int* n_sel_out)
+{
+	double W = 0.0; int nsel = 0;
+	for (int i = 0; i < n; i++)
+	{
+		if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: a weight is negative or not finite");
+		W += w[i]; if (w[i] > 0.0) nsel++;
+	}
+	if (W_out) *W_out = std::isfinite(W) ? W : 0.0;
+	if (n_sel_out) *n_sel_out = nsel;
+	if (!std::isfinite(W)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: the weights' sum is not finite");
+	if (!(W > 0.0))
+	{
+		for (int i = 0; i < n; i++) { if (q) q[i] = 0.f; if (alias) alias[i] = i; if (pmf) pmf[i] = 0.f; }
+		return JP_OK;
+	}
+	std::vector<double> p((size_t)n); std::vector<int> small, large, al((size_t)n); std::vector<float> th((size_t)n);
+	small.reserve((size_t)n); large.reserve((size_t)n);
+	for (int i = 0; i < n; i++) { p[i] = w[i] * (double)n / W; al[i] = i; th[i] = 1.f; }
+	for (int i = n - 1; i >= 0; i--) if (w[i] > 0.0 && p[i] < 1.0) small.push_back(i);
+	for (int i = n - 1; i >= 0; i--) if (w[i] == 0.0) small.push_back(i);          // on top of the stack: taken first
+	for (int i = n - 1; i >= 0; i--) if (p[i] >= 1.0) large.push_back(i);
+	while (!small.empty() && !large.empty())
+	{
+		const int s = small.back(); small.pop_back();
+		const int l = large.back();
+		th[s] = (float)p[s]; al[s] = l;
+		p[l] = (p[l] + p[s]) - 1.0;
+		if (p[l] < 1.0) { large.pop_back(); small.push_back(l); }
+	}
+	// what is left has its whole bin (threshold 1): bins above average, and bins that rounding left a hair below it.  A bin of weight 0 left
+	// here would mean every positive weight was used up first, which the order above excludes; refused rather than made selectable.
+	for (int s : small) if (w[s] == 0.0) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_light_table: weights too extreme for the table");
+	for (int i = 0; i < n; i++)
+	{
+		if (q) q[i] = th[i];
+		if (alias) alias[i] = al[i];
+		if (pmf) pmf[i] = (float)(w[i] / W);
+	}
+	return JP_OK;
+}
+
+// ---- environment map (jp_env.h; INTEGRATION.md "Environment maps"): the check and the tables, in double from the tinted fp32 texels ------
+int check_environment_map(const char* who, const JpEnvMap* m)
+{
+	const std::string w(who);
+	if (m->struct_bytes < (int32_t)sizeof(JpEnvMap)) return fail(JP_ERR_INVALID_ARGUMENT, w + ": set JpEnvMap.struct_bytes to sizeof(JpEnvMap)");
+	if (m->width < 1 || m->width > 4096 || m->height < 1 || m->height > 4096) return fail(JP_ERR_INVALID_ARGUMENT, w + ": map size out of range (1 .. 4096 per side)");
+	if (m->up_axis != JP_ENV_UP_Z && m->up_axis != JP_ENV_UP_Y) return fail(JP_ERR_INVALID_ARGUMENT, w + ": unknown up_axis");
+	if (m->importance != 0 && m->importance != -1) return fail(JP_ERR_INVALID_ARGUMENT, w + ": importance must be 0 or -1");
+	if (!m->rgb) return fail(JP_ERR_INVALID_ARGUMENT, w + ": null rgb");
+	const size_t n = 3 * (size_t)m->width * m->height;
+	for (size_t i = 0; i < n; i++) if (!(m->rgb[i] >= 0.f) || !std::isfinite(m->rgb[i])) return fail(JP_ERR_INVALID_ARGUMENT, w + ": a texel value is negative or not finite");
+	return JP_OK;
+}
+struct EnvTables
+{
+	std::vector<double> weight; std::vector<float> q; std::vector<int32_t> alias; std::vector<float4> texel; std::vector<float2> row_cos;
+	double total = 0.0, mean_sum = 0.0; int n_selectable = 0;
+};
+// texel = tint * map in fp32; Omega_r = (2 pi / W) (ct_r - cb_r); w_t = ((R + G) + B) Omega_r (importance -1: Omega_r); the alias table is build_light_table's
+int build_environment_table(const JpEnvMap* m, const float* tint, EnvTables& e)
+{
+	if (const int st = check_environment_map("jp_build_environment_table", m); st != JP_OK) return st;
+	for (int k = 0; k < 3; k++) if (!(tint[k] >= 0.f) || !std::isfinite(tint[k])) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_environment_table: the tint is negative or not finite");
+	const double kPi = 3.14159265358979323846;
+	const int W = m->width, H = m->height; const size_t n = (size_t)W * H;
+	e.weight.resize(n); e.q.resize(n); e.alias.resize(n); e.texel.resize(n); e.row_cos.resize((size_t)H);
+	std::vector<double> omega((size_t)H);
+	double lum = 0.0;
+	for (int r = 0; r < H; r++)
+	{
+		const double ct = std::cos(kPi * (double)r / (double)H), cb = std::cos(kPi * (double)(r + 1) / (double)H);
+		omega[r] = (2.0 * kPi / (double)W) * (ct - cb);
+		e.row_cos[r] = make_float2((float)ct, (float)cb);
+		for (int c = 0; c < W; c++)
+		{
+			const size_t t = (size_t)r * W + c;
+			const float R = tint[0] * m->rgb[3 * t], G = tint[1] * m->rgb[3 * t + 1], B = tint[2] * m->rgb[3 * t + 2];
+			if (!std::isfinite(R) || !std::isfinite(G) || !std::isfinite(B)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_build_environment_table: tint x texel is not finite");
+			const double s = (((double)R + (double)G) + (double)B) * omega[r];
+			lum += s;
+			e.weight[t] = m->importance == -1 ? omega[r] : s;
+			e.texel[t] = make_float4(R, G, B, 0.f);
+		}
+	}
+	if (const int st = build_light_table((int)n, e.weight.data(), e.q.data(), e.alias.data(), nullptr, &e.total, &e.n_selectable); st != JP_OK) return st;
+	if (e.total > 0.0) for (size_t t = 0; t < n; t++) e.texel[t].w = (float)((e.weight[t] / e.total) / omega[t / (size_t)W]);
+	e.mean_sum = lum / (4.0 * kPi);
+	return JP_OK;
+}
+
 // ---- the plan: a pure function of the scene, the options and the sizes the builders (host or device) arrived at ------------------------
 // Fills every scalar of the plan; the caller binds the views (sv, tv, pv) to its device tables.
 ScenePlan plan_scene(const JpScene* s, const JpOptions& op, bool pick, bool device_build, const PlanSizes& z)

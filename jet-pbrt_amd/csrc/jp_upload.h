@@ -91,6 +91,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	for (int i = 0; i < TAB_COUNT; i++) if (tb[i].present) HIP_TRY(upload(T.*kDst[i], tb[i].data, tb[i].bytes));
 	ScenePlan p = plan_scene(s, c->opt, pick, k.device_build, t.sizes());
 	bind_scene_view(p.sv, T, t, s);
+	if (c->env_map.W > 0) { if (const int st = upload_environment_map(c, T, p, s, pick); st != JP_OK) return st; c->env_importance = c->env_map.importance; }   // before the light table, which weighs the map light
 	if (pick) if (const int st = upload_light_table(c, T, p, s, t.light_area); st != JP_OK) return st;
 
 	c->tab = std::move(T); c->plan = p; c->plan.have_scene = true;

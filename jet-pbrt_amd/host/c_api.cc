@@ -16,6 +16,7 @@ struct HostScene
 	std::vector<std::shared_ptr<FTexture>> texs;
 	FlatScene flat; bool flattened = false;
 	std::unique_ptr<FGpuPathIntegrator> integ; int integDepth = -1;
+	JpEnvMap envView;                                             // jp_host_flatten_envmap
 	std::string error;
 };
 FColor C3(const float* v) { return FColor(v[0], v[1], v[2]); }
@@ -95,6 +96,39 @@ void jp_host_scene_disk(void* h, const float* pos, const float* normal, float ra
 void jp_host_scene_set_reference_tree(void* h, int on) { ((HostScene*)h)->scene->referenceTree = on != 0; ((HostScene*)h)->scene->certifiedWalk = on == 2; }   // 1: verbatim walk, 2: certified walk
 void jp_host_scene_set_device_build(void* h, int on) { ((HostScene*)h)->scene->deviceBuild = on != 0; ((HostScene*)h)->scene->hostBuild = on == 0; }   // explicit either way
 void jp_host_scene_set_light_sampling(void* h, int mode) { ((HostScene*)h)->scene->SetLightSampling(mode); }   // FScene::SetLightSampling (JP_LIGHTS_*)
+// FScene::SetEnvironmentMap from memory (3 * w * hgt floats, top row first; null: no map) or from a file (FEnvironmentMap::FromFile); importance -1:
+// the A/B hook of JpEnvMap.  0, or -1 with jp_host_last_error set
+int jp_host_scene_envmap(void* h, const float* rgb, int w, int hgt, int up_axis, int importance)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!rgb) { hs->scene->SetEnvironmentMap(nullptr); return 0; }
+	auto m = std::make_shared<FEnvironmentMap>(rgb, w, hgt);
+	if (!m->Valid()) { hs->error = "jp_host_scene_envmap: size out of range (1 .. 4096 per side)"; return -1; }
+	if (up_axis != JP_ENV_UP_Z && up_axis != JP_ENV_UP_Y) { hs->error = "jp_host_scene_envmap: unknown up axis"; return -1; }
+	hs->scene->SetEnvironmentMap(m, up_axis); hs->scene->environmentImportance = importance;
+	return 0;
+}
+int jp_host_scene_envmap_file(void* h, const char* path, int up_axis)
+{
+	HostScene* hs = (HostScene*)h;
+	std::string err;
+	auto m = FEnvironmentMap::FromFile(path, &err);
+	if (!m) { hs->error = std::string("jp_host_scene_envmap_file: ") + (path ? path : "") + ": " + err; return -1; }
+	if (up_axis != JP_ENV_UP_Z && up_axis != JP_ENV_UP_Y) { hs->error = "jp_host_scene_envmap_file: unknown up axis"; return -1; }
+	hs->scene->SetEnvironmentMap(m, up_axis); hs->scene->environmentImportance = 0;
+	return 0;
+}
+// the scene's map as the JpEnvMap FGpuPathIntegrator::Render hands to jp_set_environment_map (owned by the handle; null: no map)
+const JpEnvMap* jp_host_flatten_envmap(void* h)
+{
+	HostScene* hs = (HostScene*)h;
+	const FEnvironmentMap* m = hs->scene->environmentMap.get();
+	if (!m || !m->Valid()) return nullptr;
+	JpEnvMap& v = hs->envView;
+	v.struct_bytes = (int32_t)sizeof(JpEnvMap); v.width = m->width; v.height = m->height; v.up_axis = hs->scene->environmentUp; v.importance = hs->scene->environmentImportance; v.rgb = m->data.data();
+	return &v;
+}
+
 void jp_host_scene_preprocess(void* h) { HostScene* hs = (HostScene*)h; hs->scene->Preprocess(); hs->flattened = false; }
 int  jp_host_num_primitives(void* h) { return (int)((HostScene*)h)->scene->primitives.size(); }
 int  jp_host_num_lights(void* h) { return ((HostScene*)h)->scene->LightNum(); }

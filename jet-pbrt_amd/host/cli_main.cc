@@ -1,6 +1,8 @@
 // jet-pbrt_amd/host/cli_main.cc -- the reference's command line (main.cc:113-163) on the GPU integrator:
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
-//             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power]
+//             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]]
+// --envmap FILE: light the scene with a lat-long image (PFM, Radiance .hdr, binary PPM, BMP; FScene::SetEnvironmentMap): the scene script's background
+// becomes the tint (S, S, S), S = 1 unless --envmap-scale says otherwise; --envmap-up: the map's up axis (default y, the scenes' up); power sampling is implied.
 // --light-sampling power: one light per bounce, picked by power (FScene::SetLightSampling(JP_LIGHTS_POWER_ONE)); all (default): every light at every bounce.
 // --denoise: the edge-avoiding filter on the rendered film (FFilm::RequestDenoise); --guide-spp: camera samples per pixel of its guides (default 8,
 // 1 .. 1024); --aov: the guides as images PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5), PREFIX_depth (t / max t) in the chosen format.
@@ -23,12 +25,12 @@ static FColor LightRadiance()                                    // main.cc:35
 	return FColor(r.x, r.y, r.z);
 }
 
-static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize, const std::string& dir)   // main.cc:13-62
+static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr)   // main.cc:13-62; background: --envmap's tint
 {
 	const FPoint3 lookfrom(278, 273, 960), lookat(278, 273, 0);
 	std::shared_ptr<FScene> scene = std::make_shared<FScene>("cornell_box_scene");
 	scene->CreateCamera<FCamera>(lookfrom, Normalize(lookat - lookfrom), FVector3(0, 1, 0), (Float)60.0, filmsize);
-	scene->CreateLight<FEnvironmentLight>(FPoint3(0, 0, 0), 1, FColor(0.f, 0.f, 0.f));
+	scene->CreateLight<FEnvironmentLight>(FPoint3(0, 0, 0), 1, background ? *background : FColor(0.f, 0.f, 0.f));
 	std::shared_ptr<FMaterial> red = scene->CreateMaterial<FMatteMaterial>(FColor(0.63f, 0.065f, 0.05f));
 	std::shared_ptr<FMaterial> green = scene->CreateMaterial<FMatteMaterial>(FColor(0.14f, 0.45f, 0.091f));
 	std::shared_ptr<FMaterial> white = scene->CreateMaterial<FMatteMaterial>(FColor(0.725f, 0.71f, 0.68f));
@@ -45,12 +47,12 @@ static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize,
 	return scene;
 }
 
-static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, const std::string& dir)        // main.cc:64-111
+static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr)        // main.cc:64-111
 {
 	const FPoint3 lookfrom(-300, 300, -300), lookat(0, 0, 0);
 	std::shared_ptr<FScene> scene = std::make_shared<FScene>("bunny_scene");
 	scene->CreateCamera<FCamera>(lookfrom, Normalize(lookat - lookfrom), FVector3(0, 1, 0), (Float)60.0, filmsize);
-	scene->CreateLight<FEnvironmentLight>(FPoint3(0, 0, 0), 1, FColor(0.1f, 0.1f, 0.5f));
+	scene->CreateLight<FEnvironmentLight>(FPoint3(0, 0, 0), 1, background ? *background : FColor(0.1f, 0.1f, 0.5f));
 	std::shared_ptr<FMaterial> red = scene->CreateMaterial<FMatteMaterial>(FColor(0.63f, 0.065f, 0.05f));
 	std::shared_ptr<FMaterial> green = scene->CreateMaterial<FMatteMaterial>(FColor(0.14f, 0.45f, 0.091f));
 	scene->CreateMaterial<FMatteMaterial>(FColor(0.725f, 0.71f, 0.68f));
@@ -76,8 +78,9 @@ int main(int argc, char* argv[])
 	int width = 1024, height = 1024, samples_per_pixel = 50;     // main.cc:115,119
 	std::string assets = "scene", out, format = "bmp", integratorName = "path";
 	bool denoise = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL;
+	std::string envmap; int envUp = JP_ENV_UP_Y; float envScale = 1.f;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
-	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power]\n");
+	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -97,6 +100,14 @@ int main(int argc, char* argv[])
 			if (!strcmp(m, "power")) lightSampling = JP_LIGHTS_POWER_ONE; else if (!strcmp(m, "all")) lightSampling = JP_LIGHTS_ALL;
 			else { fprintf(stderr, "--light-sampling must be all or power\n"); return 5; }
 		}
+		else if (!strcmp(argv[i], "--envmap") && i + 1 < argc) envmap = argv[++i];
+		else if (!strcmp(argv[i], "--envmap-up") && i + 1 < argc)
+		{
+			const char* m = argv[++i];
+			if (!strcmp(m, "y")) envUp = JP_ENV_UP_Y; else if (!strcmp(m, "z")) envUp = JP_ENV_UP_Z;
+			else { fprintf(stderr, "--envmap-up must be y or z\n"); return 5; }
+		}
+		else if (!strcmp(argv[i], "--envmap-scale") && i + 1 < argc) { envScale = (float)atof(argv[++i]); if (!(envScale >= 0.f) || !std::isfinite(envScale)) { fprintf(stderr, "--envmap-scale must be a number >= 0\n"); return 5; } }
 		else pos.push_back(argv[i]);
 	}
 	if (pos.empty()) return 0;                                    // main.cc:122-125
@@ -104,13 +115,22 @@ int main(int argc, char* argv[])
 	if (pos.size() > 1) { int spp = atoi(pos[1]); if (spp > 0) samples_per_pixel = spp; }
 	if (pos.size() > 3) { int w = atoi(pos[2]), h = atoi(pos[3]); if (w > 0 && h > 0) { width = w; height = h; } }
 	FFilm film(width, height);
+	std::shared_ptr<FEnvironmentMap> map;
+	if (!envmap.empty())
+	{
+		std::string err;
+		map = FEnvironmentMap::FromFile(envmap.c_str(), &err);
+		if (!map) { fprintf(stderr, "--envmap %s: %s\n", envmap.c_str(), err.c_str()); return 5; }
+	}
+	const FColor tint(envScale, envScale, envScale);
 	std::shared_ptr<FScene> scene;
 	switch (sceneId)
 	{
-	case 0: scene = create_cornellbox_scene(film.GetResolution(), assets); break;
-	case 1: scene = create_bunny_scene(film.GetResolution(), assets); break;
+	case 0: scene = create_cornellbox_scene(film.GetResolution(), assets, map ? &tint : nullptr); break;
+	case 1: scene = create_bunny_scene(film.GetResolution(), assets, map ? &tint : nullptr); break;
 	default: return 0;
 	}
+	if (map) scene->SetEnvironmentMap(map, envUp);
 	fprintf(stderr, "current scene: %s\n", scene->NameStr());
 	scene->SetLightSampling(lightSampling);
 	if (scene->primitives.empty()) { fprintf(stderr, "no geometry loaded from %s\n", assets.c_str()); return 2; }

@@ -14,6 +14,7 @@
 #include <fstream>
 #include <iostream>
 #include <iterator>
+#include <atomic>
 
 namespace jetpbrt
 {
@@ -198,5 +199,163 @@ FImageTexture::FImageTexture(const char* filename) : width(0), height(0)
 FImageTexture::FImageTexture(const uint8_t* rgb8, int w, int h) : width(0), height(0)
 {
 	if (rgb8 && w > 0 && h > 0) { data.assign(rgb8, rgb8 + (size_t)w * h * 3); width = w; height = h; }
+}
+} // namespace jetpbrt
+
+// ---- float image readers of FEnvironmentMap: files from outside, every offset checked against the bytes read ------------------------------
+namespace jetpbrt
+{
+namespace
+{
+bool Refuse(std::string* error, const std::string& msg) { if (error) *error = msg; return false; }
+bool ReadWhole(const char* filename, std::vector<uint8_t>& f)
+{
+	if (!filename) return false;
+	std::ifstream in(filename, std::ios::binary);
+	if (!in) return false;
+	f.assign((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+	return true;
+}
+bool MapSizeOk(long w, long h) { return w >= 1 && w <= 4096 && h >= 1 && h <= 4096; }
+bool TexelsOk(const std::vector<float>& rgb) { for (float v : rgb) if (!(v >= 0.f) || !std::isfinite(v)) return false; return true; }
+}
+
+bool ReadImagePFM(const char* filename, std::vector<float>& rgb, int& width, int& height, std::string* error)
+{
+	rgb.clear(); width = height = 0;
+	std::vector<uint8_t> f;
+	if (!ReadWhole(filename, f)) return Refuse(error, "cannot read the file");
+	if (f.size() < 3 || f[0] != 'P' || (f[1] != 'F' && f[1] != 'f') || !std::isspace(f[2])) return Refuse(error, "not a PFM file");
+	const int nch = f[1] == 'F' ? 3 : 1;
+	size_t at = 2; long w = 0, h = 0;
+	if (!PpmToken(f, at, w) || !PpmToken(f, at, h)) return Refuse(error, "PFM: bad size");
+	if (!MapSizeOk(w, h)) return Refuse(error, "PFM: size out of range (1 .. 4096 per side)");
+	// the scale line: a decimal number, negative for little-endian floats; one whitespace byte ends the header
+	while (at < f.size() && (f[at] == ' ' || f[at] == '\t' || f[at] == '\r' || f[at] == '\n')) at++;
+	const size_t s0 = at;
+	while (at < f.size() && !std::isspace(f[at]) && at - s0 < 64) at++;
+	if (at == s0 || at >= f.size() || !std::isspace(f[at])) return Refuse(error, "PFM: bad scale line");
+	const std::string tok((const char*)&f[s0], at - s0);
+	char* end = nullptr; const double scale = std::strtod(tok.c_str(), &end);
+	if (end == tok.c_str() || *end != 0 || !(scale != 0.0) || !std::isfinite(scale)) return Refuse(error, "PFM: bad scale line");
+	at++;
+	const size_t n = (size_t)w * h, need = n * nch * 4;
+	if (f.size() - at < need) return Refuse(error, "PFM: truncated");
+	const bool little = scale < 0.0;
+	rgb.resize(n * 3);
+	for (long y = 0; y < h; y++)
+		for (long x = 0; x < w; x++)
+		{
+			const uint8_t* p = &f[at + ((size_t)(h - 1 - y) * w + x) * nch * 4];          // the file's first row is the image's bottom row
+			for (int k = 0; k < 3; k++)
+			{
+				const uint8_t* b = p + (nch == 3 ? 4 * k : 0);
+				const uint32_t u = little ? ((uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24))
+				                          : ((uint32_t)b[3] | ((uint32_t)b[2] << 8) | ((uint32_t)b[1] << 16) | ((uint32_t)b[0] << 24));
+				float v; std::memcpy(&v, &u, 4);
+				rgb[3 * ((size_t)y * w + x) + k] = v;
+			}
+		}
+	if (!TexelsOk(rgb)) { rgb.clear(); return Refuse(error, "PFM: a value is negative or not finite"); }
+	width = (int)w; height = (int)h;
+	return true;
+}
+
+bool ReadImageHDR(const char* filename, std::vector<float>& rgb, int& width, int& height, std::string* error)
+{
+	rgb.clear(); width = height = 0;
+	std::vector<uint8_t> f;
+	if (!ReadWhole(filename, f)) return Refuse(error, "cannot read the file");
+	if (f.size() < 2 || f[0] != '#' || f[1] != '?') return Refuse(error, "not a Radiance HDR file");
+	// header lines up to the empty one, then the resolution line
+	size_t at = 0; bool blank = false, rgbe = false;
+	while (at < f.size())
+	{
+		const size_t e = std::find(f.begin() + at, f.end(), (uint8_t)'\n') - f.begin();
+		if (e >= f.size()) return Refuse(error, "HDR: truncated header");
+		const std::string line((const char*)&f[at], e - at);
+		at = e + 1;
+		if (line.empty()) { blank = true; break; }
+		if (line == "FORMAT=32-bit_rle_rgbe") rgbe = true;
+	}
+	if (!blank || !rgbe) return Refuse(error, "HDR: no FORMAT=32-bit_rle_rgbe header");
+	const size_t e = std::find(f.begin() + std::min(at, f.size()), f.end(), (uint8_t)'\n') - f.begin();
+	if (e >= f.size()) return Refuse(error, "HDR: truncated header");
+	const std::string res((const char*)&f[at], e - at);
+	at = e + 1;
+	long h = 0, w = 0; char tail = 0;
+	if (std::sscanf(res.c_str(), "-Y %ld +X %ld%c", &h, &w, &tail) != 2) return Refuse(error, "HDR: resolution line is not \"-Y h +X w\"");
+	if (!MapSizeOk(w, h)) return Refuse(error, "HDR: size out of range (1 .. 4096 per side)");
+	std::vector<uint8_t> px((size_t)w * h * 4);
+	for (long y = 0; y < h; y++)
+	{
+		uint8_t* row = &px[(size_t)y * w * 4];
+		if (w >= 8 && w < 32768 && f.size() - at >= 4 && f[at] == 2 && f[at + 1] == 2 && ((size_t)f[at + 2] << 8 | f[at + 3]) == (size_t)w)
+		{   // a run-length encoded scanline: the four channels one after another, runs (count > 128: count - 128 copies) and literals
+			at += 4;
+			for (int k = 0; k < 4; k++)
+				for (long x = 0; x < w;)
+				{
+					if (at >= f.size()) return Refuse(error, "HDR: truncated");
+					int cnt = f[at++];
+					if (cnt > 128)
+					{
+						cnt -= 128;
+						if (cnt > w - x || at >= f.size()) return Refuse(error, "HDR: bad run");
+						const uint8_t v = f[at++];
+						for (int i = 0; i < cnt; i++) row[4 * (x++) + k] = v;
+					}
+					else
+					{
+						if (cnt == 0 || cnt > w - x || f.size() - at < (size_t)cnt) return Refuse(error, "HDR: bad run");
+						for (int i = 0; i < cnt; i++) row[4 * (x++) + k] = f[at++];
+					}
+				}
+		}
+		else
+		{
+			if (f.size() - at < (size_t)w * 4) return Refuse(error, "HDR: truncated");
+			std::memcpy(row, &f[at], (size_t)w * 4); at += (size_t)w * 4;
+		}
+	}
+	rgb.resize((size_t)w * h * 3);
+	for (size_t i = 0; i < (size_t)w * h; i++)
+	{
+		const uint8_t* p = &px[4 * i];
+		const float s = p[3] ? std::ldexp(1.0f, (int)p[3] - (128 + 8)) : 0.f;              // byte * 2^(e - 128) / 256
+		rgb[3 * i] = p[0] * s; rgb[3 * i + 1] = p[1] * s; rgb[3 * i + 2] = p[2] * s;
+	}
+	if (!TexelsOk(rgb)) { rgb.clear(); return Refuse(error, "HDR: a value is not finite"); }
+	width = (int)w; height = (int)h;
+	return true;
+}
+
+static unsigned long long NextMapId() { static std::atomic<unsigned long long> n{ 0 }; return ++n; }
+
+FEnvironmentMap::FEnvironmentMap(const float* rgb, int w, int h) : id(NextMapId())
+{
+	if (rgb && MapSizeOk(w, h)) { data.assign(rgb, rgb + (size_t)w * h * 3); width = w; height = h; }
+}
+
+std::shared_ptr<FEnvironmentMap> FEnvironmentMap::FromFile(const char* filename, std::string* error)
+{
+	std::vector<uint8_t> head;
+	{
+		std::ifstream in(filename ? filename : "", std::ios::binary);
+		if (!in) { Refuse(error, "cannot read the file"); return nullptr; }
+		char b[2] = { 0, 0 }; in.read(b, 2); head.assign(b, b + in.gcount());
+	}
+	std::vector<float> rgb; int w = 0, h = 0;
+	if (head.size() == 2 && head[0] == 'P' && (head[1] == 'F' || head[1] == 'f')) { if (!ReadImagePFM(filename, rgb, w, h, error)) return nullptr; }
+	else if (head.size() == 2 && head[0] == '#' && head[1] == '?') { if (!ReadImageHDR(filename, rgb, w, h, error)) return nullptr; }
+	else
+	{
+		std::vector<uint8_t> b8;
+		if (!ReadImageRGB8(filename, b8, w, h)) { Refuse(error, "not a PFM, Radiance HDR, binary PPM or uncompressed BMP file (or truncated)"); return nullptr; }
+		if (!MapSizeOk(w, h)) { Refuse(error, "size out of range (1 .. 4096 per side)"); return nullptr; }
+		rgb.resize(b8.size());
+		for (size_t i = 0; i < b8.size(); i++) rgb[i] = (float)b8[i] / 255.f;
+	}
+	return std::make_shared<FEnvironmentMap>(rgb.data(), w, h);
 }
 } // namespace jetpbrt

@@ -29,6 +29,7 @@ struct HipApi
 	int (*upload_scene_textured)(JpContext*, const JpScene*, const JpTextures*) = nullptr;   // (looked up, needed by textured scenes only)
 	int (*render_denoised)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*) = nullptr;   // (looked up, needed by FFilm::RequestGuides / RequestDenoise only)
 	int (*set_light_sampling)(JpContext*, const JpLightSampling*) = nullptr;                 // (looked up, needed by FScene::SetLightSampling only)
+	int (*set_environment_map)(JpContext*, const JpEnvMap*) = nullptr;                       // (looked up, needed by FScene::SetEnvironmentMap only)
 	std::string error;
 };
 
@@ -57,6 +58,7 @@ HipApi& Api()
 		api.upload_scene_textured = (int (*)(JpContext*, const JpScene*, const JpTextures*))dlsym(api.lib, "jp_upload_scene_textured");
 		api.render_denoised = (decltype(api.render_denoised))dlsym(api.lib, "jp_render_denoised");
 		api.set_light_sampling = (decltype(api.set_light_sampling))dlsym(api.lib, "jp_set_light_sampling");
+		api.set_environment_map = (decltype(api.set_environment_map))dlsym(api.lib, "jp_set_environment_map");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
 		else if (api.abi_version() != JP_ABI_VERSION)            // a stale build would be handed structs of another size (JpCounters, JpBuildInfo, JpOptions)
@@ -116,15 +118,28 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 	if (!scene || !sampler || !film) { fprintf(stderr, "FGpuPathIntegrator::Render: null argument\n"); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
 	if (!ctx) { lastStatus = api.create_context(deviceId, &ctx); if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); ctx = nullptr; return; } }
 	if (optionsDirty) { lastStatus = api.set_options(ctx, &options); if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; } optionsDirty = false; }
-	if (uploaded != scene || uploadedLights != scene->lightSampling)
+	const FEnvironmentMap* const emap = scene->environmentMap && scene->environmentMap->Valid() ? scene->environmentMap.get() : nullptr;
+	if (scene->environmentMap && !emap) { fprintf(stderr, "FGpuPathIntegrator::Render: FScene::SetEnvironmentMap was given an empty map\n"); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
+	const unsigned long long envId = emap ? emap->id : 0;
+	const int lightMode = emap ? JP_LIGHTS_POWER_ONE : scene->lightSampling;            // a mapped scene: the map light is an entry of the light table
+	if (uploaded != scene || uploadedLights != lightMode || uploadedEnv != envId || uploadedEnvUp != scene->environmentUp || uploadedEnvImp != scene->environmentImportance)
 	{
-		if (ctxLights != scene->lightSampling)
+		if (ctxEnv != envId || (envId && (ctxEnvUp != scene->environmentUp || ctxEnvImp != scene->environmentImportance)))
+		{   // FScene::SetEnvironmentMap: the map goes to the context before the upload it is to affect (and leaves it the same way); a scene that never set one makes no such call
+			if (!api.set_environment_map) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_environment_map\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			JpEnvMap m; std::memset(&m, 0, sizeof(m));
+			if (emap) { m.struct_bytes = (int32_t)sizeof(m); m.width = emap->width; m.height = emap->height; m.up_axis = scene->environmentUp; m.importance = scene->environmentImportance; m.rgb = emap->data.data(); }
+			lastStatus = api.set_environment_map(ctx, emap ? &m : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxEnv = envId; ctxEnvUp = scene->environmentUp; ctxEnvImp = scene->environmentImportance; uploaded = nullptr;
+		}
+		if (ctxLights != lightMode)
 		{   // FScene::SetLightSampling: the mode goes to the context before the upload it is to affect; a scene that never set one makes no such call
 			if (!api.set_light_sampling) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_light_sampling\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
-			JpLightSampling ls; ls.struct_bytes = (int32_t)sizeof(ls); ls.mode = scene->lightSampling;
+			JpLightSampling ls; ls.struct_bytes = (int32_t)sizeof(ls); ls.mode = lightMode;
 			lastStatus = api.set_light_sampling(ctx, &ls);
 			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
-			ctxLights = scene->lightSampling; uploaded = nullptr;
+			ctxLights = lightMode; uploaded = nullptr;
 		}
 		FlatScene flat; std::string err;
 		if (!FlattenScene(*scene, flat, &err)) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", err.c_str()); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
@@ -144,8 +159,8 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			flat.view.n_bvh_prim_indices = (int)flat.bvh.prim_index.size(); flat.view.bvh_prim_index = flat.bvh.prim_index.data();
 			lastStatus = upload();
 		}
-		if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
-		uploaded = scene; uploadedLights = scene->lightSampling;
+		if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); uploaded = nullptr; return; }
+		uploaded = scene; uploadedLights = lightMode; uploadedEnv = envId; uploadedEnvUp = scene->environmentUp; uploadedEnvImp = scene->environmentImportance;
 	}
 	JpRenderParams rp; std::memset(&rp, 0, sizeof(rp));
 	rp.width = film->Width(); rp.height = film->Height();

@@ -163,6 +163,25 @@ public:
 // image readers of film_io.cc: RGB8, top row first; false for any other format or a file that cannot be read
 bool ReadImageRGB8(const char* filename, std::vector<uint8_t>& rgb, int& width, int& height);
 
+// ---- environment map (include/jetpbrt_amd.h "Environment maps"): a lat-long float image, top row first, the light of FScene::SetEnvironmentMap ----
+// Float readers of film_io.cc; false (with a message) for a file that cannot be read, is malformed or truncated, holds a value that is negative or not
+// finite, or is not 1 .. 4096 texels per side.  PFM: "PF" (colour) or "Pf" (grey, copied to the three channels), rows bottom first as the format has them,
+// either byte order (the scale line's sign; its magnitude is not applied).  HDR: Radiance RGBE, "-Y h +X w", flat pixels as FFilm::SaveAsImage writes
+// them or the run-length encoded scanlines other writers produce.
+bool ReadImagePFM(const char* filename, std::vector<float>& rgb, int& width, int& height, std::string* error = nullptr);
+bool ReadImageHDR(const char* filename, std::vector<float>& rgb, int& width, int& height, std::string* error = nullptr);
+class FEnvironmentMap
+{
+public:
+	FEnvironmentMap(const float* rgb, int w, int h);                // from memory: 3 * w * h floats, row-major, top row first
+	// by content: PFM, Radiance .hdr, or binary PPM / uncompressed BMP through ReadImageRGB8 at 1/255 per step; null (with a message) when the file is refused
+	static std::shared_ptr<FEnvironmentMap> FromFile(const char* filename, std::string* error = nullptr);
+	bool Valid() const { return width > 0 && height > 0 && data.size() == (size_t)width * height * 3; }
+	std::vector<float> data;
+	int width = 0, height = 0;
+	unsigned long long id;                                         // distinct per object: how an integrator tells which map its context holds
+};
+
 // ---- materials: parameter holders with a flatten hook -------------------------------------------------------
 class FMaterial
 {
@@ -421,6 +440,12 @@ public:
 	// power -- what a scene lit by CreateAreaLights(mesh) needs.  Read by FGpuPathIntegrator::Render at its next upload of this scene.
 	int lightSampling = JP_LIGHTS_ALL;
 	void SetLightSampling(int mode) { lightSampling = mode; }
+	// Image-based lighting (INTEGRATION.md "Environment maps"): the scene's one FEnvironmentLight takes its radiance from `map` (the light's own
+	// radiance tints it), looked up by nearest texel on a miss and importance-sampled by texel; up_axis JP_ENV_UP_Z / JP_ENV_UP_Y.  A mapped scene
+	// renders with JP_LIGHTS_POWER_ONE whatever lightSampling says; one with no FEnvironmentLight, or more than one, is refused by Render.
+	// nullptr: no map.  Read by FGpuPathIntegrator::Render at its next upload of this scene.
+	std::shared_ptr<FEnvironmentMap> environmentMap; int environmentUp = JP_ENV_UP_Z, environmentImportance = 0;
+	void SetEnvironmentMap(const std::shared_ptr<FEnvironmentMap>& map, int up_axis = JP_ENV_UP_Z) { environmentMap = map; environmentUp = up_axis; }
 };
 
 // binned-SAH BVH over primitive bounds -> the flat node arrays of JpScene (own topology)
@@ -482,6 +507,7 @@ protected:
 	mutable JpContext* ctx = nullptr;
 	mutable const FScene* uploaded = nullptr;
 	mutable int uploadedLights = JP_LIGHTS_ALL, ctxLights = JP_LIGHTS_ALL;   // FScene::lightSampling of the uploaded scene; the mode the context was last told
+	mutable unsigned long long uploadedEnv = 0, ctxEnv = 0; mutable int uploadedEnvUp = 0, ctxEnvUp = 0, uploadedEnvImp = 0, ctxEnvImp = 0;   // FEnvironmentMap::id (0: none), up axis and importance: of the uploaded scene; last sent to the context
 	mutable int lastStatus = 0;
 	mutable JpCounters counters;
 protected:

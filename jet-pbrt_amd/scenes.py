@@ -282,6 +282,28 @@ class HostBackend:
         from . import LIGHT_SAMPLING_MODES
         self._f("scene_set_light_sampling")(self.h, LIGHT_SAMPLING_MODES[mode])
 
+    def envmap(self, rgb, up_axis="z", importance=0):
+        """FScene::SetEnvironmentMap: an (H, W, 3) float32 array top row first, the path of a PFM / Radiance .hdr / binary PPM / BMP file, or None for no
+        map; up_axis "z" (map space = world space) or "y"; importance -1: sample by solid angle alone, arrays only (host backend only; takes effect
+        with the integrator's next upload).  The scene's one envlight() tints the map."""
+        from . import ENV_UP_AXES
+        if rgb is None:
+            st = self._f("scene_envmap")(self.h, None, 0, 0, 0, 0)
+        elif isinstance(rgb, (str, bytes, os.PathLike)):
+            st = self._f("scene_envmap_file")(self.h, os.fsencode(rgb), ENV_UP_AXES[up_axis])
+        else:
+            a = np.ascontiguousarray(rgb, np.float32)
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise RuntimeError("an environment map is an (H, W, 3) array")
+            st = self._f("scene_envmap")(self.h, a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0], ENV_UP_AXES[up_axis], importance)
+        if st != 0:
+            raise RuntimeError("envmap failed: %s" % self.L.jp_host_last_error(self.h).decode())
+
+    def flatten_envmap(self):
+        """the scene's map as a JpEnvMap pointer for Context.set_environment_map (None: no map); valid until the map changes"""
+        p = self.L.jp_host_flatten_envmap(self.h)
+        return p.contents if p else None
+
     def set_device_build(self, on=True):
         """FScene::deviceBuild: leave the hierarchy to jp_upload_scene's device LBVH pass (host backend only)."""
         self._f("scene_set_device_build")(self.h, 1 if on else 0)

@@ -19,7 +19,7 @@ def demangle(names):
 
 
 def short(n):
-    n = re.sub(r"\(jp::SceneView.*|\((?:unsigned|int|float|HIP|Queues|JpBsdf|Wide).*", "", n)   # drop the argument list, keep template arguments
+    n = re.sub(r"\(jp::SceneView.*|\((?:unsigned|int|float|HIP|Queues|JpBsdf|Wide|EnvView).*", "", n)   # drop the argument list, keep template arguments
     n = n.replace("(anonymous namespace)::", "").replace("void ", "")
     # feature sets (jp_device.h): the instance with everything in it keeps the name it always had, the lean ones say which they are
     n = n.replace(", jp::Feat<true, true, true> >", ">").replace("jp::Feat<false, true, true> >", "FeatFlat>").replace("jp::Feat<false, false, false> >", "FeatLean>")
