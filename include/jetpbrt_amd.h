@@ -479,6 +479,26 @@ typedef struct JpUploadInfo {
 } JpUploadInfo;
 int  jp_describe_upload(const JpOptions* options_or_null, int32_t light_mode, const JpScene* scene, JpUploadInfo* out);
 
+/* Reading the tables back (additive to ABI 7; INTEGRATION.md "Reading the tables back"): test hooks, read-only.  `which` is an index into
+ * JpUploadInfo.table (JP_TABLE_*).  out NULL: *bytes receives the table's size and nothing is copied; a table the upload does not have: 0 bytes, JP_OK;
+ * capacity_bytes smaller than the table: JP_ERR_INVALID_ARGUMENT, nothing copied.
+ * jp_copy_upload_table: pure host code, no GPU needed -- the options, validation, builders of jp_describe_upload, then the bytes whose count and FNV-1a
+ *   that function reports for table `which` (any of the eleven).  JP_ERR_UNSUPPORTED for a scene without a hierarchy, as there.
+ * jp_read_scene_table: the same table of the scene the context holds, copied from the device, host-built or device-built alike; the hierarchy tables only
+ *   (nodes, prims, meta, wide, q4, flat; anything else: JP_ERR_INVALID_ARGUMENT).  Blocking.
+ * jp_get_tree_info: the entry counts and heights that belong to those tables, as the upload's plan holds them (JpBuildInfo has no room for the wide heights). */
+enum { JP_TABLE_NODES = 0, JP_TABLE_PRIMS = 1, JP_TABLE_META = 2, JP_TABLE_WIDE = 7, JP_TABLE_Q4 = 8, JP_TABLE_FLAT = 10 };
+typedef struct JpTreeInfo {
+    int32_t struct_bytes;                    /* sizeof(JpTreeInfo) of the caller; a shorter struct is truncated                     */
+    int32_t n_prims, n_nodes, bvh_height;    /* primitive records; slots of the binary node table; emitted interior nodes on the longest root-to-leaf path */
+    int32_t n_wide, wide_height;             /* 8-wide tree: nodes, levels (0 0: none)                                              */
+    int32_t n_q4, q4_height;                 /* 4-wide tree: nodes, levels (0 0: none)                                              */
+    int32_t n_flat;                          /* entries of the flat leaf list                                                       */
+} JpTreeInfo;
+int  jp_copy_upload_table(const JpOptions* options_or_null, int32_t light_mode, const JpScene* scene, int32_t which, void* out, int64_t capacity_bytes, int64_t* bytes);
+int  jp_read_scene_table(JpContext* ctx, int32_t which, void* out, int64_t capacity_bytes, int64_t* bytes);
+int  jp_get_tree_info(JpContext* ctx, JpTreeInfo* out);
+
 #ifdef __cplusplus
 }
 #endif

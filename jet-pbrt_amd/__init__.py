@@ -208,6 +208,41 @@ def describe_upload(scene, options=None, light_mode=JP_LIGHTS_ALL):
     return info
 
 
+class JpTreeInfo(C.Structure):
+    """include/jetpbrt_amd.h: JpTreeInfo (jp_get_tree_info)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_prims", C.c_int32), ("n_nodes", C.c_int32), ("bvh_height", C.c_int32), ("n_wide", C.c_int32), ("wide_height", C.c_int32),
+                ("n_q4", C.c_int32), ("q4_height", C.c_int32), ("n_flat", C.c_int32)]
+
+
+def _table_index(which):
+    return UPLOAD_TABLES.index(which) if isinstance(which, str) else int(which)
+
+
+def _read_table(call):
+    """the size query, then the copy, of jp_copy_upload_table / jp_read_scene_table -> the table's bytes as a uint8 array (empty: no such table)"""
+    import numpy as np
+    n = C.c_int64(0)
+    st = call(None, 0, C.byref(n))
+    if st == JP_OK:
+        out = np.zeros(n.value, np.uint8)
+        if n.value:
+            st = call(out.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, hip_lib().jp_last_error().decode()))
+    return out
+
+
+def copy_upload_table(scene, which, options=None, light_mode=JP_LIGHTS_ALL):
+    """jp_copy_upload_table: the bytes jp_upload_scene would copy to the device for table `which` (a name of UPLOAD_TABLES or its index) of `scene`
+    (a JpScene or a pointer to one): what JpUploadInfo.table[which] counts and hashes (pure host code, no GPU) -> uint8 array"""
+    L = hip_lib()
+    if options is not None:
+        options.struct_bytes = C.sizeof(JpOptions)
+    o = None if options is None else C.byref(options)
+    sp = scene if isinstance(scene, C._Pointer) else C.byref(scene)
+    return _read_table(lambda out, cap, n: L.jp_copy_upload_table(o, LIGHT_SAMPLING_MODES[light_mode], sp, _table_index(which), out, cap, n))
+
+
 def build_light_table(weights):
     """jp_build_light_table: the alias table of the upload for `weights` (pure host code, no GPU) -> (q float32, alias int32, pmf float32)"""
     import numpy as np
@@ -384,6 +419,9 @@ def hip_lib():
         L.jp_env_sample.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5
         L.jp_build_environment_table.argtypes = [C.POINTER(JpEnvMap)] + [C.c_void_p] * 6 + [C.POINTER(C.c_double)] * 2
         L.jp_describe_upload.argtypes = [C.POINTER(JpOptions), C.c_int32, C.POINTER(JpScene), C.POINTER(JpUploadInfo)]
+        L.jp_copy_upload_table.argtypes = [C.POINTER(JpOptions), C.c_int32, C.POINTER(JpScene), C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.jp_read_scene_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.jp_get_tree_info.argtypes = [C.c_void_p, C.POINTER(JpTreeInfo)]
         _hip = L
     return _hip
 
@@ -589,6 +627,16 @@ class Context:
         b = JpBuildInfo()
         self._check(self.lib.jp_get_build_info(self.h, C.byref(b)))
         return b
+
+    def read_table(self, which):
+        """jp_read_scene_table: one hierarchy table of the uploaded scene ("nodes", "prims", "meta", "wide", "q4", "flat"), copied from the device -> uint8 array"""
+        return _read_table(lambda out, cap, n: self.lib.jp_read_scene_table(self.h, _table_index(which), out, cap, n))
+
+    def tree_info(self):
+        i = JpTreeInfo()
+        i.struct_bytes = C.sizeof(JpTreeInfo)
+        self._check(self.lib.jp_get_tree_info(self.h, C.byref(i)))
+        return i
 
     def trace(self, origin, direction, tmin, tmax):
         import numpy as np

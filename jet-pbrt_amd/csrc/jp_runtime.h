@@ -95,6 +95,7 @@ struct JpContext
 	bool cert_fell_back = false; int cert_eye_leaves = 0;          // certified walk: did the last renders leave it (a result of rendering, cleared at upload)
 	int sincosf_mode = 0, libm_mode = 0;
 	bool build_on_device = false; float build_ms = 0.f; int bvh_height = 0, bvh_nodes = 0;
+	int wide_height = 0, q4_height = 0; size_t tab_bytes[JP_UPLOAD_TABLES] = {};   // levels of the 8-wide / 4-wide trees; bytes in use of every table of the upload (jp_read_scene_table)
 	// queues
 	Queues q = {}; QueueBufs qb; unsigned int cap = 0; int planes_alloc = 0; unsigned int blk_alloc = 0; int blocks_per_cu = 16;
 	DevBuf pix_acc, spill, film;

@@ -97,23 +97,40 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	c->tab = std::move(T); c->plan = p; c->plan.have_scene = true;
 	c->build_on_device = k.device_build; c->build_ms = build_ms; c->bvh_height = t.height; c->bvh_nodes = k.ref_sem ? s->n_bvh_nodes : t.n_nodes;
 	c->cert_eye_leaves = t.eye_leaves; c->cert_fell_back = false;
+	// what jp_read_scene_table / jp_get_tree_info hand back: the bytes of every table in use (a device build's buffers are sized for the worst case) and the wide heights
+	for (int i = 0; i < TAB_COUNT; i++) c->tab_bytes[i] = tb[i].present ? tb[i].bytes : 0;
+	if (k.device_build)
+	{
+		c->tab_bytes[TAB_NODES] = (size_t)t.n_nodes * 4 * sizeof(float4); c->tab_bytes[TAB_PRIMS] = (size_t)s->n_primitives * 4 * sizeof(float4); c->tab_bytes[TAB_META] = (size_t)s->n_primitives * sizeof(int4);
+		c->tab_bytes[TAB_WIDE] = (size_t)t.n_wide * 20 * sizeof(uint32_t); c->tab_bytes[TAB_Q4] = (size_t)t.n_q4 * 16 * sizeof(uint32_t);
+	}
+	c->wide_height = t.wide_height; c->q4_height = t.q4_height;
 	return JP_OK;
 }
 
 // What jp_upload_scene would decide for this scene, and the bytes it would hand to the device -- check_scene, build_host_tables and plan_scene, no device
+namespace
+{
+// the host half of an upload for the two entry points that run it without a device: options, check, tables (the plan is the caller's)
+int host_upload_tables(const std::string& who, const JpOptions* o, int32_t light_mode, const JpScene* s, JpOptions& op, SceneCheck& k, HostTables& t)
+{
+	if (light_mode != JP_LIGHTS_ALL && light_mode != JP_LIGHTS_POWER_ONE) return fail(JP_ERR_INVALID_ARGUMENT, who + ": unknown light sampling mode");
+	std::memset(&op, 0, sizeof(op)); op.struct_bytes = (int32_t)sizeof(JpOptions);                   // NULL: the defaults, no environment
+	if (o) if (const int st = read_options(who.c_str(), o, op); st != JP_OK) return st;
+	const bool pick = light_mode == JP_LIGHTS_POWER_ONE;
+	if (const int st = check_scene(s, pick, k); st != JP_OK) return st;
+	if (k.device_build) return fail(JP_ERR_UNSUPPORTED, who + ": a scene without a hierarchy (n_bvh_nodes == 0) gets its trees from the device builders");
+	return build_host_tables(s, op, pick, k, t);
+}
+}
+
 extern "C" int jp_describe_upload(const JpOptions* o, int32_t light_mode, const JpScene* s, JpUploadInfo* out)
 {
 	if (!s || !out) return fail(JP_ERR_INVALID_ARGUMENT, "jp_describe_upload: null argument");
 	if (out->struct_bytes < (int32_t)sizeof(int32_t)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_describe_upload: set JpUploadInfo.struct_bytes to sizeof(JpUploadInfo)");
-	if (light_mode != JP_LIGHTS_ALL && light_mode != JP_LIGHTS_POWER_ONE) return fail(JP_ERR_INVALID_ARGUMENT, "jp_describe_upload: unknown light sampling mode");
-	JpOptions op; std::memset(&op, 0, sizeof(op)); op.struct_bytes = (int32_t)sizeof(JpOptions);      // NULL: the defaults, no environment
-	if (o) if (const int st = read_options("jp_describe_upload", o, op); st != JP_OK) return st;
+	JpOptions op; SceneCheck k; HostTables t;
+	if (const int st = host_upload_tables("jp_describe_upload", o, light_mode, s, op, k, t); st != JP_OK) return st;
 	const bool pick = light_mode == JP_LIGHTS_POWER_ONE;
-	SceneCheck k;
-	if (const int st = check_scene(s, pick, k); st != JP_OK) return st;
-	if (k.device_build) return fail(JP_ERR_UNSUPPORTED, "jp_describe_upload: a scene without a hierarchy (n_bvh_nodes == 0) gets its trees from the device builders");
-	HostTables t;
-	if (const int st = build_host_tables(s, op, pick, k, t); st != JP_OK) return st;
 	const ScenePlan p = plan_scene(s, op, pick, false, t.sizes());
 	JpUploadInfo i; std::memset(&i, 0, sizeof(i));
 	i.trav_mode = p.trav_mode; i.stack_depth = p.stack_depth; i.stack_depth_q4 = p.stack_depth_q4;
@@ -134,6 +151,52 @@ extern "C" int jp_describe_upload(const JpOptions* o, int32_t light_mode, const 
 	return JP_OK;
 }
 
+// The bytes behind one entry of JpUploadInfo.table: the same options, check and builders, then the table the upload would copy to the device
+extern "C" int jp_copy_upload_table(const JpOptions* o, int32_t light_mode, const JpScene* s, int32_t which, void* out, int64_t capacity_bytes, int64_t* bytes)
+{
+	if (!s || !bytes) return fail(JP_ERR_INVALID_ARGUMENT, "jp_copy_upload_table: null argument");
+	if (which < 0 || which >= TAB_COUNT) return fail(JP_ERR_INVALID_ARGUMENT, "jp_copy_upload_table: no such table");
+	JpOptions op; SceneCheck k; HostTables t;
+	if (const int st = host_upload_tables("jp_copy_upload_table", o, light_mode, s, op, k, t); st != JP_OK) return st;
+	TableBytes tb[TAB_COUNT]; t.tables(tb);
+	*bytes = tb[which].present ? (int64_t)tb[which].bytes : 0;
+	if (!out) return JP_OK;                                                    // the size only
+	if (capacity_bytes < *bytes) return fail(JP_ERR_INVALID_ARGUMENT, "jp_copy_upload_table: capacity_bytes smaller than the table");
+	if (*bytes > 0) std::memcpy(out, tb[which].data, (size_t)*bytes);
+	return JP_OK;
+}
+
+// ---- the uploaded scene's hierarchy tables back on the host (tests: tests/tree_ref.py validates them), and the counts and heights that go with them
+extern "C" int jp_read_scene_table(JpContext* c, int32_t which, void* out, int64_t capacity_bytes, int64_t* bytes)
+{
+	if (!c || !bytes) return fail(JP_ERR_INVALID_ARGUMENT, "jp_read_scene_table: null argument");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_read_scene_table: no scene uploaded");
+	const DevBuf* src = which == TAB_NODES ? &c->tab.nodes : which == TAB_PRIMS ? &c->tab.prims : which == TAB_META ? &c->tab.meta : which == TAB_WIDE ? &c->tab.wide
+	                  : which == TAB_Q4 ? &c->tab.q4 : which == TAB_FLAT ? &c->tab.flat : nullptr;
+	if (!src) return fail(JP_ERR_INVALID_ARGUMENT, "jp_read_scene_table: not a hierarchy table (nodes, prims, meta, wide, q4, flat)");
+	*bytes = (int64_t)c->tab_bytes[which];
+	if ((size_t)*bytes > src->bytes()) return fail(JP_ERR_DEVICE, "jp_read_scene_table: the table is larger than its device buffer");
+	if (!out) return JP_OK;                                                    // the size only
+	if (capacity_bytes < *bytes) return fail(JP_ERR_INVALID_ARGUMENT, "jp_read_scene_table: capacity_bytes smaller than the table");
+	HIP_TRY(hipSetDevice(c->device));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	if (*bytes > 0) HIP_TRY(hipMemcpy(out, src->get<void>(), (size_t)*bytes, hipMemcpyDeviceToHost));
+	return JP_OK;
+}
+extern "C" int jp_get_tree_info(JpContext* c, JpTreeInfo* out)
+{
+	if (!c || !out) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_tree_info: null argument");
+	if (out->struct_bytes < (int32_t)sizeof(int32_t)) return fail(JP_ERR_INVALID_ARGUMENT, "jp_get_tree_info: set JpTreeInfo.struct_bytes to sizeof(JpTreeInfo)");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_get_tree_info: no scene uploaded");
+	const SceneView& v = c->plan.sv;
+	JpTreeInfo i; std::memset(&i, 0, sizeof(i));
+	i.n_prims = v.n_prims; i.n_nodes = v.n_nodes; i.bvh_height = c->bvh_height;
+	i.n_wide = v.n_wide; i.wide_height = c->wide_height; i.n_q4 = v.n_q4; i.q4_height = c->q4_height; i.n_flat = v.n_flat;
+	const size_t n = std::min((size_t)out->struct_bytes, sizeof(i));
+	i.struct_bytes = (int32_t)n;
+	std::memcpy(out, &i, n);
+	return JP_OK;
+}
 
 
 // ---- textures: validation on the host, then the scene, then the texture tables (TexView) ------------------------------------------
