@@ -346,6 +346,52 @@ __device__ __forceinline__ typename FlatMask<k64>::type flat_boxes(const float4*
 	return mask;
 }
 
+// flat_boxes_lean: the box phase of the flat-shape instances (k_extend<2, FeatFlat>, k_shadow<2, FeatFlat>, k_trace_flat; <= 32 primitives).
+// Every leaf is tested against every ray with flat_boxes' own subtraction, reciprocal, multiplication, min / max, slack compare and
+// primitive order, and the mask returned is bit for bit the one flat_boxes returns; what is left out are vector instructions whose
+// result is known beforehand (ledger and measurements: DESIGN.md section 5, "The box phase of the flat-shape instances").
+//  1. kInfTmax (the closest-hit call site, tmax = +inf at compile time): no fminf(.., tmax).  fminf drops a NaN operand, so the clamp
+//     only matters where everything else under the outer fminf is NaN, which needs fmaxf(z0, z1) = NaN, i.e. z0 AND z1 NaN.  With a
+//     finite origin a product (plane - o) * i is NaN only as 0 * inf (i = +-inf from a zero / denormal direction component, the
+//     origin exactly on that plane), and the two planes of an axis differ (the leaf boxes are padded: bmin < bmax), so at most one
+//     of z0, z1 is NaN.  (The weaker argument: all three far distances NaN needs three zero / denormal components -- no direction.)
+//  2. mask |= bits under the execution mask (or_bits_if_le): v_cmp, then v_or of the SCALAR primitive bits executed by the passing
+//     lanes only; exec is saved, narrowed and restored by scalar instructions inside the one asm block.  The plain `if` is
+//     if-converted into v_cmp + v_mov (the bits, SGPR -> VGPR: constant-bus limit) + v_cndmask + v_or.
+__device__ __forceinline__ void or_bits_if_le(unsigned int& mask, float a, float b, unsigned int bits)
+{   // per lane: if (a <= b) mask |= bits  (bits wave-uniform).  VALU and scalar exec moves only; exec leaves the block as it entered it
+	u64 saved;
+	asm("v_cmp_le_f32 vcc, %2, %3\n\ts_and_saveexec_b64 %1, vcc\n\tv_or_b32 %0, %4, %0\n\ts_mov_b64 exec, %1"
+	    : "+v"(mask), "=&s"(saved) : "v"(a), "v"(b), "s"(bits) : "vcc", "scc");
+}
+
+template <bool kInfTmax>
+__device__ __forceinline__ unsigned int flat_boxes_lean(const float4* flat_g, int n_flat, V3 o, V3 d, float tmin, float tmax)
+{
+	ConstFPtr flat = (ConstFPtr)flat_g;
+	const float ix = __builtin_amdgcn_rcpf(d.x), iy = __builtin_amdgcn_rcpf(d.y), iz = __builtin_amdgcn_rcpf(d.z);
+	unsigned int mask = 0;
+	#define JP_FLAT_BOX(i) \
+	{ \
+		const float x0 = (flat[8 * (i) + 0] - o.x) * ix, x1 = (flat[8 * (i) + 4] - o.x) * ix; \
+		const float y0 = (flat[8 * (i) + 1] - o.y) * iy, y1 = (flat[8 * (i) + 5] - o.y) * iy; \
+		const float z0 = (flat[8 * (i) + 2] - o.z) * iz, z1 = (flat[8 * (i) + 6] - o.z) * iz; \
+		const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin)); \
+		const float fxy = fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fz = fmaxf(z0, z1); \
+		const float tf = kInfTmax ? fminf(fxy, fz) : fminf(fxy, fminf(fz, tmax)); \
+		or_bits_if_le(mask, tn, tf * 1.000002f, __float_as_uint(flat[8 * (i) + 3])); \
+	}
+	int i0 = 0;
+	for (; i0 + 4 <= n_flat; i0 += 4)
+	{
+		#pragma unroll
+		for (int u = 0; u < 4; u++) JP_FLAT_BOX(i0 + u)
+	}
+	for (; i0 < n_flat; i0++) JP_FLAT_BOX(i0)
+	#undef JP_FLAT_BOX
+	return mask;
+}
+
 template <bool kAnyHit, bool k64, int kS, typename F = FeatAll, typename PrimPtr>
 __device__ __forceinline__ int flat_prims(typename FlatMask<k64>::type mask, PrimPtr prims, V3 o, V3 d, float tmin, float& tmax)
 {
@@ -362,9 +408,12 @@ __device__ __forceinline__ int flat_prims(typename FlatMask<k64>::type mask, Pri
 	return hit;
 }
 
-template <bool kAnyHit, int kS, typename F = FeatAll, typename PrimPtr>
+// kInfTmax: the caller passes tmax = +inf as a compile-time fact (k_extend); only the flat-shape instances (F without curved shapes) look at it
+template <bool kAnyHit, int kS, typename F = FeatAll, bool kInfTmax = false, typename PrimPtr>
 __device__ __forceinline__ int traverse_flat(const float4* flat_g, int n_flat, int n_prims, PrimPtr prims, V3 o, V3 d, float tmin, float& tmax)
 {
+	if constexpr (!F::curved)
+		if (n_prims <= 32) return flat_prims<kAnyHit, false, kS, F>(flat_boxes_lean<kInfTmax>(flat_g, n_flat, o, d, tmin, tmax), prims, o, d, tmin, tmax);
 	if (n_prims > 32) return flat_prims<kAnyHit, true, kS, F>(flat_boxes<true>(flat_g, n_flat, o, d, tmin, tmax), prims, o, d, tmin, tmax);   // wave-uniform branch
 	return flat_prims<kAnyHit, false, kS, F>(flat_boxes<false>(flat_g, n_flat, o, d, tmin, tmax), prims, o, d, tmin, tmax);
 }

@@ -143,6 +143,9 @@ template <typename F> struct SceneAccess<2, F>
 	}
 	template <bool kAnyHit> __device__ __forceinline__ int trace(const SceneView& sc, V3 o, V3 d, float tmin, float& tmax) const
 	{ return traverse_flat<kAnyHit, 5, F>(sc.flat, sc.n_flat, sc.n_prims, prims, o, d, tmin, tmax); }
+	// closest hit of a ray without a far end (k_extend: tmax enters as +inf), which the flat-shape box phase knows at compile time
+	__device__ __forceinline__ int trace_unbounded(const SceneView& sc, V3 o, V3 d, float tmin, float& tmax) const
+	{ return traverse_flat<false, 5, F, true>(sc.flat, sc.n_flat, sc.n_prims, prims, o, d, tmin, tmax); }
 };
 
 template <> struct SceneAccess<3>
@@ -196,7 +199,9 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 		const float4 co = ro, cd = rd;
 		if (j + JP_BLOCK < n) { ro = q.ray_o[cur][i + JP_BLOCK]; rd = q.ray_d[cur][i + JP_BLOCK]; }
 		float tmax = JP_INF;                                         // FRay defaults geometry.h:399: min_t 0.001, max_t infinity
-		const int hit = acc.template trace<false>(sc, xyz(co), xyz(cd), 0.001f, tmax);
+		int hit;
+		if constexpr (kMode == 2) hit = acc.trace_unbounded(sc, xyz(co), xyz(cd), 0.001f, tmax);
+		else hit = acc.template trace<false>(sc, xyz(co), xyz(cd), 0.001f, tmax);
 		q.hit[i] = make_float2(tmax, __int_as_float(hit));
 		h += hit >= 0 ? 1u : 0u;
 	}
@@ -702,7 +707,9 @@ __global__ void __launch_bounds__(JP_BLOCK, 4) k_shadow(SceneView sc, Queues q, 
 			int hit;
 			if constexpr (kMode == 2)
 			{
-				const unsigned int m = flat_boxes<false>(sc.flat, sc.n_flat, xyz(so), dir, 0.001f, tmax);
+				unsigned int m;
+				if constexpr (F::curved) m = flat_boxes<false>(sc.flat, sc.n_flat, xyz(so), dir, 0.001f, tmax);
+				else m = flat_boxes_lean<false>(sc.flat, sc.n_flat, xyz(so), dir, 0.001f, tmax);
 				JP_TT(4);                                          // [4] box phase
 				hit = flat_prims<true, false, 5, F>(m, acc.prims, xyz(so), dir, 0.001f, tmax);
 				JP_TT(5);                                          // [5] primitive phase
@@ -1168,6 +1175,27 @@ __global__ void __launch_bounds__(JP_BLOCK) k_trace(SceneView sc, int depth, int
 			else if (type == JP_SHAPE_RECTANGLE) N = dot(xyz(g3), rd) <= 0 ? xyz(g3) : -xyz(g3);
 			else if (type == JP_SHAPE_DISK) N = xyz(sc.prims[4 * h + 1]);
 			else N = normalize(p - xyz(sc.prims[4 * h]));
+		}
+		nrm[3 * i] = N.x; nrm[3 * i + 1] = N.y; nrm[3 * i + 2] = N.z;
+	}
+}
+
+// k_trace for tiny scenes of flat shapes: the walk of k_extend<2, FeatFlat> with the caller's tmax (flat_boxes_lean<false>); triangle and rectangle normals only
+__global__ void __launch_bounds__(JP_BLOCK) k_trace_flat(SceneView sc, int depth, int n, const float* o, const float* d, const float* tmin, const float* tmax_in,
+                                                         int* hit, float* t, int* prim, float* nrm)
+{
+	SceneAccess<2, FeatFlat> acc(sc, depth);
+	for (int i = blockIdx.x * JP_BLOCK + threadIdx.x; i < n; i += gridDim.x * JP_BLOCK)
+	{
+		const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+		float tmax = tmax_in[i];
+		const int h = acc.template trace<false>(sc, ro, rd, tmin[i], tmax);
+		hit[i] = h >= 0; t[i] = tmax; prim[i] = h >= 0 ? sc.meta[h].x : -1;
+		V3 N = mk(0, 0, 0);
+		if (h >= 0)
+		{
+			const float4 g3 = sc.prims[4 * h + 3];
+			N = (__float_as_int(g3.w) == JP_SHAPE_TRIANGLE || dot(xyz(g3), rd) <= 0) ? xyz(g3) : -xyz(g3);
 		}
 		nrm[3 * i] = N.x; nrm[3 * i + 1] = N.y; nrm[3 * i + 2] = N.z;
 	}

@@ -175,13 +175,14 @@ typedef void (*TraceKernel)(SceneView, int, int, const float*, const float*, con
 typedef void (*SurfaceKernel)(SceneView, TexView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*);
 struct TraceLaunch { TraceKernel trace; SurfaceKernel surface; size_t lds; int depth; };     // (surface: null for the 8-wide walk, which only trace_walk = 2 selects)
 template <int M> TraceLaunch trace_row(size_t lds, int depth) { TraceLaunch t = { k_trace<M>, k_surface<M>, lds, depth }; return t; }
-TraceLaunch trace_kernel(const ScenePlan& p, int tw)
+TraceLaunch trace_kernel(const ScenePlan& p, int tw, bool generic = true)   // generic false (jp_trace without JpOptions::reserved[0] == 1): a scene of flat shapes gets the lean closest-hit walk
 {
 	const size_t q4lds = (size_t)p.stack_depth_q4 * JP_BLOCK * sizeof(int);
 	if (p.trav_mode == 3 && tw == 2) { TraceLaunch t = { k_trace<3>, nullptr, p.lds_bytes_shadow, p.stack_depth }; return t; }
 	if (p.trav_mode == 5 && p.cert && q4lds <= 64 * 1024 && tw != 3) return trace_row<6>(q4lds, p.stack_depth_q4);
 	if (p.trav_mode == 5) return trace_row<5>(p.lds_bytes, p.stack_depth);
 	if (p.use_q4 && q4lds <= 64 * 1024 && tw != 1) return trace_row<4>(q4lds, p.stack_depth_q4);
+	if (lean_traversal(p, generic)) { TraceLaunch t = { k_trace_flat, k_surface<2>, p.lds_bytes, p.stack_depth }; return t; }
 	return p.trav_mode == 2 ? trace_row<2>(p.lds_bytes, p.stack_depth) : (p.trav_mode == 1 ? trace_row<1>(p.lds_bytes, p.stack_depth) : trace_row<0>(p.lds_bytes, p.stack_depth));
 }
 
@@ -700,7 +701,7 @@ int jp_trace(JpContext* c, int32_t n, const float* origin, const float* dir, con
 	HIP_TRY(hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
 	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-	const TraceLaunch tk = trace_kernel(c->plan, c->opt.trace_walk);
+	const TraceLaunch tk = trace_kernel(c->plan, c->opt.trace_walk, c->opt.reserved[0] == 1);
 	hipLaunchKernelGGL(tk.trace, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
 	HIP_TRY(hipMemcpyAsync(hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(normal, d_n, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
