@@ -454,6 +454,29 @@ int  jp_env_sample(JpContext* ctx, int32_t n, const float* u, int32_t* texel_ind
  * texel: 4 floats per texel (tinted r g b, pdf); row_cos: 2 floats per row; total: W_env; mean_sum: as JpEnvInfo. */
 int  jp_build_environment_table(const JpEnvMap* map, const float* tint, double* weight, float* q, int32_t* alias, float* texel, float* row_cos, double* total, double* mean_sum);
 
+/* Estimator (additive to ABI 7; INTEGRATION.md "Estimator" has the definition).  JP_ESTIMATOR_NEE: the reference's -- emission counts on bounce 0 and after
+ * a specular bounce, next-event estimation does the rest.  JP_ESTIMATOR_MIS: at a non-delta shading event both ways of reaching an emitter count -- the
+ * direction drawn on the picked light and the direction the BSDF sample takes -- each weighted with the power heuristic (exponent 2) of the two pdfs, so a
+ * glossy surface under a large emitter, or a matte one just below it, no longer hangs on the strategy that samples it badly.  The draws, their order and
+ * every ray are those of JP_LIGHTS_POWER_ONE: the same paths with other weights, the same JpCounters ray counts, and the same film wherever every weight
+ * is 1 (delta lights, specular chains).  Render-time state: takes effect with the next jp_render*, so one upload serves both.  Needs a scene uploaded with
+ * JP_LIGHTS_POWER_ONE (else JP_ERR_UNSUPPORTED from jp_render*, the context stays usable), with or without a map, textured or not.  Path integrator only
+ * (Whitted: JP_ERR_UNSUPPORTED; the debug integrator and jp_render_guides ignore it); JpOptions.fused falls back to the per-bounce launches. */
+enum { JP_ESTIMATOR_NEE = 0, JP_ESTIMATOR_MIS = 1 };
+typedef struct JpEstimator { int32_t struct_bytes; int32_t mode; } JpEstimator;
+/* NULL: back to JP_ESTIMATOR_NEE; an unknown mode: JP_ERR_INVALID_ARGUMENT */
+int  jp_set_estimator(JpContext* ctx, const JpEstimator* estimator);
+typedef struct JpEstimatorInfo {
+    int32_t struct_bytes, mode;              /* the mode in force                                                              */
+    int32_t mis_last_render;                 /* the last jp_render* ran the MIS kernels (k_shade_mis*)                          */
+    int64_t side_bytes_device;               /* device bytes of the per-path side records (0 until the first MIS render)        */
+} JpEstimatorInfo;
+int  jp_get_estimator_info(JpContext* ctx, JpEstimatorInfo* out);
+/* test hook like jp_trace: n rays (unit directions) through the walk jp_trace uses -> the light reached (the emitter primitive's light where it emits toward
+ * the origin; on a miss the map light, else the first non-black constant environment light; -1: none) and the light strategy's solid-angle pdf at the origin
+ * for it, pmf * pdf_Li -- 0 where that light cannot be sampled from there (delta lights, the interior of a sphere light, a pdf that is not finite or not
+ * positive).  JP_ERR_UNSUPPORTED for a scene uploaded with JP_LIGHTS_ALL. */
+int  jp_light_pdf(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, int32_t* light, float* pdf);
 
 /* What jp_upload_scene would do with `scene` (additive to ABI 7; INTEGRATION.md "Describing an upload"): the scalars of the plan every later launch
  * reads, and for each table the host builds the byte count and the 64-bit FNV-1a of exactly the bytes the upload copies to the device.  Pure host code, no GPU

@@ -127,6 +127,18 @@ class JpLightInfo(C.Structure):
                 ("total_weight", C.c_double), ("picked_last_render", C.c_int32)]
 
 
+JP_ESTIMATOR_NEE, JP_ESTIMATOR_MIS = 0, 1
+ESTIMATOR_MODES = {None: JP_ESTIMATOR_NEE, "nee": JP_ESTIMATOR_NEE, "mis": JP_ESTIMATOR_MIS, JP_ESTIMATOR_NEE: JP_ESTIMATOR_NEE, JP_ESTIMATOR_MIS: JP_ESTIMATOR_MIS}
+
+
+class JpEstimator(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("mode", C.c_int32)]
+
+
+class JpEstimatorInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("mode", C.c_int32), ("mis_last_render", C.c_int32), ("side_bytes_device", C.c_int64)]
+
+
 JP_ENV_UP_Z, JP_ENV_UP_Y = 0, 1
 ENV_UP_AXES = {"z": JP_ENV_UP_Z, "y": JP_ENV_UP_Y, JP_ENV_UP_Z: JP_ENV_UP_Z, JP_ENV_UP_Y: JP_ENV_UP_Y}
 
@@ -366,6 +378,7 @@ def host_lib():
         L.jp_host_render_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.jp_host_render_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.jp_host_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
+        L.jp_host_scene_set_estimator.argtypes = [C.c_void_p, C.c_int]
         L.jp_host_scene_envmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.jp_host_scene_envmap_file.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.jp_host_flatten_envmap.restype = C.POINTER(JpEnvMap)
@@ -413,6 +426,9 @@ def hip_lib():
         L.jp_light_pick.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4
         L.jp_build_light_table.argtypes = [C.c_int32] + [C.c_void_p] * 4
         L.jp_device_bytes_in_use.restype = C.c_longlong
+        L.jp_set_estimator.argtypes = [C.c_void_p, C.POINTER(JpEstimator)]
+        L.jp_get_estimator_info.argtypes = [C.c_void_p, C.POINTER(JpEstimatorInfo)]
+        L.jp_light_pdf.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
         L.jp_set_environment_map.argtypes = [C.c_void_p, C.POINTER(JpEnvMap)]
         L.jp_get_env_info.argtypes = [C.c_void_p, C.POINTER(JpEnvInfo)]
         L.jp_env_lookup.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 3
@@ -575,6 +591,33 @@ class Context:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         self._check(self.lib.jp_light_pick(self.h, n, p(a), p(b), p(idx), p(pmf)))
         return idx, pmf
+
+    def set_estimator(self, mode):
+        """jp_set_estimator for the next render: None / "nee" / JP_ESTIMATOR_NEE, or "mis" / JP_ESTIMATOR_MIS (needs a scene uploaded with "power" light sampling)"""
+        if mode not in ESTIMATOR_MODES:
+            raise JetPbrtError("unknown estimator %r" % (mode,))
+        if mode is None:
+            self._check(self.lib.jp_set_estimator(self.h, None))
+            return
+        e = JpEstimator(C.sizeof(JpEstimator), ESTIMATOR_MODES[mode])
+        self._check(self.lib.jp_set_estimator(self.h, C.byref(e)))
+
+    def estimator_info(self):
+        i = JpEstimatorInfo()
+        i.struct_bytes = C.sizeof(JpEstimatorInfo)
+        self._check(self.lib.jp_get_estimator_info(self.h, C.byref(i)))
+        return i
+
+    def light_pdf(self, origin, direction, tmin, tmax):
+        """jp_light_pdf: the light a ray reaches and the light strategy's solid-angle pdf at its origin -> (light int32 (n,), pdf float32 (n,))"""
+        import numpy as np
+        o = np.ascontiguousarray(origin, np.float32).reshape(-1, 3); d = np.ascontiguousarray(direction, np.float32).reshape(-1, 3)
+        n = o.shape[0]
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(tmin, np.float32), (n,))); t1 = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        light = np.zeros(n, np.int32); pdf = np.zeros(n, np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_light_pdf(self.h, n, p(o), p(d), p(t0), p(t1), p(light), p(pdf)))
+        return light, pdf
 
     def set_environment_map(self, rgb, up_axis=JP_ENV_UP_Z, importance=0):
         """jp_set_environment_map for the next upload: an (H, W, 3) float32 array top row first, a JpEnvMap, or None for no map.

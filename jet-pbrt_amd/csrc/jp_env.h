@@ -67,13 +67,14 @@ __device__ __forceinline__ int env_sample(const EnvView& ev, float a0, float a1,
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_env(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, PickView pv, EnvView ev)
 {
-	const TexView tv = {};
-	shade_body<kTab, kPrims, kStage, kSort, false, true, true>(sc, q, rc, cur, cnt, tv, pv, ev);
+	const TexView tv = {}; const MisView mv = {};
+	shade_body<kTab, kPrims, kStage, kSort, false, true, true, false>(sc, q, rc, cur, cnt, tv, pv, ev, mv);
 }
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_env_tex(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, TexView tv, PickView pv, EnvView ev)
 {
-	shade_body<kTab, kPrims, kStage, kSort, true, true, true>(sc, q, rc, cur, cnt, tv, pv, ev);
+	const MisView mv = {};
+	shade_body<kTab, kPrims, kStage, kSort, true, true, true, false>(sc, q, rc, cur, cnt, tv, pv, ev, mv);
 }
 // jp_env_lookup (mode 0: in = 3 floats a direction) / jp_env_sample (mode 1: in = 5 floats a sample): the functions the render calls
 __global__ void __launch_bounds__(JP_BLOCK) k_env_probe(EnvView ev, int mode, int n, const float* __restrict__ in, int* __restrict__ index, float* __restrict__ wi, float* __restrict__ Li, float* __restrict__ pdf)

@@ -22,6 +22,7 @@
 #include "jp_common.h"
 #include "jp_tex.h"
 #include "jp_env.h"              // part 1: EnvView, env_lookup, env_sample (the kernels and entry points: part 2, at the end)
+#include "jp_mis.h"              // part 1: MisView, mis_weight, pdf_local, light_pdf (the kernels and entry points: part 2, at the end)
 #include "jp_xbsdf.h"
 
 #include <cstdio>
@@ -232,10 +233,13 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 // draws, its contribution divided by its pmf.  The light records stay in global memory (the LDS tables start at the materials: an emissive mesh of
 // 70k triangles has 2.2 MB of them), the one picked light's two float4 come from HBM / L2, and the miss branch walks pv.env, the short list of
 // non-black environment lights, instead of every light.
+// kMis (k_shade_mis*, JP_ESTIMATOR_MIS; jp_mis.h): the emission a BSDF-sampled ray finds is counted too, and it and the next-event sample are weighted with
+// the power heuristic; mv carries the BSDF sample's pdf (and the distance travelled through null-material primitives) from one bounce to the next.
 // F: the scene's feature set (jp_device.h, DESIGN.md "Feature sets"); the lean instances exist for k_shade<true, true, true, kSort> only.
-template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, bool kEnv, typename F = FeatAll>
-__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv, const EnvView& ev)
+template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, bool kEnv, bool kMis, typename F = FeatAll>
+__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv, const EnvView& ev, const MisView& mv)
 {
+	static_assert(kPick || !kMis, "k_shade: the light strategy's pdf needs the light table");
 	static_assert(kTab || !kPrims, "k_shade: primitive records in LDS only together with the tables");
 	static_assert(kPick || !kEnv, "k_shade: the map light is an entry of the light table");
 	constexpr int kWaves = JP_BLOCK / 64, kMaxSeg = (JP_SHADE_TILE / JP_BLOCK) * kWaves;  // (pass, wave) segments of a tile, in queue order
@@ -369,14 +373,14 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 	// The tile is shaded in 64-path chunks that the waves take from an LDS counter: a wave with expensive paths (a chunk of the
 	// microfacet class) takes fewer chunks, and no wave waits for another before the end of the tile.  The records of the chunk
 	// a wave takes next are fetched while it shades the current one (software prefetch).
-	float4 ro_n = make_float4(0, 0, 0, 0), rd_n = ro_n, rb_n = ro_n; float2 h_n = make_float2(0, 0); unsigned int s_n = 0;
+	float4 ro_n = make_float4(0, 0, 0, 0), rd_n = ro_n, rb_n = ro_n; float2 h_n = make_float2(0, 0); unsigned int s_n = 0; float2 m_n = make_float2(0, 0);
 	// Chunks are taken from the END of the sorted tile: the expensive classes (plastic, metal) sort last, and taking them first
 	// leaves the cheap chunks to even out the waves before the barrier at the end of the tile.
 	JP_TS(1);                                                     // [1] partition
 	const unsigned int nch = (count + 63u) >> 6;
 	unsigned int tk = wave_take(&s_ctr[0], 1u);                  // wave-uniform
 	unsigned int c0 = (nch - 1u - tk) << 6;                      // first tile position of the wave's chunk (meaningful while tk < nch)
-	if (tk < nch && c0 + lane < count) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; }
+	if (tk < nch && c0 + lane < count) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; }
 	while (tk < nch)
 	{
 		const bool valid = c0 + lane < count;
@@ -386,23 +390,24 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 		JP_TS(3);                                                 // [3] wait for the prefetched records (and for the stores before them)
 #endif
 #ifdef JP_SHADE_NO_PREFETCH
-		if (valid) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; }
-		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n;
+		if (valid) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; }
+		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n; const float2 ms = m_n;
 		tk = wave_take(&s_ctr[0], 1u); c0 = (nch - 1u - tk) << 6;
 #else
-		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n;
+		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n; const float2 ms = m_n;
 		tk = wave_take(&s_ctr[0], 1u); c0 = (nch - 1u - tk) << 6;
 		if (tk < nch && c0 + lane < count)
 		{
 			const unsigned int pos = c0 + lane;
 			const unsigned int i1 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos);
-			ro_n = q.ray_o[cur][i1]; rd_n = q.ray_d[cur][i1]; rb_n = q.beta[cur][i1]; h_n = q.hit[i1]; if (kTex) s_n = tv.side[i1];
+			ro_n = q.ray_o[cur][i1]; rd_n = q.ray_d[cur][i1]; rb_n = q.beta[cur][i1]; h_n = q.hit[i1]; if (kTex) s_n = tv.side[i1]; if (kMis) m_n = mv.side[cur][i1];
 		}
 #endif
 		bool shaded = false, wantNee = false, alive = false;
 		V3 o = mk(0, 0, 0), d = mk(0, 0, 1), beta = mk(0, 0, 0), p = mk(0, 0, 0), N = mk(0, 0, 1);
 		int slot = 0, bounce = 0; bool spec = false; unsigned int dim = 0; uint32_t key = 0;
 		Closure c; c.kind = CL_LAMBERT; Frame fr; fr.s = fr.t = fr.n = mk(0, 0, 1);
+		float2 nm = make_float2(0.f, 0.f);                             // kMis: the survivor's side record
 		if (valid)
 		{
 			o = xyz(ro); d = xyz(rd); beta = xyz(rb);
@@ -413,6 +418,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 			const bool found = pi >= 0;
 			int mat = -1, hitprim = 0; bool nflip = false, tabframe = kPrims;
 			V3 Le = splat(0);
+			float wLe = 1.f;                                                          // kMis: the BSDF strategy's weight of Le
 			if (found)
 			{
 				const float4 g3 = prims[4 * pi + 3];
@@ -429,6 +435,21 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 				{
 					const V3 wo = -d;
 					if (dot(N, wo) > 0.f) Le = xyz(lights[2 * meta.z]);
+				}
+				else if (kMis && meta.z >= 0)
+				{   // the BSDF sample of the last shading event reached an emitter: its emission, weighted against the light strategy's pdf for this
+					// direction, taken from that shading point (o - ms.y d: null-material primitives moved the origin on)
+					const V3 wo = -d;
+					if (dot(N, wo) > 0.f)
+					{
+						Le = xyz(lights[2 * meta.z]);
+						if (!isblack(Le))
+						{
+							bool unweighed;
+							const float a = light_pdf(sc, prims, lights, pv, ev, kEnv, meta.z, o - ms.y * d, d, ms.y + h.x, N, unweighed);
+							wLe = unweighed ? 0.f : (a > 0.f ? mis_weight(ms.x, a) : 1.f);
+						}
+					}
 				}
 			}
 			else if (F::other_lights && (bounce == 0 || spec))                        // integrator.cc:334-336, light.h:300-303
@@ -461,15 +482,31 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					}
 				}
 			}
+			else if (kMis)
+			{   // the BSDF sample left the scene: every environment light it sees, each weighted as a strategy of its own, in light order
+				const int ne = kEnv ? 1 : pv.n_env;
+				for (int e = 0; e < ne; e++)
+				{
+					int l2; V3 Lr;
+					if (kEnv) { l2 = ev.light; Lr = xyz(ev.texel[env_lookup(ev, d)]); }
+					else { const float4 r4 = pv.env[e]; l2 = __float_as_int(r4.w); Lr = xyz(r4); }
+					bool unweighed;
+					const float a = light_pdf(sc, prims, lights, pv, ev, kEnv, l2, o, d, 0.f, N, unweighed);
+					const float w = a > 0.f ? mis_weight(ms.x, a) : 1.f;
+					float4 L = q.lacc[slot];
+					V3 s2 = mk(L.x, L.y, L.z) + cmul(beta, Lr) * w;
+					q.lacc[slot] = make_float4(s2.x, s2.y, s2.z, 0.f);
+				}
+			}
 			if (!isblack(Le))
 			{
 				float4 L = q.lacc[slot];
-				V3 a = mk(L.x, L.y, L.z) + cmul(beta, Le);                            // integrator.cc:331
+				V3 a = mk(L.x, L.y, L.z) + (kMis ? cmul(beta, Le) * wLe : cmul(beta, Le));   // integrator.cc:331
 				q.lacc[slot] = make_float4(a.x, a.y, a.z, 0.f);
 			}
 			if (found && bounce < rc.max_depth)                                       // integrator.cc:340-343
 			{
-				if (mat < 0) alive = true;                                            // integrator.cc:349-353: pass through, same bounce
+				if (mat < 0) { alive = true; if (kMis) nm = make_float2(ms.x, ms.y + h.x); }   // integrator.cc:349-353: pass through, same bounce (kMis: the carried values go along)
 				else
 				{
 					float up = 0.f;
@@ -551,6 +588,8 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					const float dist = (!F::other_lights || ls.dist >= 0.f) ? ls.dist : len(p - ls.pos);
 					V3 contrib = cmul(cmul(beta, f), ls.Li) * absdot(ls.wi, N) / ls.pdf;   // integrator.cc:369
 					if (kPick) contrib = contrib / pmf;                                 // the one-light estimator: a pmf of 1 changes no bit
+					if (kMis && (mapped || light_weighed(prims, lights, li, p)))           // the light strategy's weight against the pdf the BSDF sample would draw this direction with
+						contrib = contrib * mis_weight(pmf * ls.pdf, pdf_local(c, wo, to_local(fr, ls.wi)));
 					if (k < rc.n_planes)
 					{
 						if (kStage)
@@ -599,6 +638,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					alive = true;
 				}
 				nd = bs.wi; nbounce = bounce + 1;
+				if (kMis) nm = make_float2(bs.pdf, 0.f);
 			}
 		}
 		// ---- compact survivors into the next ray queue (and, when staged, the shadow entries): the wave takes room for its survivors
@@ -633,6 +673,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 			q.ray_o[nxt][j] = make_float4(p.x, p.y, p.z, __int_as_float(slot));       // SpawnRay shape.h:61-64
 			q.ray_d[nxt][j] = make_float4(nd.x, nd.y, nd.z, __int_as_float(MK_FLAGS(nbounce, nspec, dim)));
 			q.beta[nxt][j] = make_float4(nbeta.x, nbeta.y, nbeta.z, __int_as_float((int)key));
+			if (kMis) mv.side[nxt][j] = nm;
 		}
 		JP_TS(7);                                                 // [7] room in the output regions, store issue
 #ifdef JP_SHADE_TIMING
@@ -658,8 +699,8 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 template <bool kTab, bool kPrims, bool kStage, bool kSort, typename F = FeatAll>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt)
 {
-	const TexView tv = {}; const PickView pv = {}; const EnvView ev = {};
-	shade_body<kTab, kPrims, kStage, kSort, false, false, false, F>(sc, q, rc, cur, cnt, tv, pv, ev);
+	const TexView tv = {}; const PickView pv = {}; const EnvView ev = {}; const MisView mv = {};
+	shade_body<kTab, kPrims, kStage, kSort, false, false, false, false, F>(sc, q, rc, cur, cnt, tv, pv, ev, mv);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1234,8 +1275,8 @@ __global__ void __launch_bounds__(JP_BLOCK, 8) k_texel(SceneView sc, Queues q, i
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_tex(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, TexView tv)
 {
-	const PickView pv = {}; const EnvView ev = {};
-	shade_body<kTab, kPrims, kStage, kSort, true, false, false>(sc, q, rc, cur, cnt, tv, pv, ev);
+	const PickView pv = {}; const EnvView ev = {}; const MisView mv = {};
+	shade_body<kTab, kPrims, kStage, kSort, true, false, false, false>(sc, q, rc, cur, cnt, tv, pv, ev, mv);
 }
 
 // k_surface (jp_surface): the closest hit of k_trace's walk, then the uv k_texel computes and the colour k_shade_tex puts in the textured
@@ -1283,3 +1324,5 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #define JP_ENV_RUNTIME
 #include "jp_env.h"              // environment maps, part 2: k_shade_env / k_shade_env_tex, k_env_probe and their entry points (jp_render.h declares the selector)
 #include "jp_pick.h"             // light selection: the alias table, k_shade_pick / k_shade_pick_tex, k_light_pick and their entry points (jp_render.h declares its two hooks)
+#define JP_MIS_RUNTIME
+#include "jp_mis.h"              // estimator, part 2: k_shade_mis*, k_light_pdf and their entry points (jp_render.h declares the selector)

@@ -9,14 +9,14 @@
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_pick(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, PickView pv)
 {
-	const TexView tv = {}; const EnvView ev = {};
-	shade_body<kTab, kPrims, kStage, kSort, false, true, false>(sc, q, rc, cur, cnt, tv, pv, ev);
+	const TexView tv = {}; const EnvView ev = {}; const MisView mv = {};
+	shade_body<kTab, kPrims, kStage, kSort, false, true, false, false>(sc, q, rc, cur, cnt, tv, pv, ev, mv);
 }
 template <bool kTab, bool kPrims, bool kStage, bool kSort>
 __global__ void __launch_bounds__(JP_BLOCK) k_shade_pick_tex(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, TexView tv, PickView pv)
 {
-	const EnvView ev = {};
-	shade_body<kTab, kPrims, kStage, kSort, true, true, false>(sc, q, rc, cur, cnt, tv, pv, ev);
+	const EnvView ev = {}; const MisView mv = {};
+	shade_body<kTab, kPrims, kStage, kSort, true, true, false, false>(sc, q, rc, cur, cnt, tv, pv, ev, mv);
 }
 // jp_light_pick: the render's selection for n pairs of draws
 __global__ void __launch_bounds__(JP_BLOCK) k_light_pick(PickView pv, int n, const float* __restrict__ u0, const float* __restrict__ u1, int* __restrict__ index, float* __restrict__ pmf)
@@ -62,7 +62,7 @@ static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, con
 		else if (plan.env && ty == JP_LIGHT_ENVIRONMENT) w[i] = (plan.env_mean_sum * kPi) * ((double)s->world_radius * (double)s->world_radius);   // the map light (jp_env.h): the map's mean in place of the sum
 		else w[i] = (sum * kPi) * ((double)s->world_radius * (double)s->world_radius);          // light.cc:17-33
 		if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return fail(JP_ERR_INVALID_ARGUMENT, "jp_upload_scene: a light's power is negative or not finite (JP_LIGHTS_POWER_ONE)");
-		if (ty == JP_LIGHT_ENVIRONMENT && !(rad[0] == 0.f && rad[1] == 0.f && rad[2] == 0.f)) env.push_back(make_float4(rad[0], rad[1], rad[2], 0.f));
+		if (ty == JP_LIGHT_ENVIRONMENT && !(rad[0] == 0.f && rad[1] == 0.f && rad[2] == 0.f)) { float lf; const int32_t li = i; std::memcpy(&lf, &li, 4); env.push_back(make_float4(rad[0], rad[1], rad[2], lf)); }   // (.w: the light's index as int bits, for jp_mis.h)
 	}
 	std::vector<float> q((size_t)std::max(1, n), 0.f), pmf((size_t)std::max(1, n), 0.f); std::vector<int32_t> alias((size_t)std::max(1, n), 0);
 	double W = 0.0; int nsel = 0;

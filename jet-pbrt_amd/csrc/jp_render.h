@@ -164,6 +164,17 @@ typedef void (*ShadeEnvKernel)(SceneView, Queues, RenderConst, int, DevCounters*
 typedef void (*ShadeEnvTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView);
 struct ShadeEnvKernels { ShadeEnvKernel plain; ShadeEnvTexKernel tex; };
 ShadeEnvKernels shade_env_kernels(const ScenePlan& p);
+// JP_ESTIMATOR_MIS: the pick and map kernels with both strategies weighted, same rows once more (selector and side records in jp_mis.h)
+typedef void (*ShadeMisKernel)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, MisView);
+typedef void (*ShadeMisTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, MisView);
+typedef void (*ShadeMisEnvKernel)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, EnvView, MisView);
+typedef void (*ShadeMisEnvTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView, MisView);
+struct ShadeMisKernels { ShadeMisKernel pick; ShadeMisTexKernel pick_tex; ShadeMisEnvKernel env; ShadeMisEnvTexKernel env_tex; };
+ShadeMisKernels shade_mis_kernels(const ScenePlan& p);
+}
+static int ensure_mis_side(JpContext* c, unsigned int cap, MisView& mv);
+namespace
+{
 
 // the other two integrators' megakernel: one ray per lane, launched like the plain k_extend (plan.lds_bytes, plan.stack_depth)
 typedef void (*OtherKernel)(SceneView, Queues, RenderConst, int, int, DevCounters*);
@@ -241,6 +252,10 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		// the side words of k_texel: one per queue position, allocated for textured scenes only
 		if (tex) if (const int e = reserve_idle(c, c->side, (size_t)cap * sizeof(unsigned int)); e != JP_OK) return e;
 		TexView tv = p.tv; tv.side = c->side.get<unsigned int>();
+		// JP_ESTIMATOR_MIS (render_impl refused a scene without the light table): the side records of this queue set
+		const bool mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH;
+		MisView mv = {};
+		if (mis) if (const int e = ensure_mis_side(c, cap, mv); e != JP_OK) return e;
 		if (const int e = reserve_idle(c, c->spill, spill_need(p, p.persist ? deepest_walk(p) : 0, G) * sizeof(int)); e != JP_OK) return e;
 		if (const int e = reserve_idle(c, c->pix_acc, (size_t)npix * 16); e != JP_OK) return e;
 		int* const d_spill = c->spill.get<int>(); float4* const d_pix_acc = c->pix_acc.get<float4>();
@@ -262,6 +277,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		const ExtendLaunch ek = extend_kernel(p, generic); const ShadowLaunch sk = shadow_kernel(p, R, generic); const ShadeKernels hk = shade_kernels(p, generic); const OtherKernel ok = other_kernel(p);
 		const ShadePickKernels pk = p.pick ? shade_pick_kernels(p) : ShadePickKernels{ nullptr, nullptr };
 		const ShadeEnvKernels vk = p.env ? shade_env_kernels(p) : ShadeEnvKernels{ nullptr, nullptr };
+		const ShadeMisKernels mk2 = mis ? shade_mis_kernels(p) : ShadeMisKernels{ nullptr, nullptr, nullptr, nullptr };
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
@@ -293,10 +309,14 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 					if (tex)
 					{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
 						hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
-						if (p.env) hipLaunchKernelGGL(vk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev);
+						if (mis && p.env) hipLaunchKernelGGL(mk2.env_tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev, mv);
+						else if (mis) hipLaunchKernelGGL(mk2.pick_tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, mv);
+						else if (p.env) hipLaunchKernelGGL(vk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev);
 						else if (p.pick) hipLaunchKernelGGL(pk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv);
 						else hipLaunchKernelGGL(hk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv);
 					}
+					else if (mis && p.env) hipLaunchKernelGGL(mk2.env, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev, mv);
+					else if (mis) hipLaunchKernelGGL(mk2.pick, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, mv);
 					else if (p.env) hipLaunchKernelGGL(vk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev);
 					else if (p.pick) hipLaunchKernelGGL(pk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv);
 					else hipLaunchKernelGGL(hk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt);
@@ -352,6 +372,7 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 	l->plan = c->plan;                                               // (the lane's side array is its own, allocated with its queues)
 	if (!l->plan.textured && l->side) { hipStreamSynchronize(l->stream); l->side.reset(); }   // untextured scene: not kept
 	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
+	l->estimator = c->estimator;                                     // ... and the estimator (its side records are its own, like its queues)
 }
 
 // ---- fused schedule: one k_path launch per batch (jp_path.h) --------------------------------------------------------------
@@ -500,14 +521,18 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0;
 	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
 	if (c->plan.pick && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator samples every light (scene uploaded with JP_LIGHTS_POWER_ONE)");
 	if (c->plan.textured && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample textures (scene uploaded by jp_upload_scene_textured)");
+	if (c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator has one estimator (jp_set_estimator: JP_ESTIMATOR_MIS is the path integrator's)");
+	if (c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH && c->plan.have_scene && !c->plan.pick)
+		return fail(JP_ERR_UNSUPPORTED, "jp_render: JP_ESTIMATOR_MIS needs a scene uploaded with JP_LIGHTS_POWER_ONE (jp_set_light_sampling): the light strategy's pdf comes from the light table");
 	if (fused_eligible(c, rp)) return render_fused(c, rp, film_dev, sync);
 	c->last_textured = c->plan.textured && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_picked = c->plan.pick && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_mapped = c->plan.env && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
 	// Gsamples/s).  JETPBRT_LANES = 1 .. 4 forces a count, JETPBRT_LANE_ROWS the group height.

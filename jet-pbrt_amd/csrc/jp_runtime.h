@@ -136,6 +136,10 @@ struct JpContext
 	// environment map (jp_env.h): the map the next upload takes (jp_set_environment_map), and what jp_get_env_info reports of the uploaded scene's
 	EnvMapHost env_map;
 	int env_importance = 0, env_n_selectable = 0; double env_total_weight = 0.0; long long env_table_bytes = 0; int last_mapped = 0;
+	// estimator (jp_mis.h): render-time state (jp_set_estimator; a lane takes its parent's before it renders), what the last render ran, and the side records of
+	// this context's queue set, one float2 per position of each ray queue, allocated by the first MIS render
+	int estimator = JP_ESTIMATOR_NEE, last_mis = 0;
+	DevBuf mis_side[2];
 };
 // jp_pick.h / jp_env.h (included last) define the upload's table steps
 static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area);

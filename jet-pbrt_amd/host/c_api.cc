@@ -96,6 +96,7 @@ void jp_host_scene_disk(void* h, const float* pos, const float* normal, float ra
 void jp_host_scene_set_reference_tree(void* h, int on) { ((HostScene*)h)->scene->referenceTree = on != 0; ((HostScene*)h)->scene->certifiedWalk = on == 2; }   // 1: verbatim walk, 2: certified walk
 void jp_host_scene_set_device_build(void* h, int on) { ((HostScene*)h)->scene->deviceBuild = on != 0; ((HostScene*)h)->scene->hostBuild = on == 0; }   // explicit either way
 void jp_host_scene_set_light_sampling(void* h, int mode) { ((HostScene*)h)->scene->SetLightSampling(mode); }   // FScene::SetLightSampling (JP_LIGHTS_*)
+void jp_host_scene_set_estimator(void* h, int mode) { ((HostScene*)h)->scene->SetEstimator(mode); }   // FScene::SetEstimator (JP_ESTIMATOR_*)
 // FScene::SetEnvironmentMap from memory (3 * w * hgt floats, top row first; null: no map) or from a file (FEnvironmentMap::FromFile); importance -1:
 // the A/B hook of JpEnvMap.  0, or -1 with jp_host_last_error set
 int jp_host_scene_envmap(void* h, const float* rgb, int w, int hgt, int up_axis, int importance)

@@ -1,6 +1,8 @@
 // jet-pbrt_amd/host/cli_main.cc -- the reference's command line (main.cc:113-163) on the GPU integrator:
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
-//             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]]
+//             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]]
+// --estimator mis: next-event estimation and the BSDF sample weighted against each other (FScene::SetEstimator(JP_ESTIMATOR_MIS)); implies --light-sampling power.
+// nee (default): the reference's estimator.
 // --envmap FILE: light the scene with a lat-long image (PFM, Radiance .hdr, binary PPM, BMP; FScene::SetEnvironmentMap): the scene script's background
 // becomes the tint (S, S, S), S = 1 unless --envmap-scale says otherwise; --envmap-up: the map's up axis (default y, the scenes' up); power sampling is implied.
 // --light-sampling power: one light per bounce, picked by power (FScene::SetLightSampling(JP_LIGHTS_POWER_ONE)); all (default): every light at every bounce.
@@ -77,10 +79,10 @@ int main(int argc, char* argv[])
 {
 	int width = 1024, height = 1024, samples_per_pixel = 50;     // main.cc:115,119
 	std::string assets = "scene", out, format = "bmp", integratorName = "path";
-	bool denoise = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL;
+	bool denoise = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL, estimator = JP_ESTIMATOR_NEE;
 	std::string envmap; int envUp = JP_ENV_UP_Y; float envScale = 1.f;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
-	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]]\n");
+	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -99,6 +101,12 @@ int main(int argc, char* argv[])
 			const char* m = argv[++i];
 			if (!strcmp(m, "power")) lightSampling = JP_LIGHTS_POWER_ONE; else if (!strcmp(m, "all")) lightSampling = JP_LIGHTS_ALL;
 			else { fprintf(stderr, "--light-sampling must be all or power\n"); return 5; }
+		}
+		else if (!strcmp(argv[i], "--estimator") && i + 1 < argc)
+		{
+			const char* m = argv[++i];
+			if (!strcmp(m, "mis")) estimator = JP_ESTIMATOR_MIS; else if (!strcmp(m, "nee")) estimator = JP_ESTIMATOR_NEE;
+			else { fprintf(stderr, "--estimator must be nee or mis\n"); return 5; }
 		}
 		else if (!strcmp(argv[i], "--envmap") && i + 1 < argc) envmap = argv[++i];
 		else if (!strcmp(argv[i], "--envmap-up") && i + 1 < argc)
@@ -132,7 +140,8 @@ int main(int argc, char* argv[])
 	}
 	if (map) scene->SetEnvironmentMap(map, envUp);
 	fprintf(stderr, "current scene: %s\n", scene->NameStr());
-	scene->SetLightSampling(lightSampling);
+	scene->SetLightSampling(estimator == JP_ESTIMATOR_MIS ? JP_LIGHTS_POWER_ONE : lightSampling);
+	scene->SetEstimator(estimator);
 	if (scene->primitives.empty()) { fprintf(stderr, "no geometry loaded from %s\n", assets.c_str()); return 2; }
 	std::shared_ptr<FSampler> sampler = std::make_shared<FRandomSampler>(samples_per_pixel);
 	// main.cc:154 constructs FPathIntegratorIteration(5); the commented-out alternatives of main.cc:150-153 are selectable here

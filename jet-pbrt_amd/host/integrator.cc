@@ -30,6 +30,7 @@ struct HipApi
 	int (*render_denoised)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*) = nullptr;   // (looked up, needed by FFilm::RequestGuides / RequestDenoise only)
 	int (*set_light_sampling)(JpContext*, const JpLightSampling*) = nullptr;                 // (looked up, needed by FScene::SetLightSampling only)
 	int (*set_environment_map)(JpContext*, const JpEnvMap*) = nullptr;                       // (looked up, needed by FScene::SetEnvironmentMap only)
+	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                          // (looked up, needed by FScene::SetEstimator only)
 	std::string error;
 };
 
@@ -59,6 +60,7 @@ HipApi& Api()
 		api.render_denoised = (decltype(api.render_denoised))dlsym(api.lib, "jp_render_denoised");
 		api.set_light_sampling = (decltype(api.set_light_sampling))dlsym(api.lib, "jp_set_light_sampling");
 		api.set_environment_map = (decltype(api.set_environment_map))dlsym(api.lib, "jp_set_environment_map");
+		api.set_estimator = (decltype(api.set_estimator))dlsym(api.lib, "jp_set_estimator");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
 		else if (api.abi_version() != JP_ABI_VERSION)            // a stale build would be handed structs of another size (JpCounters, JpBuildInfo, JpOptions)
@@ -121,7 +123,16 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 	const FEnvironmentMap* const emap = scene->environmentMap && scene->environmentMap->Valid() ? scene->environmentMap.get() : nullptr;
 	if (scene->environmentMap && !emap) { fprintf(stderr, "FGpuPathIntegrator::Render: FScene::SetEnvironmentMap was given an empty map\n"); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
 	const unsigned long long envId = emap ? emap->id : 0;
-	const int lightMode = emap ? JP_LIGHTS_POWER_ONE : scene->lightSampling;            // a mapped scene: the map light is an entry of the light table
+	const bool mis = scene->estimator == JP_ESTIMATOR_MIS && kind == JP_INTEGRATOR_PATH;   // FScene::SetEstimator: the path integrator's (the other two render as they always did)
+	const int lightMode = (emap || mis) ? JP_LIGHTS_POWER_ONE : scene->lightSampling;   // a mapped scene: the map light is an entry of the light table; MIS: the light strategy's pdf comes from it
+	if (ctxEstimator != (mis ? JP_ESTIMATOR_MIS : JP_ESTIMATOR_NEE))
+	{   // render-time state of the context: sent when it changes; a scene that never asked for MIS makes no such call
+		if (!api.set_estimator) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_estimator\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+		JpEstimator es; es.struct_bytes = (int32_t)sizeof(es); es.mode = mis ? JP_ESTIMATOR_MIS : JP_ESTIMATOR_NEE;
+		lastStatus = api.set_estimator(ctx, &es);
+		if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+		ctxEstimator = es.mode;
+	}
 	if (uploaded != scene || uploadedLights != lightMode || uploadedEnv != envId || uploadedEnvUp != scene->environmentUp || uploadedEnvImp != scene->environmentImportance)
 	{
 		if (ctxEnv != envId || (envId && (ctxEnvUp != scene->environmentUp || ctxEnvImp != scene->environmentImportance)))

@@ -440,6 +440,10 @@ public:
 	// power -- what a scene lit by CreateAreaLights(mesh) needs.  Read by FGpuPathIntegrator::Render at its next upload of this scene.
 	int lightSampling = JP_LIGHTS_ALL;
 	void SetLightSampling(int mode) { lightSampling = mode; }
+	// JP_ESTIMATOR_NEE (default: the reference's estimator) or JP_ESTIMATOR_MIS: next-event estimation and the BSDF sample weighted against each other (power
+	// heuristic).  Render-time state, sent before every render; a scene that asks for MIS is uploaded with JP_LIGHTS_POWER_ONE whatever lightSampling says.
+	int estimator = JP_ESTIMATOR_NEE;
+	void SetEstimator(int mode) { estimator = mode; }
 	// Image-based lighting (INTEGRATION.md "Environment maps"): the scene's one FEnvironmentLight takes its radiance from `map` (the light's own
 	// radiance tints it), looked up by nearest texel on a miss and importance-sampled by texel; up_axis JP_ENV_UP_Z / JP_ENV_UP_Y.  A mapped scene
 	// renders with JP_LIGHTS_POWER_ONE whatever lightSampling says; one with no FEnvironmentLight, or more than one, is refused by Render.
@@ -506,6 +510,7 @@ protected:
 	int shardIndex = 0, shardCount = 1, bandRows = 20;
 	mutable JpContext* ctx = nullptr;
 	mutable const FScene* uploaded = nullptr;
+	mutable int ctxEstimator = JP_ESTIMATOR_NEE;                    // the estimator the context was last told (FScene::SetEstimator)
 	mutable int uploadedLights = JP_LIGHTS_ALL, ctxLights = JP_LIGHTS_ALL;   // FScene::lightSampling of the uploaded scene; the mode the context was last told
 	mutable unsigned long long uploadedEnv = 0, ctxEnv = 0; mutable int uploadedEnvUp = 0, ctxEnvUp = 0, uploadedEnvImp = 0, ctxEnvImp = 0;   // FEnvironmentMap::id (0: none), up axis and importance: of the uploaded scene; last sent to the context
 	mutable int lastStatus = 0;

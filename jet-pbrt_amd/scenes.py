@@ -282,6 +282,12 @@ class HostBackend:
         from . import LIGHT_SAMPLING_MODES
         self._f("scene_set_light_sampling")(self.h, LIGHT_SAMPLING_MODES[mode])
 
+    def set_estimator(self, mode="mis"):
+        """FScene::SetEstimator: "mis" = next-event estimation and the BSDF sample weighted against each other (JP_ESTIMATOR_MIS; the scene is then
+        uploaded with JP_LIGHTS_POWER_ONE), None / "nee" = the reference's estimator (host backend only; takes effect with the integrator's next render)"""
+        from . import ESTIMATOR_MODES
+        self._f("scene_set_estimator")(self.h, ESTIMATOR_MODES[mode])
+
     def envmap(self, rgb, up_axis="z", importance=0):
         """FScene::SetEnvironmentMap: an (H, W, 3) float32 array top row first, the path of a PFM / Radiance .hdr / binary PPM / BMP file, or None for no
         map; up_axis "z" (map space = world space) or "y"; importance -1: sample by solid angle alone, arrays only (host backend only; takes effect
