@@ -236,7 +236,12 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 // kMis (k_shade_mis*, JP_ESTIMATOR_MIS; jp_mis.h): the emission a BSDF-sampled ray finds is counted too, and it and the next-event sample are weighted with
 // the power heuristic; mv carries the BSDF sample's pdf (and the distance travelled through null-material primitives) from one bounce to the next.
 // F: the scene's feature set (jp_device.h, DESIGN.md "Feature sets"); the lean instances exist for k_shade<true, true, true, kSort> only.
-template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, bool kEnv, bool kMis, typename F = FeatAll>
+// kOne (k_shade_lean_one; scenes without a null-material primitive): the lean instance shades two classes at most, matte and
+// metal, and a path that hit nothing does nothing in it (no emission, no survivor, no store).  The partition is then a two-way split that needs no scan: one
+// sweep, matte positions fill s_idx from the front and metal positions from the back of the region, each wave takes room for its ballot counts with one
+// wave-aggregated LDS add per eight passes, misses are left out of the list.  One barrier, no s_key, no s_cnt.  The order inside a class is the waves'
+// arrival order, as in the output regions.  -DJP_NO_ONE_SWEEP: the selector never picks it.
+template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, bool kEnv, bool kMis, typename F = FeatAll, bool kOne = false>
 __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv, const EnvView& ev, const MisView& mv)
 {
 	static_assert(kPick || !kMis, "k_shade: the light strategy's pdf needs the light table");
@@ -245,8 +250,10 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 	constexpr int kWaves = JP_BLOCK / 64, kMaxSeg = (JP_SHADE_TILE / JP_BLOCK) * kWaves;  // (pass, wave) segments of a tile, in queue order
 	static_assert(JP_SHADE_TILE % JP_BLOCK == 0 && JP_SHADE_TILE <= 65536, "k_shade: tile positions are 16-bit");
 	__shared__ unsigned short s_idx[kSort ? JP_SHADE_TILE : 1];
-	__shared__ unsigned char s_key[kSort ? JP_SHADE_TILE : 1];
-	__shared__ unsigned int s_cnt[kSort ? JP_SHADE_CLASSES * kMaxSeg : 1];
+	static_assert(!kOne || (kSort && kPrims && !F::delta && !F::other_lights && !kTex && !kPick && !kMis), "k_shade: the one-sweep partition is the lean sorted instance's");
+	__shared__ unsigned char s_key[kSort && !kOne ? JP_SHADE_TILE : 1];
+	__shared__ unsigned int s_cnt[kSort && !kOne ? JP_SHADE_CLASSES * kMaxSeg : 1];
+	__shared__ unsigned int s_two;         // kOne: entries of the two segments so far, matte in the low half and metal in the high half (a region holds <= 8192 < 2^16)
 	__shared__ unsigned int s_wsum[kWaves];
 	__shared__ unsigned int s_ctr[3];      // [0] next 64-path chunk of the tile; [1], [2] fill of this block's ray / shadow output regions
 	const unsigned int lane = threadIdx.x & 63u;
@@ -280,7 +287,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 		}
 	}
 	if (n == 0) { if (threadIdx.x == 0) { q.blk_q[nxt][b] = 0; q.blk_sh[b] = 0; } return; }
-	if (threadIdx.x == 0) { s_ctr[0] = 0; s_ctr[1] = 0; s_ctr[2] = 0; }
+	if (threadIdx.x == 0) { s_ctr[0] = 0; s_ctr[1] = 0; s_ctr[2] = 0; if (kOne) s_two = 0; }
 	__syncthreads();
 	const float4* lights = (kTab && !kPick) ? (const float4*)s_lights : sc.lights;
 	const float4* mats = kTab ? (const float4*)s_mats : sc.mats;
@@ -290,7 +297,47 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 	const unsigned int rbase = b * q.R;
 	const unsigned int t0 = 0, count = n;                        // one tile: the host keeps R <= JP_SHADE_TILE for the sorted variant
 	JP_TS(0);                                                     // [0] table staging
-	if (kSort)
+	if (kOne)
+	{   // ---- two-way split of the region's paths: s_idx[a] = position of the a-th matte path, s_idx[count - 1 - m] = position of the m-th metal path ----
+		const unsigned int tid = threadIdx.x, npass = (count + JP_BLOCK - 1) / JP_BLOCK;
+		const unsigned long long ltm = (1ull << lane) - 1ull;
+		#pragma unroll 1
+		for (unsigned int r0 = 0; r0 < npass; r0 += 8)
+		{
+			int pi[8];                                                   // eight hit records in flight per thread
+			#pragma unroll
+			for (int u = 0; u < 8; u++)
+			{
+				const unsigned int j = (r0 + u) * JP_BLOCK + tid;
+				pi[u] = j < count ? __float_as_int(q.hit[rbase + t0 + j].y) : -2;
+			}
+			int mt[8]; unsigned long long ma[8], mb[8];                  // material type per pass (beyond the region, miss: none) and the wave's matte / metal lanes
+			unsigned int na = 0, nb = 0;
+			#pragma unroll
+			for (int u = 0; u < 8; u++)
+			{
+				mt[u] = -1;
+				if (pi[u] >= 0) { const int m = meta_t[pi[u]].y; if (m >= 0) mt[u] = mat_type[m]; }
+				ma[u] = __ballot(mt[u] == JP_MAT_MATTE); mb[u] = __ballot(mt[u] == JP_MAT_METAL);
+				na += (unsigned int)__popcll(ma[u]); nb += (unsigned int)__popcll(mb[u]);
+			}
+			if (na | nb)
+			{   // room for the eight passes' entries in one add; inside it pass by pass, lane by lane
+				const unsigned int base = wave_take(&s_two, na | (nb << 16));
+				unsigned int a = base & 0xffffu, m = base >> 16;
+				#pragma unroll
+				for (int u = 0; u < 8; u++)
+				{
+					const unsigned short j = (unsigned short)((r0 + u) * JP_BLOCK + tid);
+					if (mt[u] == JP_MAT_MATTE) s_idx[a + (unsigned int)__popcll(ma[u] & ltm)] = j;
+					if (mt[u] == JP_MAT_METAL) s_idx[count - 1u - (m + (unsigned int)__popcll(mb[u] & ltm))] = j;
+					a += (unsigned int)__popcll(ma[u]); m += (unsigned int)__popcll(mb[u]);
+				}
+			}
+		}
+		__syncthreads();
+	}
+	else if (kSort)
 	{   // ---- stable partition of the tile's paths by material class: s_idx[sorted position] = position in the tile ----
 		// Two sweeps over the tile (the whole region of the block as a rule: one partition and one closing barrier per launch):
 		// count per (class, pass, wave) with wave ballots, one block-wide exclusive scan of the counters in class-major order,
@@ -377,28 +424,33 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 	// Chunks are taken from the END of the sorted tile: the expensive classes (plastic, metal) sort last, and taking them first
 	// leaves the cheap chunks to even out the waves before the barrier at the end of the tile.
 	JP_TS(1);                                                     // [1] partition
-	const unsigned int nch = (count + 63u) >> 6;
+	// kOne: the same loop over a list of whole chunks -- those of the front segment (n_front matte entries at s_idx[0 ...]), then from `fence` on those of the
+	// back segment (n_back metal entries, entry m at s_idx[count - 1 - m]); a segment's last chunk may be partial, so a position is tested against its segment
+	const unsigned int n_front = kOne ? (s_two & 0xffffu) : 0u, n_back = kOne ? (s_two >> 16) : 0u, fence = ((n_front + 63u) >> 6) << 6;
+#define JP_CHUNK_HAS(v)  (kOne ? ((v) < fence ? (v) < n_front : (v) - fence < n_back) : (v) < count)      /* position v of the chunk list holds a path */
+#define JP_CHUNK_SPOT(v) (kOne ? ((v) < fence ? (v) : count - 1u - ((v) - fence)) : (v))                    /* ... whose tile position is s_idx[this] */
+	const unsigned int nch = kOne ? (fence >> 6) + ((n_back + 63u) >> 6) : (count + 63u) >> 6;
 	unsigned int tk = wave_take(&s_ctr[0], 1u);                  // wave-uniform
 	unsigned int c0 = (nch - 1u - tk) << 6;                      // first tile position of the wave's chunk (meaningful while tk < nch)
-	if (tk < nch && c0 + lane < count) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; }
+	if (tk < nch && JP_CHUNK_HAS(c0 + lane)) { const unsigned int pos = JP_CHUNK_SPOT(c0 + lane), i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; }
 	while (tk < nch)
 	{
-		const bool valid = c0 + lane < count;
+		const bool valid = JP_CHUNK_HAS(c0 + lane);
 #ifdef JP_SHADE_TIMING
 		JP_TS(2);                                                 // [2] loop overhead
 		asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 		JP_TS(3);                                                 // [3] wait for the prefetched records (and for the stores before them)
 #endif
 #ifdef JP_SHADE_NO_PREFETCH
-		if (valid) { const unsigned int pos = c0 + lane, i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; }
+		if (valid) { const unsigned int pos = JP_CHUNK_SPOT(c0 + lane), i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; }
 		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n; const float2 ms = m_n;
 		tk = wave_take(&s_ctr[0], 1u); c0 = (nch - 1u - tk) << 6;
 #else
 		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n; const float2 ms = m_n;
 		tk = wave_take(&s_ctr[0], 1u); c0 = (nch - 1u - tk) << 6;
-		if (tk < nch && c0 + lane < count)
+		if (tk < nch && JP_CHUNK_HAS(c0 + lane))
 		{
-			const unsigned int pos = c0 + lane;
+			const unsigned int pos = JP_CHUNK_SPOT(c0 + lane);
 			const unsigned int i1 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos);
 			ro_n = q.ray_o[cur][i1]; rd_n = q.ray_d[cur][i1]; rb_n = q.beta[cur][i1]; h_n = q.hit[i1]; if (kTex) s_n = tv.side[i1]; if (kMis) m_n = mv.side[cur][i1];
 		}
@@ -681,6 +733,8 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 		JP_TS(9);                                                 // [9] memory wait at the end of the chunk
 #endif
 	}
+#undef JP_CHUNK_HAS
+#undef JP_CHUNK_SPOT
 	JP_TS(2);
 	__syncthreads();                                              // every wave has added its survivors to the fill counters
 	JP_TS(8);                                                     // [8] closing barrier
@@ -701,6 +755,12 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shade(SceneView sc, Queues q, Rend
 {
 	const TexView tv = {}; const PickView pv = {}; const EnvView ev = {}; const MisView mv = {};
 	shade_body<kTab, kPrims, kStage, kSort, false, false, false, false, F>(sc, q, rc, cur, cnt, tv, pv, ev, mv);
+}
+// k_shade<true, true, true, true, FeatLean> with the one-sweep partition (kOne), a kernel of its own name so that every k_shade instance keeps its name
+__global__ void __launch_bounds__(JP_BLOCK) k_shade_lean_one(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt)
+{
+	const TexView tv = {}; const PickView pv = {}; const EnvView ev = {}; const MisView mv = {};
+	shade_body<true, true, true, true, false, false, false, false, FeatLean, true>(sc, q, rc, cur, cnt, tv, pv, ev, mv);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -147,6 +147,9 @@ ShadeKernels shade_kernels(const ScenePlan& p, bool generic)
 	{   // the textured twin stays generic (a textured scene is outside the lean sets' measurements)
 		ShadeKernels k = shade_row<true, true, true>(p.shade_sort);
 		k.plain = p.shade_sort ? k_shade<true, true, true, true, FeatLean> : k_shade<true, true, true, false, FeatLean>;
+#ifndef JP_NO_ONE_SWEEP
+		if (p.shade_sort && !p.has_null_material) k.plain = k_shade_lean_one;   // one-sweep partition: a miss does nothing in this instance only while no primitive is without a material
+#endif
 		return k;
 	}
 	if (p.shade_prims_in_lds) return p.stage_nee ? shade_row<true, true, true>(p.shade_sort) : shade_row<true, true, false>(p.shade_sort);

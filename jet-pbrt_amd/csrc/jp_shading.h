@@ -447,6 +447,9 @@ __device__ __forceinline__ LightSample sample_li(const SceneView& sc, PrimPtr pr
 	const float4 g0 = prims[4 * pi + 0], g3 = prims[4 * pi + 3];
 	const int type = __float_as_int(g3.w);
 	V3 lp, ln; float pdf;
+#ifndef JP_NO_KEEP_WI
+	V3 kept = mk(0, 0, 0); bool have_kept = false;                // the flat shapes' Normalize(lp - p), kept for s.wi below (-DJP_NO_KEEP_WI: computed twice, as before)
+#endif
 	if (!F::other_lights || type != JP_SHAPE_SPHERE)
 	{
 		const float4 g1 = prims[4 * pi + 1], g2 = prims[4 * pi + 2];
@@ -472,6 +475,9 @@ __device__ __forceinline__ LightSample sample_li(const SceneView& sc, PrimPtr pr
 			const float l = sqrtf(dist2);                         // Normalize(wi) = wi / sqrt(|wi|^2), with the length kept: FScene::Occluded's
 			wi = wi / l;                                          // |position - target| squares the negated differences -- the same bits
 			s.dist = l;
+#ifndef JP_NO_KEEP_WI
+			kept = wi; have_kept = true;
+#endif
 			pdf *= dist2 / absdot(ln, -wi);
 			if (isinf(pdf)) pdf = 0;
 		}
@@ -514,6 +520,13 @@ __device__ __forceinline__ LightSample sample_li(const SceneView& sc, PrimPtr pr
 	if (pdf == 0 || len2(lp - p) == 0) s.Li = splat(0);           // light.h:205-214
 	else
 	{
+#ifndef JP_NO_KEEP_WI
+		// Triangle, rectangle, disk: pdf != 0 implies the `else` branch above ran (dist2 == 0 set pdf to exactly 0), and its wi / sqrtf(len2(wi)) with
+		// wi = lp - p is the expression tree of Normalize(lp - p) -- the same operations on the same inputs in the same order, so the same bits.  The three
+		// divisions and the square root are not executed a second time.  Sphere lights normalise inside other expressions and keep theirs.
+		if (!F::other_lights || have_kept) s.wi = kept;
+		else
+#endif
 		s.wi = normalize(lp - p);
 		s.Li = (dot(ln, -s.wi) > 0.f) ? radiance : splat(0);      // FAreaLight::L light.h:234-238
 	}
