@@ -478,6 +478,32 @@ int  jp_get_estimator_info(JpContext* ctx, JpEstimatorInfo* out);
  * positive).  JP_ERR_UNSUPPORTED for a scene uploaded with JP_LIGHTS_ALL. */
 int  jp_light_pdf(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, int32_t* light, float* pdf);
 
+/* Vertex normals (additive to ABI 7; INTEGRATION.md "Vertex normals" has the definition).  tri_vn: 9 floats per triangle of JpScene's triangle arrays, the unit
+ * normals n0 n1 n2 at p0 p1 p2.  Nine zeros mark the triangle flat (shaded with tri_n, as without normals); otherwise every value must be finite and each
+ * normal satisfy 0.81 <= |n|^2 <= 1.21 (else JP_ERR_INVALID_ARGUMENT with a message, the context stays usable).  Context state like the map and the light mode:
+ * validated and copied here, read by the next jp_upload_scene* (whose n_triangles must equal this one's, else JP_ERR_INVALID_ARGUMENT); NULL removes them.
+ * At a hit on a smooth triangle the path integrator builds the BSDF frame, wo and both cosine factors from the interpolated normal Ns (include/jp_normals.h)
+ * and keeps tri_n for everything that belongs to the surface as an emitter or as geometry; a sampled direction on the other geometric side than wo is refused
+ * (matte, mirror, plastic, metal).  All eight combinations of light sampling x map x estimator, textured or not.  Whitted: JP_ERR_UNSUPPORTED for a scene with
+ * at least one smooth triangle; the debug integrator ignores the normals; JpOptions.fused falls back to the per-bounce launches; jp_render_guides delivers Ns
+ * in its normal buffer.  Normals that are all flat: exactly the upload without normals (smooth_last_render 0, bit-identical films and guides). */
+typedef struct JpVertexNormals { int32_t struct_bytes; int32_t n_triangles; const float* tri_vn; } JpVertexNormals;
+int  jp_set_vertex_normals(JpContext* ctx, const JpVertexNormals* normals);
+typedef struct JpNormalInfo {
+    int32_t struct_bytes, n_triangles, n_smooth_triangles;   /* of the uploaded scene's normals (0 0: uploaded without)                          */
+    int64_t table_bytes_device;              /* device bytes of the 48-byte-per-primitive normal table (0: no smooth triangle)              */
+    int32_t smooth_last_render;              /* the last jp_render* ran k_normal and the smooth kernels (k_shade_smooth*)                    */
+    double  normal_ms;                       /* with jp_set_profiling: k_normal's launches of the last render (a share of JpCounters.shade_ms) */
+} JpNormalInfo;
+int  jp_get_normal_info(JpContext* ctx, JpNormalInfo* out);
+/* test hook like jp_surface: the walk jp_trace takes, then prim (the caller's primitive index, -1 on a miss), Ng as jp_trace returns its normal and the Ns the
+ * render uses there (3n floats each; Ns == Ng on flat triangles and other shapes; both 0 on a miss) */
+int  jp_shading_normal(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, int32_t* prim, float* ng, float* ns);
+/* the very function the device runs (include/jp_normals.h), for n points: p0 p1 p2 ng p 3 floats each, vn9 9 floats each -> ns_out 3 floats each.  Pure host
+ * code, no GPU needed; so is jp_check_vertex_normals, the validation of jp_set_vertex_normals with its status and message (n_smooth may be NULL). */
+int  jp_interpolate_normals(int32_t n, const float* p0, const float* p1, const float* p2, const float* ng, const float* vn9, const float* p, float* ns_out);
+int  jp_check_vertex_normals(const JpVertexNormals* normals, int32_t* n_smooth);
+
 /* What jp_upload_scene would do with `scene` (additive to ABI 7; INTEGRATION.md "Describing an upload"): the scalars of the plan every later launch
  * reads, and for each table the host builds the byte count and the 64-bit FNV-1a of exactly the bytes the upload copies to the device.  Pure host code, no GPU
  * needed: the same validation (same status codes and jp_last_error texts), table builders and plan function the upload runs, nothing decided twice.

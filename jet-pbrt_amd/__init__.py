@@ -154,6 +154,50 @@ class JpEnvInfo(C.Structure):
                 ("table_bytes_device", C.c_int64)]
 
 
+class JpVertexNormals(C.Structure):
+    """include/jetpbrt_amd.h: JpVertexNormals (jp_set_vertex_normals); struct_bytes = sizeof(JpVertexNormals)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_triangles", C.c_int32), ("tri_vn", _fp)]
+
+
+class JpNormalInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_triangles", C.c_int32), ("n_smooth_triangles", C.c_int32), ("table_bytes_device", C.c_int64),
+                ("smooth_last_render", C.c_int32), ("normal_ms", C.c_double)]
+
+
+def vertex_normals(tri_vn):
+    """A JpVertexNormals over an (n_triangles, 9) float32 array: n0 n1 n2 per triangle, nine zeros = flat (kept alive on the returned object as ._keep)"""
+    import numpy as np
+    a = np.ascontiguousarray(tri_vn, np.float32).reshape(-1, 9)
+    v = JpVertexNormals(C.sizeof(JpVertexNormals), a.shape[0], a.ctypes.data_as(_fp))
+    v._keep = a
+    return v
+
+
+def check_vertex_normals(tri_vn):
+    """jp_check_vertex_normals: the validation of jp_set_vertex_normals (pure host code, no GPU) -> number of smooth triangles; raises JetPbrtError with its message"""
+    v = tri_vn if isinstance(tri_vn, JpVertexNormals) else vertex_normals(tri_vn)
+    n = C.c_int32(0)
+    L = hip_lib()
+    st = L.jp_check_vertex_normals(C.byref(v), C.byref(n))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    return n.value
+
+
+def interpolate_normals(p0, p1, p2, ng, vn9, p):
+    """jp_interpolate_normals: the shading normal the device computes (include/jp_normals.h) for n points; (n, 3) arrays, vn9 (n, 9) -> (n, 3) float32.  Pure host code."""
+    import numpy as np
+    a = [np.ascontiguousarray(x, np.float32) for x in (p0, p1, p2, ng, vn9, p)]
+    n = a[0].shape[0]
+    out = np.zeros((n, 3), np.float32)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    st = L.jp_interpolate_normals(n, q(a[0]), q(a[1]), q(a[2]), q(a[3]), q(a[4]), q(a[5]), q(out))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    return out
+
+
 def env_map(rgb, up_axis=JP_ENV_UP_Z, importance=0):
     """A JpEnvMap over an (H, W, 3) float32 array, top row first (kept alive on the returned object as ._keep)"""
     import numpy as np
@@ -381,6 +425,9 @@ def host_lib():
         L.jp_host_scene_set_estimator.argtypes = [C.c_void_p, C.c_int]
         L.jp_host_scene_envmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.jp_host_scene_envmap_file.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        L.jp_host_scene_mesh_smooth.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, _fp, C.c_int, C.c_float]
+        L.jp_host_flatten_normals.restype = C.POINTER(JpVertexNormals)
+        L.jp_host_flatten_normals.argtypes = [C.c_void_p]
         L.jp_host_flatten_envmap.restype = C.POINTER(JpEnvMap)
         L.jp_host_flatten_envmap.argtypes = [C.c_void_p]
         _host = L
@@ -438,6 +485,11 @@ def hip_lib():
         L.jp_copy_upload_table.argtypes = [C.POINTER(JpOptions), C.c_int32, C.POINTER(JpScene), C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.jp_read_scene_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.jp_get_tree_info.argtypes = [C.c_void_p, C.POINTER(JpTreeInfo)]
+        L.jp_set_vertex_normals.argtypes = [C.c_void_p, C.POINTER(JpVertexNormals)]
+        L.jp_get_normal_info.argtypes = [C.c_void_p, C.POINTER(JpNormalInfo)]
+        L.jp_shading_normal.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+        L.jp_interpolate_normals.argtypes = [C.c_int32] + [C.c_void_p] * 7
+        L.jp_check_vertex_normals.argtypes = [C.POINTER(JpVertexNormals), C.POINTER(C.c_int32)]
         _hip = L
     return _hip
 
@@ -654,6 +706,31 @@ class Context:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         self._check(self.lib.jp_env_sample(self.h, n, p(a), p(idx), p(wi), p(Li), p(pdf)))
         return idx, wi, Li, pdf
+
+    def set_vertex_normals(self, tri_vn):
+        """jp_set_vertex_normals for the next upload: an (n_triangles, 9) float32 array (nine zeros: a flat triangle), a JpVertexNormals, or None for none"""
+        if tri_vn is None:
+            self._check(self.lib.jp_set_vertex_normals(self.h, None))
+            return
+        v = tri_vn if isinstance(tri_vn, JpVertexNormals) else vertex_normals(tri_vn)
+        self._check(self.lib.jp_set_vertex_normals(self.h, C.byref(v)))
+
+    def normal_info(self):
+        i = JpNormalInfo()
+        i.struct_bytes = C.sizeof(JpNormalInfo)
+        self._check(self.lib.jp_get_normal_info(self.h, C.byref(i)))
+        return i
+
+    def shading_normal(self, origin, direction, tmin, tmax):
+        """jp_shading_normal: closest hit of jp_trace's walk -> (prim (n,), ng (n, 3), ns (n, 3)): the geometric normal and the shading normal the render uses"""
+        import numpy as np
+        n = origin.shape[0]
+        o = np.ascontiguousarray(origin, np.float32); d = np.ascontiguousarray(direction, np.float32)
+        t0 = np.ascontiguousarray(tmin, np.float32); t1 = np.ascontiguousarray(tmax, np.float32)
+        prim = np.zeros(n, np.int32); ng = np.zeros((n, 3), np.float32); ns = np.zeros((n, 3), np.float32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_shading_normal(self.h, n, p(o), p(d), p(t0), p(t1), p(prim), p(ng), p(ns)))
+        return prim, ng, ns
 
     def synchronize(self):
         self._check(self.lib.jp_synchronize(self.h))

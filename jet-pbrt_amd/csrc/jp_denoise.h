@@ -17,8 +17,9 @@ struct GuideConst
 	int band_rows, shard_index, shard_count;
 };
 
-template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist)
+// kSmooth (k_guides_smooth, scenes with vertex normals; jp_normals.h): the normal of a hit on a smooth triangle is the shading normal Ns the render uses there
+template <int kMode, bool kSmooth>
+__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv)
 {
 	SceneAccess<kMode> acc(sc, depth);
 	const int npix = gc.width * gc.height;
@@ -51,6 +52,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, i
 					else if (type == JP_SHAPE_RECTANGLE) n = dot(xyz(g3), rd) <= 0 ? xyz(g3) : -xyz(g3);
 					else if (type == JP_SHAPE_DISK) n = xyz(sc.prims[4 * h + 1]);
 					else n = normalize(p - xyz(sc.prims[4 * h]));
+					if (kSmooth) shading_normal(sc.prims, nv, h, meta.x, p, n);
 					t = tmax;
 					const int mat = meta.y;
 					if (mat >= 0)
@@ -69,6 +71,16 @@ __global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, i
 		if (normal) { normal[3 * pix] = N.x; normal[3 * pix + 1] = N.y; normal[3 * pix + 2] = N.z; }
 		if (dist) dist[pix] = T;
 	}
+}
+template <int kMode>
+__global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist)
+{
+	guides_body<kMode, false>(sc, tv, depth, gc, albedo, normal, dist, NormView());
+}
+template <int kMode>
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv)
+{
+	guides_body<kMode, true>(sc, tv, depth, gc, albedo, normal, dist, nv);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -153,8 +165,9 @@ namespace
 #define JP_DENOISE_SIGMA_DEPTH  0.03f
 
 typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*);
-struct GuideLaunch { GuideKernel k; size_t lds; int depth; };
-template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth }; return g; }
+typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView);
+struct GuideLaunch { GuideKernel k; size_t lds; int depth; GuideSmoothKernel smooth; };      // smooth: the twin a scene with vertex normals runs
+template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth, k_guides_smooth<M> }; return g; }
 // the walk trace_kernel(p, 0) gives jp_surface
 GuideLaunch guide_kernel(const ScenePlan& p)
 {
@@ -193,7 +206,8 @@ int guides_launch(JpContext* c, const GuideConst& gc, float* albedo, float* norm
 	const int npix = gc.width * gc.height;
 	const int grid = std::min(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK);
 	HIP_TRY(hipEventRecord(c->gd_ev[0], c->stream));
-	hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist);
+	if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv);
+	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->gd_ev[1], c->stream));
 	c->gd_timed = true; c->last_guide_spp = gc.spp;

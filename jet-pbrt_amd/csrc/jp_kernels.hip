@@ -21,6 +21,7 @@
 // layout is deterministic.  Launches are asynchronous on one stream, no host round trip inside a batch.
 #include "jp_common.h"
 #include "jp_tex.h"
+#include "jp_normals.h"          // part 1: NormView, shading_normal (the kernels and entry points: part 2, at the end)
 #include "jp_env.h"              // part 1: EnvView, env_lookup, env_sample (the kernels and entry points: part 2, at the end)
 #include "jp_mis.h"              // part 1: MisView, mis_weight, pdf_local, light_pdf (the kernels and entry points: part 2, at the end)
 #include "jp_xbsdf.h"
@@ -241,12 +242,25 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 // sweep, matte positions fill s_idx from the front and metal positions from the back of the region, each wave takes room for its ballot counts with one
 // wave-aggregated LDS add per eight passes, misses are left out of the list.  One barrier, no s_key, no s_cnt.  The order inside a class is the waves'
 // arrival order, as in the output regions.  -DJP_NO_ONE_SWEEP: the selector never picks it.
-template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, bool kEnv, bool kMis, typename F = FeatAll, bool kOne = false>
-__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv, const EnvView& ev, const MisView& mv)
+// What shade_body keeps per path of a smooth instance; empty otherwise, so every other instance compiles from the code it had
+template <bool kSmooth> struct SmoothVars { };
+template <> struct SmoothVars<true> { float4 next, rec; V3 Ns; bool on, guard; };
+template <bool kSmooth> __device__ __forceinline__ V3 shade_n(const SmoothVars<kSmooth>& sm, V3 N) { if constexpr (kSmooth) return sm.Ns; else return N; }
+// the geometric-side guard: w and wo on different sides of the geometric normal (smooth triangles; matte, mirror, plastic, metal)
+template <bool kSmooth> __device__ __forceinline__ bool shade_refuses(const SmoothVars<kSmooth>& sm, V3 w, V3 wo, V3 Ng)
+{
+	if constexpr (kSmooth) return sm.guard && dot(w, Ng) * dot(wo, Ng) <= 0.f; else return false;
+}
+// kSmooth (k_shade_smooth*, scenes with vertex normals; jp_normals.h): where k_normal left a shading normal Ns for the queue position, the BSDF frame, wo and both cosine
+// factors take Ns; everything that belongs to the surface as an emitter or as geometry keeps the geometric normal, and a direction on the other geometric side
+// than wo is refused (matte, mirror, plastic, metal).
+template <bool kTab, bool kPrims, bool kStage, bool kSort, bool kTex, bool kPick, bool kEnv, bool kMis, typename F = FeatAll, bool kOne = false, bool kSmooth = false>
+__device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst rc, int cur, DevCounters* cnt, const TexView& tv, const PickView& pv, const EnvView& ev, const MisView& mv, const NormView& nv = NormView())
 {
 	static_assert(kPick || !kMis, "k_shade: the light strategy's pdf needs the light table");
 	static_assert(kTab || !kPrims, "k_shade: primitive records in LDS only together with the tables");
 	static_assert(kPick || !kEnv, "k_shade: the map light is an entry of the light table");
+	static_assert(!kSmooth || !kPrims, "k_shade: a shading normal has no entry in the frame table");
 	constexpr int kWaves = JP_BLOCK / 64, kMaxSeg = (JP_SHADE_TILE / JP_BLOCK) * kWaves;  // (pass, wave) segments of a tile, in queue order
 	static_assert(JP_SHADE_TILE % JP_BLOCK == 0 && JP_SHADE_TILE <= 65536, "k_shade: tile positions are 16-bit");
 	__shared__ unsigned short s_idx[kSort ? JP_SHADE_TILE : 1];
@@ -420,6 +434,8 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 	// The tile is shaded in 64-path chunks that the waves take from an LDS counter: a wave with expensive paths (a chunk of the
 	// microfacet class) takes fewer chunks, and no wave waits for another before the end of the tile.  The records of the chunk
 	// a wave takes next are fetched while it shades the current one (software prefetch).
+	SmoothVars<kSmooth> sm;                                        // kSmooth: the side record of the chunk and of the next one, Ns, the guard (else empty)
+	if constexpr (kSmooth) sm.next = make_float4(0, 0, 0, 0);
 	float4 ro_n = make_float4(0, 0, 0, 0), rd_n = ro_n, rb_n = ro_n; float2 h_n = make_float2(0, 0); unsigned int s_n = 0; float2 m_n = make_float2(0, 0);
 	// Chunks are taken from the END of the sorted tile: the expensive classes (plastic, metal) sort last, and taking them first
 	// leaves the cheap chunks to even out the waves before the barrier at the end of the tile.
@@ -432,7 +448,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 	const unsigned int nch = kOne ? (fence >> 6) + ((n_back + 63u) >> 6) : (count + 63u) >> 6;
 	unsigned int tk = wave_take(&s_ctr[0], 1u);                  // wave-uniform
 	unsigned int c0 = (nch - 1u - tk) << 6;                      // first tile position of the wave's chunk (meaningful while tk < nch)
-	if (tk < nch && JP_CHUNK_HAS(c0 + lane)) { const unsigned int pos = JP_CHUNK_SPOT(c0 + lane), i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; }
+	if (tk < nch && JP_CHUNK_HAS(c0 + lane)) { const unsigned int pos = JP_CHUNK_SPOT(c0 + lane), i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; if constexpr (kSmooth) sm.next = nv.side[i0]; }
 	while (tk < nch)
 	{
 		const bool valid = JP_CHUNK_HAS(c0 + lane);
@@ -442,21 +458,24 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 		JP_TS(3);                                                 // [3] wait for the prefetched records (and for the stores before them)
 #endif
 #ifdef JP_SHADE_NO_PREFETCH
-		if (valid) { const unsigned int pos = JP_CHUNK_SPOT(c0 + lane), i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; }
+		if (valid) { const unsigned int pos = JP_CHUNK_SPOT(c0 + lane), i0 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos); ro_n = q.ray_o[cur][i0]; rd_n = q.ray_d[cur][i0]; rb_n = q.beta[cur][i0]; h_n = q.hit[i0]; if (kTex) s_n = tv.side[i0]; if (kMis) m_n = mv.side[cur][i0]; if constexpr (kSmooth) sm.next = nv.side[i0]; }
 		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n; const float2 ms = m_n;
+		if constexpr (kSmooth) sm.rec = sm.next;
 		tk = wave_take(&s_ctr[0], 1u); c0 = (nch - 1u - tk) << 6;
 #else
 		const float4 ro = ro_n, rd = rd_n, rb = rb_n; const float2 h = h_n; const unsigned int sw = s_n; const float2 ms = m_n;
+		if constexpr (kSmooth) sm.rec = sm.next;
 		tk = wave_take(&s_ctr[0], 1u); c0 = (nch - 1u - tk) << 6;
 		if (tk < nch && JP_CHUNK_HAS(c0 + lane))
 		{
 			const unsigned int pos = JP_CHUNK_SPOT(c0 + lane);
 			const unsigned int i1 = rbase + t0 + (kSort ? (unsigned int)s_idx[pos] : pos);
-			ro_n = q.ray_o[cur][i1]; rd_n = q.ray_d[cur][i1]; rb_n = q.beta[cur][i1]; h_n = q.hit[i1]; if (kTex) s_n = tv.side[i1]; if (kMis) m_n = mv.side[cur][i1];
+			ro_n = q.ray_o[cur][i1]; rd_n = q.ray_d[cur][i1]; rb_n = q.beta[cur][i1]; h_n = q.hit[i1]; if (kTex) s_n = tv.side[i1]; if (kMis) m_n = mv.side[cur][i1]; if constexpr (kSmooth) sm.next = nv.side[i1];
 		}
 #endif
 		bool shaded = false, wantNee = false, alive = false;
 		V3 o = mk(0, 0, 0), d = mk(0, 0, 1), beta = mk(0, 0, 0), p = mk(0, 0, 0), N = mk(0, 0, 1);
+		if constexpr (kSmooth) { sm.Ns = N; sm.on = false; sm.guard = false; }
 		int slot = 0, bounce = 0; bool spec = false; unsigned int dim = 0; uint32_t key = 0;
 		Closure c; c.kind = CL_LAMBERT; Frame fr; fr.s = fr.t = fr.n = mk(0, 0, 1);
 		float2 nm = make_float2(0.f, 0.f);                             // kMis: the survivor's side record
@@ -563,6 +582,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 				{
 					float up = 0.f;
 					const int mtype = mat_type[mat];
+					if constexpr (kSmooth) { sm.on = sm.rec.w != 0.f; sm.Ns = sm.on ? xyz(sm.rec) : N; sm.guard = sm.on && mtype != JP_MAT_GLASS; }
 					if (F::delta && mtype == JP_MAT_PLASTIC) up = rngf(rc, key, dim++);   // material.cc:14
 					if (kTex && sw != 0u) make_closure_tex(mats, mtype, mat, up, tex_color(tv, sw), c);
 					else make_closure<F>(mats, mtype, mat, up, c);
@@ -576,7 +596,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 						const float4 fn = s_frames[3 * hitprim], fs = s_frames[3 * hitprim + 1], ft = s_frames[3 * hitprim + 2];
 						fr.n = nflip ? -xyz(fn) : xyz(fn); fr.s = xyz(fs); fr.t = nflip ? -xyz(ft) : xyz(ft);
 					}
-					else fr = frame_from_z(N);
+					else fr = frame_from_z(shade_n<kSmooth>(sm, N));
 #endif
 					shaded = true;
 					wantNee = !is_delta<F>(c);
@@ -633,12 +653,13 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					if (isblack(ls.Li) || ls.pdf == 0.f) continue;
 					const V3 f = eval_local<F>(c, wo, to_local(fr, ls.wi));            // FBSDF::Evalf bsdf.h:284-287
 					if (isblack(f)) continue;
+					if constexpr (kSmooth) { if (shade_refuses<kSmooth>(sm, ls.wi, wo_w, N)) continue; }   // the other geometric side: a light leak or a black reflection
 					// FScene::Occluded scene.h:36-47: dir and distance recomputed from the sampled position
 					// (for an area light Normalize(target - position) is the very expression that produced ls.wi)
 					// (area lights on flat shapes only: the sampler kept the length of every sample that gets here -- pdf != 0 means dist2 != 0)
 					const V3 sdir = (!F::other_lights || __float_as_int(lrad.w) == JP_LIGHT_AREA) ? ls.wi : normalize(ls.pos - p);
 					const float dist = (!F::other_lights || ls.dist >= 0.f) ? ls.dist : len(p - ls.pos);
-					V3 contrib = cmul(cmul(beta, f), ls.Li) * absdot(ls.wi, N) / ls.pdf;   // integrator.cc:369
+					V3 contrib = cmul(cmul(beta, f), ls.Li) * absdot(ls.wi, shade_n<kSmooth>(sm, N)) / ls.pdf;   // integrator.cc:369
 					if (kPick) contrib = contrib / pmf;                                 // the one-light estimator: a pmf of 1 changes no bit
 					if (kMis && (mapped || light_weighed(prims, lights, li, p)))           // the light strategy's weight against the pdf the BSDF sample would draw this direction with
 						contrib = contrib * mis_weight(pmf * ls.pdf, pdf_local(c, wo, to_local(fr, ls.wi)));
@@ -671,7 +692,7 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 			const float ux = rngf(rc, key, dim), uy = rngf(rc, key, dim + 1); dim += 2;
 			BsdfSample bs = sample_local<F>(c, wo, ux, uy);
 			bs.wi = to_world(fr, bs.wi);                                              // bsdf.h:295-301
-			if (!(isblack(bs.f) || bs.pdf == 0.f))
+			if (!(isblack(bs.f) || bs.pdf == 0.f || shade_refuses<kSmooth>(sm, bs.wi, -d, N)))
 			{
 				nspec = (bs.flags & BS_SPECULAR) != 0;                                // integrator.cc:381
 				if (bounce >= 3)                                                      // integrator.cc:383-393
@@ -680,13 +701,13 @@ __device__ __forceinline__ void shade_body(SceneView sc, Queues q, RenderConst r
 					const float ur = rngf(rc, key, dim++);
 					if (!(ur < qq))
 					{
-						nbeta = cmul(beta, bs.f * absdot(bs.wi, N) / (bs.pdf * (1 - qq)));
+						nbeta = cmul(beta, bs.f * absdot(bs.wi, shade_n<kSmooth>(sm, N)) / (bs.pdf * (1 - qq)));
 						alive = true;
 					}
 				}
 				else
 				{
-					nbeta = cmul(beta, bs.f * absdot(bs.wi, N) / bs.pdf);             // integrator.cc:397
+					nbeta = cmul(beta, bs.f * absdot(bs.wi, shade_n<kSmooth>(sm, N)) / bs.pdf);             // integrator.cc:397
 					alive = true;
 				}
 				nd = bs.wi; nbounce = bounce + 1;
@@ -1386,3 +1407,5 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_pick.h"             // light selection: the alias table, k_shade_pick / k_shade_pick_tex, k_light_pick and their entry points (jp_render.h declares its two hooks)
 #define JP_MIS_RUNTIME
 #include "jp_mis.h"              // estimator, part 2: k_shade_mis*, k_light_pdf and their entry points (jp_render.h declares the selector)
+#define JP_NORMALS_RUNTIME
+#include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points (jp_render.h declares the selector)

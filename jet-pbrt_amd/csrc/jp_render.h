@@ -5,7 +5,7 @@
 // ---- render ---------------------------------------------------------------------------------------------------------------
 namespace
 {
-enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4 };
+enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4, CLS_NORMAL = 5 };   // (CLS_NORMAL: k_normal, stamped inside its CLS_SHADE pair -- a share of shade_ms, JpNormalInfo)
 
 void free_queues(JpContext* c) { c->qb = QueueBufs(); c->cap = 0; c->planes_alloc = 0; c->blk_alloc = 0; }
 
@@ -174,8 +174,25 @@ typedef void (*ShadeMisEnvKernel)(SceneView, Queues, RenderConst, int, DevCounte
 typedef void (*ShadeMisEnvTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView, MisView);
 struct ShadeMisKernels { ShadeMisKernel pick; ShadeMisTexKernel pick_tex; ShadeMisEnvKernel env; ShadeMisEnvTexKernel env_tex; };
 ShadeMisKernels shade_mis_kernels(const ScenePlan& p);
+// scenes with vertex normals: k_normal after k_texel, then the smooth twin of the family the scene would take (selector and side records in jp_normals.h)
+struct SmoothKernels
+{
+	void (*normal)(SceneView, Queues, int, NormView);
+	void (*plain)(SceneView, Queues, RenderConst, int, DevCounters*, NormView);
+	void (*tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, NormView);
+	void (*pick)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, NormView);
+	void (*pick_tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, NormView);
+	void (*env)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, EnvView, NormView);
+	void (*env_tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView, NormView);
+	void (*mis)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, MisView, NormView);
+	void (*mis_tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, MisView, NormView);
+	void (*mis_env)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, EnvView, MisView, NormView);
+	void (*mis_env_tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView, MisView, NormView);
+};
+SmoothKernels shade_smooth_kernels(const ScenePlan& p);
 }
 static int ensure_mis_side(JpContext* c, unsigned int cap, MisView& mv);
+static int ensure_normal_side(JpContext* c, unsigned int cap, NormView& nv);
 namespace
 {
 
@@ -225,7 +242,8 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		// shared by the lanes that render concurrently (each lane sizes its own queue set from its share), and when the allocation still
 		// fails (another process took the memory in between) the batch is halved and tried again before the call gives up
 		size_t freeB = 0, totalB = 0; hipMemGetInfo(&freeB, &totalB);
-		const size_t per = 136 + 32 * (size_t)p.n_planes;
+		const bool smooth = p.smooth && rp->integrator == JP_INTEGRATOR_PATH;    // vertex normals: k_normal + k_shade_smooth* (the debug integrator ignores them)
+		const size_t per = 136 + 32 * (size_t)p.n_planes + (smooth ? 16 : 0);
 		size_t budget = std::min<size_t>((size_t)24 << 30, (freeB / (size_t)std::max(1, lane_count) + (c->cap ? (size_t)c->cap * (136 + 32 * (size_t)c->planes_alloc) : 0)) / 2);
 		if (c->opt.max_slots > 0) budget = std::min<size_t>(budget, (size_t)c->opt.max_slots * per);
 		int sbatch = 1; unsigned int P = 0, G = 1, R = JP_BLOCK, cap = 0;
@@ -259,6 +277,8 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		const bool mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH;
 		MisView mv = {};
 		if (mis) if (const int e = ensure_mis_side(c, cap, mv); e != JP_OK) return e;
+		NormView nv = p.nv;
+		if (smooth) if (const int e = ensure_normal_side(c, cap, nv); e != JP_OK) return e;
 		if (const int e = reserve_idle(c, c->spill, spill_need(p, p.persist ? deepest_walk(p) : 0, G) * sizeof(int)); e != JP_OK) return e;
 		if (const int e = reserve_idle(c, c->pix_acc, (size_t)npix * 16); e != JP_OK) return e;
 		int* const d_spill = c->spill.get<int>(); float4* const d_pix_acc = c->pix_acc.get<float4>();
@@ -281,6 +301,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		const ShadePickKernels pk = p.pick ? shade_pick_kernels(p) : ShadePickKernels{ nullptr, nullptr };
 		const ShadeEnvKernels vk = p.env ? shade_env_kernels(p) : ShadeEnvKernels{ nullptr, nullptr };
 		const ShadeMisKernels mk2 = mis ? shade_mis_kernels(p) : ShadeMisKernels{ nullptr, nullptr, nullptr, nullptr };
+		const SmoothKernels nk = smooth ? shade_smooth_kernels(p) : SmoothKernels{};
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
@@ -309,7 +330,26 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 				}
 				{
 					Stamper t(c, CLS_SHADE);
-					if (tex)
+					if (smooth)
+					{   // scenes with vertex normals: k_texel as ever, k_normal leaves Ns for every hit on a smooth triangle, the family's smooth twin shades with it
+						if (tex) hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
+						{ Stamper tn(c, CLS_NORMAL); hipLaunchKernelGGL(nk.normal, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv); }
+						const size_t l = p.shade_lds_bytes;
+						if (tex)
+						{
+							if (mis && p.env) hipLaunchKernelGGL(nk.mis_env_tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev, mv, nv);
+							else if (mis) hipLaunchKernelGGL(nk.mis_tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, mv, nv);
+							else if (p.env) hipLaunchKernelGGL(nk.env_tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev, nv);
+							else if (p.pick) hipLaunchKernelGGL(nk.pick_tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, nv);
+							else hipLaunchKernelGGL(nk.tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, nv);
+						}
+						else if (mis && p.env) hipLaunchKernelGGL(nk.mis_env, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev, mv, nv);
+						else if (mis) hipLaunchKernelGGL(nk.mis, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, mv, nv);
+						else if (p.env) hipLaunchKernelGGL(nk.env, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev, nv);
+						else if (p.pick) hipLaunchKernelGGL(nk.pick, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, nv);
+						else hipLaunchKernelGGL(nk.plain, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, nv);
+					}
+					else if (tex)
 					{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
 						hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
 						if (mis && p.env) hipLaunchKernelGGL(mk2.env_tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev, mv);
@@ -374,6 +414,7 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 {
 	l->plan = c->plan;                                               // (the lane's side array is its own, allocated with its queues)
 	if (!l->plan.textured && l->side) { hipStreamSynchronize(l->stream); l->side.reset(); }   // untextured scene: not kept
+	if (!l->plan.smooth && l->nside) { hipStreamSynchronize(l->stream); l->nside.reset(); }   // (the same for the side records of k_normal)
 	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
 	l->estimator = c->estimator;                                     // ... and the estimator (its side records are its own, like its queues)
 }
@@ -394,6 +435,7 @@ bool fused_eligible(const JpContext* c, const JpRenderParams* rp)
 	if (c->plan.cert) return false;                                       // the certified walk lives in the per-bounce traversal kernels
 	if (c->plan.textured) return false;                                   // textures: k_texel + k_shade_tex live in the per-bounce launches
 	if (c->plan.pick) return false;                                       // JP_LIGHTS_POWER_ONE: k_shade_pick lives there too
+	if (c->plan.smooth) return false;                                     // vertex normals: k_normal + k_shade_smooth* as well
 	if (c->plan.trav_mode == 2) return c->plan.shade_prims_in_lds;
 	return c->plan.trav_mode == 0 || c->plan.trav_mode == 3 || c->plan.trav_mode == 5;
 }
@@ -524,7 +566,8 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0;
+	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
 	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
 	if (c->plan.pick && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator samples every light (scene uploaded with JP_LIGHTS_POWER_ONE)");
 	if (c->plan.textured && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample textures (scene uploaded by jp_upload_scene_textured)");
@@ -536,6 +579,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	c->last_picked = c->plan.pick && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_mapped = c->plan.env && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_smooth = c->plan.smooth && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
 	// Gsamples/s).  JETPBRT_LANES = 1 .. 4 forces a count, JETPBRT_LANE_ROWS the group height.
@@ -597,6 +641,7 @@ int finish_one(JpContext* c, JpCounters& o)
 {
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	DevCounters h; HIP_TRY(hipMemcpy(&h, c->cnt.get<void>(), sizeof(h), hipMemcpyDeviceToHost));
+	c->normal_ms = 0.0;
 	o.closest_rays += h.closest; o.closest_hits += h.closest_hit; o.shadow_rays += h.shadow; o.shadow_occluded += h.shadow_occ; o.certified_fallback_rays += h.cert_fallback;
 	for (const JpContext::Stamp& s : c->stamps)
 	{
@@ -605,6 +650,7 @@ int finish_one(JpContext* c, JpCounters& o)
 		else if (s.cls == CLS_SHADE) { o.shade_ms += t; o.shade_launches++; }
 		else if (s.cls == CLS_SHADOW) { o.shadow_ms += t; o.shadow_launches++; }
 		else if (s.cls == CLS_PATH) { o.path_ms += t; o.path_launches++; }
+		else if (s.cls == CLS_NORMAL) c->normal_ms += t;
 		else o.other_ms += t;
 	}
 	return JP_OK;

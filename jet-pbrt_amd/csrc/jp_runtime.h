@@ -56,6 +56,7 @@ struct ScenePlan
 	bool have_scene = false;
 	SceneView sv; TexView tv = {}; bool textured = false;
 	PickView pv = {}; bool pick = false;                                               // JP_LIGHTS_POWER_ONE (jp_pick.h): the alias table; one shadow plane, no light records in k_shade's LDS tables
+	NormView nv = {}; bool smooth = false;                                             // vertex normals (jp_normals.h): at least one smooth triangle; k_shade's row is then <false, false, false>
 	EnvView ev = {}; bool env = false; double env_mean_sum = 0.0;                      // environment map (jp_env.h): the texel tables; the map light's weight in the light table is (env_mean_sum * pi) * R^2
 	int trav_mode = 0, stack_depth = 1, stack_depth_q4 = 0; bool scene_in_lds = false, shade_prims_in_lds = false; size_t lds_bytes = 0, lds_bytes_shadow = 0;
 	bool cert = false;                                                                 // reference semantics, certified walk (Walker<6>)
@@ -78,12 +79,15 @@ struct SceneTables
 	DevBuf tex_desc, tex_col, texels, mat_tex, prim_uv;             // jp_upload_scene_textured
 	DevBuf pick_bins, pick_pmf, pick_env;                            // JP_LIGHTS_POWER_ONE (jp_pick.h)
 	DevBuf env_texel, env_bins, env_rows;                            // environment map (jp_env.h)
+	DevBuf prim_vn;                                                  // vertex normals (jp_normals.h)
 };
 // The arrays behind a Queues view (the fused schedule's region queues have no hit records and no per-block counts)
 struct QueueBufs { DevBuf ray_o[2], ray_d[2], beta[2], blk_q[2], hit, lacc, sh_o, sh_d, sh_c, blk_sh; };
 
 // the map jp_set_environment_map copied, waiting for the next upload (W == 0: none)
 struct EnvMapHost { int W = 0, H = 0, up = 0, importance = 0; std::vector<float> rgb; };
+// the normals jp_set_vertex_normals copied, waiting for the next upload (set false: none)
+struct VertexNormalsHost { bool set = false; int n_triangles = 0, n_smooth = 0; std::vector<float> vn; };
 
 struct JpContext
 {
@@ -140,10 +144,16 @@ struct JpContext
 	// this context's queue set, one float2 per position of each ray queue, allocated by the first MIS render
 	int estimator = JP_ESTIMATOR_NEE, last_mis = 0;
 	DevBuf mis_side[2];
+	// vertex normals (jp_normals.h): the normals the next upload takes (jp_set_vertex_normals), what jp_get_normal_info reports of the uploaded scene's, and the
+	// side records of this context's queue set (k_normal -> k_shade_smooth*, one float4 per queue position)
+	VertexNormalsHost vnormals;
+	int vn_triangles = 0, vn_smooth = 0, last_smooth = 0; long long vn_table_bytes = 0; double normal_ms = 0.0;   // normal_ms: k_normal's launches of the last render (profiling)
+	DevBuf nside;
 };
 // jp_pick.h / jp_env.h (included last) define the upload's table steps
 static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area);
 static int upload_environment_map(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, bool pick);
+static int upload_vertex_normals(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s);   // jp_normals.h
 
 // a context buffer that kernels in flight may still use: grown only once the stream is idle (nothing happens when the capacity suffices)
 static int reserve_idle(JpContext* c, DevBuf& b, size_t bytes)
@@ -163,6 +173,7 @@ static void free_scene(JpContext* c)
 	c->plan.ev = EnvView(); c->plan.env = false; c->plan.env_mean_sum = 0.0; c->env_n_selectable = 0; c->env_total_weight = 0.0; c->env_table_bytes = 0;
 	c->plan.tv = TexView(); c->plan.textured = false; c->n_textures = c->n_tex_mats = 0; c->texel_bytes = 0;   // (jp_upload_scene drops the textures of an earlier textured upload)
 	c->side.reset();                                               // ... and the side array only textured frames use (callers synchronise first)
+	c->plan.nv = NormView(); c->plan.smooth = false; c->vn_triangles = c->vn_smooth = 0; c->vn_table_bytes = 0; c->nside.reset();
 }
 
 // Which build of glibc's sinf / cosf / sincosf does this host run (jp_shading.h, sincosf_libm)?  The reference computes its

@@ -2,6 +2,7 @@
 // and the closure of a textured material.  k_texel, k_shade_tex and k_surface call these and nothing else (INTEGRATION.md "Textures").
 #pragma once
 #include "jp_common.h"
+#include "jp_normals.h"
 
 namespace jp
 {
@@ -19,10 +20,8 @@ __device__ __forceinline__ float2 tex_uv(const float4* prims, const TexView& tv,
 		{
 			const float4 g1 = prims[4 * h + 1], g2 = prims[4 * h + 2];
 			const V3 e = xyz(g1) - xyz(g0), f = xyz(g2) - xyz(g0), g = p - xyz(g0);
-			const float d00 = dot(e, e), d01 = dot(e, f), d11 = dot(f, f), d20 = dot(g, e), d21 = dot(g, f);
-			const float den = d00 * d11 - d01 * d01;
-			float b1 = 0.f, b2 = 0.f;
-			if (den != 0.f) { b1 = (d11 * d20 - d01 * d21) / den; b2 = (d00 * d21 - d01 * d20) / den; }
+			float b1, b2;
+			jp_barycentrics(e.x, e.y, e.z, f.x, f.y, f.z, g.x, g.y, g.z, &b1, &b2);   // (jp_normals.h: the shading normal's barycentrics are these)
 			const float b0 = 1.f - b1 - b2;
 			const float2 t0 = tv.prim_uv[3 * prim], t1 = tv.prim_uv[3 * prim + 1], t2 = tv.prim_uv[3 * prim + 2];
 			u = b0 * t0.x + b1 * t1.x + b2 * t2.x;

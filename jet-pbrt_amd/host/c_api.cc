@@ -80,6 +80,18 @@ int jp_host_scene_mesh(void* h, const char* path, int flip_normal, int flip_hand
 	return (int)mesh.size();
 }
 
+// ... with FSmoothing: smooth_mode 0 flat, 1 the file's vn, 2 computed with the crease angle `angle` (degrees)
+int jp_host_scene_mesh_smooth(void* h, const char* path, int flip_normal, int flip_handedness, const float* offset, float scale, int mat, const float* radiance, int smooth_mode, float angle)
+{
+	HostScene* hs = (HostScene*)h;
+	const FSmoothing sm = smooth_mode == FSmoothing::kFile ? FSmoothing::File() : (smooth_mode == FSmoothing::kAngle ? FSmoothing::Angle(angle) : FSmoothing::Flat());
+	std::vector<std::shared_ptr<FShape>> mesh = hs->scene->CreateTriangleMesh(path, flip_normal != 0, flip_handedness != 0, V3(offset), scale, sm);
+	std::shared_ptr<FMaterial> m = mat >= 0 ? hs->mats[mat] : nullptr;
+	if (radiance) hs->scene->CreateAreaLights(1, C3(radiance), mesh, m);
+	else hs->scene->CreatePrimitives(mesh, m);
+	return (int)mesh.size();
+}
+
 void jp_host_scene_rect(void* h, int axis, float a0, float a1, float b0, float b1, float c, int flip, int mat, const float* radiance)
 {
 	HostScene* hs = (HostScene*)h;
@@ -148,6 +160,14 @@ const JpTextures* jp_host_flatten_textures(void* h)
 	HostScene* hs = (HostScene*)h;
 	if (!jp_host_flatten(h)) return nullptr;
 	return &hs->flat.textures;
+}
+
+// the flattened vertex normals (valid with jp_host_flatten's view; null: the scene has no smooth triangle, or the flattening failed)
+const JpVertexNormals* jp_host_flatten_normals(void* h)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!jp_host_flatten(h) || hs->flat.n_smooth == 0) return nullptr;
+	return &hs->flat.normals;
 }
 
 // FGpuPathIntegrator(maxdepth).Render(scene, FCounterSampler(spp, seed), film, numthreads) -> rgb (added onto zeros)

@@ -1,6 +1,7 @@
 // jet-pbrt_amd/host/cli_main.cc -- the reference's command line (main.cc:113-163) on the GPU integrator:
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
-//             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]]
+//             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
+// --smooth: vertex normals for the scenes' meshes (FSmoothing; lights excepted): `file` takes the OBJ's vn, a number computes them with that crease angle in degrees.
 // --estimator mis: next-event estimation and the BSDF sample weighted against each other (FScene::SetEstimator(JP_ESTIMATOR_MIS)); implies --light-sampling power.
 // nee (default): the reference's estimator.
 // --envmap FILE: light the scene with a lat-long image (PFM, Radiance .hdr, binary PPM, BMP; FScene::SetEnvironmentMap): the scene script's background
@@ -27,7 +28,7 @@ static FColor LightRadiance()                                    // main.cc:35
 	return FColor(r.x, r.y, r.z);
 }
 
-static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr)   // main.cc:13-62; background: --envmap's tint
+static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr, const FSmoothing& sm = FSmoothing())   // main.cc:13-62; background: --envmap's tint; sm: --smooth
 {
 	const FPoint3 lookfrom(278, 273, 960), lookat(278, 273, 0);
 	std::shared_ptr<FScene> scene = std::make_shared<FScene>("cornell_box_scene");
@@ -40,16 +41,16 @@ static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize,
 	std::shared_ptr<FMaterial> mat_light = scene->CreateMaterial<FMatteMaterial>(FColor(0.65f, 0.65f, 0.65f));
 	const std::string d = dir + "/cornellbox/";
 	scene->CreateAreaLights(1, LightRadiance(), scene->CreateTriangleMesh((d + "light.obj").c_str(), true, true), mat_light);
-	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "floor.obj").c_str(), true, true), white);
-	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "shortbox.obj").c_str(), true, true), white);
-	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "tallbox.obj").c_str(), true, true), golden);
-	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "left.obj").c_str(), true, true), red);
-	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "right.obj").c_str(), true, true), green);
+	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "floor.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), white);
+	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "shortbox.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), white);
+	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "tallbox.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), golden);
+	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "left.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), red);
+	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "right.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), green);
 	scene->Preprocess();
 	return scene;
 }
 
-static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr)        // main.cc:64-111
+static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr, const FSmoothing& sm = FSmoothing())        // main.cc:64-111
 {
 	const FPoint3 lookfrom(-300, 300, -300), lookat(0, 0, 0);
 	std::shared_ptr<FScene> scene = std::make_shared<FScene>("bunny_scene");
@@ -64,13 +65,13 @@ static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, cons
 	std::shared_ptr<FShape> floor = scene->CreateShape<FRectangle>(FRectangle::FromXZ(-200, 200, -200, 200, 0));
 	scene->CreatePrimitive(floor.get(), green.get(), (const FAreaLight*)nullptr);
 	const std::string obj = dir + "/bunny/bunny.obj";
-	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(0, 0, 0), 500.f), red);
+	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(0, 0, 0), 500.f, sm), red);
 	std::shared_ptr<FMaterial> plastic = scene->CreateMaterial<FPlasticMaterial>(FColor(0.35f, 0.12f, 0.48f), FColor(1) - FColor(0.35f, 0.12f, 0.48f), 0.1f, false);
-	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(-100, 0, -100), 500.f), plastic);
+	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(-100, 0, -100), 500.f, sm), plastic);
 	std::shared_ptr<FMaterial> golden = scene->CreateMaterial<FMetalMaterial>(FColor(0.18f, 0.15f, 0.81f), FColor(0.11f, 0.11f, 0.11f), 0.2f, 0.2f, false);
-	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(0, 0, -100), 500.f), golden);
+	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(0, 0, -100), 500.f, sm), golden);
 	std::shared_ptr<FMaterial> glass = scene->CreateMaterial<FGlassMaterial>(1.5f, FColor(0.98f), FColor(0.98f));
-	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(-100, 0, 0), 500.f), glass);
+	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(-100, 0, 0), 500.f, sm), glass);
 	scene->Preprocess();
 	return scene;
 }
@@ -81,8 +82,9 @@ int main(int argc, char* argv[])
 	std::string assets = "scene", out, format = "bmp", integratorName = "path";
 	bool denoise = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL, estimator = JP_ESTIMATOR_NEE;
 	std::string envmap; int envUp = JP_ENV_UP_Y; float envScale = 1.f;
+	FSmoothing smoothing;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
-	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]]\n");
+	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -116,6 +118,13 @@ int main(int argc, char* argv[])
 			else { fprintf(stderr, "--envmap-up must be y or z\n"); return 5; }
 		}
 		else if (!strcmp(argv[i], "--envmap-scale") && i + 1 < argc) { envScale = (float)atof(argv[++i]); if (!(envScale >= 0.f) || !std::isfinite(envScale)) { fprintf(stderr, "--envmap-scale must be a number >= 0\n"); return 5; } }
+		else if (!strcmp(argv[i], "--smooth") && i + 1 < argc)
+		{
+			const char* m = argv[++i]; char* e = nullptr; const float a = strtof(m, &e);
+			if (!strcmp(m, "file")) smoothing = FSmoothing::File();
+			else if (e != m && *e == 0 && a >= 0.f && a <= 180.f) smoothing = FSmoothing::Angle(a);
+			else { fprintf(stderr, "--smooth must be file or an angle of 0 .. 180 degrees\n"); return 5; }
+		}
 		else pos.push_back(argv[i]);
 	}
 	if (pos.empty()) return 0;                                    // main.cc:122-125
@@ -134,8 +143,8 @@ int main(int argc, char* argv[])
 	std::shared_ptr<FScene> scene;
 	switch (sceneId)
 	{
-	case 0: scene = create_cornellbox_scene(film.GetResolution(), assets, map ? &tint : nullptr); break;
-	case 1: scene = create_bunny_scene(film.GetResolution(), assets, map ? &tint : nullptr); break;
+	case 0: scene = create_cornellbox_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing); break;
+	case 1: scene = create_bunny_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing); break;
 	default: return 0;
 	}
 	if (map) scene->SetEnvironmentMap(map, envUp);

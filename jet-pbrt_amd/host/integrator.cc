@@ -30,6 +30,7 @@ struct HipApi
 	int (*render_denoised)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*) = nullptr;   // (looked up, needed by FFilm::RequestGuides / RequestDenoise only)
 	int (*set_light_sampling)(JpContext*, const JpLightSampling*) = nullptr;                 // (looked up, needed by FScene::SetLightSampling only)
 	int (*set_environment_map)(JpContext*, const JpEnvMap*) = nullptr;                       // (looked up, needed by FScene::SetEnvironmentMap only)
+	int (*set_vertex_normals)(JpContext*, const JpVertexNormals*) = nullptr;                 // (looked up, needed by scenes with smooth meshes only)
 	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                          // (looked up, needed by FScene::SetEstimator only)
 	std::string error;
 };
@@ -61,6 +62,7 @@ HipApi& Api()
 		api.set_light_sampling = (decltype(api.set_light_sampling))dlsym(api.lib, "jp_set_light_sampling");
 		api.set_environment_map = (decltype(api.set_environment_map))dlsym(api.lib, "jp_set_environment_map");
 		api.set_estimator = (decltype(api.set_estimator))dlsym(api.lib, "jp_set_estimator");
+		api.set_vertex_normals = (decltype(api.set_vertex_normals))dlsym(api.lib, "jp_set_vertex_normals");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
 		else if (api.abi_version() != JP_ABI_VERSION)            // a stale build would be handed structs of another size (JpCounters, JpBuildInfo, JpOptions)
@@ -154,6 +156,13 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 		}
 		FlatScene flat; std::string err;
 		if (!FlattenScene(*scene, flat, &err)) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", err.c_str()); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
+		if (flat.n_smooth > 0 || ctxNormals)
+		{   // FSmoothing: the vertex normals go to the context before the upload they are to affect (and leave it the same way); a scene of flat meshes makes no such call
+			if (!api.set_vertex_normals) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_vertex_normals\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_vertex_normals(ctx, flat.n_smooth > 0 ? &flat.normals : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxNormals = flat.n_smooth > 0;
+		}
 		// a scene with a textured material goes through jp_upload_scene_textured; any other makes exactly the calls it always made
 		const bool textured = flat.textures.n_textures > 0;
 		if (textured && !api.upload_scene_textured) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_upload_scene_textured\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }

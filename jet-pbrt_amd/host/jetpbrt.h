@@ -90,6 +90,21 @@ public:
 	int Kind() const override { return JP_SHAPE_TRIANGLE; }
 	FPoint3 p0, p1, p2; FNormal3 normal;
 	FPoint2 uv0, uv1, uv2;                                       // texture coordinates of the vertices (0 unless given)
+	// unit vertex normals (INTEGRATION.md "Vertex normals"): shading interpolates them when `smooth`; a flat triangle (the default) shades with `normal`
+	FNormal3 n0, n1, n2; bool smooth = false;
+	void SetVertexNormals(const FNormal3& a, const FNormal3& b, const FNormal3& c) { n0 = a; n1 = b; n2 = c; smooth = true; }
+};
+
+// How a mesh gets vertex normals: flat (the default -- as ever, even when the file has `vn`), the file's `vn` where a face carries them, or computed:
+// corner k of triangle T at OBJ position index v gets normalize(sum of angle_U(v) * Ng_U) over the triangles U sharing v with dot(Ng_T, Ng_U) >= cos(angle),
+// T itself always; accumulated in double, in face order; a zero sum gives Ng_T.
+struct FSmoothing
+{
+	enum { kFlat = 0, kFile = 1, kAngle = 2 };
+	int mode = kFlat; Float angle = 0;
+	static FSmoothing Flat() { return FSmoothing(); }
+	static FSmoothing File() { FSmoothing s; s.mode = kFile; return s; }
+	static FSmoothing Angle(Float degrees) { FSmoothing s; s.mode = kAngle; s.angle = degrees; return s; }
 };
 
 class FRectangle : public FShape                                 // shape.h:380-472, shape.cc:76-95
@@ -120,9 +135,10 @@ public:
 };
 
 // triangulated OBJ ingest with the reference's transform order (shape.cc:23-68): z flip, scale, offset; `vt` texture coordinates ride along
-// untransformed (faces v, v/vt, v/vt/vn, v//vn; negative indices count back; a face without vt gets uv 0)
+// untransformed (faces v, v/vt, v/vt/vn, v//vn; negative indices count back; a face without vt gets uv 0).  `vn` normals are used only when `smoothing`
+// asks for them: flip_normal negates them, bFlipHandedness mirrors them as it mirrors positions, offset and the uniform scale leave them alone.
 bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangle>>& outTriangles, bool flip_normal = false,
-                      bool bFlipHandedness = false, const FVector3& offset = FVector3(0, 0, 0), Float inScale = 1.f);
+                      bool bFlipHandedness = false, const FVector3& offset = FVector3(0, 0, 0), Float inScale = 1.f, const FSmoothing& smoothing = FSmoothing());
 
 // ---- textures (texture.h / texture.cc): descriptions, sampled on the device (JpTextures) ------------------------
 class FTexture
@@ -401,7 +417,8 @@ public:
 	template<typename T, typename... U> std::shared_ptr<T> CreateLight(const U&... args) { auto l = std::make_shared<T>(args...); lights.push_back(l); return l; }
 	template<typename... U> std::shared_ptr<FPrimitive> CreatePrimitive(const U&... args) { auto p = std::make_shared<FPrimitive>(args...); primitives.push_back(p); return p; }
 
-	std::vector<std::shared_ptr<FShape>> CreateTriangleMesh(const char* filename, bool flip_normal = false, bool bFlipHandedness = false, const FVector3& offset = FVector3(0, 0, 0), Float inScale = 1.f);
+	std::vector<std::shared_ptr<FShape>> CreateTriangleMesh(const char* filename, bool flip_normal = false, bool bFlipHandedness = false, const FVector3& offset = FVector3(0, 0, 0), Float inScale = 1.f,
+	                                                        const FSmoothing& smoothing = FSmoothing());
 	std::vector<std::shared_ptr<FPrimitive>> CreatePrimitives(const std::vector<std::shared_ptr<FShape>>& inMesh, const std::shared_ptr<FMaterial>& inMaterial);
 	std::vector<std::shared_ptr<FAreaLight>> CreateAreaLights(int samplesNum, const FColor& radiance, const std::vector<std::shared_ptr<FShape>>& inShapes, const std::shared_ptr<FMaterial>& inMaterial);
 	std::shared_ptr<FAreaLight> CreateAreaLight(int samplesNum, const FColor& radiance, const std::shared_ptr<FShape>& inShape, const std::shared_ptr<FMaterial>& inMaterial);
@@ -473,6 +490,9 @@ struct FlatScene
 	std::vector<float> tex_color, tri_uv;
 	std::vector<int64_t> tex_offset;
 	std::vector<uint8_t> texels;
+	// vertex normals (jp_set_vertex_normals): nine floats per triangle in tri_* order, nine zeros for a flat one; n_smooth == 0: the scene has none
+	JpVertexNormals normals;
+	std::vector<float> tri_vn; int n_smooth = 0;
 };
 bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error = nullptr);
 
@@ -513,6 +533,7 @@ protected:
 	mutable int ctxEstimator = JP_ESTIMATOR_NEE;                    // the estimator the context was last told (FScene::SetEstimator)
 	mutable int uploadedLights = JP_LIGHTS_ALL, ctxLights = JP_LIGHTS_ALL;   // FScene::lightSampling of the uploaded scene; the mode the context was last told
 	mutable unsigned long long uploadedEnv = 0, ctxEnv = 0; mutable int uploadedEnvUp = 0, ctxEnvUp = 0, uploadedEnvImp = 0, ctxEnvImp = 0;   // FEnvironmentMap::id (0: none), up axis and importance: of the uploaded scene; last sent to the context
+	mutable bool ctxNormals = false;                                // the context holds vertex normals of an earlier upload (jp_set_vertex_normals)
 	mutable int lastStatus = 0;
 	mutable JpCounters counters;
 protected:

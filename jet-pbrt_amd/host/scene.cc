@@ -97,14 +97,16 @@ FDisk::FDisk(const FPoint3& pos, const FVector3& nrm, Float r) : position(pos), 
 }
 
 // ---- OBJ ingest: own reader, the reference's vertex transform (shape.cc:23-68) ------------------------------
-bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangle>>& out, bool flip_normal, bool bFlipHandedness, const FVector3& offset, Float inScale)
+bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangle>>& out, bool flip_normal, bool bFlipHandedness, const FVector3& offset, Float inScale, const FSmoothing& smoothing)
 {
 	out.clear();
 	std::ifstream file(filename);
 	if (!file.is_open()) { fprintf(stderr, "load triangle mesh failed. %s\n", filename); return false; }
 	std::vector<FVector3> pos;
 	std::vector<FPoint2> tex;
-	std::vector<int> face, faceT;                                        // position / texture coordinate index per face vertex (-1: none)
+	std::vector<FVector3> nrm;
+	std::vector<int> face, faceT, faceN;                                 // position / texture coordinate / normal index per face vertex (-1: none)
+	std::vector<int> corner;                                             // OBJ position index of every corner of `out` (FSmoothing::kAngle)
 	std::string line;
 	auto xform = [&](FVector3 v) {
 		if (bFlipHandedness) v.z = -v.z;
@@ -128,9 +130,15 @@ bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangl
 			float u = strtof(p, &e); p = e; float v = strtof(p, &e);
 			tex.push_back(FPoint2(u, v));
 		}
+		else if (s[0] == 'v' && s[1] == 'n' && (s[2] == ' ' || s[2] == '\t'))
+		{
+			char* e = nullptr; const char* p = s + 2;
+			float x = strtof(p, &e); p = e; float y = strtof(p, &e); p = e; float z = strtof(p, &e);
+			nrm.push_back(FVector3(x, y, bFlipHandedness ? -z : z));          // mirrored like the positions
+		}
 		else if (s[0] == 'f' && (s[1] == ' ' || s[1] == '\t'))
 		{
-			face.clear(); faceT.clear();
+			face.clear(); faceT.clear(); faceN.clear();
 			const char* p = s + 1;
 			for (;;)
 			{
@@ -154,14 +162,83 @@ bool LoadTriangleMesh(const char* filename, std::vector<std::shared_ptr<FTriangl
 					}
 				}
 				faceT.push_back(ti);
-				while (*p && *p != ' ' && *p != '\t') p++;                    // skip the rest of the vertex (/vn)
+				int ni = -1;
+				if (*p == '/')
+				{   // v/vt/vn or v//vn: the field after the second slash
+					const char* q = p + 1;
+					while (*q && *q != '/' && *q != ' ' && *q != '\t') q++;
+					if (*q == '/')
+					{
+						long t = strtol(q + 1, &e, 10);
+						if (e != q + 1)
+						{
+							if (t < 0) t = (long)nrm.size() + t + 1;
+							if (t < 1 || t > (long)nrm.size()) { fprintf(stderr, "load triangle mesh failed. %s: normal index out of range\n", filename); out.clear(); return false; }
+							ni = (int)t - 1;
+						}
+					}
+				}
+				faceN.push_back(ni);
+				while (*p && *p != ' ' && *p != '\t') p++;                    // on to the next vertex
 			}
 			auto uv = [&](size_t k) { return faceT[k] >= 0 ? tex[faceT[k]] : FPoint2(0, 0); };   // untransformed
 			for (size_t k = 1; k + 1 < face.size(); k++)                      // triangles as given; polygons as a fan
 			{
 				FVector3 v0 = xform(pos[face[0]]), v1 = xform(pos[face[k]]), v2 = xform(pos[face[k + 1]]);
 				out.push_back(std::make_shared<FTriangle>(v0, v1, v2, uv(0), uv(k), uv(k + 1), flip_normal));
+				corner.push_back(face[0]); corner.push_back(face[k]); corner.push_back(face[k + 1]);
+				if (smoothing.mode == FSmoothing::kFile && faceN[0] >= 0 && faceN[k] >= 0 && faceN[k + 1] >= 0)
+				{   // the file's normals, unit length; a face with a normal of length 0 (or none) stays flat
+					const FVector3 a = nrm[faceN[0]], b = nrm[faceN[k]], c = nrm[faceN[k + 1]];
+					if (a.Length() > 0 && b.Length() > 0 && c.Length() > 0)
+					{
+						const Float sg = flip_normal ? (Float)-1 : (Float)1;
+						out.back()->SetVertexNormals(Normalize(a) * sg, Normalize(b) * sg, Normalize(c) * sg);
+					}
+				}
 			}
+		}
+	}
+	if (smoothing.mode == FSmoothing::kAngle && !out.empty())
+	{   // computed normals: per corner the angle-weighted sum of the facet normals around its vertex that lie within the crease angle of the corner's own
+		const double cosA = std::cos((double)smoothing.angle * 3.14159265358979323846 / 180.0);
+		struct D3 { double x, y, z; };
+		auto sub = [](const FVector3& a, const FVector3& b) { D3 r = { (double)a.x - b.x, (double)a.y - b.y, (double)a.z - b.z }; return r; };
+		auto dot = [](const D3& a, const D3& b) { return a.x * b.x + a.y * b.y + a.z * b.z; };
+		const size_t nt = out.size();
+		std::vector<double> ang(3 * nt);
+		std::vector<std::vector<int>> users(pos.size());                  // corners (3 * triangle + k) at every position index, in face order
+		for (size_t t = 0; t < nt; t++)
+		{
+			const FVector3 P[3] = { out[t]->p0, out[t]->p1, out[t]->p2 };
+			for (int k = 0; k < 3; k++)
+			{
+				const D3 a = sub(P[(k + 1) % 3], P[k]), b = sub(P[(k + 2) % 3], P[k]);
+				const double la = std::sqrt(dot(a, a)), lb = std::sqrt(dot(b, b));
+				double c = la > 0 && lb > 0 ? dot(a, b) / (la * lb) : 1.0;
+				c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);
+				ang[3 * t + k] = std::acos(c);
+				users[corner[3 * t + k]].push_back((int)(3 * t + k));
+			}
+		}
+		for (size_t t = 0; t < nt; t++)
+		{
+			const D3 ngT = { out[t]->normal.x, out[t]->normal.y, out[t]->normal.z };
+			FNormal3 n[3];
+			for (int k = 0; k < 3; k++)
+			{
+				D3 s = { 0, 0, 0 };
+				for (int cu : users[corner[3 * t + k]])
+				{
+					const size_t u = (size_t)cu / 3;
+					const D3 ngU = { out[u]->normal.x, out[u]->normal.y, out[u]->normal.z };
+					if (u != t && !(dot(ngT, ngU) >= cosA)) continue;
+					s.x += ang[cu] * ngU.x; s.y += ang[cu] * ngU.y; s.z += ang[cu] * ngU.z;
+				}
+				const double l = std::sqrt(dot(s, s));
+				n[k] = l > 0 ? FNormal3((Float)(s.x / l), (Float)(s.y / l), (Float)(s.z / l)) : out[t]->normal;
+			}
+			out[t]->SetVertexNormals(n[0], n[1], n[2]);
 		}
 	}
 	return true;
@@ -225,11 +302,11 @@ void FDirectionLight::Preprocess(const FScene& scene)                    // ligh
 }
 
 // ---- scene (scene.cc) -------------------------------------------------------------------------------------------
-std::vector<std::shared_ptr<FShape>> FScene::CreateTriangleMesh(const char* filename, bool flip_normal, bool bFlipHandedness, const FVector3& offset, Float inScale)
+std::vector<std::shared_ptr<FShape>> FScene::CreateTriangleMesh(const char* filename, bool flip_normal, bool bFlipHandedness, const FVector3& offset, Float inScale, const FSmoothing& smoothing)
 {
 	std::vector<std::shared_ptr<FTriangle>> mesh;
 	std::vector<std::shared_ptr<FShape>> newshapes;
-	if (LoadTriangleMesh(filename, mesh, flip_normal, bFlipHandedness, offset, inScale))
+	if (LoadTriangleMesh(filename, mesh, flip_normal, bFlipHandedness, offset, inScale, smoothing))
 		for (auto& t : mesh) { shapes.push_back(t); newshapes.push_back(t); }
 	return newshapes;
 }
@@ -343,7 +420,10 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 		{
 			int kind = P.shape->Kind(), idx = 0;
 			if (kind == JP_SHAPE_TRIANGLE) { const FTriangle* t = static_cast<const FTriangle*>(P.shape); idx = (int)out.tri_p0.size() / 3; push3(out.tri_p0, t->p0); push3(out.tri_p1, t->p1); push3(out.tri_p2, t->p2); push3(out.tri_n, t->normal);
-			                                   const float uv[6] = { t->uv0.x, t->uv0.y, t->uv1.x, t->uv1.y, t->uv2.x, t->uv2.y }; out.tri_uv.insert(out.tri_uv.end(), uv, uv + 6); }
+			                                   const float uv[6] = { t->uv0.x, t->uv0.y, t->uv1.x, t->uv1.y, t->uv2.x, t->uv2.y }; out.tri_uv.insert(out.tri_uv.end(), uv, uv + 6);
+			                                   float vn[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+			                                   if (t->smooth) { const float w[9] = { t->n0.x, t->n0.y, t->n0.z, t->n1.x, t->n1.y, t->n1.z, t->n2.x, t->n2.y, t->n2.z }; std::memcpy(vn, w, sizeof(vn)); out.n_smooth++; }
+			                                   out.tri_vn.insert(out.tri_vn.end(), vn, vn + 9); }
 			else if (kind == JP_SHAPE_RECTANGLE) { const FRectangle* r = static_cast<const FRectangle*>(P.shape); idx = (int)out.rect_p0.size() / 3; push3(out.rect_p0, r->p0); push3(out.rect_p1, r->p1); push3(out.rect_p2, r->p2); push3(out.rect_p3, r->p3); push3(out.rect_n, r->normal); }
 			else if (kind == JP_SHAPE_DISK) { const FDisk* k = static_cast<const FDisk*>(P.shape); idx = (int)out.disk_radius.size(); push3(out.disk_center, k->position); push3(out.disk_normal, k->normal); out.disk_radius.push_back(k->radius); }
 			else { const FSphere* s = static_cast<const FSphere*>(P.shape); idx = (int)out.sph_radius.size(); push3(out.sph_center, s->center); out.sph_radius.push_back(s->radius); }
@@ -406,6 +486,7 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 	t.tex_offset = out.tex_offset.data(); t.n_texel_bytes = (int64_t)out.texels.size(); t.texels = out.texels.data();
 	t.n_materials = v.n_materials; t.mat_texture = out.mat_texture.data();
 	t.n_triangles = v.n_triangles; t.tri_uv = out.tri_uv.data();
+	out.normals.struct_bytes = (int32_t)sizeof(JpVertexNormals); out.normals.n_triangles = v.n_triangles; out.normals.tri_vn = out.tri_vn.data();
 	return true;
 }
 

@@ -31,12 +31,16 @@ def asset_dir():
     return d
 
 
-def write_obj(path, verts, faces, uvs=None):
-    """verts (n,3) float32, faces (m,3) int 0-based -> triangulated single-mesh OBJ; uvs (n,2): `vt` per vertex, faces v/vt."""
+def write_obj(path, verts, faces, uvs=None, normals=None):
+    """verts (n,3) float32, faces (m,3) int 0-based -> triangulated single-mesh OBJ; uvs (n,2): `vt` per vertex, faces v/vt; normals (n,3): `vn` per
+    vertex, faces v//vn (not together with uvs)."""
     verts = np.asarray(verts, np.float32)
     lines = ["o mesh"]
     lines += ["v %.9g %.9g %.9g" % (float(v[0]), float(v[1]), float(v[2])) for v in verts]
-    if uvs is None:
+    if normals is not None:
+        lines += ["vn %.9g %.9g %.9g" % (float(v[0]), float(v[1]), float(v[2])) for v in np.asarray(normals, np.float32)]
+        lines += ["f %d//%d %d//%d %d//%d" % (f[0] + 1, f[0] + 1, f[1] + 1, f[1] + 1, f[2] + 1, f[2] + 1) for f in np.asarray(faces)]
+    elif uvs is None:
         lines += ["f %d %d %d" % (f[0] + 1, f[1] + 1, f[2] + 1) for f in np.asarray(faces)]
     else:
         lines += ["vt %.9g %.9g" % (float(t[0]), float(t[1])) for t in np.asarray(uvs, np.float32)]
@@ -247,9 +251,13 @@ class HostBackend:
     def mat_metal(self, eta, k, ur, vr, remap=False):
         a, _a = _fa(eta); b, _b = _fa(k); return self._f("mat_metal")(self.h, a, b, C.c_float(ur), C.c_float(vr), int(remap))
 
-    def mesh(self, path, flip_normal, flip_hand, offset=(0, 0, 0), scale=1.0, mat=-1, radiance=None):
+    def mesh(self, path, flip_normal, flip_hand, offset=(0, 0, 0), scale=1.0, mat=-1, radiance=None, smooth=None):
+        """smooth (host backend only): None flat (as ever, even when the file has vn), "file" the file's vn, a number: normals computed with that crease angle in degrees"""
         o, _o = _fa(offset)
         r, _r = _fa(radiance) if radiance is not None else (None, None)
+        if smooth is not None:
+            mode, angle = (1, 0.0) if smooth == "file" else (2, float(smooth))
+            return self._f("scene_mesh_smooth")(self.h, path.encode(), int(flip_normal), int(flip_hand), o, C.c_float(scale), mat, r, mode, C.c_float(angle))
         return self._f("scene_mesh")(self.h, path.encode(), int(flip_normal), int(flip_hand), o, C.c_float(scale), mat, r)
 
     def rect(self, axis, a0, a1, b0, b1, c, flip=False, mat=-1, radiance=None):
@@ -304,6 +312,11 @@ class HostBackend:
             st = self._f("scene_envmap")(self.h, a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0], ENV_UP_AXES[up_axis], importance)
         if st != 0:
             raise RuntimeError("envmap failed: %s" % self.L.jp_host_last_error(self.h).decode())
+
+    def flatten_normals(self):
+        """the scene's vertex normals as a JpVertexNormals for Context.set_vertex_normals (None: no smooth triangle); valid until the next preprocess"""
+        p = self.L.jp_host_flatten_normals(self.h)
+        return p.contents if p else None
 
     def flatten_envmap(self):
         """the scene's map as a JpEnvMap pointer for Context.set_environment_map (None: no map); valid until the map changes"""
@@ -484,8 +497,8 @@ def lamp_66(be, m):
     lamp_mesh(8, 4, (12.0, 11.0, 9.0), (200.0, 360.0, 240.0, 320.0, 548.7), warp=0.6)(be, m)
 
 
-def build_bunny(be, width, height, n_lon=187, n_lat=188, instances=4, obj_path=None):
-    """create_bunny_scene main.cc:64-111 with the procedural stand-in mesh (4 instances as in the reference)."""
+def build_bunny(be, width, height, n_lon=187, n_lat=188, instances=4, obj_path=None, smooth=None):
+    """create_bunny_scene main.cc:64-111 with the procedural stand-in mesh (4 instances as in the reference); smooth: HostBackend.mesh's (host backend only)."""
     lookfrom = np.array([-300, 300, -300], np.float32); lookat = np.array([0, 0, 0], np.float32)
     be.camera(lookfrom, _normalize(lookat - lookfrom), (0, 1, 0), 60.0, width, height)
     be.envlight((0.1, 0.1, 0.5))
@@ -503,7 +516,10 @@ def build_bunny(be, width, height, n_lon=187, n_lat=188, instances=4, obj_path=N
             lambda: be.mat_glass(1.5, (0.98, 0.98, 0.98), (0.98, 0.98, 0.98))]
     offsets = [(0, 0, 0), (-100, 0, -100), (0, 0, -100), (-100, 0, 0)]
     for i in range(instances):
-        be.mesh(obj, True, True, offsets[i], 500.0, mats[i](), None)
+        if smooth is None:
+            be.mesh(obj, True, True, offsets[i], 500.0, mats[i](), None)
+        else:
+            be.mesh(obj, True, True, offsets[i], 500.0, mats[i](), None, smooth=smooth)
     be.preprocess()
     return be
 
