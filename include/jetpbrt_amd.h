@@ -504,6 +504,40 @@ int  jp_shading_normal(JpContext* ctx, int32_t n, const float* origin, const flo
 int  jp_interpolate_normals(int32_t n, const float* p0, const float* p1, const float* p2, const float* ng, const float* vn9, const float* p, float* ns_out);
 int  jp_check_vertex_normals(const JpVertexNormals* normals, int32_t* n_smooth);
 
+/* Lens (additive to ABI 7; INTEGRATION.md "Lens" has the definition).  The reference's camera is a pinhole: every camera ray starts at JpCamera.pos.  A lens of
+ * radius > 0 gives depth of field: the camera ray of a sample starts at a point of the aperture -- a disk (blades 0) or a regular polygon of 3 .. 16 blades with
+ * circumradius `radius`, its first vertex rotation_deg from the camera's right axis toward its up axis -- and passes through the point where the pinhole ray meets
+ * the plane of focus, the set pos + focus_distance * d0 with d0 = front + right * a + up * b the pinhole's direction before normalisation (a plane at depth
+ * focus_distance * |front| along front when right and up are perpendicular to front).  Rays are weighted uniformly, like the pinhole's.  Draws: dims 0, 1 the
+ * film position as ever, dims 2, 3 the lens, the path's first bounce starts at dim 4 (without a lens: 2).  JP_SAMPLER_DEBUG draws (0.5, 0.5): the centre of the
+ * disk -- the pinhole's rays from origin pos -- and for a polygon the point the formula gives: the centre again for an even number of blades (w = 0), and
+ * v[(n-1)/2] * b + v[(n+1)/2] * b with b = 0.5f * sqrtf(0.5f) for an odd one, a point on the axis of the middle blade, not the centre.  Render-time state like the estimator: read by the next jp_render* /
+ * jp_render_guides* (sample s of the guides stays the camera ray of sample s of the render), so one upload serves every lens; NULL or radius 0: the pinhole,
+ * the kernels and films of a context that never heard of a lens.  Every integrator, every combination of the additive features; JpOptions.fused falls back to the
+ * per-bounce launches.  Reference semantics 1 and 2 are allowed: lens rays do not start at the camera position, so the certified walk treats them like
+ * secondary rays (the wider distance-cull slack, the verbatim walk behind it).  The lens owns no device memory. */
+typedef struct JpLens { int32_t struct_bytes; float radius, focus_distance; int32_t blades; float rotation_deg; } JpLens;
+/* validates (jp_check_lens: JP_ERR_INVALID_ARGUMENT with a message, the lens in force stays): radius finite and >= 0; focus_distance finite and > 0 whenever
+ * radius > 0; blades 0 or 3 .. 16; rotation_deg finite */
+int  jp_set_lens(JpContext* ctx, const JpLens* lens);
+typedef struct JpLensInfo { int32_t struct_bytes; float radius, focus_distance; int32_t blades; float rotation_deg; int32_t lens_last_render; } JpLensInfo;   /* the lens in force (all 0: the pinhole); the last jp_render* ran k_raygen<true> / the lens branch of k_other */
+int  jp_get_lens_info(JpContext* ctx, JpLensInfo* out);
+/* pure host code, no GPU needed: the validation of jp_set_lens with its status and message */
+int  jp_check_lens(const JpLens* lens);
+/* pure host code: the JpLensPlan (include/jp_lens.h) the kernels receive by value for `lens` on `camera`.  plan_out NULL: *bytes receives its size and nothing is
+ * copied; capacity smaller than the plan: JP_ERR_INVALID_ARGUMENT.  lens NULL or radius 0: JP_OK and 0 bytes (no plan: the pinhole). */
+int  jp_lens_plan(const JpCamera* camera, const JpLens* lens, void* plan_out, int64_t capacity, int64_t* bytes);
+/* pure host code: the very function the device runs (include/jp_lens.h) for n samples: fxfy 2n floats (the film position: pixel + draws 0, 1), u 2n floats (draws
+ * 2, 3) -> origin, dir 3n floats each.  lens NULL or radius 0: the pinhole's rays (u may then be NULL). */
+int  jp_lens_rays(const JpCamera* camera, const JpLens* lens, int32_t n, const float* fxfy, const float* u, float* origin, float* dir);
+/* test hook like jp_trace: what k_raygen forms for sample s[i] of pixel (x[i], y[i]) (0 <= x < width, 0 <= y < height, s >= 0) under params' seed and sampler_mode
+ * (width and height bound x and y; its other fields are not read) and the lens in force, on the uploaded scene's camera: origin, dir 3n floats each, dim_next n values -- the dimension the path's
+ * first bounce draws from (4 with a lens, 2 without).  Any output pointer may be NULL. */
+int  jp_camera_rays(JpContext* ctx, const JpRenderParams* params, int32_t n, const int32_t* x, const int32_t* y, const int32_t* s, float* origin, float* dir, int32_t* dim_next);
+/* autofocus: the pinhole ray through the film position (fx, fy) (pixels, fractional) of the uploaded scene's camera, along the walk jp_trace takes (tmin 0.001, no
+ * far end): *focus_out = t / |d0|, the focus_distance that puts the hit on the plane of focus; a miss: JP_OK and 0 */
+int  jp_focus_distance(JpContext* ctx, float fx, float fy, float* focus_out);
+
 /* What jp_upload_scene would do with `scene` (additive to ABI 7; INTEGRATION.md "Describing an upload"): the scalars of the plan every later launch
  * reads, and for each table the host builds the byte count and the 64-bit FNV-1a of exactly the bytes the upload copies to the device.  Pure host code, no GPU
  * needed: the same validation (same status codes and jp_last_error texts), table builders and plan function the upload runs, nothing decided twice.

@@ -198,6 +198,75 @@ def interpolate_normals(p0, p1, p2, ng, vn9, p):
     return out
 
 
+class JpLens(C.Structure):
+    """include/jetpbrt_amd.h: JpLens (jp_set_lens); struct_bytes = sizeof(JpLens)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("radius", C.c_float), ("focus_distance", C.c_float), ("blades", C.c_int32), ("rotation_deg", C.c_float)]
+
+
+class JpLensInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("radius", C.c_float), ("focus_distance", C.c_float), ("blades", C.c_int32), ("rotation_deg", C.c_float),
+                ("lens_last_render", C.c_int32)]
+
+
+JP_LENS_MAX_BLADES = 16
+
+
+class JpLensPlan(C.Structure):
+    """include/jp_lens.h: JpLensPlan, what the kernels receive by value (jp_lens_plan)"""
+    _fields_ = [("radius", C.c_float), ("focus", C.c_float), ("n_verts", C.c_int32), ("ex", C.c_float * 3), ("ey", C.c_float * 3),
+                ("v", (C.c_float * 2) * (JP_LENS_MAX_BLADES + 1))]
+
+
+def lens(radius, focus_distance=1.0, blades=0, rotation_deg=0.0):
+    """A JpLens (or pass one through)"""
+    return radius if isinstance(radius, JpLens) else JpLens(C.sizeof(JpLens), radius, focus_distance, blades, rotation_deg)
+
+
+def _lens_ptr(l):
+    return None if l is None else C.byref(l)
+
+
+def check_lens(l):
+    """jp_check_lens: the validation of jp_set_lens (pure host code, no GPU); raises JetPbrtError with its message.  l: a JpLens or None"""
+    L = hip_lib()
+    st = L.jp_check_lens(_lens_ptr(l))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+
+
+def lens_plan(camera, l):
+    """jp_lens_plan: the JpLensPlan of lens `l` (a JpLens or None) on a JpCamera (pure host code, no GPU) -> JpLensPlan, or None for the pinhole"""
+    L = hip_lib()
+    n = C.c_int64(0)
+    plan = JpLensPlan()
+    st = L.jp_lens_plan(C.byref(camera), _lens_ptr(l), C.byref(plan), C.sizeof(plan), C.byref(n))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    if n.value == 0:
+        return None
+    if n.value != C.sizeof(plan):
+        raise JetPbrtError("jp_lens_plan: the library's JpLensPlan has %d bytes, this binding's %d" % (n.value, C.sizeof(plan)))
+    return plan
+
+
+def lens_rays(camera, l, fxfy, u=None):
+    """jp_lens_rays: the camera rays the device forms (include/jp_lens.h) for film positions fxfy (n, 2) and lens draws u (n, 2) through lens `l`
+    (a JpLens, or None for the pinhole) -> (origin (n, 3), dir (n, 3)) float32.  Pure host code."""
+    import numpy as np
+    f = np.ascontiguousarray(fxfy, np.float32).reshape(-1, 2)
+    n = f.shape[0]
+    uu = None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+    if uu is not None and uu.shape[0] != n:
+        raise JetPbrtError("lens_rays: fxfy and u differ in length")
+    o = np.zeros((n, 3), np.float32); d = np.zeros((n, 3), np.float32)
+    q = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    st = L.jp_lens_rays(C.byref(camera), _lens_ptr(l), n, q(f), q(uu), q(o), q(d))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    return o, d
+
+
 def env_map(rgb, up_axis=JP_ENV_UP_Z, importance=0):
     """A JpEnvMap over an (H, W, 3) float32 array, top row first (kept alive on the returned object as ._keep)"""
     import numpy as np
@@ -423,6 +492,9 @@ def host_lib():
         L.jp_host_render_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.jp_host_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         L.jp_host_scene_set_estimator.argtypes = [C.c_void_p, C.c_int]
+        L.jp_host_scene_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float]
+        L.jp_host_last_focus.restype = C.c_float
+        L.jp_host_last_focus.argtypes = [C.c_void_p]
         L.jp_host_scene_envmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.jp_host_scene_envmap_file.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         L.jp_host_scene_mesh_smooth.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, _fp, C.c_int, C.c_float]
@@ -490,6 +562,13 @@ def hip_lib():
         L.jp_shading_normal.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
         L.jp_interpolate_normals.argtypes = [C.c_int32] + [C.c_void_p] * 7
         L.jp_check_vertex_normals.argtypes = [C.POINTER(JpVertexNormals), C.POINTER(C.c_int32)]
+        L.jp_set_lens.argtypes = [C.c_void_p, C.POINTER(JpLens)]
+        L.jp_get_lens_info.argtypes = [C.c_void_p, C.POINTER(JpLensInfo)]
+        L.jp_check_lens.argtypes = [C.POINTER(JpLens)]
+        L.jp_lens_plan.argtypes = [C.POINTER(JpCamera), C.POINTER(JpLens), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.jp_lens_rays.argtypes = [C.POINTER(JpCamera), C.POINTER(JpLens), C.c_int32] + [C.c_void_p] * 4
+        L.jp_camera_rays.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32] + [C.c_void_p] * 6
+        L.jp_focus_distance.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_float)]
         _hip = L
     return _hip
 
@@ -706,6 +785,39 @@ class Context:
         p = lambda x: x.ctypes.data_as(C.c_void_p)
         self._check(self.lib.jp_env_sample(self.h, n, p(a), p(idx), p(wi), p(Li), p(pdf)))
         return idx, wi, Li, pdf
+
+    def set_lens(self, radius=None, focus_distance=1.0, blades=0, rotation_deg=0.0):
+        """jp_set_lens for the next render / guides: a radius (with focus_distance, blades 0 = disk or 3 .. 16, rotation_deg), a JpLens, or None for the pinhole"""
+        if radius is None:
+            self._check(self.lib.jp_set_lens(self.h, None))
+            return
+        l = lens(radius, focus_distance, blades, rotation_deg)
+        self._check(self.lib.jp_set_lens(self.h, C.byref(l)))
+
+    def lens_info(self):
+        i = JpLensInfo()
+        i.struct_bytes = C.sizeof(JpLensInfo)
+        self._check(self.lib.jp_get_lens_info(self.h, C.byref(i)))
+        return i
+
+    def camera_rays(self, params, x, y, s):
+        """jp_camera_rays: what k_raygen forms for sample s[i] of pixel (x[i], y[i]) under params' seed / sampler_mode and the lens in force ->
+        (origin (n, 3) float32, dir (n, 3) float32, dim_next (n,) int32)"""
+        import numpy as np
+        xs = np.ascontiguousarray(x, np.int32).reshape(-1); ys = np.ascontiguousarray(y, np.int32).reshape(-1); ss = np.ascontiguousarray(s, np.int32).reshape(-1)
+        n = xs.shape[0]
+        if ys.shape[0] != n or ss.shape[0] != n:
+            raise JetPbrtError("camera_rays: x, y and s differ in length")
+        o = np.zeros((n, 3), np.float32); d = np.zeros((n, 3), np.float32); k = np.zeros(n, np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_camera_rays(self.h, C.byref(params), n, p(xs), p(ys), p(ss), p(o), p(d), p(k)))
+        return o, d, k
+
+    def focus_distance(self, fx, fy):
+        """jp_focus_distance: the focus_distance that puts what the pinhole ray through film position (fx, fy) hits on the plane of focus; 0.0 on a miss"""
+        f = C.c_float(0.0)
+        self._check(self.lib.jp_focus_distance(self.h, fx, fy, C.byref(f)))
+        return f.value
 
     def set_vertex_normals(self, tri_vn):
         """jp_set_vertex_normals for the next upload: an (n_triangles, 9) float32 array (nine zeros: a flat triangle), a JpVertexNormals, or None for none"""

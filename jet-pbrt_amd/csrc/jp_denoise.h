@@ -18,15 +18,13 @@ struct GuideConst
 };
 
 // kSmooth (k_guides_smooth, scenes with vertex normals; jp_normals.h): the normal of a hit on a smooth triangle is the shading normal Ns the render uses there
-template <int kMode, bool kSmooth>
-__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv)
+// kLens (k_guides_lens, k_guides_smooth_lens; jp_set_lens in force): the lens ray of the sample, draws 2 and 3 of its key -- instances of their own, so the pinhole's
+// kernels keep their registers and their instruction streams
+template <int kMode, bool kSmooth, bool kLens>
+__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp)
 {
 	SceneAccess<kMode> acc(sc, depth);
 	const int npix = gc.width * gc.height;
-	const V3 front = mk(sc.cam.front[0], sc.cam.front[1], sc.cam.front[2]);
-	const V3 right = mk(sc.cam.right[0], sc.cam.right[1], sc.cam.right[2]);
-	const V3 up = mk(sc.cam.up[0], sc.cam.up[1], sc.cam.up[2]);
-	const V3 ro = mk(sc.cam.pos[0], sc.cam.pos[1], sc.cam.pos[2]);
 	const float inv = 1.0f / (float)gc.spp;
 	for (int pix = blockIdx.x * JP_BLOCK + threadIdx.x; pix < npix; pix += gridDim.x * JP_BLOCK)
 	{
@@ -38,8 +36,9 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 			{
 				const uint32_t key = jp_rng_key(gc.seed, (uint32_t)x, (uint32_t)y, (uint32_t)s);
 				const float fx = (float)x + (gc.sampler_debug ? 0.5f : jp_rng_float(key, 0)), fy = (float)y + (gc.sampler_debug ? 0.5f : jp_rng_float(key, 1));
-				V3 rd = front + right * (fx / sc.cam.res_x - 0.5f) + up * (0.5f - fy / sc.cam.res_y);   // k_raygen's expression
-				rd = normalize(rd);
+				V3 ro, rd;                                                                          // k_raygen's ray
+				if constexpr (kLens) camera_ray<true>(sc.cam, lp, fx, fy, gc.sampler_debug ? 0.5f : jp_rng_float(key, 2), gc.sampler_debug ? 0.5f : jp_rng_float(key, 3), ro, rd);
+				else camera_ray<false>(sc.cam, nullptr, fx, fy, 0.f, 0.f, ro, rd);
 				float tmax = JP_INF;
 				const int h = acc.template trace<false>(sc, ro, rd, 0.001f, tmax);
 				V3 a = splat(1), n = splat(0); float t = 0.f;
@@ -75,12 +74,22 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 template <int kMode>
 __global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist)
 {
-	guides_body<kMode, false>(sc, tv, depth, gc, albedo, normal, dist, NormView());
+	guides_body<kMode, false, false>(sc, tv, depth, gc, albedo, normal, dist, NormView(), nullptr);
 }
 template <int kMode>
 __global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv)
 {
-	guides_body<kMode, true>(sc, tv, depth, gc, albedo, normal, dist, nv);
+	guides_body<kMode, true, false>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr);
+}
+template <int kMode>
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, JpLensPlan lp)
+{
+	guides_body<kMode, false, true>(sc, tv, depth, gc, albedo, normal, dist, NormView(), &lp);
+}
+template <int kMode>
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, JpLensPlan lp)
+{
+	guides_body<kMode, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -166,8 +175,10 @@ namespace
 
 typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*);
 typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView);
-struct GuideLaunch { GuideKernel k; size_t lds; int depth; GuideSmoothKernel smooth; };      // smooth: the twin a scene with vertex normals runs
-template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth, k_guides_smooth<M> }; return g; }
+typedef void (*GuideLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, JpLensPlan);
+typedef void (*GuideSmoothLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, JpLensPlan);
+struct GuideLaunch { GuideKernel k; size_t lds; int depth; GuideSmoothKernel smooth; GuideLensKernel lens; GuideSmoothLensKernel smooth_lens; };   // smooth: the twin a scene with vertex normals runs; lens: the twins of jp_set_lens
+template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth, k_guides_smooth<M>, k_guides_lens<M>, k_guides_smooth_lens<M> }; return g; }
 // the walk trace_kernel(p, 0) gives jp_surface
 GuideLaunch guide_kernel(const ScenePlan& p)
 {
@@ -205,8 +216,15 @@ int guides_launch(JpContext* c, const GuideConst& gc, float* albedo, float* norm
 	const GuideLaunch gk = guide_kernel(c->plan);
 	const int npix = gc.width * gc.height;
 	const int grid = std::min(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK);
+	JpLensPlan lp;
+	if (const int e = lens_plan_of(c, lp); e != JP_OK) return e;
 	HIP_TRY(hipEventRecord(c->gd_ev[0], c->stream));
-	if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv);
+	if (c->lens_on)
+	{   // jp_set_lens: sample s stays the camera ray of sample s of the render
+		if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, lp);
+		else hipLaunchKernelGGL(gk.lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, lp);
+	}
+	else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv);
 	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->gd_ev[1], c->stream));

@@ -24,6 +24,7 @@
 #include "jp_normals.h"          // part 1: NormView, shading_normal (the kernels and entry points: part 2, at the end)
 #include "jp_env.h"              // part 1: EnvView, env_lookup, env_sample (the kernels and entry points: part 2, at the end)
 #include "jp_mis.h"              // part 1: MisView, mis_weight, pdf_local, light_pdf (the kernels and entry points: part 2, at the end)
+#include "jp_lens.h"             // the thin-lens camera: JpLensPlan, jp_lens_ray (shared with the host; the hook kernel and the entry points: jp_lens_runtime.h, at the end)
 #include "jp_xbsdf.h"
 
 #include <cstdio>
@@ -43,7 +44,36 @@
 // Block b takes the 256-slot chunks b, b+G, b+2G, ... (an even sample of the image, so every region ages alike) and
 // writes them contiguously into region b of queue 0.
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(JP_BLOCK) k_raygen(SceneView sc, Queues q, RenderConst rc, DevCounters* cnt)
+// kLens (jp_set_lens with radius > 0; include/jp_lens.h): the thin-lens ray -- two more draws (dims 2, 3), a per-ray origin on the aperture, the path's
+// first bounce draws from dim 4.  The plan is a by-value argument of that instance only; k_raygen<false> is the pinhole's kernel, expression for expression.
+struct NoLens {};
+template <bool kLens> struct LensArg { typedef NoLens type; };
+template <> struct LensArg<true> { typedef JpLensPlan type; };
+
+// the camera ray of a film position: the lens ray of jp_lens.h, or FCamera::GenerateRay (camera.h:52-58) -- the one definition k_raygen, k_other, k_guides
+// and k_camera_rays share (u0, u1: the lens draws, read by the lens ray only)
+template <bool kLens>
+__device__ __forceinline__ void camera_ray(const JpCamera& cam, const JpLensPlan* lp, float fx, float fy, float u0, float u1, V3& o, V3& dir)
+{
+	if constexpr (kLens)
+	{
+		float oo[3], dd[3];
+		jp_lens_ray(&cam, lp, fx, fy, u0, u1, oo, dd);
+		o = mk(oo[0], oo[1], oo[2]); dir = mk(dd[0], dd[1], dd[2]);
+	}
+	else
+	{
+		const V3 front = mk(cam.front[0], cam.front[1], cam.front[2]);
+		const V3 right = mk(cam.right[0], cam.right[1], cam.right[2]);
+		const V3 up = mk(cam.up[0], cam.up[1], cam.up[2]);
+		dir = front + right * (fx / cam.res_x - 0.5f) + up * (0.5f - fy / cam.res_y);
+		dir = normalize(dir);
+		o = mk(cam.pos[0], cam.pos[1], cam.pos[2]);
+	}
+}
+
+template <bool kLens>
+__global__ void __launch_bounds__(JP_BLOCK) k_raygen(SceneView sc, Queues q, RenderConst rc, DevCounters* cnt, typename LensArg<kLens>::type lp)
 {
 	const unsigned int total = (unsigned int)rc.npix * rc.sbatch;
 	const unsigned int nchunks = (total + JP_BLOCK - 1) / JP_BLOCK;
@@ -68,13 +98,11 @@ __global__ void __launch_bounds__(JP_BLOCK) k_raygen(SceneView sc, Queues q, Ren
 			int x, y; pixel_of(rc, pix, x, y);
 			const uint32_t key = jp_rng_key(rc.seed, (uint32_t)x, (uint32_t)y, (uint32_t)s);
 			const float fx = (float)x + rngf(rc, key, 0), fy = (float)y + rngf(rc, key, 1);
-			const V3 front = mk(sc.cam.front[0], sc.cam.front[1], sc.cam.front[2]);
-			const V3 right = mk(sc.cam.right[0], sc.cam.right[1], sc.cam.right[2]);
-			const V3 up = mk(sc.cam.up[0], sc.cam.up[1], sc.cam.up[2]);
-			V3 dir = front + right * (fx / sc.cam.res_x - 0.5f) + up * (0.5f - fy / sc.cam.res_y);
-			dir = normalize(dir);
-			q.ray_o[0][i] = make_float4(sc.cam.pos[0], sc.cam.pos[1], sc.cam.pos[2], __int_as_float((int)slot));
-			q.ray_d[0][i] = make_float4(dir.x, dir.y, dir.z, __int_as_float(MK_FLAGS(0, 0, 2)));
+			V3 o, dir;
+			if constexpr (kLens) camera_ray<true>(sc.cam, &lp, fx, fy, rngf(rc, key, 2), rngf(rc, key, 3), o, dir);
+			else camera_ray<false>(sc.cam, nullptr, fx, fy, 0.f, 0.f, o, dir);
+			q.ray_o[0][i] = make_float4(o.x, o.y, o.z, __int_as_float((int)slot));
+			q.ray_d[0][i] = make_float4(dir.x, dir.y, dir.z, __int_as_float(MK_FLAGS(0, 0, kLens ? 4 : 2)));
 			q.beta[0][i] = make_float4(1.f, 1.f, 1.f, __int_as_float((int)key));
 			q.lacc[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
 		}
@@ -1062,7 +1090,7 @@ __global__ void __launch_bounds__(JP_BLOCK, (kMode == 6 ? JP_CERT_WAVES : 8)) k_
 struct WFrame { V3 L, p, N, wo, f; float absd, pdf, up; int mat, k; };
 
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_other(SceneView sc, Queues q, RenderConst rc, int kind, int depth_lds, DevCounters* cnt)
+__global__ void __launch_bounds__(JP_BLOCK) k_other(SceneView sc, Queues q, RenderConst rc, int kind, int depth_lds, DevCounters* cnt, int lens_on, JpLensPlan lp)
 {
 	SceneAccess<kMode> acc(sc, depth_lds);
 	const unsigned int total = (unsigned int)rc.npix * rc.sbatch;
@@ -1072,13 +1100,12 @@ __global__ void __launch_bounds__(JP_BLOCK) k_other(SceneView sc, Queues q, Rend
 		const int pix = slot % rc.npix, s = rc.s0 + slot / rc.npix;
 		int x, y; pixel_of(rc, pix, x, y);
 		const uint32_t key = jp_rng_key(rc.seed, (uint32_t)x, (uint32_t)y, (uint32_t)s);
-		unsigned int dim = 2;
+		unsigned int dim = lens_on ? 4 : 2;                                       // (a lens draws dims 2, 3)
 		V3 o, d;
 		{
 			const float fx = (float)x + rngf(rc, key, 0), fy = (float)y + rngf(rc, key, 1);
-			const V3 front = mk(sc.cam.front[0], sc.cam.front[1], sc.cam.front[2]), right = mk(sc.cam.right[0], sc.cam.right[1], sc.cam.right[2]), up = mk(sc.cam.up[0], sc.cam.up[1], sc.cam.up[2]);
-			o = mk(sc.cam.pos[0], sc.cam.pos[1], sc.cam.pos[2]);
-			d = normalize(front + right * (fx / sc.cam.res_x - 0.5f) + up * (0.5f - fy / sc.cam.res_y));
+			if (lens_on) camera_ray<true>(sc.cam, &lp, fx, fy, rngf(rc, key, 2), rngf(rc, key, 3), o, d);
+			else camera_ray<false>(sc.cam, nullptr, fx, fy, 0.f, 0.f, o, d);
 		}
 		V3 result = mk(0, 0, 0);
 		if (kind == JP_INTEGRATOR_DEBUG_NORMAL)
@@ -1409,3 +1436,4 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_mis.h"              // estimator, part 2: k_shade_mis*, k_light_pdf and their entry points (jp_render.h declares the selector)
 #define JP_NORMALS_RUNTIME
 #include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points (jp_render.h declares the selector)
+#include "jp_lens_runtime.h"     // thin-lens camera: k_camera_rays and the lens entry points (jp_render.h reads the context's lens state)

@@ -7,6 +7,15 @@ namespace
 {
 enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4, CLS_NORMAL = 5 };   // (CLS_NORMAL: k_normal, stamped inside its CLS_SHADE pair -- a share of shade_ms, JpNormalInfo)
 
+// the lens in force as the kernels take it (zeros while none is set: the kernels then do not read it); the camera is the uploaded scene's
+int lens_plan_of(const JpContext* c, JpLensPlan& lp)
+{
+	std::memset(&lp, 0, sizeof(lp));
+	if (!c->lens_on) return JP_OK;
+	if (jp_lens_make_plan(&c->plan.sv.cam, &c->lens, &lp) != 0) return fail(JP_ERR_INVALID_ARGUMENT, "jp_set_lens: the uploaded camera's right / up vectors have no finite positive length");
+	return JP_OK;
+}
+
 void free_queues(JpContext* c) { c->qb = QueueBufs(); c->cap = 0; c->planes_alloc = 0; c->blk_alloc = 0; }
 
 int ensure_queues(JpContext* c, unsigned int cap, int planes, unsigned int nblocks)
@@ -197,7 +206,7 @@ namespace
 {
 
 // the other two integrators' megakernel: one ray per lane, launched like the plain k_extend (plan.lds_bytes, plan.stack_depth)
-typedef void (*OtherKernel)(SceneView, Queues, RenderConst, int, int, DevCounters*);
+typedef void (*OtherKernel)(SceneView, Queues, RenderConst, int, int, DevCounters*, int, JpLensPlan);
 OtherKernel other_kernel(const ScenePlan& p) { return p.trav_mode == 5 ? k_other<5> : (p.trav_mode == 2 ? k_other<2> : (p.trav_mode == 1 ? k_other<1> : k_other<0>)); }
 
 // jp_trace / jp_surface.  JpOptions::trace_walk (tests; jp_surface passes 0): 1 the binary tree, 2 the 8-wide tree, 3 the caller's tree verbatim; else what the
@@ -302,15 +311,21 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		const ShadeEnvKernels vk = p.env ? shade_env_kernels(p) : ShadeEnvKernels{ nullptr, nullptr };
 		const ShadeMisKernels mk2 = mis ? shade_mis_kernels(p) : ShadeMisKernels{ nullptr, nullptr, nullptr, nullptr };
 		const SmoothKernels nk = smooth ? shade_smooth_kernels(p) : SmoothKernels{};
+		JpLensPlan lp;                                                 // jp_set_lens: k_raygen<true> / k_other form the lens ray; the bounces never know
+		if (const int e = lens_plan_of(c, lp); e != JP_OK) return e;
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
-			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_raygen, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt); }
+			{
+				Stamper t(c, CLS_OTHER);
+				if (c->lens_on) hipLaunchKernelGGL(k_raygen<true>, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, lp);
+				else hipLaunchKernelGGL(k_raygen<false>, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, NoLens());
+			}
 			if (rp->integrator != JP_INTEGRATOR_PATH)
 			{   // the other two integrators: one megakernel launch per batch (k_other), then the same per-pixel sum
 				Stamper t(c, CLS_OTHER);
 				const int ogrid = (int)std::min<unsigned int>((P + JP_BLOCK - 1) / JP_BLOCK, (unsigned int)(c->n_cus * 16));
-				hipLaunchKernelGGL(ok, dim3(ogrid), dim3(JP_BLOCK), p.lds_bytes, c->stream, p.sv, c->q, rc, rp->integrator, p.stack_depth, d_cnt);
+				hipLaunchKernelGGL(ok, dim3(ogrid), dim3(JP_BLOCK), p.lds_bytes, c->stream, p.sv, c->q, rc, rp->integrator, p.stack_depth, d_cnt, c->lens_on ? 1 : 0, lp);
 			}
 			int cur = 0;
 			int iters = rp->integrator != JP_INTEGRATOR_PATH ? 0 : rp->max_depth + 1;
@@ -417,6 +432,7 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 	if (!l->plan.smooth && l->nside) { hipStreamSynchronize(l->stream); l->nside.reset(); }   // (the same for the side records of k_normal)
 	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
 	l->estimator = c->estimator;                                     // ... and the estimator (its side records are its own, like its queues)
+	l->lens = c->lens; l->lens_on = c->lens_on;                      // ... and the lens
 }
 
 // ---- fused schedule: one k_path launch per batch (jp_path.h) --------------------------------------------------------------
@@ -436,6 +452,7 @@ bool fused_eligible(const JpContext* c, const JpRenderParams* rp)
 	if (c->plan.textured) return false;                                   // textures: k_texel + k_shade_tex live in the per-bounce launches
 	if (c->plan.pick) return false;                                       // JP_LIGHTS_POWER_ONE: k_shade_pick lives there too
 	if (c->plan.smooth) return false;                                     // vertex normals: k_normal + k_shade_smooth* as well
+	if (c->lens_on) return false;                                         // a lens: k_raygen<true> lives in the per-bounce launches (k_path forms the pinhole ray)
 	if (c->plan.trav_mode == 2) return c->plan.shade_prims_in_lds;
 	return c->plan.trav_mode == 0 || c->plan.trav_mode == 3 || c->plan.trav_mode == 5;
 }
@@ -566,7 +583,7 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0;
 	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
 	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
 	if (c->plan.pick && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator samples every light (scene uploaded with JP_LIGHTS_POWER_ONE)");
@@ -580,6 +597,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	c->last_mapped = c->plan.env && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_smooth = c->plan.smooth && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_lens = c->lens_on ? 1 : 0;                                    // (every integrator forms the lens ray)
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
 	// Gsamples/s).  JETPBRT_LANES = 1 .. 4 forces a count, JETPBRT_LANE_ROWS the group height.

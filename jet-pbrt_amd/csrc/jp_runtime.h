@@ -149,6 +149,9 @@ struct JpContext
 	VertexNormalsHost vnormals;
 	int vn_triangles = 0, vn_smooth = 0, last_smooth = 0; long long vn_table_bytes = 0; double normal_ms = 0.0;   // normal_ms: k_normal's launches of the last render (profiling)
 	DevBuf nside;
+	// thin-lens camera (jp_lens_runtime.h): render-time state like the estimator (jp_set_lens; a lane takes its parent's before it renders) and what the last
+	// render ran.  The plan is a kernel argument made per launch from the uploaded camera: the lens owns no device memory.
+	JpLens lens = {}; bool lens_on = false; int last_lens = 0;
 };
 // jp_pick.h / jp_env.h (included last) define the upload's table steps
 static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area);

@@ -9,6 +9,11 @@
 #pragma once
 #include "jp_device.h"
 #define JP_HD_INLINE __host__ __device__ __forceinline__
+// the concentric disk mapping lives in include/jp_lens.h (one text for the sampling warps below, the lens kernels and the host's jp_lens_rays);
+// on the device its sine / cosine is sincos_f below
+namespace jp { __device__ __forceinline__ void sincos_f(float xf, float* s, float* c); }
+#define JP_LENS_SINCOSF_DEVICE jp::sincos_f
+#include "jp_lens.h"
 
 namespace jp
 {
@@ -147,16 +152,7 @@ struct BsdfSample { V3 f, wi; float pdf; int flags; };
 // ---- sampling warps (sampling.h) ---------------------------------------------------------------------------------
 __device__ __forceinline__ void concentric_disk(float ux, float uy, float& px, float& py)   // sampling.h:25-50
 {
-	ux = ux * 2.f - 1.f; uy = uy * 2.f - 1.f;
-	if (ux == 0 && uy == 0) { px = 0; py = 0; }
-	else
-	{
-		float radius, theta;
-		if (fabsf(ux) > fabsf(uy)) { radius = ux; theta = JP_PI_OVER4 * (uy / ux); }
-		else { radius = uy; theta = JP_PI_OVER2 - JP_PI_OVER4 * (ux / uy); }
-		float st, ct; sincos_f(theta, &st, &ct);
-		px = ct * radius; py = st * radius;
-	}
+	jp_lens_concentric_disk(ux, uy, &px, &py);
 }
 __device__ __forceinline__ V3 cosine_hemisphere(float ux, float uy)                     // sampling.h:53-59
 {

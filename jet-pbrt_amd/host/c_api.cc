@@ -109,6 +109,17 @@ void jp_host_scene_set_reference_tree(void* h, int on) { ((HostScene*)h)->scene-
 void jp_host_scene_set_device_build(void* h, int on) { ((HostScene*)h)->scene->deviceBuild = on != 0; ((HostScene*)h)->scene->hostBuild = on == 0; }   // explicit either way
 void jp_host_scene_set_light_sampling(void* h, int mode) { ((HostScene*)h)->scene->SetLightSampling(mode); }   // FScene::SetLightSampling (JP_LIGHTS_*)
 void jp_host_scene_set_estimator(void* h, int mode) { ((HostScene*)h)->scene->SetEstimator(mode); }   // FScene::SetEstimator (JP_ESTIMATOR_*)
+// FCamera::SetLens / FocusAt on the scene's camera (radius 0: the pinhole again; focus_at != 0: focus on what film position (fx, fy) sees); -1 without a camera.
+// jp_host_last_focus: FCamera::LastFocus, the focus distance of the last render with a lens
+int jp_host_scene_set_lens(void* h, float radius, float focus, int blades, float rotation, int focus_at, float fx, float fy)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!hs->scene->camera) { hs->error = "jp_host_scene_set_lens: the scene has no camera"; return -1; }
+	hs->scene->camera->SetLens(radius, focus, blades, rotation);
+	if (focus_at) hs->scene->camera->FocusAt(fx, fy);
+	return 0;
+}
+float jp_host_last_focus(void* h) { HostScene* hs = (HostScene*)h; return hs->scene->camera ? hs->scene->camera->LastFocus() : 0.f; }
 // FScene::SetEnvironmentMap from memory (3 * w * hgt floats, top row first; null: no map) or from a file (FEnvironmentMap::FromFile); importance -1:
 // the A/B hook of JpEnvMap.  0, or -1 with jp_host_last_error set
 int jp_host_scene_envmap(void* h, const float* rgb, int w, int hgt, int up_axis, int importance)

@@ -1,6 +1,10 @@
 // jet-pbrt_amd/host/cli_main.cc -- the reference's command line (main.cc:113-163) on the GPU integrator:
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
 //             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
+//             [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]
+// --aperture R: a thin lens of radius R scene units instead of the pinhole (FCamera::SetLens): depth of field.  --focus D: the focus distance (the plane of focus lies D * |front|
+// along the viewing direction; default 1); --focus-pixel X Y: focus on whatever film position (X, Y) sees (FCamera::FocusAt; the distance found is echoed); --blades N: a regular
+// polygon of 3 .. 16 blades instead of a disk; --aperture-rotation DEG: turns the polygon.
 // --smooth: vertex normals for the scenes' meshes (FSmoothing; lights excepted): `file` takes the OBJ's vn, a number computes them with that crease angle in degrees.
 // --estimator mis: next-event estimation and the BSDF sample weighted against each other (FScene::SetEstimator(JP_ESTIMATOR_MIS)); implies --light-sampling power.
 // nee (default): the reference's estimator.
@@ -83,8 +87,10 @@ int main(int argc, char* argv[])
 	bool denoise = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL, estimator = JP_ESTIMATOR_NEE;
 	std::string envmap; int envUp = JP_ENV_UP_Y; float envScale = 1.f;
 	FSmoothing smoothing;
+	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
 	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
+	fprintf(stderr, "          [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -125,6 +131,11 @@ int main(int argc, char* argv[])
 			else if (e != m && *e == 0 && a >= 0.f && a <= 180.f) smoothing = FSmoothing::Angle(a);
 			else { fprintf(stderr, "--smooth must be file or an angle of 0 .. 180 degrees\n"); return 5; }
 		}
+		else if (!strcmp(argv[i], "--aperture") && i + 1 < argc) { aperture = (float)atof(argv[++i]); if (!(aperture >= 0.f) || !std::isfinite(aperture)) { fprintf(stderr, "--aperture must be a number >= 0\n"); return 5; } }
+		else if (!strcmp(argv[i], "--focus") && i + 1 < argc) { focus = (float)atof(argv[++i]); focusPixel = false; if (!(focus > 0.f) || !std::isfinite(focus)) { fprintf(stderr, "--focus must be a number > 0\n"); return 5; } }
+		else if (!strcmp(argv[i], "--focus-pixel") && i + 2 < argc) { focusX = (float)atof(argv[i + 1]); focusY = (float)atof(argv[i + 2]); i += 2; focusPixel = true; if (!std::isfinite(focusX) || !std::isfinite(focusY)) { fprintf(stderr, "--focus-pixel takes two numbers\n"); return 5; } }
+		else if (!strcmp(argv[i], "--blades") && i + 1 < argc) { blades = atoi(argv[++i]); if (blades != 0 && (blades < 3 || blades > 16)) { fprintf(stderr, "--blades must be 0 (a disk) or 3 .. 16\n"); return 5; } }
+		else if (!strcmp(argv[i], "--aperture-rotation") && i + 1 < argc) { apertureRotation = (float)atof(argv[++i]); if (!std::isfinite(apertureRotation)) { fprintf(stderr, "--aperture-rotation must be a number\n"); return 5; } }
 		else pos.push_back(argv[i]);
 	}
 	if (pos.empty()) return 0;                                    // main.cc:122-125
@@ -151,6 +162,11 @@ int main(int argc, char* argv[])
 	fprintf(stderr, "current scene: %s\n", scene->NameStr());
 	scene->SetLightSampling(estimator == JP_ESTIMATOR_MIS ? JP_LIGHTS_POWER_ONE : lightSampling);
 	scene->SetEstimator(estimator);
+	if (aperture > 0.f && scene->camera)
+	{
+		scene->camera->SetLens(aperture, focus, blades, apertureRotation);
+		if (focusPixel) scene->camera->FocusAt(focusX, focusY);
+	}
 	if (scene->primitives.empty()) { fprintf(stderr, "no geometry loaded from %s\n", assets.c_str()); return 2; }
 	std::shared_ptr<FSampler> sampler = std::make_shared<FRandomSampler>(samples_per_pixel);
 	// main.cc:154 constructs FPathIntegratorIteration(5); the commented-out alternatives of main.cc:150-153 are selectable here
@@ -163,6 +179,7 @@ int main(int argc, char* argv[])
 	if (denoise) film.RequestDenoise(guideSpp); else if (!aov.empty()) film.RequestGuides(guideSpp);
 	integrator->Render(scene.get(), sampler.get(), &film, 16);    // main.cc:156
 	if (integrator->LastStatus() != JP_OK) return 3;              // no GPU / no library: fail loudly, nothing is written
+	if (aperture > 0.f && scene->camera) fprintf(stderr, "lens: aperture %g, focus distance %g%s\n", aperture, scene->camera->LastFocus(), focusPixel ? " (found at the focus pixel)" : "");
 	char fullname[512];
 	snprintf(fullname, sizeof(fullname), "%s_%d", scene->NameStr(), samples_per_pixel);
 	const std::string name = out.empty() ? fullname : out;

@@ -32,6 +32,8 @@ struct HipApi
 	int (*set_environment_map)(JpContext*, const JpEnvMap*) = nullptr;                       // (looked up, needed by FScene::SetEnvironmentMap only)
 	int (*set_vertex_normals)(JpContext*, const JpVertexNormals*) = nullptr;                 // (looked up, needed by scenes with smooth meshes only)
 	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                          // (looked up, needed by FScene::SetEstimator only)
+	int (*set_lens)(JpContext*, const JpLens*) = nullptr;                                    // (looked up, needed by FCamera::SetLens only)
+	int (*focus_distance)(JpContext*, float, float, float*) = nullptr;                       // (looked up, needed by FCamera::FocusAt only)
 	std::string error;
 };
 
@@ -63,6 +65,8 @@ HipApi& Api()
 		api.set_environment_map = (decltype(api.set_environment_map))dlsym(api.lib, "jp_set_environment_map");
 		api.set_estimator = (decltype(api.set_estimator))dlsym(api.lib, "jp_set_estimator");
 		api.set_vertex_normals = (decltype(api.set_vertex_normals))dlsym(api.lib, "jp_set_vertex_normals");
+		api.set_lens = (decltype(api.set_lens))dlsym(api.lib, "jp_set_lens");
+		api.focus_distance = (decltype(api.focus_distance))dlsym(api.lib, "jp_focus_distance");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
 		else if (api.abi_version() != JP_ABI_VERSION)            // a stale build would be handed structs of another size (JpCounters, JpBuildInfo, JpOptions)
@@ -181,6 +185,31 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 		}
 		if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); uploaded = nullptr; return; }
 		uploaded = scene; uploadedLights = lightMode; uploadedEnv = envId; uploadedEnvUp = scene->environmentUp; uploadedEnvImp = scene->environmentImportance;
+	}
+	{   // FCamera::SetLens / FocusAt: render-time state of the context, sent when it changes; a camera that never asked for a lens makes no such call
+		const FCamera* cam = scene->Camera();
+		JpLens l; std::memset(&l, 0, sizeof(l));
+		if (cam && cam->lensRadius != 0)
+		{
+			l.struct_bytes = (int32_t)sizeof(l); l.radius = cam->lensRadius; l.focus_distance = cam->lensFocus; l.blades = cam->lensBlades; l.rotation_deg = cam->lensRotation;
+			if (cam->focusAt)
+			{   // autofocus on the uploaded scene: the pinhole ray through the film position
+				if (!api.focus_distance) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_focus_distance\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+				float f = 0.f;
+				lastStatus = api.focus_distance(ctx, cam->focusFx, cam->focusFy, &f);
+				if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+				if (!(f > 0.f)) { fprintf(stderr, "FGpuPathIntegrator::Render: FCamera::FocusAt(%g, %g): the ray through that film position hits nothing to focus on\n", cam->focusFx, cam->focusFy); lastStatus = JP_ERR_INVALID_ARGUMENT; return; }
+				l.focus_distance = f;
+			}
+			cam->lastFocus = l.focus_distance;
+		}
+		if (std::memcmp(&l, &ctxLens, sizeof(l)) != 0)
+		{
+			if (!api.set_lens) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_lens\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_lens(ctx, l.struct_bytes ? &l : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxLens = l;
+		}
 	}
 	JpRenderParams rp; std::memset(&rp, 0, sizeof(rp));
 	rp.width = film->Width(); rp.height = film->Height();

@@ -300,6 +300,16 @@ public:
 	virtual ~FCamera() {}
 	FCamera(const FVector3& ipos, const FVector3& ifront, const FVector3& iup, Float ifov, const FVector2& iresolution);
 	FVector3 pos, front, right, up; FVector2 resolution;
+	// Thin lens (INTEGRATION.md "Lens"; the reference's camera is the pinhole, radius 0): an aperture of `radius` scene units -- a disk (blades 0) or a regular polygon of
+	// 3 .. 16 blades, its first vertex `rotation` degrees from `right` toward `up` -- focused on the plane pos + focus * d0 (depth focus * |front| along front).  Render-time
+	// state: FGpuPathIntegrator::Render forwards it to jp_set_lens, no new upload.  FocusAt: the focus distance comes from jp_focus_distance at render time, after the
+	// upload -- whatever the pinhole ray through film position (fx, fy) (pixels) hits is in focus; LastFocus() then tells the distance found (a miss fails the render).
+	void SetLens(Float radius, Float focus, int blades = 0, Float rotation = 0) { lensRadius = radius; lensFocus = focus; lensBlades = blades; lensRotation = rotation; focusAt = false; }
+	void FocusAt(Float fx, Float fy) { focusAt = true; focusFx = fx; focusFy = fy; }
+	Float LastFocus() const { return lastFocus; }
+	Float lensRadius = 0, lensFocus = 1, lensRotation = 0; int lensBlades = 0;
+	bool focusAt = false; Float focusFx = 0, focusFy = 0;
+	mutable Float lastFocus = 0;                                 // the focus distance of the last render with a lens
 };
 
 enum class EImageType { PPM, BMP, HDR };                         // film.h:15-20
@@ -533,6 +543,7 @@ protected:
 	mutable int ctxEstimator = JP_ESTIMATOR_NEE;                    // the estimator the context was last told (FScene::SetEstimator)
 	mutable int uploadedLights = JP_LIGHTS_ALL, ctxLights = JP_LIGHTS_ALL;   // FScene::lightSampling of the uploaded scene; the mode the context was last told
 	mutable unsigned long long uploadedEnv = 0, ctxEnv = 0; mutable int uploadedEnvUp = 0, ctxEnvUp = 0, uploadedEnvImp = 0, ctxEnvImp = 0;   // FEnvironmentMap::id (0: none), up axis and importance: of the uploaded scene; last sent to the context
+	mutable JpLens ctxLens = {};                                    // the lens the context was last told (FCamera::SetLens; radius 0: none)
 	mutable bool ctxNormals = false;                                // the context holds vertex normals of an earlier upload (jp_set_vertex_normals)
 	mutable int lastStatus = 0;
 	mutable JpCounters counters;

@@ -296,6 +296,18 @@ class HostBackend:
         from . import ESTIMATOR_MODES
         self._f("scene_set_estimator")(self.h, ESTIMATOR_MODES[mode])
 
+    def set_lens(self, radius, focus=1.0, blades=0, rotation=0.0, focus_at=None):
+        """FCamera::SetLens on the scene's camera: a thin lens of `radius` scene units focused at distance `focus` (blades 0: a disk, 3 .. 16: a polygon turned by
+        `rotation` degrees); focus_at=(fx, fy): FCamera::FocusAt, the focus distance is found at render time from what that film position sees (last_focus() tells it).
+        radius 0: the pinhole again (host backend only; takes effect with the integrator's next render)"""
+        fx, fy = focus_at if focus_at is not None else (0.0, 0.0)
+        if self._f("scene_set_lens")(self.h, C.c_float(radius), C.c_float(focus), int(blades), C.c_float(rotation), 0 if focus_at is None else 1, C.c_float(fx), C.c_float(fy)) != 0:
+            raise RuntimeError("set_lens failed: %s" % self.L.jp_host_last_error(self.h).decode())
+
+    def last_focus(self):
+        """FCamera::LastFocus: the focus distance of the last render with a lens"""
+        return float(self.L.jp_host_last_focus(self.h))
+
     def envmap(self, rgb, up_axis="z", importance=0):
         """FScene::SetEnvironmentMap: an (H, W, 3) float32 array top row first, the path of a PFM / Radiance .hdr / binary PPM / BMP file, or None for no
         map; up_axis "z" (map space = world space) or "y"; importance -1: sample by solid angle alone, arrays only (host backend only; takes effect
