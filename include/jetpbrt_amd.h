@@ -300,6 +300,14 @@ int  jp_bsdf(JpContext* ctx, const JpBsdfDesc* desc, int32_t n, const float* nor
 int  jp_trace(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax,
               int32_t* hit, float* t, int32_t* prim, float* normal);
 
+/* test hook like jp_trace (additive to ABI 7): the any-hit query for n rays (FScene::Occluded), one ray per lane through the any-hit half of the device traversal
+ * (what the render's shadow rays run).  Host arrays as for jp_trace -> occluded (0/1), nothing else.  It walks the structure the render's shadow rays walk;
+ * JpOptions::trace_walk 1 / 2 / 3 force the binary tree, the 8-wide tree and the caller's tree verbatim exactly as for jp_trace, so both hooks can be put on
+ * one structure; reserved[0] == 1 the generic tiny-scene instance.  walk_out (may be NULL): the traversal mode that ran (0 binary tree in global memory, 1 in
+ * LDS, 2 flat leaf list, 3 8-wide tree, 4 4-wide tree, 5 caller's tree verbatim, 6 certified walk), + 16 for the flat-shape instance of mode 2. */
+int  jp_occluded(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax,
+                 int32_t* occluded, int32_t* walk_out);
+
 /* Texture-mapped materials (additive to ABI 7; INTEGRATION.md "Textures").  A material's main colour -- MATTE diffuseColor, MIRROR specularColor,
  * PLASTIC Kd (its Qd then follows the sampled Kd at every shading point, material.h:94-98) -- may come from a texture of texture.h / texture.cc,
  * sampled on the device at every bounce of the path integrator.  Textures on GLASS / METAL are refused ([0..2] is eta there).

@@ -528,6 +528,7 @@ def hip_lib():
         L.jp_get_counters.argtypes = [C.c_void_p, C.POINTER(JpCounters)]
         L.jp_get_build_info.argtypes = [C.c_void_p, C.POINTER(JpBuildInfo)]
         L.jp_trace.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
+        L.jp_occluded.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)]
         L.jp_render_rgb8.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_void_p, C.c_void_p]
         L.jp_gamma_thresholds.argtypes = [C.c_void_p]
         L.jp_bsdf.argtypes = [C.c_void_p, C.POINTER(JpBsdfDesc), C.c_int32] + [C.c_void_p] * 10
@@ -879,6 +880,18 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         self._check(self.lib.jp_trace(self.h, n, p(o), p(d), p(t0), p(t1), p(hit), p(t), p(prim), p(nrm)))
         return hit, t, prim, nrm
+
+    def occluded(self, origin, direction, tmin, tmax):
+        """jp_occluded: the any-hit query of the render's shadow rays -> (occluded int32 (n,), walk): walk is the traversal mode that ran, + 16 for the
+        flat-shape instance of the tiny-scene walk"""
+        import numpy as np
+        n = origin.shape[0]
+        o = np.ascontiguousarray(origin, np.float32); d = np.ascontiguousarray(direction, np.float32)
+        t0 = np.ascontiguousarray(tmin, np.float32); t1 = np.ascontiguousarray(tmax, np.float32)
+        occ = np.zeros(n, np.int32); walk = C.c_int32(-1)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_occluded(self.h, n, p(o), p(d), p(t0), p(t1), p(occ), C.byref(walk)))
+        return occ, int(walk.value)
 
     def bsdf(self, desc, normal, wo, wi, u):
         """jp_bsdf: FBSDF::Evalf / Pdf / Sample of a by-value BSDF on the device -> dict of arrays"""

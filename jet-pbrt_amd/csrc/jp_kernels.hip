@@ -1350,6 +1350,19 @@ __global__ void __launch_bounds__(JP_BLOCK) k_trace_flat(SceneView sc, int depth
 	}
 }
 
+// k_occluded (jp_occluded): test hook, arbitrary rays through the any-hit half of the same traversal (SceneAccess::trace<true>, what k_shadow calls): the verdict only
+template <int kMode, typename F = FeatAll>
+__global__ void __launch_bounds__(JP_BLOCK) k_occluded(SceneView sc, int depth, int n, const float* o, const float* d, const float* tmin, const float* tmax_in, int* occluded)
+{
+	SceneAccess<kMode, F> acc(sc, depth);
+	for (int i = blockIdx.x * JP_BLOCK + threadIdx.x; i < n; i += gridDim.x * JP_BLOCK)
+	{
+		const V3 ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
+		float tmax = tmax_in[i];
+		occluded[i] = acc.template trace<true>(sc, ro, rd, tmin[i], tmax) >= 0;
+	}
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // textures (jp_tex.h; DESIGN.md "Textures"): k_texel between extend and shade, k_shade_tex, and the test hook k_surface
 // ---------------------------------------------------------------------------------------------------------------------

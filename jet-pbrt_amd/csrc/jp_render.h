@@ -226,6 +226,24 @@ TraceLaunch trace_kernel(const ScenePlan& p, int tw, bool generic = true)   // g
 	return p.trav_mode == 2 ? trace_row<2>(p.lds_bytes, p.stack_depth) : (p.trav_mode == 1 ? trace_row<1>(p.lds_bytes, p.stack_depth) : trace_row<0>(p.lds_bytes, p.stack_depth));
 }
 
+// jp_occluded: the any-hit twin of k_trace, one ray per lane.  tw == 0: the structure shadow_kernel gives the render's shadow rays (the lane refill kernels drive
+// the same Walker steps); tw 1 / 2 / 3 as for trace_kernel, so that both hooks can be put on one structure.  Each row takes the grid and the LDS of k_trace's row
+// for that mode; walk: the kMode that runs, + 16 for the lean flat instance (jp_occluded's walk_out)
+typedef void (*OccludedKernel)(SceneView, int, int, const float*, const float*, const float*, const float*, int*);
+struct OccludedLaunch { OccludedKernel occluded; size_t lds; int depth; int walk; };
+template <int M> OccludedLaunch occluded_row(size_t lds, int depth) { OccludedLaunch t = { k_occluded<M>, lds, depth, M }; return t; }
+OccludedLaunch occluded_kernel(const ScenePlan& p, int tw, bool generic)
+{
+	const size_t q4lds = (size_t)p.stack_depth_q4 * JP_BLOCK * sizeof(int);
+	if (p.trav_mode == 3 && tw == 2) return occluded_row<3>(p.lds_bytes_shadow, p.stack_depth);
+	if (p.trav_mode == 5 && p.cert && q4lds <= 64 * 1024 && tw != 3) return occluded_row<6>(q4lds, p.stack_depth_q4);
+	if (p.trav_mode == 5) return occluded_row<5>(p.lds_bytes, p.stack_depth);
+	if (p.q4_shadow && q4lds <= 64 * 1024 && tw != 1) return occluded_row<4>(q4lds, p.stack_depth_q4);
+	if (p.trav_mode == 3 && tw != 1) return occluded_row<3>(p.lds_bytes_shadow, p.stack_depth);
+	if (lean_traversal(p, generic)) { OccludedLaunch t = { k_occluded<2, FeatFlat>, p.lds_bytes, p.stack_depth, 2 + 16 }; return t; }
+	return p.trav_mode == 2 ? occluded_row<2>(p.lds_bytes, p.stack_depth) : (p.trav_mode == 1 ? occluded_row<1>(p.lds_bytes, p.stack_depth) : occluded_row<0>(p.lds_bytes, p.stack_depth));
+}
+
 int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync, int lane_index = 0, int lane_count = 1, int lane_group = 4, bool ev0_recorded = false)
 {
 	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_render: no scene uploaded");
@@ -797,6 +815,28 @@ int jp_trace(JpContext* c, int32_t n, const float* origin, const float* dir, con
 	hipLaunchKernelGGL(tk.trace, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_hit, d_t, d_prim, d_n);
 	HIP_TRY(hipMemcpyAsync(hit, d_hit, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(t, d_t, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(normal, d_n, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return JP_OK;
+}
+
+int jp_occluded(JpContext* c, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, int32_t* occluded, int32_t* walk_out)
+{
+	if (!c || n < 0 || !origin || !dir || !tmin || !tmax || !occluded) return fail(JP_ERR_INVALID_ARGUMENT, "jp_occluded: null argument");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_occluded: no scene uploaded");
+	const OccludedLaunch ok = occluded_kernel(c->plan, c->opt.trace_walk, c->opt.reserved[0] == 1);
+	if (walk_out) *walk_out = ok.walk;
+	if (n == 0) return JP_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	DevBuf b_o, b_d, b_t0, b_t1, b_occ;                             // per-call scratch: freed on every return
+	float *d_o, *d_d, *d_t0, *d_t1; int* d_occ;
+	HIP_TRY(reserve(b_o, d_o, (size_t)n * 12)); HIP_TRY(reserve(b_d, d_d, (size_t)n * 12)); HIP_TRY(reserve(b_t0, d_t0, (size_t)n * 4)); HIP_TRY(reserve(b_t1, d_t1, (size_t)n * 4));
+	HIP_TRY(reserve(b_occ, d_occ, (size_t)n * 4));
+	HIP_TRY(hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
+	HIP_TRY(hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
+	hipLaunchKernelGGL(ok.occluded, dim3(grid), dim3(JP_BLOCK), ok.lds, c->stream, c->plan.sv, ok.depth, n, d_o, d_d, d_t0, d_t1, d_occ);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(occluded, d_occ, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return JP_OK;
 }

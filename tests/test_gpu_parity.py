@@ -478,8 +478,9 @@ def test_large_film_and_deep_paths(H, gpu_ctx):
 
 
 def test_wide_bvh_closest_hit_records(H, gpu_ctx, tmp_path, monkeypatch):
-    """large-scene mode: shadow rays walk the 8-wide quantised tree; its closest-hit variant (test hook) must return the
-    very same hit records as the oracle's reference-style binary tree"""
+    """large-scene mode: the 8-wide quantised tree's closest-hit variant (test hook, trace_walk = 2) must return the very same hit records as the
+    oracle's reference-style binary tree.  Its any-hit variant -- what the shadow rays run -- is held to the same rays, ray by ray, in
+    tests/test_gpu_occluded.py (jp_occluded)"""
     hb = H.build_random_scene(H.scenes.HostBackend("r"), 32, 32, 11, n_tris=2000, tmpdir=str(tmp_path))
     sp = hb.flatten()
     gpu_ctx.upload(sp)

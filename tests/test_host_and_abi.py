@@ -19,7 +19,7 @@ def _flat(H, name, W=32, Hh=24):
 def test_abi_exports_every_declared_symbol(H):
     hdr = open(os.path.join(H.REPO, "include", "jetpbrt_amd.h")).read()
     names = sorted(set(re.findall(r"\b(jp_[a-z_]+)\s*\(", hdr)))
-    assert {"jp_create_context", "jp_upload_scene", "jp_render", "jp_render_device", "jp_get_counters", "jp_trace", "jp_last_error"} <= set(names)
+    assert {"jp_create_context", "jp_upload_scene", "jp_render", "jp_render_device", "jp_get_counters", "jp_trace", "jp_occluded", "jp_last_error"} <= set(names)
     lib = C.CDLL(H.jp.HIP_LIB_PATH)
     for n in names:
         assert hasattr(lib, n), "libjetpbrt_amd.so does not export %s" % n
