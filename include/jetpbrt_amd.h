@@ -512,6 +512,39 @@ int  jp_shading_normal(JpContext* ctx, int32_t n, const float* origin, const flo
 int  jp_interpolate_normals(int32_t n, const float* p0, const float* p1, const float* p2, const float* ng, const float* vn9, const float* p, float* ns_out);
 int  jp_check_vertex_normals(const JpVertexNormals* normals, int32_t* n_smooth);
 
+/* Normal maps (additive to ABI 7; INTEGRATION.md "Normal maps" has the definition, include/jp_normal_map.h the code).  A material may carry a tangent-space
+ * normal map: RGB8 texels (row-major, top row first) decoded as max((b - 128) / 127, -1), looked up bilinearly between texel centres with clamp addressing at the
+ * uv of the hit (tri_uv here for triangles -- the struct's own set, independent of JpTextures.tri_uv; GetUV of the other shapes), x and y multiplied by the
+ * material's strength, and turned into the shading normal Ns' in the frame (T, B, Nb) of the base normal Nb -- Ns of a smooth triangle, else the geometric
+ * normal.  Context state like the vertex normals: validated and copied here (JP_ERR_INVALID_ARGUMENT with a message, the context keeps what it had), read by the
+ * next jp_upload_scene*, whose n_materials and n_triangles must equal these; NULL removes them.  Ns' takes Ns's place everywhere (jp_set_vertex_normals above):
+ * every material kind, all combinations of light sampling x map x estimator, textured or not; Whitted: JP_ERR_UNSUPPORTED; the debug integrator ignores the
+ * maps; JpOptions.fused falls back; jp_shading_normal and the normal guide deliver Ns'.  No mapped material, strength 0 or maps whose R and G are 128
+ * everywhere: exactly the upload without maps (mapped_last_render 0, bit-identical films and guides). */
+typedef struct JpNormalMaps {
+    int32_t struct_bytes;
+    int32_t n_maps;        const int32_t *map_width, *map_height;   /* 1 .. 16384 each */
+    const int64_t *map_offset;  int64_t n_texel_bytes;  const uint8_t *texels;   /* RGB8, row-major, top row first */
+    int32_t n_materials;   const int32_t *mat_map;      /* == JpScene.n_materials; -1: none */
+    const float *mat_strength;                          /* per material, finite; NULL: 1 for all */
+    int32_t n_triangles;   const float *tri_uv;         /* == JpScene.n_triangles; uv0 uv1 uv2; NULL: 0 (triangles then stay unperturbed) */
+} JpNormalMaps;
+int  jp_set_normal_maps(JpContext* ctx, const JpNormalMaps* maps);          /* NULL removes them */
+int  jp_check_normal_maps(const JpNormalMaps* maps, int32_t* n_mapped_materials);   /* pure host: the same validation, status and message; materials with mat_map >= 0 (may be NULL) */
+typedef struct JpNormalMapInfo {
+    int32_t struct_bytes, n_maps, n_mapped_materials;   /* of the uploaded scene's maps (0 0: uploaded without)                                  */
+    int64_t texel_bytes_device, table_bytes_device;     /* the texel pool (one dword per texel); descriptors, material and uv records (0: nothing perturbs) */
+    int32_t mapped_last_render;                         /* the last jp_render* ran k_normal_map                                                 */
+    double  normal_map_ms;                              /* with jp_set_profiling: k_normal_map's launches of the last render (a share of JpCounters.shade_ms) */
+} JpNormalMapInfo;
+int  jp_get_normal_map_info(JpContext* ctx, JpNormalMapInfo* out);
+/* pure host, the very function the device runs, for n points: nb, ng, dpdu, dpdv 3 floats each, uv 2 floats, one map (w, h, rgb8), strength -> ns_out 3 floats
+ * (nb where unperturbed), perturbed_out 0/1 */
+int  jp_perturb_normals(int32_t n, const float* nb, const float* ng, const float* dpdu, const float* dpdv, const float* uv,
+                        int32_t width, int32_t height, const uint8_t* rgb8, float strength, float* ns_out, int32_t* perturbed_out);
+/* pure host: dpdu, dpdv of a triangle from its corners and uvs as the header defines them; ok_out 0 (and both 0) where det is 0 or not finite */
+int  jp_triangle_tangents(int32_t n, const float* p0, const float* p1, const float* p2, const float* uv6, float* dpdu, float* dpdv, int32_t* ok_out);
+
 /* Lens (additive to ABI 7; INTEGRATION.md "Lens" has the definition).  The reference's camera is a pinhole: every camera ray starts at JpCamera.pos.  A lens of
  * radius > 0 gives depth of field: the camera ray of a sample starts at a point of the aperture -- a disk (blades 0) or a regular polygon of 3 .. 16 blades with
  * circumradius `radius`, its first vertex rotation_deg from the camera's right axis toward its up axis -- and passes through the point where the pinhole ray meets

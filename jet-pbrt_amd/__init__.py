@@ -198,6 +198,83 @@ def interpolate_normals(p0, p1, p2, ng, vn9, p):
     return out
 
 
+class JpNormalMaps(C.Structure):
+    """include/jetpbrt_amd.h: JpNormalMaps (jp_set_normal_maps); struct_bytes = sizeof(JpNormalMaps)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_maps", C.c_int32), ("map_width", _ip), ("map_height", _ip),
+                ("map_offset", C.POINTER(C.c_int64)), ("n_texel_bytes", C.c_int64), ("texels", C.POINTER(C.c_uint8)),
+                ("n_materials", C.c_int32), ("mat_map", _ip), ("mat_strength", _fp), ("n_triangles", C.c_int32), ("tri_uv", _fp)]
+
+
+class JpNormalMapInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_maps", C.c_int32), ("n_mapped_materials", C.c_int32), ("texel_bytes_device", C.c_int64),
+                ("table_bytes_device", C.c_int64), ("mapped_last_render", C.c_int32), ("normal_map_ms", C.c_double)]
+
+
+def normal_maps(maps, mat_map, mat_strength=None, tri_uv=None, n_triangles=None):
+    """A JpNormalMaps: maps a list of (h, w, 3) uint8 arrays (top row first), mat_map one map index per material (-1: none), mat_strength one float per
+    material or None (1 for all), tri_uv an (n_triangles, 6) float32 array or None (then n_triangles gives the count).  The arrays are kept alive on the
+    returned object as ._keep."""
+    import numpy as np
+    imgs = [np.ascontiguousarray(m, np.uint8) for m in maps]
+    for m in imgs:
+        if m.ndim != 3 or m.shape[2] != 3:
+            raise ValueError("a normal map is an (h, w, 3) uint8 array")
+    w = np.array([m.shape[1] for m in imgs], np.int32); h = np.array([m.shape[0] for m in imgs], np.int32)
+    sizes = [m.size for m in imgs]
+    off = np.array([sum(sizes[:i]) for i in range(len(imgs))], np.int64)
+    tex = np.concatenate([m.reshape(-1) for m in imgs]) if imgs else np.zeros(0, np.uint8)
+    mm = np.ascontiguousarray(mat_map, np.int32).reshape(-1)
+    st = None if mat_strength is None else np.ascontiguousarray(mat_strength, np.float32).reshape(-1)
+    if st is not None and st.shape[0] != mm.shape[0]:
+        raise ValueError("mat_strength needs one value per material")
+    uv = None if tri_uv is None else np.ascontiguousarray(tri_uv, np.float32).reshape(-1, 6)
+    nt = uv.shape[0] if uv is not None else int(n_triangles or 0)
+    v = JpNormalMaps(C.sizeof(JpNormalMaps), len(imgs), w.ctypes.data_as(_ip), h.ctypes.data_as(_ip), off.ctypes.data_as(C.POINTER(C.c_int64)), tex.size,
+                     tex.ctypes.data_as(C.POINTER(C.c_uint8)), mm.shape[0], mm.ctypes.data_as(_ip), st.ctypes.data_as(_fp) if st is not None else None,
+                     nt, uv.ctypes.data_as(_fp) if uv is not None else None)
+    v._keep = (w, h, off, tex, mm, st, uv)
+    return v
+
+
+def _hip_status(L, st):
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+
+
+def check_normal_maps(maps):
+    """jp_check_normal_maps: the validation of jp_set_normal_maps (pure host code, no GPU) on a JpNormalMaps -> number of materials with a map; raises JetPbrtError with its message"""
+    n = C.c_int32(0)
+    L = hip_lib()
+    _hip_status(L, L.jp_check_normal_maps(C.byref(maps), C.byref(n)))
+    return n.value
+
+
+def perturb_normals(nb, ng, dpdu, dpdv, uv, rgb8, strength=1.0):
+    """jp_perturb_normals: the shading normal the device computes under a normal map (include/jp_normal_map.h) for n points; nb ng dpdu dpdv (n, 3), uv (n, 2),
+    rgb8 an (h, w, 3) uint8 map -> (ns (n, 3) float32, perturbed (n,) int32).  Pure host code."""
+    import numpy as np
+    a = [np.ascontiguousarray(x, np.float32) for x in (nb, ng, dpdu, dpdv, uv)]
+    img = np.ascontiguousarray(rgb8, np.uint8)
+    n = a[0].shape[0]
+    ns = np.zeros((n, 3), np.float32); on = np.zeros(n, np.int32)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_perturb_normals(n, q(a[0]), q(a[1]), q(a[2]), q(a[3]), q(a[4]), img.shape[1], img.shape[0], q(img), float(strength), q(ns), q(on)))
+    return ns, on
+
+
+def triangle_tangents(p0, p1, p2, uv6):
+    """jp_triangle_tangents: dpdu, dpdv of n triangles from their corners (n, 3) and uvs (n, 6) -> (dpdu (n, 3), dpdv (n, 3), ok (n,) int32).  Pure host code."""
+    import numpy as np
+    a = [np.ascontiguousarray(x, np.float32) for x in (p0, p1, p2, uv6)]
+    n = a[0].shape[0]
+    du = np.zeros((n, 3), np.float32); dv = np.zeros((n, 3), np.float32); ok = np.zeros(n, np.int32)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_triangle_tangents(n, q(a[0]), q(a[1]), q(a[2]), q(a[3]), q(du), q(dv), q(ok)))
+    return du, dv, ok
+
+
 class JpLens(C.Structure):
     """include/jetpbrt_amd.h: JpLens (jp_set_lens); struct_bytes = sizeof(JpLens)"""
     _fields_ = [("struct_bytes", C.c_int32), ("radius", C.c_float), ("focus_distance", C.c_float), ("blades", C.c_int32), ("rotation_deg", C.c_float)]
@@ -500,6 +577,13 @@ def host_lib():
         L.jp_host_scene_mesh_smooth.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, _fp, C.c_float, C.c_int, _fp, C.c_int, C.c_float]
         L.jp_host_flatten_normals.restype = C.POINTER(JpVertexNormals)
         L.jp_host_flatten_normals.argtypes = [C.c_void_p]
+        L.jp_host_normal_map.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.jp_host_normal_map_file.argtypes = [C.c_void_p, C.c_char_p]
+        L.jp_host_normal_map_from_height.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
+        L.jp_host_normal_map_read.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]
+        L.jp_host_mat_set_normal_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
+        L.jp_host_flatten_normal_maps.restype = C.POINTER(JpNormalMaps)
+        L.jp_host_flatten_normal_maps.argtypes = [C.c_void_p]
         L.jp_host_flatten_envmap.restype = C.POINTER(JpEnvMap)
         L.jp_host_flatten_envmap.argtypes = [C.c_void_p]
         _host = L
@@ -563,6 +647,11 @@ def hip_lib():
         L.jp_shading_normal.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 7
         L.jp_interpolate_normals.argtypes = [C.c_int32] + [C.c_void_p] * 7
         L.jp_check_vertex_normals.argtypes = [C.POINTER(JpVertexNormals), C.POINTER(C.c_int32)]
+        L.jp_set_normal_maps.argtypes = [C.c_void_p, C.POINTER(JpNormalMaps)]
+        L.jp_check_normal_maps.argtypes = [C.POINTER(JpNormalMaps), C.POINTER(C.c_int32)]
+        L.jp_get_normal_map_info.argtypes = [C.c_void_p, C.POINTER(JpNormalMapInfo)]
+        L.jp_perturb_normals.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        L.jp_triangle_tangents.argtypes = [C.c_int32] + [C.c_void_p] * 7
         L.jp_set_lens.argtypes = [C.c_void_p, C.POINTER(JpLens)]
         L.jp_get_lens_info.argtypes = [C.c_void_p, C.POINTER(JpLensInfo)]
         L.jp_check_lens.argtypes = [C.POINTER(JpLens)]
@@ -832,6 +921,16 @@ class Context:
         i = JpNormalInfo()
         i.struct_bytes = C.sizeof(JpNormalInfo)
         self._check(self.lib.jp_get_normal_info(self.h, C.byref(i)))
+        return i
+
+    def set_normal_maps(self, maps):
+        """jp_set_normal_maps for the next upload: a JpNormalMaps (normal_maps(...) builds one), or None for none"""
+        self._check(self.lib.jp_set_normal_maps(self.h, None if maps is None else C.byref(maps)))
+
+    def normal_map_info(self):
+        i = JpNormalMapInfo()
+        i.struct_bytes = C.sizeof(JpNormalMapInfo)
+        self._check(self.lib.jp_get_normal_map_info(self.h, C.byref(i)))
         return i
 
     def shading_normal(self, origin, direction, tmin, tmax):

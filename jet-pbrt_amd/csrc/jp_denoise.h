@@ -20,8 +20,10 @@ struct GuideConst
 // kSmooth (k_guides_smooth, scenes with vertex normals; jp_normals.h): the normal of a hit on a smooth triangle is the shading normal Ns the render uses there
 // kLens (k_guides_lens, k_guides_smooth_lens; jp_set_lens in force): the lens ray of the sample, draws 2 and 3 of its key -- instances of their own, so the pinhole's
 // kernels keep their registers and their instruction streams
-template <int kMode, bool kSmooth, bool kLens>
-__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp)
+// kMapped (k_guides_mapped, k_guides_mapped_lens, scenes with normal maps; jp_normal_map.h): the normal is the Ns the render uses there -- the smooth triangle's Ns where the scene has vertex
+// normals (nv.prim_vn may be null), then the material's map on top; instances of their own again
+template <int kMode, bool kSmooth, bool kLens, bool kMapped = false>
+__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp, const NMapView* mp = nullptr)
 {
 	SceneAccess<kMode> acc(sc, depth);
 	const int npix = gc.width * gc.height;
@@ -51,7 +53,8 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 					else if (type == JP_SHAPE_RECTANGLE) n = dot(xyz(g3), rd) <= 0 ? xyz(g3) : -xyz(g3);
 					else if (type == JP_SHAPE_DISK) n = xyz(sc.prims[4 * h + 1]);
 					else n = normalize(p - xyz(sc.prims[4 * h]));
-					if (kSmooth) shading_normal(sc.prims, nv, h, meta.x, p, n);
+					if constexpr (kMapped) n = mapped_shading_normal(sc.prims, nv, *mp, h, meta.x, meta.y, p, n);
+					else if (kSmooth) shading_normal(sc.prims, nv, h, meta.x, p, n);
 					t = tmax;
 					const int mat = meta.y;
 					if (mat >= 0)
@@ -90,6 +93,17 @@ template <int kMode>
 __global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, JpLensPlan lp)
 {
 	guides_body<kMode, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp);
+}
+
+template <int kMode>
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp)
+{
+	guides_body<kMode, false, false, true>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, &mp);
+}
+template <int kMode>
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, JpLensPlan lp)
+{
+	guides_body<kMode, false, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, &mp);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -177,8 +191,10 @@ typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*,
 typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView);
 typedef void (*GuideLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, JpLensPlan);
 typedef void (*GuideSmoothLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, JpLensPlan);
-struct GuideLaunch { GuideKernel k; size_t lds; int depth; GuideSmoothKernel smooth; GuideLensKernel lens; GuideSmoothLensKernel smooth_lens; };   // smooth: the twin a scene with vertex normals runs; lens: the twins of jp_set_lens
-template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth, k_guides_smooth<M>, k_guides_lens<M>, k_guides_smooth_lens<M> }; return g; }
+typedef void (*GuideMappedKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView);
+typedef void (*GuideMappedLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, JpLensPlan);
+struct GuideLaunch { GuideKernel k; size_t lds; int depth; GuideSmoothKernel smooth; GuideLensKernel lens; GuideSmoothLensKernel smooth_lens; GuideMappedKernel mapped; GuideMappedLensKernel mapped_lens; };   // smooth: the twin a scene with vertex normals runs; lens: the twins of jp_set_lens
+template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth, k_guides_smooth<M>, k_guides_lens<M>, k_guides_smooth_lens<M>, k_guides_mapped<M>, k_guides_mapped_lens<M> }; return g; }
 // the walk trace_kernel(p, 0) gives jp_surface
 GuideLaunch guide_kernel(const ScenePlan& p)
 {
@@ -221,9 +237,11 @@ int guides_launch(JpContext* c, const GuideConst& gc, float* albedo, float* norm
 	HIP_TRY(hipEventRecord(c->gd_ev[0], c->stream));
 	if (c->lens_on)
 	{   // jp_set_lens: sample s stays the camera ray of sample s of the render
-		if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, lp);
+		if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, lp);
+		else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, lp);
 		else hipLaunchKernelGGL(gk.lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, lp);
 	}
+	else if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp);
 	else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv);
 	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist);
 	HIP_TRY(hipGetLastError());

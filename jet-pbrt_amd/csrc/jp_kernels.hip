@@ -22,6 +22,7 @@
 #include "jp_common.h"
 #include "jp_tex.h"
 #include "jp_normals.h"          // part 1: NormView, shading_normal (the kernels and entry points: part 2, at the end)
+#include "jp_normal_map.h"       // part 1: NMapView, mapped_normal (the kernels and entry points: part 2, at the end)
 #include "jp_env.h"              // part 1: EnvView, env_lookup, env_sample (the kernels and entry points: part 2, at the end)
 #include "jp_mis.h"              // part 1: MisView, mis_weight, pdf_local, light_pdf (the kernels and entry points: part 2, at the end)
 #include "jp_lens.h"             // the thin-lens camera: JpLensPlan, jp_lens_ray (shared with the host; the hook kernel and the entry points: jp_lens_runtime.h, at the end)
@@ -1447,6 +1448,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_pick.h"             // light selection: the alias table, k_shade_pick / k_shade_pick_tex, k_light_pick and their entry points (jp_render.h declares its two hooks)
 #define JP_MIS_RUNTIME
 #include "jp_mis.h"              // estimator, part 2: k_shade_mis*, k_light_pdf and their entry points (jp_render.h declares the selector)
+#define JP_NORMAL_MAP_RUNTIME
+#include "jp_normal_map.h"       // normal maps, part 2: k_normal_map, k_shading_normal_mapped and their entry points (before the vertex normals' part 2, whose selector and hook hand out its kernels)
 #define JP_NORMALS_RUNTIME
 #include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points (jp_render.h declares the selector)
 #include "jp_lens_runtime.h"     // thin-lens camera: k_camera_rays and the lens entry points (jp_render.h reads the context's lens state)

@@ -122,7 +122,7 @@ namespace
 SmoothKernels shade_smooth_kernels(const ScenePlan& p)
 {
 	SmoothKernels k;
-	k.normal = k_normal;
+	k.normal = k_normal; k.normal_map = k_normal_map;
 	if (p.shade_sort)
 	{
 		k.plain = k_shade_smooth<true>; k.tex = k_shade_smooth_tex<true>; k.pick = k_shade_smooth_pick<true>; k.pick_tex = k_shade_smooth_pick_tex<true>;
@@ -258,7 +258,8 @@ int jp_shading_normal(JpContext* c, int32_t n, const float* origin, const float*
 	if (n == 0) return JP_OK;
 	const TraceLaunch tk = trace_kernel(c->plan, c->opt.trace_walk, true);      // the walk jp_trace takes (generic: the instance with every shape's normal)
 	const ShadingNormalKernel k = shading_normal_kernel(tk);
-	if (!k) return fail(JP_ERR_UNSUPPORTED, "jp_shading_normal: no instance for this scene's walk");
+	const ShadingNormalMappedKernel km = c->plan.mapped ? shading_normal_mapped_kernel(tk) : nullptr;   // normal maps (jp_normal_map.h): the hook's twin
+	if (!k || (c->plan.mapped && !km)) return fail(JP_ERR_UNSUPPORTED, "jp_shading_normal: no instance for this scene's walk");
 	HIP_TRY(hipSetDevice(c->device));
 	DevBuf b_in, b_g, b_s, b_prim; float *d_in, *d_g, *d_s; int* d_prim;        // per-call scratch: freed on every return
 	HIP_TRY(reserve(b_in, d_in, (size_t)n * 32)); HIP_TRY(reserve(b_g, d_g, (size_t)n * 12)); HIP_TRY(reserve(b_s, d_s, (size_t)n * 12)); HIP_TRY(reserve(b_prim, d_prim, (size_t)n * 4));
@@ -266,7 +267,8 @@ int jp_shading_normal(JpContext* c, int32_t n, const float* origin, const float*
 	HIP_TRY(hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
 	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-	hipLaunchKernelGGL(k, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.nv, c->plan.smooth ? 1 : 0, tk.depth, n, (const float*)d_o, (const float*)d_d, (const float*)d_t0, (const float*)d_t1, d_prim, d_g, d_s);
+	if (km) hipLaunchKernelGGL(km, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.nv, c->plan.mp, tk.depth, n, (const float*)d_o, (const float*)d_d, (const float*)d_t0, (const float*)d_t1, d_prim, d_g, d_s);
+	else hipLaunchKernelGGL(k, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.nv, c->plan.smooth ? 1 : 0, tk.depth, n, (const float*)d_o, (const float*)d_d, (const float*)d_t0, (const float*)d_t1, d_prim, d_g, d_s);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(ng, d_g, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(ns, d_s, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));

@@ -5,7 +5,7 @@
 // ---- render ---------------------------------------------------------------------------------------------------------------
 namespace
 {
-enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4, CLS_NORMAL = 5 };   // (CLS_NORMAL: k_normal, stamped inside its CLS_SHADE pair -- a share of shade_ms, JpNormalInfo)
+enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4, CLS_NORMAL = 5, CLS_NMAP = 6 };   // (CLS_NORMAL: k_normal, stamped inside its CLS_SHADE pair -- a share of shade_ms, JpNormalInfo)
 
 // the lens in force as the kernels take it (zeros while none is set: the kernels then do not read it); the camera is the uploaded scene's
 int lens_plan_of(const JpContext* c, JpLensPlan& lp)
@@ -187,6 +187,7 @@ ShadeMisKernels shade_mis_kernels(const ScenePlan& p);
 struct SmoothKernels
 {
 	void (*normal)(SceneView, Queues, int, NormView);
+	void (*normal_map)(SceneView, Queues, int, NormView, NMapView);          // k_normal's twin of a mapped scene (jp_normal_map.h)
 	void (*plain)(SceneView, Queues, RenderConst, int, DevCounters*, NormView);
 	void (*tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, NormView);
 	void (*pick)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, NormView);
@@ -366,7 +367,8 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 					if (smooth)
 					{   // scenes with vertex normals: k_texel as ever, k_normal leaves Ns for every hit on a smooth triangle, the family's smooth twin shades with it
 						if (tex) hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
-						{ Stamper tn(c, CLS_NORMAL); hipLaunchKernelGGL(nk.normal, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv); }
+						if (p.mapped) { Stamper tn(c, CLS_NMAP); hipLaunchKernelGGL(nk.normal_map, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv, p.mp); }   // normal maps: one kernel leaves Ns or Ns'
+						else { Stamper tn(c, CLS_NORMAL); hipLaunchKernelGGL(nk.normal, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv); }
 						const size_t l = p.shade_lds_bytes;
 						if (tex)
 						{
@@ -601,7 +603,8 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0;
+	if (c->plan.mapped && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with normal maps, jp_set_normal_maps)");
 	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
 	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
 	if (c->plan.pick && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator samples every light (scene uploaded with JP_LIGHTS_POWER_ONE)");
@@ -615,6 +618,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	c->last_mapped = c->plan.env && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_smooth = c->plan.smooth && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_nmapped = c->plan.mapped && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_lens = c->lens_on ? 1 : 0;                                    // (every integrator forms the lens ray)
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
@@ -677,7 +681,7 @@ int finish_one(JpContext* c, JpCounters& o)
 {
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	DevCounters h; HIP_TRY(hipMemcpy(&h, c->cnt.get<void>(), sizeof(h), hipMemcpyDeviceToHost));
-	c->normal_ms = 0.0;
+	c->normal_ms = 0.0; c->normal_map_ms = 0.0;
 	o.closest_rays += h.closest; o.closest_hits += h.closest_hit; o.shadow_rays += h.shadow; o.shadow_occluded += h.shadow_occ; o.certified_fallback_rays += h.cert_fallback;
 	for (const JpContext::Stamp& s : c->stamps)
 	{
@@ -687,6 +691,7 @@ int finish_one(JpContext* c, JpCounters& o)
 		else if (s.cls == CLS_SHADOW) { o.shadow_ms += t; o.shadow_launches++; }
 		else if (s.cls == CLS_PATH) { o.path_ms += t; o.path_launches++; }
 		else if (s.cls == CLS_NORMAL) c->normal_ms += t;
+		else if (s.cls == CLS_NMAP) c->normal_map_ms += t;
 		else o.other_ms += t;
 	}
 	return JP_OK;

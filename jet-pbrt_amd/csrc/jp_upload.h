@@ -94,6 +94,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	if (c->env_map.W > 0) { if (const int st = upload_environment_map(c, T, p, s, pick); st != JP_OK) return st; c->env_importance = c->env_map.importance; }   // before the light table, which weighs the map light
 	if (pick) if (const int st = upload_light_table(c, T, p, s, t.light_area); st != JP_OK) return st;
 	if (c->vnormals.set) if (const int st = upload_vertex_normals(c, T, p, s); st != JP_OK) return st;   // (a scene whose normals are all flat keeps its plan)
+	if (c->nmaps.set) if (const int st = upload_normal_maps(c, T, p, s); st != JP_OK) return st;          // (so does a scene whose maps perturb nothing)
 
 	c->tab = std::move(T); c->plan = p; c->plan.have_scene = true;
 	c->build_on_device = k.device_build; c->build_ms = build_ms; c->bvh_height = t.height; c->bvh_nodes = k.ref_sem ? s->n_bvh_nodes : t.n_nodes;

@@ -14,6 +14,7 @@ struct HostScene
 	std::shared_ptr<FScene> scene;
 	std::vector<std::shared_ptr<FMaterial>> mats;
 	std::vector<std::shared_ptr<FTexture>> texs;
+	std::vector<std::shared_ptr<FNormalMap>> nmaps;
 	FlatScene flat; bool flattened = false;
 	std::unique_ptr<FGpuPathIntegrator> integ; int integDepth = -1;
 	JpEnvMap envView;                                             // jp_host_flatten_envmap
@@ -153,6 +154,35 @@ const JpEnvMap* jp_host_flatten_envmap(void* h)
 	return &v;
 }
 
+// normal maps (FNormalMap) -> handle index, -1 with jp_host_last_error set: from RGB8 memory, from a file, from a grey height map
+static int add_normal_map(HostScene* hs, const std::shared_ptr<FNormalMap>& m, const char* who)
+{
+	if (!m || !m->Valid()) { hs->error = std::string(who) + ": no image, or a size out of range (1 .. 16384 per side)"; return -1; }
+	hs->nmaps.push_back(m); return (int)hs->nmaps.size() - 1;
+}
+int jp_host_normal_map(void* h, const unsigned char* rgb8, int w, int hgt) { return add_normal_map((HostScene*)h, std::make_shared<FNormalMap>(rgb8, w, hgt), "jp_host_normal_map"); }
+int jp_host_normal_map_file(void* h, const char* path) { return add_normal_map((HostScene*)h, FNormalMap::FromFile(path), "jp_host_normal_map_file"); }
+int jp_host_normal_map_from_height(void* h, const unsigned char* grey, int w, int hgt, float scale) { return add_normal_map((HostScene*)h, FNormalMap::FromHeight(grey, w, hgt, scale), "jp_host_normal_map_from_height"); }
+// the map's size (either pointer may be null) and, with rgb8_out, its 3 * w * hgt bytes
+int jp_host_normal_map_read(void* h, int map, int* w, int* hgt, unsigned char* rgb8_out)
+{
+	HostScene* hs = (HostScene*)h;
+	if (map < 0 || map >= (int)hs->nmaps.size()) { hs->error = "jp_host_normal_map_read: no such map"; return -1; }
+	const FNormalMap& m = *hs->nmaps[map];
+	if (w) *w = m.width;
+	if (hgt) *hgt = m.height;
+	if (rgb8_out) std::memcpy(rgb8_out, m.data.data(), m.data.size());
+	return 0;
+}
+// FMaterial::normalMap / normalStrength of any material (map -1: none)
+int jp_host_mat_set_normal_map(void* h, int mat, int map, float strength)
+{
+	HostScene* hs = (HostScene*)h;
+	if (mat < 0 || mat >= (int)hs->mats.size() || map < -1 || map >= (int)hs->nmaps.size()) { hs->error = "jp_host_mat_set_normal_map: no such material or map"; return -1; }
+	hs->mats[mat]->normalMap = map >= 0 ? hs->nmaps[map] : nullptr; hs->mats[mat]->normalStrength = strength; hs->flattened = false;
+	return 0;
+}
+
 void jp_host_scene_preprocess(void* h) { HostScene* hs = (HostScene*)h; hs->scene->Preprocess(); hs->flattened = false; }
 int  jp_host_num_primitives(void* h) { return (int)((HostScene*)h)->scene->primitives.size(); }
 int  jp_host_num_lights(void* h) { return ((HostScene*)h)->scene->LightNum(); }
@@ -179,6 +209,14 @@ const JpVertexNormals* jp_host_flatten_normals(void* h)
 	HostScene* hs = (HostScene*)h;
 	if (!jp_host_flatten(h) || hs->flat.n_smooth == 0) return nullptr;
 	return &hs->flat.normals;
+}
+
+// the flattened normal maps (valid with jp_host_flatten's view; null: no material carries a map, or the flattening failed)
+const JpNormalMaps* jp_host_flatten_normal_maps(void* h)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!jp_host_flatten(h) || hs->flat.n_normal_mapped == 0) return nullptr;
+	return &hs->flat.normalMaps;
 }
 
 // FGpuPathIntegrator(maxdepth).Render(scene, FCounterSampler(spp, seed), film, numthreads) -> rgb (added onto zeros)

@@ -2,6 +2,10 @@
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
 //             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
 //             [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]
+//             [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]
+// --normal-map FILE: a tangent-space normal map (binary PPM or BMP; FMaterial::normalMap) on the floor of either scene -- the bunny scene's floor rectangle, the Cornell box's
+// floor mesh, which then gets a material of its own and must carry `vt`; --normal-strength S scales the map's x and y (default 1); --normal-from-height SCALE reads FILE as a
+// height map (its red channel) and derives the normals from it (FNormalMap::FromHeight).
 // --aperture R: a thin lens of radius R scene units instead of the pinhole (FCamera::SetLens): depth of field.  --focus D: the focus distance (the plane of focus lies D * |front|
 // along the viewing direction; default 1); --focus-pixel X Y: focus on whatever film position (X, Y) sees (FCamera::FocusAt; the distance found is echoed); --blades N: a regular
 // polygon of 3 .. 16 blades instead of a disk; --aperture-rotation DEG: turns the polygon.
@@ -32,7 +36,9 @@ static FColor LightRadiance()                                    // main.cc:35
 	return FColor(r.x, r.y, r.z);
 }
 
-static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr, const FSmoothing& sm = FSmoothing())   // main.cc:13-62; background: --envmap's tint; sm: --smooth
+// nmap (--normal-map): the floor gets a material of its own that carries it; *floorHasUV tells whether the floor mesh has texture coordinates at all
+static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr, const FSmoothing& sm = FSmoothing(),
+                                                       const std::shared_ptr<FNormalMap>& nmap = nullptr, float nstrength = 1.f, bool* floorHasUV = nullptr)   // main.cc:13-62; background: --envmap's tint; sm: --smooth
 {
 	const FPoint3 lookfrom(278, 273, 960), lookat(278, 273, 0);
 	std::shared_ptr<FScene> scene = std::make_shared<FScene>("cornell_box_scene");
@@ -45,7 +51,16 @@ static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize,
 	std::shared_ptr<FMaterial> mat_light = scene->CreateMaterial<FMatteMaterial>(FColor(0.65f, 0.65f, 0.65f));
 	const std::string d = dir + "/cornellbox/";
 	scene->CreateAreaLights(1, LightRadiance(), scene->CreateTriangleMesh((d + "light.obj").c_str(), true, true), mat_light);
-	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "floor.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), white);
+	const std::vector<std::shared_ptr<FShape>> floorMesh = scene->CreateTriangleMesh((d + "floor.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm);
+	std::shared_ptr<FMaterial> floorMat = white;
+	if (nmap)
+	{
+		floorMat = scene->CreateMaterial<FMatteMaterial>(FColor(0.725f, 0.71f, 0.68f)); floorMat->normalMap = nmap; floorMat->normalStrength = nstrength;
+		bool uv = floorMesh.empty();                                  // (a mesh that did not load is reported as such, below)
+		for (auto& sh : floorMesh) { const FTriangle* t = static_cast<const FTriangle*>(sh.get()); if (t->uv0.x != t->uv1.x || t->uv0.y != t->uv1.y || t->uv0.x != t->uv2.x || t->uv0.y != t->uv2.y) uv = true; }
+		if (floorHasUV) *floorHasUV = uv;
+	}
+	scene->CreatePrimitives(floorMesh, floorMat);
 	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "shortbox.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), white);
 	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "tallbox.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), golden);
 	scene->CreatePrimitives(scene->CreateTriangleMesh((d + "left.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm), red);
@@ -54,7 +69,8 @@ static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize,
 	return scene;
 }
 
-static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr, const FSmoothing& sm = FSmoothing())        // main.cc:64-111
+static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr, const FSmoothing& sm = FSmoothing(),
+                                                  const std::shared_ptr<FNormalMap>& nmap = nullptr, float nstrength = 1.f)        // main.cc:64-111
 {
 	const FPoint3 lookfrom(-300, 300, -300), lookat(0, 0, 0);
 	std::shared_ptr<FScene> scene = std::make_shared<FScene>("bunny_scene");
@@ -67,6 +83,7 @@ static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, cons
 	std::shared_ptr<FShape> light = scene->CreateShape<FRectangle>(FRectangle::FromXZ(-100, 100, -100, 100, 350, true));
 	scene->CreateAreaLight(1, LightRadiance(), light, mat_light);
 	std::shared_ptr<FShape> floor = scene->CreateShape<FRectangle>(FRectangle::FromXZ(-200, 200, -200, 200, 0));
+	if (nmap) { green->normalMap = nmap; green->normalStrength = nstrength; }     // (green is the floor's alone)
 	scene->CreatePrimitive(floor.get(), green.get(), (const FAreaLight*)nullptr);
 	const std::string obj = dir + "/bunny/bunny.obj";
 	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(0, 0, 0), 500.f, sm), red);
@@ -87,10 +104,12 @@ int main(int argc, char* argv[])
 	bool denoise = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL, estimator = JP_ESTIMATOR_NEE;
 	std::string envmap; int envUp = JP_ENV_UP_Y; float envScale = 1.f;
 	FSmoothing smoothing;
+	std::string normalMap; float normalStrength = 1.f, normalFromHeight = 0.f; bool fromHeight = false;
 	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
 	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
 	fprintf(stderr, "          [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]\n");
+	fprintf(stderr, "          [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -136,6 +155,9 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--focus-pixel") && i + 2 < argc) { focusX = (float)atof(argv[i + 1]); focusY = (float)atof(argv[i + 2]); i += 2; focusPixel = true; if (!std::isfinite(focusX) || !std::isfinite(focusY)) { fprintf(stderr, "--focus-pixel takes two numbers\n"); return 5; } }
 		else if (!strcmp(argv[i], "--blades") && i + 1 < argc) { blades = atoi(argv[++i]); if (blades != 0 && (blades < 3 || blades > 16)) { fprintf(stderr, "--blades must be 0 (a disk) or 3 .. 16\n"); return 5; } }
 		else if (!strcmp(argv[i], "--aperture-rotation") && i + 1 < argc) { apertureRotation = (float)atof(argv[++i]); if (!std::isfinite(apertureRotation)) { fprintf(stderr, "--aperture-rotation must be a number\n"); return 5; } }
+		else if (!strcmp(argv[i], "--normal-map") && i + 1 < argc) normalMap = argv[++i];
+		else if (!strcmp(argv[i], "--normal-strength") && i + 1 < argc) { normalStrength = (float)atof(argv[++i]); if (!std::isfinite(normalStrength)) { fprintf(stderr, "--normal-strength must be a number\n"); return 5; } }
+		else if (!strcmp(argv[i], "--normal-from-height") && i + 1 < argc) { normalFromHeight = (float)atof(argv[++i]); fromHeight = true; if (!std::isfinite(normalFromHeight)) { fprintf(stderr, "--normal-from-height must be a number\n"); return 5; } }
 		else pos.push_back(argv[i]);
 	}
 	if (pos.empty()) return 0;                                    // main.cc:122-125
@@ -150,14 +172,28 @@ int main(int argc, char* argv[])
 		map = FEnvironmentMap::FromFile(envmap.c_str(), &err);
 		if (!map) { fprintf(stderr, "--envmap %s: %s\n", envmap.c_str(), err.c_str()); return 5; }
 	}
+	std::shared_ptr<FNormalMap> nmap;
+	if (!normalMap.empty())
+	{
+		nmap = FNormalMap::FromFile(normalMap.c_str());
+		if (!nmap) { fprintf(stderr, "--normal-map %s: not a binary PPM or an uncompressed BMP of 1 .. 16384 texels per side\n", normalMap.c_str()); return 5; }
+		if (fromHeight)
+		{   // the red channel as the height
+			std::vector<uint8_t> grey((size_t)nmap->width * nmap->height);
+			for (size_t k = 0; k < grey.size(); k++) grey[k] = nmap->data[3 * k];
+			nmap = FNormalMap::FromHeight(grey.data(), nmap->width, nmap->height, normalFromHeight);
+		}
+	}
+	bool floorHasUV = true;
 	const FColor tint(envScale, envScale, envScale);
 	std::shared_ptr<FScene> scene;
 	switch (sceneId)
 	{
-	case 0: scene = create_cornellbox_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing); break;
-	case 1: scene = create_bunny_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing); break;
+	case 0: scene = create_cornellbox_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing, nmap, normalStrength, &floorHasUV); break;
+	case 1: scene = create_bunny_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing, nmap, normalStrength); break;
 	default: return 0;
 	}
+	if (nmap && !floorHasUV) { fprintf(stderr, "--normal-map: %s/cornellbox/floor.obj has no texture coordinates (vt), so nothing would be mapped\n", assets.c_str()); return 5; }
 	if (map) scene->SetEnvironmentMap(map, envUp);
 	fprintf(stderr, "current scene: %s\n", scene->NameStr());
 	scene->SetLightSampling(estimator == JP_ESTIMATOR_MIS ? JP_LIGHTS_POWER_ONE : lightSampling);

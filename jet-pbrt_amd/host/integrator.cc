@@ -31,6 +31,7 @@ struct HipApi
 	int (*set_light_sampling)(JpContext*, const JpLightSampling*) = nullptr;                 // (looked up, needed by FScene::SetLightSampling only)
 	int (*set_environment_map)(JpContext*, const JpEnvMap*) = nullptr;                       // (looked up, needed by FScene::SetEnvironmentMap only)
 	int (*set_vertex_normals)(JpContext*, const JpVertexNormals*) = nullptr;                 // (looked up, needed by scenes with smooth meshes only)
+	int (*set_normal_maps)(JpContext*, const JpNormalMaps*) = nullptr;                       // (looked up, needed by scenes with FMaterial::normalMap only)
 	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                          // (looked up, needed by FScene::SetEstimator only)
 	int (*set_lens)(JpContext*, const JpLens*) = nullptr;                                    // (looked up, needed by FCamera::SetLens only)
 	int (*focus_distance)(JpContext*, float, float, float*) = nullptr;                       // (looked up, needed by FCamera::FocusAt only)
@@ -66,6 +67,7 @@ HipApi& Api()
 		api.set_estimator = (decltype(api.set_estimator))dlsym(api.lib, "jp_set_estimator");
 		api.set_vertex_normals = (decltype(api.set_vertex_normals))dlsym(api.lib, "jp_set_vertex_normals");
 		api.set_lens = (decltype(api.set_lens))dlsym(api.lib, "jp_set_lens");
+		api.set_normal_maps = (decltype(api.set_normal_maps))dlsym(api.lib, "jp_set_normal_maps");
 		api.focus_distance = (decltype(api.focus_distance))dlsym(api.lib, "jp_focus_distance");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
@@ -166,6 +168,13 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			lastStatus = api.set_vertex_normals(ctx, flat.n_smooth > 0 ? &flat.normals : nullptr);
 			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
 			ctxNormals = flat.n_smooth > 0;
+		}
+		if (flat.n_normal_mapped > 0 || ctxNormalMaps)
+		{   // FMaterial::normalMap: the maps go to the context before the upload they are to affect (and leave it the same way); a scene without one makes no such call
+			if (!api.set_normal_maps) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_normal_maps\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_normal_maps(ctx, flat.n_normal_mapped > 0 ? &flat.normalMaps : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxNormalMaps = flat.n_normal_mapped > 0;
 		}
 		// a scene with a textured material goes through jp_upload_scene_textured; any other makes exactly the calls it always made
 		const bool textured = flat.textures.n_textures > 0;

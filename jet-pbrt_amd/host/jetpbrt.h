@@ -198,6 +198,21 @@ public:
 	unsigned long long id;                                         // distinct per object: how an integrator tells which map its context holds
 };
 
+// ---- normal map (include/jetpbrt_amd.h "Normal maps"): an RGB8 tangent-space map, top row first, the FMaterial::normalMap of any material ----
+class FNormalMap
+{
+public:
+	FNormalMap(const uint8_t* rgb8, int w, int h);                  // from memory: 3 * w * h bytes, row-major, top row first
+	// binary PPM or uncompressed BMP through ReadImageRGB8; null when the file is refused
+	static std::shared_ptr<FNormalMap> FromFile(const char* filename);
+	// a height map (w * h grey bytes, top row first) as a normal map: central differences with clamped neighbours, heights in 0 .. 1,
+	// n = normalize(-scale * dh/dx, -scale * dh/dy_up, 1) per texel, each component encoded as round(127 * c) + 128 (the inverse of the decode)
+	static std::shared_ptr<FNormalMap> FromHeight(const uint8_t* grey, int w, int h, float scale);
+	bool Valid() const { return width >= 1 && width <= 16384 && height >= 1 && height <= 16384 && data.size() == (size_t)width * height * 3; }
+	std::vector<uint8_t> data;
+	int width = 0, height = 0;
+};
+
 // ---- materials: parameter holders with a flatten hook -------------------------------------------------------
 class FMaterial
 {
@@ -207,6 +222,8 @@ public:
 	virtual void Flatten(float out[JP_MAT_PARAM_STRIDE]) const = 0;
 	// the texture of the main colour (matte, mirror, plastic); FlattenScene refuses one on glass or metal, whose [0..2] is eta
 	std::shared_ptr<FTexture> texture;
+	// a tangent-space normal map on any material kind (jp_set_normal_maps): the shading normal is perturbed by the map at the hit's uv, x and y scaled by normalStrength
+	std::shared_ptr<FNormalMap> normalMap; Float normalStrength = 1;
 };
 Float RoughnessToAlpha(Float roughness);                         // microfacet.h:85-90
 
@@ -503,6 +520,10 @@ struct FlatScene
 	// vertex normals (jp_set_vertex_normals): nine floats per triangle in tri_* order, nine zeros for a flat one; n_smooth == 0: the scene has none
 	JpVertexNormals normals;
 	std::vector<float> tri_vn; int n_smooth = 0;
+	// normal maps (jp_set_normal_maps): shared maps are flattened once (by pointer); tri_uv is the textures'; n_normal_mapped == 0: the scene has none
+	JpNormalMaps normalMaps;
+	std::vector<int32_t> nm_width, nm_height, mat_normal_map; std::vector<int64_t> nm_offset; std::vector<uint8_t> nm_texels; std::vector<float> mat_normal_strength;
+	int n_normal_mapped = 0;
 };
 bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error = nullptr);
 
@@ -544,6 +565,7 @@ protected:
 	mutable int uploadedLights = JP_LIGHTS_ALL, ctxLights = JP_LIGHTS_ALL;   // FScene::lightSampling of the uploaded scene; the mode the context was last told
 	mutable unsigned long long uploadedEnv = 0, ctxEnv = 0; mutable int uploadedEnvUp = 0, ctxEnvUp = 0, uploadedEnvImp = 0, ctxEnvImp = 0;   // FEnvironmentMap::id (0: none), up axis and importance: of the uploaded scene; last sent to the context
 	mutable JpLens ctxLens = {};                                    // the lens the context was last told (FCamera::SetLens; radius 0: none)
+	mutable bool ctxNormalMaps = false;                             // ... or normal maps (jp_set_normal_maps)
 	mutable bool ctxNormals = false;                                // the context holds vertex normals of an earlier upload (jp_set_vertex_normals)
 	mutable int lastStatus = 0;
 	mutable JpCounters counters;

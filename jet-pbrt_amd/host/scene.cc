@@ -360,6 +360,36 @@ void FScene::Preprocess()                                                // scen
 	preprocessed = true;
 }
 
+// ---- normal maps -----------------------------------------------------------------------------------------------------
+FNormalMap::FNormalMap(const uint8_t* rgb8, int w, int h)
+{
+	if (!rgb8 || w < 1 || w > 16384 || h < 1 || h > 16384) return;
+	width = w; height = h; data.assign(rgb8, rgb8 + (size_t)w * h * 3);
+}
+std::shared_ptr<FNormalMap> FNormalMap::FromFile(const char* filename)
+{
+	std::vector<uint8_t> rgb; int w = 0, h = 0;
+	if (!filename || !ReadImageRGB8(filename, rgb, w, h)) return nullptr;
+	auto m = std::make_shared<FNormalMap>(rgb.data(), w, h);
+	return m->Valid() ? m : nullptr;
+}
+std::shared_ptr<FNormalMap> FNormalMap::FromHeight(const uint8_t* grey, int w, int h, float scale)
+{
+	if (!grey || w < 1 || w > 16384 || h < 1 || h > 16384 || !std::isfinite(scale)) return nullptr;
+	std::vector<uint8_t> rgb((size_t)w * h * 3);
+	auto at = [&](int x, int y) { x = x < 0 ? 0 : (x > w - 1 ? w - 1 : x); y = y < 0 ? 0 : (y > h - 1 ? h - 1 : y); return (double)grey[(size_t)y * w + x] / 255.0; };
+	auto enc = [](double c) { const double r = std::floor(127.0 * c + 0.5) + 128.0; return (uint8_t)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r)); };
+	for (int y = 0; y < h; y++)
+		for (int x = 0; x < w; x++)
+		{   // central differences in texel units; row 0 is the top row, so "up" is toward smaller y
+			const double dx = 0.5 * (at(x + 1, y) - at(x - 1, y)), dy = 0.5 * (at(x, y - 1) - at(x, y + 1));
+			const double nx = -(double)scale * dx, ny = -(double)scale * dy, l = std::sqrt(nx * nx + ny * ny + 1.0);
+			uint8_t* o = rgb.data() + 3 * ((size_t)y * w + x);
+			o[0] = enc(nx / l); o[1] = enc(ny / l); o[2] = enc(1.0 / l);
+		}
+	return std::make_shared<FNormalMap>(rgb.data(), w, h);
+}
+
 // ---- flattener ------------------------------------------------------------------------------------------------------
 static void push3(std::vector<float>& v, const FVector3& p) { v.push_back(p.x); v.push_back(p.y); v.push_back(p.z); }
 
@@ -408,6 +438,27 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 			ti = texRef.insert(std::make_pair(T, k)).first;
 		}
 		out.mat_texture.back() = ti->second;
+	}
+
+	// normal maps: one entry per distinct FNormalMap (by pointer), on any material kind
+	std::map<const FNormalMap*, int> nmRef;
+	for (size_t i = 0; i < scene.materials.size(); i++)
+	{
+		const FMaterial& M = *scene.materials[i];
+		const FNormalMap* N = M.normalMap.get();
+		out.mat_normal_map.push_back(-1); out.mat_normal_strength.push_back(M.normalStrength);
+		if (!N) continue;
+		if (!N->Valid()) return fail("FlattenScene: FMaterial::normalMap is empty or out of range (1 .. 16384 per side)");
+		if (!std::isfinite(M.normalStrength)) return fail("FlattenScene: FMaterial::normalStrength is not finite");
+		auto ni = nmRef.find(N);
+		if (ni == nmRef.end())
+		{
+			const int k = (int)out.nm_width.size();
+			out.nm_width.push_back(N->width); out.nm_height.push_back(N->height); out.nm_offset.push_back((int64_t)out.nm_texels.size());
+			out.nm_texels.insert(out.nm_texels.end(), N->data.begin(), N->data.end());
+			ni = nmRef.insert(std::make_pair(N, k)).first;
+		}
+		out.mat_normal_map.back() = ni->second; out.n_normal_mapped++;
 	}
 
 	std::map<const FShape*, int> shapePrim;                               // emitting shape -> primitive index
@@ -487,6 +538,12 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 	t.n_materials = v.n_materials; t.mat_texture = out.mat_texture.data();
 	t.n_triangles = v.n_triangles; t.tri_uv = out.tri_uv.data();
 	out.normals.struct_bytes = (int32_t)sizeof(JpVertexNormals); out.normals.n_triangles = v.n_triangles; out.normals.tri_vn = out.tri_vn.data();
+	JpNormalMaps& nm = out.normalMaps; std::memset(&nm, 0, sizeof(nm));
+	nm.struct_bytes = (int32_t)sizeof(JpNormalMaps);
+	nm.n_maps = (int)out.nm_width.size(); nm.map_width = out.nm_width.data(); nm.map_height = out.nm_height.data(); nm.map_offset = out.nm_offset.data();
+	nm.n_texel_bytes = (int64_t)out.nm_texels.size(); nm.texels = out.nm_texels.data();
+	nm.n_materials = v.n_materials; nm.mat_map = out.mat_normal_map.data(); nm.mat_strength = out.mat_normal_strength.data();
+	nm.n_triangles = v.n_triangles; nm.tri_uv = out.tri_uv.data();
 	return true;
 }
 

@@ -330,6 +330,47 @@ class HostBackend:
         p = self.L.jp_host_flatten_normals(self.h)
         return p.contents if p else None
 
+    # normal maps (host backend only): handles for mat_set_normal_map
+    def _nmap(self, k, what):
+        if k < 0:
+            raise RuntimeError("%s failed: %s" % (what, self.L.jp_host_last_error(self.h).decode()))
+        return k
+
+    def normal_map(self, rgb8):
+        """FNormalMap from memory: (H, W, 3) uint8, top row first; or the path of a binary PPM / BMP file (FNormalMap::FromFile)"""
+        if isinstance(rgb8, (str, bytes, os.PathLike)):
+            return self._nmap(self._f("normal_map_file")(self.h, os.fsencode(rgb8)), "normal_map")
+        img = np.ascontiguousarray(rgb8, np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise RuntimeError("a normal map is an (H, W, 3) uint8 array")
+        return self._nmap(self._f("normal_map")(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0]), "normal_map")
+
+    def normal_map_from_height(self, grey, scale):
+        """FNormalMap::FromHeight: (H, W) uint8 heights, top row first -> the map of their slopes times `scale`"""
+        img = np.ascontiguousarray(grey, np.uint8)
+        if img.ndim != 2:
+            raise RuntimeError("a height map is an (H, W) uint8 array")
+        return self._nmap(self._f("normal_map_from_height")(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0], C.c_float(scale)), "normal_map_from_height")
+
+    def normal_map_data(self, nmap):
+        """the map's texels, (H, W, 3) uint8"""
+        w = C.c_int(0); h = C.c_int(0)
+        if self._f("normal_map_read")(self.h, nmap, C.byref(w), C.byref(h), None) != 0:
+            raise RuntimeError("normal_map_data failed: %s" % self.L.jp_host_last_error(self.h).decode())
+        out = np.zeros((h.value, w.value, 3), np.uint8)
+        self._f("normal_map_read")(self.h, nmap, None, None, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def mat_set_normal_map(self, mat, nmap, strength=1.0):
+        """FMaterial::normalMap / normalStrength of any material (nmap -1 or None: none)"""
+        if self._f("mat_set_normal_map")(self.h, mat, -1 if nmap is None else nmap, C.c_float(strength)) != 0:
+            raise RuntimeError("mat_set_normal_map failed: %s" % self.L.jp_host_last_error(self.h).decode())
+
+    def flatten_normal_maps(self):
+        """the scene's normal maps as a JpNormalMaps for Context.set_normal_maps (None: no material carries one); valid until the next preprocess"""
+        p = self.L.jp_host_flatten_normal_maps(self.h)
+        return p.contents if p else None
+
     def flatten_envmap(self):
         """the scene's map as a JpEnvMap pointer for Context.set_environment_map (None: no map); valid until the map changes"""
         p = self.L.jp_host_flatten_envmap(self.h)
