@@ -370,7 +370,8 @@ int  jp_render_guides_device(JpContext* ctx, const JpRenderParams* params, int32
  *   skipped.  h = {1/16, 1/4, 3/8, 1/4, 1/16}, hh = h[dy+2] * h[dx+2].
  *     dc = ((dr*dr + dg*dg) + db*db) of c_p - c_q; dn likewise of n_p - n_q; m = max(max(z_p, z_q), 1e-20f), rz = (z_p - z_q) / m, dz = rz*rz
  *     w = hh / (((1 + dc*kc_i) * (1 + dn*kn)) * (1 + dz*kz));  num += w * c_q (per channel), den += w
- *   c_next_p = num / den;  out = Clamp01(c_n * a).
+ *   c_next_p = num / den;  out = Clamp01(c_n * a) -- or max(c_n * a, 0) while the context's film state has hdr = 1 (jp_set_film, "Film" below: the
+ *   parameters do not grow; the context decides, for jp_denoise* and jp_render_denoised alike).
  * Defaults (fields left 0): iterations 5, sigma_color 1.0, sigma_normal 0.1, sigma_depth 0.03, demodulation on (DESIGN.md "Denoiser": the grid
  * they were chosen from).  film / albedo / normal / depth / out laid out as jp_render and jp_render_guides lay them out; albedo may be NULL only
  * with demodulate = -1; out may not overlap an input (JP_ERR_INVALID_ARGUMENT).  Working buffers belong to the context and are reused. */
@@ -578,6 +579,66 @@ int  jp_camera_rays(JpContext* ctx, const JpRenderParams* params, int32_t n, con
 /* autofocus: the pinhole ray through the film position (fx, fy) (pixels, fractional) of the uploaded scene's camera, along the walk jp_trace takes (tmin 0.001, no
  * far end): *focus_out = t / |d0|, the focus_distance that puts the hit on the plane of focus; a miss: JP_OK and 0 */
 int  jp_focus_distance(JpContext* ctx, float fx, float fy, float* focus_out);
+
+/* Film (additive to ABI 7; INTEGRATION.md "Film" has the definitions in full).  The reference's film holds Clamp01(sum / spp); that stays the default.  The film state
+ * below adds the linear-light film: unclamped output, a per-sample firefly clamp, a luminance histogram for auto-exposure and a display transform.  All of it is
+ * fp32, operation by operation, no contraction (include/jp_film.h, include/jp_tonemap.h: the text the kernels and the pure-host entry points both compile), so
+ * device and host agree bit for bit.  With no film state and no tone map set, every kernel, film, guide and byte is what it is without this section.
+ *
+ * jp_set_film: render-time state like the lens (read by the next jp_render*; one upload serves every film state; lanes and the fused schedule take it too).
+ *   hdr 1: the last batch of the per-pixel sum writes max(L, 0) per channel instead of Clamp01(L); the sum itself -- L += l * (1.0f / spp) in sample order, across
+ *     batches -- is the same, so clip(film_hdr, 0, 1) is the default film bit for bit.
+ *   sample_clamp c > 0 (finite; 0: off): each sample's radiance l is replaced before it enters the sum: any channel not finite -> (0, 0, 0); else with
+ *     m = max(max(l.r, l.g), l.b): m > c -> l * (c / m) (one division, three multiplications); else l.  Works with hdr 0 or 1.
+ *   NULL, or {hdr 0, sample_clamp 0}: the reference's film, the kernels of a context that never heard of a film state; hdr_last_render is then 0.
+ *   Every integrator; band shards as ever (pixels outside the shard are 0, shards sum to the full film).
+ * While the film state in force has hdr = 1, jp_denoise* and jp_render_denoised end with max(c_n * a, 0) instead of Clamp01(c_n * a) (JpDenoiseParams does not grow). */
+typedef struct JpFilm { int32_t struct_bytes; int32_t hdr; float sample_clamp; } JpFilm;
+int  jp_set_film(JpContext* ctx, const JpFilm* film);          /* NULL: the reference's film */
+int  jp_check_film(const JpFilm* film);                        /* pure host: the validation of jp_set_film, same status and message */
+typedef struct JpFilmInfo { int32_t struct_bytes, hdr; float sample_clamp; int32_t hdr_last_render; } JpFilmInfo;   /* the state in force; hdr_last_render: the last jp_render* ran the film instance of k_resolve */
+int  jp_get_film_info(JpContext* ctx, JpFilmInfo* out);
+/* pure host, the very function the device runs on each sample: n rgb triples in -> out (may alias).  film NULL or sample_clamp 0: a copy */
+int  jp_film_samples(const JpFilm* film, int32_t n, const float* in_rgb, float* out_rgb);
+
+/* Luminance histogram of a tightly packed rgb film (needs no scene).  Per pixel Y = (0.2126f*r + 0.7152f*g) + 0.0722f*b; !(Y > 0) or Y not finite: counted in
+ * hist[JP_FILM_BINS] (excluded); else k = (int)(bits(Y) >> 21) - 380 -- four bins per octave, split by the top two mantissa bits, k = 0 at 2^-32 -- and the bin is
+ * min(max(k, 0), 255).  Integer counts: independent of the order, equal to a restatement on any host.  hist: JP_FILM_BINS + 1 dwords (the device variant zeroes
+ * them on the stream first).  The working buffer belongs to the context and is reused. */
+#define JP_FILM_BINS 256
+int  jp_film_histogram(JpContext* ctx, int32_t width, int32_t height, const float* film_rgb, uint32_t* hist);
+int  jp_film_histogram_device(JpContext* ctx, int32_t width, int32_t height, const void* film_dev, void* hist_dev, int sync);
+
+/* Display transform: exposure, a tone curve, then the byte-exact gamma table of jp_render_rgb8.
+ *   defaults (fields left 0): key 0.18, white 4.0, pct_low 0.05, pct_high 0.95.  Validation: every field finite, key and white > 0, 0 <= pct_low < pct_high <= 1,
+ *   a known curve and mode.
+ *   exposure scale (host, double): MANUAL scale = (float)exp2((double)ev).  AUTO: over bins 0 .. 255 with N their total, c_k = the part of bin k's span of the
+ *   cumulative count that lies inside [pct_low * N, pct_high * N] (bins straddling an end count fractionally); centre_k = (1.125 + 0.25 * (k & 3)) * 2^((k >> 2) - 32);
+ *   Lavg = exp2(sum(c_k * log2(centre_k)) / sum(c_k)); scale = (float)(key / Lavg * exp2(ev)); N == 0 or sum(c_k) == 0: scale 1.
+ *   per value: t = x * scale; v = t > 0 ? min(t, 1e9f) : 0 (NaN and negatives: 0);
+ *     CLAMP    y = v
+ *     REINHARD y = (v * (1 + v / (white*white))) / (1 + v)
+ *     ACES     y = (v * (2.51f*v + 0.03f)) / (v * (2.43f*v + 0.59f) + 0.14f)                                  (Narkowicz's fit)
+ *     HABLE    y = h(2*v) / h(11.2f),  h(x) = ((x*(0.15f*x + 0.05f) + 0.004f) / (x*(0.15f*x + 0.5f) + 0.06f)) - 0.02f/0.3f
+ *   y = Clamp01(y): rgb_out receives y, rgb8_out the number of thresholds of jp_gamma_thresholds that are <= y.  CLAMP, MANUAL, ev 0: jp_render_rgb8's bytes.
+ * jp_set_tonemap: render-time state; while one is in force jp_render_rgb8 and jp_render_denoised produce their bytes with it (AUTO: histogram on the device, 257
+ * dwords read back, the scale on the host, then the transform) and mapped_last_render is 1; NULL: none, k_tonemap8 as ever.  The tone map applies to whatever
+ * film the film state produced: a curve other than CLAMP wants hdr = 1 (highlights above 1 are what the curves compress). */
+enum { JP_CURVE_CLAMP = 0, JP_CURVE_REINHARD = 1, JP_CURVE_ACES = 2, JP_CURVE_HABLE = 3 };
+enum { JP_EXPOSURE_MANUAL = 0, JP_EXPOSURE_AUTO = 1 };
+typedef struct JpToneMap { int32_t struct_bytes, curve, exposure_mode; float ev, key, white, pct_low, pct_high; } JpToneMap;
+int  jp_set_tonemap(JpContext* ctx, const JpToneMap* tonemap);
+int  jp_check_tonemap(const JpToneMap* tonemap);               /* pure host: the validation, same status and message; NULL: JP_OK */
+int  jp_exposure_from_histogram(const JpToneMap* tonemap, const uint32_t* hist, float* scale_out);   /* pure host; MANUAL: hist may be NULL */
+/* tonemap NULL: the one in force (none in force: JP_ERR_INVALID_ARGUMENT).  w * h pixels of a tightly packed rgb film -> rgb8_out (3 bytes per pixel) and / or
+ * rgb_out (3 floats per pixel): either may be NULL, not both.  scale_out (may be NULL): the exposure scale used.  Needs no scene.  The device variant with AUTO
+ * synchronises the stream to read the histogram back. */
+int  jp_tonemap(JpContext* ctx, const JpToneMap* tonemap, int32_t width, int32_t height, const float* film_rgb, uint8_t* rgb8_out, float* rgb_out, float* scale_out);
+int  jp_tonemap_device(JpContext* ctx, const JpToneMap* tonemap, int32_t width, int32_t height, const void* film_dev, void* rgb8_dev, void* rgb_dev, float* scale_out, int sync);
+/* pure host, the very function the device runs: n_values floats -> bytes and / or floats under `scale` */
+int  jp_tonemap_host(const JpToneMap* tonemap, float scale, int64_t n_values, const float* in, uint8_t* rgb8_out, float* rgb_out);
+typedef struct JpToneMapInfo { int32_t struct_bytes, curve, exposure_mode; float scale_last; int32_t mapped_last_render; double histogram_ms, tonemap_ms; } JpToneMapInfo;
+int  jp_get_tonemap_info(JpContext* ctx, JpToneMapInfo* out);  /* curve / mode in force (0 0: none); scale and kernel times of the last transform; synchronises the stream */
 
 /* What jp_upload_scene would do with `scene` (additive to ABI 7; INTEGRATION.md "Describing an upload"): the scalars of the plan every later launch
  * reads, and for each table the host builds the byte count and the 64-bit FNV-1a of exactly the bytes the upload copies to the device.  Pure host code, no GPU

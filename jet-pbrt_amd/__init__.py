@@ -344,6 +344,96 @@ def lens_rays(camera, l, fxfy, u=None):
     return o, d
 
 
+JP_FILM_BINS = 256
+JP_CURVE_CLAMP, JP_CURVE_REINHARD, JP_CURVE_ACES, JP_CURVE_HABLE = 0, 1, 2, 3
+JP_EXPOSURE_MANUAL, JP_EXPOSURE_AUTO = 0, 1
+CURVES = {"clamp": JP_CURVE_CLAMP, "reinhard": JP_CURVE_REINHARD, "aces": JP_CURVE_ACES, "hable": JP_CURVE_HABLE}
+
+
+class JpFilm(C.Structure):
+    """include/jetpbrt_amd.h: JpFilm (jp_set_film); struct_bytes = sizeof(JpFilm)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("hdr", C.c_int32), ("sample_clamp", C.c_float)]
+
+
+class JpFilmInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("hdr", C.c_int32), ("sample_clamp", C.c_float), ("hdr_last_render", C.c_int32)]
+
+
+class JpToneMap(C.Structure):
+    """include/jetpbrt_amd.h: JpToneMap (jp_set_tonemap, jp_tonemap); struct_bytes = sizeof(JpToneMap); key, white and the percentiles left 0 take the defaults"""
+    _fields_ = [("struct_bytes", C.c_int32), ("curve", C.c_int32), ("exposure_mode", C.c_int32), ("ev", C.c_float), ("key", C.c_float), ("white", C.c_float),
+                ("pct_low", C.c_float), ("pct_high", C.c_float)]
+
+
+class JpToneMapInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("curve", C.c_int32), ("exposure_mode", C.c_int32), ("scale_last", C.c_float), ("mapped_last_render", C.c_int32),
+                ("histogram_ms", C.c_double), ("tonemap_ms", C.c_double)]
+
+
+def film(hdr=1, sample_clamp=0.0):
+    """A JpFilm (or pass one through)"""
+    return hdr if isinstance(hdr, JpFilm) else JpFilm(C.sizeof(JpFilm), int(hdr), sample_clamp)
+
+
+def tonemap(curve=JP_CURVE_CLAMP, exposure="manual", ev=0.0, key=0.0, white=0.0, pct_low=0.0, pct_high=0.0):
+    """A JpToneMap (or pass one through): curve a JP_CURVE_* or its name, exposure "manual" / "auto" or a JP_EXPOSURE_*"""
+    if isinstance(curve, JpToneMap):
+        return curve
+    mode = {"manual": JP_EXPOSURE_MANUAL, "auto": JP_EXPOSURE_AUTO}.get(exposure, exposure)
+    return JpToneMap(C.sizeof(JpToneMap), CURVES.get(curve, curve), mode, ev, key, white, pct_low, pct_high)
+
+
+def _ptr(s):
+    return None if s is None else C.byref(s)
+
+
+def check_film(f):
+    """jp_check_film: the validation of jp_set_film (pure host code, no GPU); raises JetPbrtError with its message.  f: a JpFilm or None"""
+    L = hip_lib()
+    _hip_status(L, L.jp_check_film(_ptr(f)))
+
+
+def check_tonemap(t):
+    """jp_check_tonemap: the validation of jp_set_tonemap (pure host code, no GPU); raises JetPbrtError with its message.  t: a JpToneMap or None"""
+    L = hip_lib()
+    _hip_status(L, L.jp_check_tonemap(_ptr(t)))
+
+
+def film_samples(f, rgb):
+    """jp_film_samples: the per-sample clamp of JpFilm `f` (or None) on (n, 3) float32 radiances -> (n, 3) float32.  Pure host code, the function the device runs."""
+    import numpy as np
+    a = np.ascontiguousarray(rgb, np.float32).reshape(-1, 3)
+    out = np.zeros_like(a)
+    L = hip_lib()
+    _hip_status(L, L.jp_film_samples(_ptr(f), a.shape[0], a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def exposure_from_histogram(t, hist):
+    """jp_exposure_from_histogram: the exposure scale of JpToneMap `t` for a histogram of JP_FILM_BINS + 1 counts (None with manual exposure).  Pure host code."""
+    import numpy as np
+    h = None if hist is None else np.ascontiguousarray(hist, np.uint32)
+    if h is not None and h.size != JP_FILM_BINS + 1:
+        raise JetPbrtError("exposure_from_histogram: the histogram has JP_FILM_BINS + 1 counts")
+    s = C.c_float(0)
+    L = hip_lib()
+    _hip_status(L, L.jp_exposure_from_histogram(C.byref(t), None if h is None else h.ctypes.data_as(C.c_void_p), C.byref(s)))
+    return s.value
+
+
+def tonemap_host(t, scale, values, want_bytes=True, want_floats=True):
+    """jp_tonemap_host: the display transform of JpToneMap `t` under `scale` on an array of float32 values -> (uint8 array or None, float32 array or None) of its
+    shape.  Pure host code, the function the device runs."""
+    import numpy as np
+    a = np.ascontiguousarray(values, np.float32)
+    b = np.zeros(a.shape, np.uint8) if want_bytes else None
+    f = np.zeros(a.shape, np.float32) if want_floats else None
+    q = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_tonemap_host(C.byref(t), C.c_float(scale), a.size, q(a), q(b), q(f)))
+    return b, f
+
+
 def env_map(rgb, up_axis=JP_ENV_UP_Z, importance=0):
     """A JpEnvMap over an (H, W, 3) float32 array, top row first (kept alive on the returned object as ._keep)"""
     import numpy as np
@@ -567,6 +657,8 @@ def host_lib():
         L.jp_host_flatten_textures.argtypes = [C.c_void_p]
         L.jp_host_render_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.jp_host_render_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.jp_host_render_film.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_char_p, C.c_int]
         L.jp_host_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         L.jp_host_scene_set_estimator.argtypes = [C.c_void_p, C.c_int]
         L.jp_host_scene_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float]
@@ -659,6 +751,20 @@ def hip_lib():
         L.jp_lens_rays.argtypes = [C.POINTER(JpCamera), C.POINTER(JpLens), C.c_int32] + [C.c_void_p] * 4
         L.jp_camera_rays.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32] + [C.c_void_p] * 6
         L.jp_focus_distance.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_float)]
+        L.jp_render_denoised.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 5
+        L.jp_set_film.argtypes = [C.c_void_p, C.POINTER(JpFilm)]
+        L.jp_check_film.argtypes = [C.POINTER(JpFilm)]
+        L.jp_get_film_info.argtypes = [C.c_void_p, C.POINTER(JpFilmInfo)]
+        L.jp_film_samples.argtypes = [C.POINTER(JpFilm), C.c_int32, C.c_void_p, C.c_void_p]
+        L.jp_film_histogram.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.jp_film_histogram_device.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]
+        L.jp_set_tonemap.argtypes = [C.c_void_p, C.POINTER(JpToneMap)]
+        L.jp_check_tonemap.argtypes = [C.POINTER(JpToneMap)]
+        L.jp_exposure_from_histogram.argtypes = [C.POINTER(JpToneMap), C.c_void_p, C.POINTER(C.c_float)]
+        L.jp_tonemap.argtypes = [C.c_void_p, C.POINTER(JpToneMap), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.jp_tonemap_device.argtypes = [C.c_void_p, C.POINTER(JpToneMap), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int]
+        L.jp_tonemap_host.argtypes = [C.POINTER(JpToneMap), C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.jp_get_tonemap_info.argtypes = [C.c_void_p, C.POINTER(JpToneMapInfo)]
         _hip = L
     return _hip
 
@@ -883,6 +989,79 @@ class Context:
             return
         l = lens(radius, focus_distance, blades, rotation_deg)
         self._check(self.lib.jp_set_lens(self.h, C.byref(l)))
+
+    def set_film(self, hdr=None, sample_clamp=0.0):
+        """jp_set_film for the next render / denoise: hdr 0 / 1 (with sample_clamp, 0 = off), a JpFilm, or None for the reference's film"""
+        if hdr is None:
+            self._check(self.lib.jp_set_film(self.h, None))
+            return
+        f = film(hdr, sample_clamp)
+        self._check(self.lib.jp_set_film(self.h, C.byref(f)))
+
+    def film_info(self):
+        i = JpFilmInfo()
+        i.struct_bytes = C.sizeof(JpFilmInfo)
+        self._check(self.lib.jp_get_film_info(self.h, C.byref(i)))
+        return i
+
+    def set_tonemap(self, curve=None, **kw):
+        """jp_set_tonemap for the next render_rgb8 / render_denoised: a curve (with exposure, ev, key, white, pct_low, pct_high), a JpToneMap, or None for none"""
+        if curve is None:
+            self._check(self.lib.jp_set_tonemap(self.h, None))
+            return
+        t = tonemap(curve, **kw)
+        self._check(self.lib.jp_set_tonemap(self.h, C.byref(t)))
+
+    def tonemap_info(self):
+        i = JpToneMapInfo()
+        i.struct_bytes = C.sizeof(JpToneMapInfo)
+        self._check(self.lib.jp_get_tonemap_info(self.h, C.byref(i)))
+        return i
+
+    def film_histogram(self, film_rgb):
+        """jp_film_histogram: the luminance histogram of an (H, W, 3) film -> JP_FILM_BINS + 1 uint32 counts (the last one: the excluded pixels)"""
+        import numpy as np
+        a = np.ascontiguousarray(film_rgb, np.float32)
+        h, w = a.shape[:2]
+        hist = np.zeros(JP_FILM_BINS + 1, np.uint32)
+        self._check(self.lib.jp_film_histogram(self.h, w, h, a.ctypes.data_as(C.c_void_p), hist.ctypes.data_as(C.c_void_p)))
+        return hist
+
+    def film_histogram_device(self, width, height, film_ptr, hist_ptr, sync=False):
+        """jp_film_histogram_device: device pointers (a tightly packed rgb film, JP_FILM_BINS + 1 dwords)"""
+        self._check(self.lib.jp_film_histogram_device(self.h, width, height, C.c_void_p(film_ptr or None), C.c_void_p(hist_ptr or None), 1 if sync else 0))
+
+    def tonemap(self, film_rgb, t=None, want_bytes=True, want_floats=True):
+        """jp_tonemap: the display transform of JpToneMap `t` (None: the one in force) on an (H, W, 3) film -> (rgb8 (H, W, 3) uint8 or None,
+        rgb (H, W, 3) float32 or None, the exposure scale used)"""
+        import numpy as np
+        a = np.ascontiguousarray(film_rgb, np.float32)
+        h, w = a.shape[:2]
+        b = np.zeros((h, w, 3), np.uint8) if want_bytes else None
+        f = np.zeros((h, w, 3), np.float32) if want_floats else None
+        q = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        s = C.c_float(0)
+        self._check(self.lib.jp_tonemap(self.h, _ptr(t), w, h, q(a), q(b), q(f), C.byref(s)))
+        return b, f, s.value
+
+    def tonemap_device(self, width, height, film_ptr, rgb8_ptr, rgb_ptr, t=None, sync=False):
+        """jp_tonemap_device: device pointers (either output may be 0 / None) -> the exposure scale used"""
+        s = C.c_float(0)
+        self._check(self.lib.jp_tonemap_device(self.h, _ptr(t), width, height, C.c_void_p(film_ptr or None), C.c_void_p(rgb8_ptr or None), C.c_void_p(rgb_ptr or None),
+                                               C.byref(s), 1 if sync else 0))
+        return s.value
+
+    def render_denoised(self, params, guide_spp=8, denoise=True, want_bytes=True, **kw):
+        """jp_render_denoised: render, guides, the filter (denoise False: guides only) and the bytes of render_rgb8 in one call ->
+        (film (H, W, 3), rgb8 (H, W, 3) or None, albedo, normal, depth).  kw: the fields of denoise_params"""
+        import numpy as np
+        h, w = params.height, params.width
+        f = np.zeros((h, w, 3), np.float32); b = np.zeros((h, w, 3), np.uint8) if want_bytes else None
+        alb = np.zeros((h, w, 3), np.float32); nrm = np.zeros((h, w, 3), np.float32); dep = np.zeros((h, w), np.float32)
+        q = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        dp = denoise_params(w, h, **kw) if denoise else None
+        self._check(self.lib.jp_render_denoised(self.h, C.byref(params), guide_spp, _ptr(dp), q(f), q(b), q(alb), q(nrm), q(dep)))
+        return f, b, alb, nrm, dep
 
     def lens_info(self):
         i = JpLensInfo()

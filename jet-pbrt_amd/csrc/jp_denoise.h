@@ -178,6 +178,20 @@ __global__ void __launch_bounds__(JP_BLOCK) k_atrous(AtrousConst ac, const float
 	}
 }
 
+// k_atrous_unpack_hdr: the last step while the context's film state has hdr = 1 (jp_set_film): the last iteration then runs as k_atrous<false>, and this
+// kernel re-modulates its records with the a of k_atrous_pack and writes max(c_n * a, 0) in the film layout -- the values k_atrous<true> clamps to 1, one
+// pass of 28 bytes per pixel more, and the two instances of k_atrous stay the kernels they were
+__global__ void __launch_bounds__(JP_BLOCK) k_atrous_unpack_hdr(int npix, const float4* __restrict__ cz, const float* __restrict__ albedo, float* __restrict__ out)
+{
+	for (int p = blockIdx.x * JP_BLOCK + threadIdx.x; p < npix; p += gridDim.x * JP_BLOCK)
+	{
+		float ar = 1.f, ag = 1.f, ab = 1.f;
+		if (albedo) { ar = smax(albedo[3 * p], 0.001f); ag = smax(albedo[3 * p + 1], 0.001f); ab = smax(albedo[3 * p + 2], 0.001f); }
+		const float4 c = cz[p];
+		out[3 * p] = smax(c.x * ar, 0.f); out[3 * p + 1] = smax(c.y * ag, 0.f); out[3 * p + 2] = smax(c.z * ab, 0.f);
+	}
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
@@ -292,7 +306,10 @@ int denoise_launch(JpContext* c, const DenoiseSetup& s, const float* film, const
 	{
 		const AtrousConst ac = { s.width, s.height, 1 << i, pow4 / sc2, kn, kz };
 		const float4* src = cz[i & 1]; float4* dst = cz[(i & 1) ^ 1];
-		if (i + 1 < s.iterations) hipLaunchKernelGGL(k_atrous<false>, grid, dim3(JP_BLOCK), 0, c->stream, ac, src, (const float4*)nr, dst, (const float*)nullptr, (float*)nullptr);
+		const bool hdr = c->film_on && c->film_state.hdr;           // jp_set_film: the unclamped last step (k_atrous_unpack_hdr)
+		if (i + 1 < s.iterations || hdr) hipLaunchKernelGGL(k_atrous<false>, grid, dim3(JP_BLOCK), 0, c->stream, ac, src, (const float4*)nr, dst, (const float*)nullptr, (float*)nullptr);
+		if (i + 1 < s.iterations) continue;
+		if (hdr) hipLaunchKernelGGL(k_atrous_unpack_hdr, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, (int)npix, (const float4*)dst, alb, out);
 		else hipLaunchKernelGGL(k_atrous<true>, grid, dim3(JP_BLOCK), 0, c->stream, ac, src, (const float4*)nr, (float4*)nullptr, alb, out);
 	}
 	HIP_TRY(hipGetLastError());
@@ -385,7 +402,7 @@ int jp_render_denoised(JpContext* c, const JpRenderParams* rp, int32_t guide_spp
 	if (rgb8_host)
 	{
 		if (const int e = ensure_rgb8(c, 3 * n); e != JP_OK) return e;
-		tonemap8(c, result, 3 * n);
+		if (const int e = film_to_rgb8(c, result, gc.width, gc.height); e != JP_OK) return e;
 		HIP_TRY(hipMemcpyAsync(rgb8_host, c->rgb8.get<void>(), 3 * n, hipMemcpyDeviceToHost, c->stream));
 	}
 	if (film_host) HIP_TRY(hipMemcpyAsync(film_host, result, 3 * n * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -27,6 +27,7 @@
 #include "jp_mis.h"              // part 1: MisView, mis_weight, pdf_local, light_pdf (the kernels and entry points: part 2, at the end)
 #include "jp_lens.h"             // the thin-lens camera: JpLensPlan, jp_lens_ray (shared with the host; the hook kernel and the entry points: jp_lens_runtime.h, at the end)
 #include "jp_xbsdf.h"
+#include "jp_film.h"             // part 1: the sample clamp, the histogram bin, the display transform (shared with the host; the kernels and entry points: part 2, at the end)
 
 #include <cstdio>
 #include <cstring>
@@ -1257,6 +1258,32 @@ __global__ void __launch_bounds__(JP_BLOCK) k_resolve(Queues q, RenderConst rc, 
 		}
 	}
 }
+// k_resolve_film: k_resolve's twin while a film state is in force (jp_set_film; include/jp_film.h): the same sum in the same order, but sample_clamp > 0
+// replaces each sample's radiance before it enters the sum, and hdr writes max(L, 0) instead of Clamp01(L).  A kernel of its own text, not a shared body:
+// k_resolve above then compiles to the instructions it always compiled to (a body shared through an inlined function changed their order).
+__global__ void __launch_bounds__(JP_BLOCK) k_resolve_film(Queues q, RenderConst rc, float4* pix_acc, float* film, int first, int last, int hdr, float sample_clamp)
+{
+	const float ratio = 1.0f / (float)rc.spp;
+	for (int pix = blockIdx.x * JP_BLOCK + threadIdx.x; pix < rc.npix; pix += gridDim.x * JP_BLOCK)
+	{
+		V3 L = mk(0, 0, 0);
+		if (!first) { const float4 a = pix_acc[pix]; L = mk(a.x, a.y, a.z); }
+		for (int s = 0; s < rc.sbatch; s++)
+		{
+			float4 l = q.lacc[(size_t)s * rc.npix + pix];
+			if (sample_clamp > 0.f) jp_film_clamp_sample(sample_clamp, &l.x, &l.y, &l.z);
+			L = L + mk(l.x, l.y, l.z) * ratio;
+		}
+		if (!last) pix_acc[pix] = make_float4(L.x, L.y, L.z, 0.f);
+		else
+		{
+			int x, y; pixel_of(rc, pix, x, y);
+			float* o = film + 3 * ((size_t)y * rc.width + x);
+			if (hdr) { o[0] = 0.f + smax(L.x, 0.f); o[1] = 0.f + smax(L.y, 0.f); o[2] = 0.f + smax(L.z, 0.f); }
+			else { o[0] = 0.f + clampf(L.x, 0.f, 1.f); o[1] = 0.f + clampf(L.y, 0.f, 1.f); o[2] = 0.f + clampf(L.z, 0.f, 1.f); }
+		}
+	}
+}
 
 #include "jp_path.h"
 
@@ -1453,3 +1480,5 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #define JP_NORMALS_RUNTIME
 #include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points (jp_render.h declares the selector)
 #include "jp_lens_runtime.h"     // thin-lens camera: k_camera_rays and the lens entry points (jp_render.h reads the context's lens state)
+#define JP_FILM_RUNTIME
+#include "jp_film.h"             // film, part 2: k_film_hist, k_display and the film / tone map entry points (jp_render.h declares film_to_rgb8 and reads the context's film state)

@@ -50,6 +50,14 @@ void tonemap8(JpContext* c, const float* src, size_t n)
 	hipLaunchKernelGGL(k_tonemap8, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, src, c->rgb8.get<unsigned char>(), c->gamma.get<const float>(), n);
 }
 
+// k_resolve of one batch, for both schedules: the film instance while a film state is in force (jp_set_film), else the kernel that always ran
+void launch_resolve(JpContext* c, const Queues& q, const RenderConst& rc, long long npix, float4* pix_acc, float* film_dev, int first, int last)
+{
+	const dim3 grid((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK));
+	if (c->film_on) { hipLaunchKernelGGL(k_resolve_film, grid, dim3(JP_BLOCK), 0, c->stream, q, rc, pix_acc, film_dev, first, last, c->film_state.hdr, c->film_state.sample_clamp); c->last_hdr = 1; }
+	else hipLaunchKernelGGL(k_resolve, grid, dim3(JP_BLOCK), 0, c->stream, q, rc, pix_acc, film_dev, first, last);
+}
+
 struct Stamper
 {
 	JpContext* c; int cls; size_t a;
@@ -201,6 +209,8 @@ struct SmoothKernels
 };
 SmoothKernels shade_smooth_kernels(const ScenePlan& p);
 }
+// the bytes of jp_render_rgb8 / jp_render_denoised, after ensure_rgb8: k_tonemap8, or the display transform while a tone map is in force (jp_film.h, part 2)
+static int film_to_rgb8(JpContext* c, const float* src, int width, int height);
 static int ensure_mis_side(JpContext* c, unsigned int cap, MisView& mv);
 static int ensure_normal_side(JpContext* c, unsigned int cap, NormView& nv);
 namespace
@@ -410,7 +420,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 				}
 				cur ^= 1;
 			}
-			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_resolve, dim3((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, c->q, rc, d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
+			{ Stamper t(c, CLS_OTHER); launch_resolve(c, c->q, rc, npix, d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
 			samples += (unsigned long long)rc.sbatch * (unsigned long long)npix;
 		}
 		HIP_TRY(hipGetLastError());
@@ -453,6 +463,7 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
 	l->estimator = c->estimator;                                     // ... and the estimator (its side records are its own, like its queues)
 	l->lens = c->lens; l->lens_on = c->lens_on;                      // ... and the lens
+	l->film_state = c->film_state; l->film_on = c->film_on;          // ... and the film state (a lane resolves its own bands)
 }
 
 // ---- fused schedule: one k_path launch per batch (jp_path.h) --------------------------------------------------------------
@@ -589,7 +600,7 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 			const unsigned int g = (unsigned int)std::min<unsigned long long>((unsigned long long)npg * pc.nsb, (unsigned long long)G);
 			{ Stamper t(c, CLS_PATH); hipLaunchKernelGGL(kern, dim3(g), dim3(JP_BLOCK), L.total, c->stream, p.sv, c->fq, rc, pc, d_spill, d_cnt); }
 			HIP_TRY(hipGetLastError());
-			{ Stamper t(c, CLS_OTHER); hipLaunchKernelGGL(k_resolve, dim3((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, c->fq, rc, d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
+			{ Stamper t(c, CLS_OTHER); launch_resolve(c, c->fq, rc, npix, d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
 			HIP_TRY(hipGetLastError());
 			samples += (unsigned long long)rc.sbatch * (unsigned long long)npix;
 		}
@@ -603,6 +614,7 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync)
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
+	c->last_hdr = 0;
 	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0;
 	if (c->plan.mapped && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with normal maps, jp_set_normal_maps)");
 	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
@@ -743,7 +755,7 @@ int jp_render_rgb8(JpContext* c, const JpRenderParams* rp, uint8_t* rgb8_host, f
 	if (const int e = ensure_rgb8(c, n); e != JP_OK) return e;
 	unsigned char* stage = c->h_rgb8.reserve(n) == hipSuccess ? c->h_rgb8.get<unsigned char>() : rgb8_host;
 	int st = render_impl(c, rp, d_film, false); if (st != JP_OK) return st;
-	tonemap8(c, d_film, n);
+	if (const int e = film_to_rgb8(c, d_film, rp->width, rp->height); e != JP_OK) return e;
 	HIP_TRY(hipMemcpyAsync(stage, c->rgb8.get<void>(), n, hipMemcpyDeviceToHost, c->stream));
 	if (film_host) HIP_TRY(hipMemcpyAsync(film_host, d_film, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));

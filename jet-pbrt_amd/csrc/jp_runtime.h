@@ -162,6 +162,12 @@ struct JpContext
 	// thin-lens camera (jp_lens_runtime.h): render-time state like the estimator (jp_set_lens; a lane takes its parent's before it renders) and what the last
 	// render ran.  The plan is a kernel argument made per launch from the uploaded camera: the lens owns no device memory.
 	JpLens lens = {}; bool lens_on = false; int last_lens = 0;
+	// film (jp_film.h): render-time state like the lens -- the film state (jp_set_film; a lane takes its parent's) and the tone map (jp_set_tonemap, resolved:
+	// defaults filled in) -- what the last render / transform ran, the histogram's 257 dwords on the device, event pairs around k_film_hist and k_display
+	JpFilm film_state = {}; bool film_on = false; int last_hdr = 0;
+	JpToneMap tonemap = {}; bool tonemap_on = false; int last_tonemapped = 0; float last_scale = 0.f;
+	DevBuf film_hist, film_stage;
+	hipEvent_t fh_ev[2] = { nullptr, nullptr }, tm_ev[2] = { nullptr, nullptr }; bool fh_timed = false, tm_timed = false;
 };
 // jp_pick.h / jp_env.h (included last) define the upload's table steps
 static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area);
@@ -406,7 +412,7 @@ int jp_destroy_context(JpContext* c)
 	if (c->stream) hipStreamSynchronize(c->stream);
 	for (JpContext* l : c->lanes) jp_destroy_context(l);
 	c->lanes.clear();
-	for (hipEvent_t e : { c->ev_added, c->dn_ev[0], c->dn_ev[1], c->gd_ev[0], c->gd_ev[1], c->ev0, c->ev1 }) if (e) hipEventDestroy(e);
+	for (hipEvent_t e : { c->ev_added, c->dn_ev[0], c->dn_ev[1], c->gd_ev[0], c->gd_ev[1], c->fh_ev[0], c->fh_ev[1], c->tm_ev[0], c->tm_ev[1], c->ev0, c->ev1 }) if (e) hipEventDestroy(e);
 	for (hipEvent_t e : c->evpool) hipEventDestroy(e);
 	if (c->stream) hipStreamDestroy(c->stream);
 	delete c;                                                      // every DevBuf / PinnedBuf member frees its memory

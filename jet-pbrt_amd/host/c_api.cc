@@ -296,6 +296,32 @@ int jp_host_render_denoised(void* h, int W, int H, int spp, int maxdepth, unsign
 	return JP_OK;
 }
 
+// The linear-light film: FFilm::SetHDR(hdr) / SetSampleClamp(sample_clamp) / SetToneMap(curve, auto_exposure, ev, white) when tonemap != 0 [+ RequestDeviceLDR(true) when
+// ldr_only] -> Render -> the fp32 film (unless ldr_only), the 8-bit pixels (with a tone map or ldr_only), FFilm::ToneMapScale() -> optionally SaveAsImage(filename, type).
+// Any output may be null.
+int jp_host_render_film(void* h, int W, int H, int spp, int maxdepth, unsigned seed, int device, int hdr, float sample_clamp, int tonemap, int curve, int auto_exposure, float ev, float white,
+                        int ldr_only, float* film_out, unsigned char* rgb8_out, float* scale_out, const char* filename, int type)
+{
+	HostScene* hs = (HostScene*)h;
+	if (ldr_only && ((filename && filename[0] && type == 2) || film_out)) return JP_ERR_INVALID_ARGUMENT;   // an LDR-only film has no fp32 pixels for an .hdr file or a float buffer
+	if (!hs->integ || hs->integDepth != maxdepth) { hs->integ.reset(new FGpuPathIntegrator(maxdepth, device)); hs->integDepth = maxdepth; }
+	hs->integ->SetShard(0, 1);
+	FFilm film(W, H);
+	if (hdr) film.SetHDR();
+	if (sample_clamp != 0) film.SetSampleClamp(sample_clamp);
+	if (tonemap) { FToneMap t; t.curve = curve; t.autoExposure = auto_exposure != 0; t.ev = ev; t.white = white; film.SetToneMap(t); }
+	if (ldr_only) film.RequestDeviceLDR(true);
+	FCounterSampler sampler(spp, seed);
+	hs->integ->Render(hs->scene.get(), &sampler, &film, 16);
+	if (hs->integ->LastStatus() != JP_OK) return hs->integ->LastStatus();
+	if ((tonemap || ldr_only) && !film.HasLDR()) return JP_ERR_DEVICE;
+	if (rgb8_out && film.HasLDR()) std::memcpy(rgb8_out, film.ldr8.data(), film.ldr8.size());
+	if (film_out) for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) { const FColor& c = static_cast<const FFilm&>(film)(x, y); float* o = film_out + 3 * ((size_t)y * W + x); o[0] = c.r; o[1] = c.g; o[2] = c.b; }
+	if (scale_out) *scale_out = film.ToneMapScale();
+	if (filename && filename[0]) return film.SaveAsImage(filename, type == 0 ? EImageType::PPM : (type == 2 ? EImageType::HDR : EImageType::BMP)) ? JP_OK : JP_ERR_INVALID_ARGUMENT;
+	return JP_OK;
+}
+
 // The reference's reflection classes by name (jetpbrt.h "reflection API"): builds the named class the way reference code would and
 // calls Evalf / Pdf / Sample once.  which: 0 FPhongSpecularReflection(Ks, exponent), 1 FMicrofacetReflection(R, Beckmann(ax, ay, vis),
 // FresnelNoOp), 2 FMicrofacetTransmission(T, TrowbridgeReitz(ax, ay, vis), etaA, etaB).  out: f[3], pdf, sample f[3], wi[3], pdf, flags

@@ -3,6 +3,11 @@
 //             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
 //             [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]
 //             [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]
+//             [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]
+// --hdr: the unclamped film (FFilm::SetHDR): --format hdr then writes radiance above 1.  --sample-clamp C: each sample's radiance is scaled down to a maximum channel of C
+// before it enters the pixel's sum (FFilm::SetSampleClamp): fireflies.  --tonemap: the display transform of BMP / PPM on the GPU (FFilm::SetToneMap; implies --hdr):
+// exposure, the curve, then the gamma table; --exposure EV: the scale 2^EV (default 0), auto: from the film's luminance histogram (key 0.18); --white W: Reinhard's
+// white point (default 4).  The exposure scale used is echoed.
 // --normal-map FILE: a tangent-space normal map (binary PPM or BMP; FMaterial::normalMap) on the floor of either scene -- the bunny scene's floor rectangle, the Cornell box's
 // floor mesh, which then gets a material of its own and must carry `vt`; --normal-strength S scales the map's x and y (default 1); --normal-from-height SCALE reads FILE as a
 // height map (its red channel) and derives the normals from it (FNormalMap::FromHeight).
@@ -105,11 +110,13 @@ int main(int argc, char* argv[])
 	std::string envmap; int envUp = JP_ENV_UP_Y; float envScale = 1.f;
 	FSmoothing smoothing;
 	std::string normalMap; float normalStrength = 1.f, normalFromHeight = 0.f; bool fromHeight = false;
+	bool hdr = false, haveToneMap = false; float sampleClamp = 0.f; FToneMap toneMap;
 	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
 	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
 	fprintf(stderr, "          [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]\n");
 	fprintf(stderr, "          [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]\n");
+	fprintf(stderr, "          [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -158,6 +165,23 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--normal-map") && i + 1 < argc) normalMap = argv[++i];
 		else if (!strcmp(argv[i], "--normal-strength") && i + 1 < argc) { normalStrength = (float)atof(argv[++i]); if (!std::isfinite(normalStrength)) { fprintf(stderr, "--normal-strength must be a number\n"); return 5; } }
 		else if (!strcmp(argv[i], "--normal-from-height") && i + 1 < argc) { normalFromHeight = (float)atof(argv[++i]); fromHeight = true; if (!std::isfinite(normalFromHeight)) { fprintf(stderr, "--normal-from-height must be a number\n"); return 5; } }
+		else if (!strcmp(argv[i], "--hdr")) hdr = true;
+		else if (!strcmp(argv[i], "--sample-clamp") && i + 1 < argc) { sampleClamp = (float)atof(argv[++i]); if (!(sampleClamp >= 0.f) || !std::isfinite(sampleClamp)) { fprintf(stderr, "--sample-clamp must be a number >= 0\n"); return 5; } }
+		else if (!strcmp(argv[i], "--tonemap") && i + 1 < argc)
+		{
+			const char* m = argv[++i]; haveToneMap = true;
+			if (!strcmp(m, "clamp")) toneMap.curve = JP_CURVE_CLAMP; else if (!strcmp(m, "reinhard")) toneMap.curve = JP_CURVE_REINHARD;
+			else if (!strcmp(m, "aces")) toneMap.curve = JP_CURVE_ACES; else if (!strcmp(m, "hable")) toneMap.curve = JP_CURVE_HABLE;
+			else { fprintf(stderr, "--tonemap must be clamp, reinhard, aces or hable\n"); return 5; }
+		}
+		else if (!strcmp(argv[i], "--exposure") && i + 1 < argc)
+		{
+			const char* m = argv[++i]; char* e = nullptr; const float v = strtof(m, &e); haveToneMap = true;
+			if (!strcmp(m, "auto")) toneMap.autoExposure = true;
+			else if (e != m && *e == 0 && std::isfinite(v)) { toneMap.autoExposure = false; toneMap.ev = v; }
+			else { fprintf(stderr, "--exposure must be a number (EV) or auto\n"); return 5; }
+		}
+		else if (!strcmp(argv[i], "--white") && i + 1 < argc) { toneMap.white = (float)atof(argv[++i]); haveToneMap = true; if (!(toneMap.white > 0.f) || !std::isfinite(toneMap.white)) { fprintf(stderr, "--white must be a number > 0\n"); return 5; } }
 		else pos.push_back(argv[i]);
 	}
 	if (pos.empty()) return 0;                                    // main.cc:122-125
@@ -212,10 +236,14 @@ int main(int argc, char* argv[])
 	else if (integratorName == "recursive") integrator.reset(new FPathIntegratorRecursive(5));
 	else integrator.reset(new FPathIntegratorIteration(5));
 	if (format != "hdr") film.RequestDeviceLDR(true);             // BMP / PPM: gamma_encoding runs on the GPU, 3 bytes per pixel come back
+	if (hdr) film.SetHDR();
+	if (sampleClamp > 0.f) film.SetSampleClamp(sampleClamp);
+	if (haveToneMap) film.SetToneMap(toneMap);                    // (turns HDR on)
 	if (denoise) film.RequestDenoise(guideSpp); else if (!aov.empty()) film.RequestGuides(guideSpp);
 	integrator->Render(scene.get(), sampler.get(), &film, 16);    // main.cc:156
 	if (integrator->LastStatus() != JP_OK) return 3;              // no GPU / no library: fail loudly, nothing is written
 	if (aperture > 0.f && scene->camera) fprintf(stderr, "lens: aperture %g, focus distance %g%s\n", aperture, scene->camera->LastFocus(), focusPixel ? " (found at the focus pixel)" : "");
+	if (haveToneMap) fprintf(stderr, "tone map: exposure scale %g\n", film.ToneMapScale());
 	char fullname[512];
 	snprintf(fullname, sizeof(fullname), "%s_%d", scene->NameStr(), samples_per_pixel);
 	const std::string name = out.empty() ? fullname : out;

@@ -35,6 +35,9 @@ struct HipApi
 	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                          // (looked up, needed by FScene::SetEstimator only)
 	int (*set_lens)(JpContext*, const JpLens*) = nullptr;                                    // (looked up, needed by FCamera::SetLens only)
 	int (*focus_distance)(JpContext*, float, float, float*) = nullptr;                       // (looked up, needed by FCamera::FocusAt only)
+	int (*set_film)(JpContext*, const JpFilm*) = nullptr;                                    // (looked up, needed by FFilm::SetHDR / SetSampleClamp / SetToneMap only)
+	int (*set_tonemap)(JpContext*, const JpToneMap*) = nullptr;                              // (looked up, needed by FFilm::SetToneMap only)
+	int (*get_tonemap_info)(JpContext*, JpToneMapInfo*) = nullptr;
 	std::string error;
 };
 
@@ -69,6 +72,9 @@ HipApi& Api()
 		api.set_lens = (decltype(api.set_lens))dlsym(api.lib, "jp_set_lens");
 		api.set_normal_maps = (decltype(api.set_normal_maps))dlsym(api.lib, "jp_set_normal_maps");
 		api.focus_distance = (decltype(api.focus_distance))dlsym(api.lib, "jp_focus_distance");
+		api.set_film = (decltype(api.set_film))dlsym(api.lib, "jp_set_film");
+		api.set_tonemap = (decltype(api.set_tonemap))dlsym(api.lib, "jp_set_tonemap");
+		api.get_tonemap_info = (decltype(api.get_tonemap_info))dlsym(api.lib, "jp_get_tonemap_info");
 		if (!api.last_error || !api.create_context || !api.destroy_context || !api.upload_scene || !api.render || !api.get_counters || !api.render_rgb8 || !api.bsdf || !api.abi_version || !api.set_options)
 		{ api.error = "libjetpbrt_amd.so lacks a required jp_* symbol"; dlclose(api.lib); api.lib = nullptr; }
 		else if (api.abi_version() != JP_ABI_VERSION)            // a stale build would be handed structs of another size (JpCounters, JpBuildInfo, JpOptions)
@@ -220,6 +226,32 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			ctxLens = l;
 		}
 	}
+	{   // FFilm::SetHDR / SetSampleClamp / SetToneMap: render-time state of the context, sent when it changes; a film that never asked for either makes no such call
+		JpFilm f; std::memset(&f, 0, sizeof(f));
+		if (film->hdr || film->sampleClamp != 0) { f.struct_bytes = (int32_t)sizeof(f); f.hdr = film->hdr ? 1 : 0; f.sample_clamp = film->sampleClamp; }
+		if (std::memcmp(&f, &ctxFilm, sizeof(f)) != 0)
+		{
+			if (!api.set_film) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_film\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_film(ctx, f.struct_bytes ? &f : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxFilm = f;
+		}
+		JpToneMap t; std::memset(&t, 0, sizeof(t));
+		if (film->haveToneMap)
+		{
+			const FToneMap& m = film->toneMap;
+			t.struct_bytes = (int32_t)sizeof(t); t.curve = m.curve; t.exposure_mode = m.autoExposure ? JP_EXPOSURE_AUTO : JP_EXPOSURE_MANUAL;
+			t.ev = m.ev; t.key = m.key; t.white = m.white; t.pct_low = m.pctLow; t.pct_high = m.pctHigh;
+		}
+		if (std::memcmp(&t, &ctxToneMap, sizeof(t)) != 0)
+		{
+			if (!api.set_tonemap || !api.get_tonemap_info) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_tonemap\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_tonemap(ctx, t.struct_bytes ? &t : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxToneMap = t;
+		}
+	}
+	const bool wantLDR = film->wantLDR || film->haveToneMap;           // a tone map: the 8-bit bytes come from the device's display transform, next to the fp32 film
 	JpRenderParams rp; std::memset(&rp, 0, sizeof(rp));
 	rp.width = film->Width(); rp.height = film->Height();
 	rp.spp = sampler->GetSamplesPerPixel(); rp.max_depth = maxDepth;
@@ -234,13 +266,13 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 		if (!api.render_denoised) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_render_denoised\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
 		const size_t n = (size_t)rp.width * rp.height;
 		galb.assign(3 * n, 0.f); gnrm.assign(3 * n, 0.f); gdep.assign(n, 0.f);
-		if (film->wantLDR) ldr.assign(3 * n, 0);
+		if (wantLDR) ldr.assign(3 * n, 0);
 		JpDenoiseParams dp; std::memset(&dp, 0, sizeof(dp));
 		dp.struct_bytes = (int32_t)sizeof(dp); dp.width = rp.width; dp.height = rp.height; dp.iterations = film->denoise.iterations;
 		dp.sigma_color = film->denoise.sigmaColor; dp.sigma_normal = film->denoise.sigmaNormal; dp.sigma_depth = film->denoise.sigmaDepth; dp.demodulate = film->denoise.demodulate ? 1 : -1;
-		lastStatus = api.render_denoised(ctx, &rp, film->guideSpp_, film->wantDenoise ? &dp : nullptr, floatFilm ? rgb.data() : nullptr, film->wantLDR ? ldr.data() : nullptr, galb.data(), gnrm.data(), gdep.data());
+		lastStatus = api.render_denoised(ctx, &rp, film->guideSpp_, film->wantDenoise ? &dp : nullptr, floatFilm ? rgb.data() : nullptr, wantLDR ? ldr.data() : nullptr, galb.data(), gnrm.data(), gdep.data());
 	}
-	else if (film->wantLDR)
+	else if (wantLDR)
 	{   // FFilm::RequestDeviceLDR: gamma_encoding (film.h:24) runs on the GPU, the film comes back as 3 bytes per pixel
 		ldr.assign((size_t)rp.width * rp.height * 3, 0);
 		lastStatus = api.render_rgb8(ctx, &rp, ldr.data(), floatFilm ? rgb.data() : nullptr);
@@ -259,7 +291,12 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 		film->albedo.resize(n); film->normal.resize(n); film->depth.swap(gdep);
 		for (size_t i = 0; i < n; i++) { film->albedo[i] = FColor(galb[3 * i], galb[3 * i + 1], galb[3 * i + 2]); film->normal[i] = FVector3(gnrm[3 * i], gnrm[3 * i + 1], gnrm[3 * i + 2]); }
 	}
-	if (film->wantLDR) { film->ldr8.swap(ldr); film->floatValid = floatFilm; }   // (after AddColor: any later change of a pixel drops the bytes again)
+	if (wantLDR) { film->ldr8.swap(ldr); film->floatValid = floatFilm; }   // (after AddColor: any later change of a pixel drops the bytes again)
+	if (film->haveToneMap)
+	{   // FFilm::ToneMapScale: the exposure scale the transform used
+		JpToneMapInfo ti; std::memset(&ti, 0, sizeof(ti)); ti.struct_bytes = (int32_t)sizeof(ti);
+		if (api.get_tonemap_info(ctx, &ti) == JP_OK) film->toneMapScale = ti.scale_last;
+	}
 	api.get_counters(ctx, &counters);
 	fprintf(stderr, "finish rendering ...\n");
 	fprintf(stderr, "FIntegrator::Render used %f seconds.\n", (float)(counters.render_ms / 1000.0));   // integrator.cc:77-79

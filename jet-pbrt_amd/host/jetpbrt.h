@@ -336,6 +336,8 @@ inline uint8_t gamma_encoding(Float x) { return (uint8_t)(std::pow(Clamp01(x), (
 
 // FFilm::RequestDenoise: the fields of JpDenoiseParams (0: the library's default; INTEGRATION.md "Guides and denoising")
 struct FDenoiseOptions { int iterations = 0; Float sigmaColor = 0, sigmaNormal = 0, sigmaDepth = 0; bool demodulate = true; };
+// FFilm::SetToneMap: the fields of JpToneMap (curve: JP_CURVE_*; 0: the library's default; INTEGRATION.md "Film")
+struct FToneMap { int curve = JP_CURVE_CLAMP; bool autoExposure = false; Float ev = 0, key = 0, white = 0, pctLow = 0, pctHigh = 0; };
 
 class FFilm                                                      // film.h:27-94
 {
@@ -364,6 +366,15 @@ public:
 	const std::vector<FColor>& Albedo() const { return albedo; }
 	const std::vector<FVector3>& Normal() const { return normal; }
 	const std::vector<Float>& Depth() const { return depth; }
+	// The linear-light film (INTEGRATION.md "Film"): SetHDR keeps radiance above 1 (SaveAsImage(HDR) then writes the unclamped film, and a denoise request filters
+	// it unclamped), SetSampleClamp tames fireflies sample by sample, SetToneMap -- which turns HDR on: highlights above 1 are what the curves compress -- has the
+	// integrator deliver the 8-bit bytes of BMP / PPM through exposure and a tone curve on the GPU (next to the fp32 film, or instead of it with RequestDeviceLDR).
+	// ToneMapScale(): the exposure scale the last render's transform used (auto-exposure: from the film's luminance histogram).
+	void SetHDR(bool on = true) { hdr = on; }
+	void SetSampleClamp(Float c) { sampleClamp = c; }
+	void SetToneMap(const FToneMap& t) { toneMap = t; haveToneMap = true; hdr = true; }
+	Float ToneMapScale() const { return toneMapScale; }
+	bool hdr = false, haveToneMap = false; Float sampleClamp = 0, toneMapScale = 0; FToneMap toneMap;
 	bool wantGuides = false, wantDenoise = false; int guideSpp_ = 8; FDenoiseOptions denoise;
 	std::vector<FColor> albedo; std::vector<FVector3> normal; std::vector<Float> depth;
 	int width, height; std::vector<FColor> pixels;
@@ -565,7 +576,8 @@ protected:
 	mutable int uploadedLights = JP_LIGHTS_ALL, ctxLights = JP_LIGHTS_ALL;   // FScene::lightSampling of the uploaded scene; the mode the context was last told
 	mutable unsigned long long uploadedEnv = 0, ctxEnv = 0; mutable int uploadedEnvUp = 0, ctxEnvUp = 0, uploadedEnvImp = 0, ctxEnvImp = 0;   // FEnvironmentMap::id (0: none), up axis and importance: of the uploaded scene; last sent to the context
 	mutable JpLens ctxLens = {};                                    // the lens the context was last told (FCamera::SetLens; radius 0: none)
-	mutable bool ctxNormalMaps = false;                             // ... or normal maps (jp_set_normal_maps)
+	mutable JpFilm ctxFilm = {}; mutable JpToneMap ctxToneMap = {};   // the film state and tone map the context was last told (FFilm::SetHDR / SetSampleClamp / SetToneMap; zeros: none)
+	mutable bool ctxNormalMaps = false;                            // ... or normal maps (jp_set_normal_maps)
 	mutable bool ctxNormals = false;                                // the context holds vertex normals of an earlier upload (jp_set_vertex_normals)
 	mutable int lastStatus = 0;
 	mutable JpCounters counters;
