@@ -546,6 +546,38 @@ int  jp_perturb_normals(int32_t n, const float* nb, const float* ng, const float
 /* pure host: dpdu, dpdv of a triangle from its corners and uvs as the header defines them; ok_out 0 (and both 0) where det is 0 or not finite */
 int  jp_triangle_tangents(int32_t n, const float* p0, const float* p1, const float* p2, const float* uv6, float* dpdu, float* dpdv, int32_t* ok_out);
 
+/* Texture sampling (additive to ABI 7; INTEGRATION.md "Texture sampling" has the definition, include/jp_tex_sampling.h the code).  A record per image texture and
+ * per normal map: a wrap mode per axis, a uv scale and offset (t = c * scale + offset) and a filter.  Bilinear colour lookups are quantised to 8 bits per channel
+ * (the side word of the nearest lookup).  Normal maps take CLAMP or REPEAT and their bilinear filter; scales are > 0.  Context state like the normal maps: validated
+ * and copied here, read by the next jp_upload_scene*, whose JpTextures.n_textures must equal n_textures where tex != NULL (a plain jp_upload_scene counts as 0) and
+ * whose JpNormalMaps.n_maps must equal n_maps where map != NULL (no maps set: 0): else JP_ERR_INVALID_ARGUMENT, and the context keeps the scene it had.  A record
+ * that is not the identity on a SOLID or CHECKER texture is refused at the upload.  No state, or identity records only (CLAMP, the kind's filter, scale 1,
+ * offset 0): exactly the upload without them -- the same kernels, sampled_last_render 0, no device bytes.  Else k_texel_s / k_normal_map_s take the place of
+ * k_texel / k_normal_map, and jp_surface, jp_shading_normal and the guides follow the records. */
+enum { JP_WRAP_CLAMP = 0, JP_WRAP_REPEAT = 1, JP_WRAP_MIRROR = 2 };
+enum { JP_FILTER_DEFAULT = 0, JP_FILTER_NEAREST = 1, JP_FILTER_BILINEAR = 2 };   /* DEFAULT: nearest for colour textures, bilinear for normal maps */
+typedef struct JpTexSampler { int32_t wrap_u, wrap_v, filter; float scale_u, scale_v, offset_u, offset_v; } JpTexSampler;
+typedef struct JpTextureSampling {
+    int32_t struct_bytes;
+    int32_t n_textures;  const JpTexSampler* tex;      /* one per texture of the next upload's JpTextures; NULL: none for colour textures */
+    int32_t n_maps;      const JpTexSampler* map;      /* one per map of jp_set_normal_maps;              NULL: none for normal maps     */
+} JpTextureSampling;
+typedef struct JpTexSamplingInfo {
+    int32_t struct_bytes, n_active_textures, n_active_maps;   /* records of the uploaded scene that are not the identity                            */
+    int64_t table_bytes_device;                               /* 32 bytes per texture and per map (0: nothing active)                                */
+    int32_t sampled_last_render;                              /* the last jp_render* ran k_texel_s or k_normal_map_s                                 */
+    double  texel_ms, normal_map_ms;                          /* with jp_set_profiling: the launches of k_texel / k_texel_s and of k_normal_map / k_normal_map_s of the last render */
+} JpTexSamplingInfo;
+int  jp_set_texture_sampling(JpContext* ctx, const JpTextureSampling* sampling);   /* NULL removes it */
+int  jp_check_texture_sampling(const JpTextureSampling* sampling, int32_t* n_active_textures, int32_t* n_active_maps);   /* pure host: the same validation, status and message (counts may be NULL) */
+int  jp_get_texture_sampling_info(JpContext* ctx, JpTexSamplingInfo* out);
+/* pure host, the very function the device runs: n uv pairs on one image (w, h, rgb8 row-major, top row first) -> rgb8_out 3 bytes each; the colour is (1 / 255) * byte.
+ * NULL or an identity record: the lookup without records */
+int  jp_texture_lookup(const JpTexSampler* s_or_null, int32_t w, int32_t h, const uint8_t* rgb8, int32_t n, const float* uv, uint8_t* rgb8_out);
+/* pure host: jp_perturb_normals with the map addressed through a record (NULL or identity: jp_perturb_normals) */
+int  jp_perturb_normals_sampled(const JpTexSampler* s_or_null, int32_t n, const float* nb, const float* ng, const float* dpdu, const float* dpdv, const float* uv,
+                                int32_t width, int32_t height, const uint8_t* rgb8, float strength, float* ns_out, int32_t* perturbed_out);
+
 /* Lens (additive to ABI 7; INTEGRATION.md "Lens" has the definition).  The reference's camera is a pinhole: every camera ray starts at JpCamera.pos.  A lens of
  * radius > 0 gives depth of field: the camera ray of a sample starts at a point of the aperture -- a disk (blades 0) or a regular polygon of 3 .. 16 blades with
  * circumradius `radius`, its first vertex rotation_deg from the camera's right axis toward its up axis -- and passes through the point where the pinhole ray meets

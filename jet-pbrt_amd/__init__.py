@@ -263,6 +263,83 @@ def perturb_normals(nb, ng, dpdu, dpdv, uv, rgb8, strength=1.0):
     return ns, on
 
 
+JP_WRAP_CLAMP, JP_WRAP_REPEAT, JP_WRAP_MIRROR = 0, 1, 2
+JP_FILTER_DEFAULT, JP_FILTER_NEAREST, JP_FILTER_BILINEAR = 0, 1, 2
+
+
+class JpTexSampler(C.Structure):
+    """include/jetpbrt_amd.h: JpTexSampler, one texture's or one normal map's sampling record"""
+    _fields_ = [("wrap_u", C.c_int32), ("wrap_v", C.c_int32), ("filter", C.c_int32), ("scale_u", C.c_float), ("scale_v", C.c_float),
+                ("offset_u", C.c_float), ("offset_v", C.c_float)]
+
+
+class JpTextureSampling(C.Structure):
+    """include/jetpbrt_amd.h: JpTextureSampling (jp_set_texture_sampling); struct_bytes = sizeof(JpTextureSampling)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_textures", C.c_int32), ("tex", C.POINTER(JpTexSampler)), ("n_maps", C.c_int32), ("map", C.POINTER(JpTexSampler))]
+
+
+class JpTexSamplingInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_active_textures", C.c_int32), ("n_active_maps", C.c_int32), ("table_bytes_device", C.c_int64),
+                ("sampled_last_render", C.c_int32), ("texel_ms", C.c_double), ("normal_map_ms", C.c_double)]
+
+
+def tex_sampler(wrap_u=JP_WRAP_CLAMP, wrap_v=None, filter=JP_FILTER_DEFAULT, scale=(1.0, 1.0), offset=(0.0, 0.0)):
+    """A JpTexSampler; wrap_v None: wrap_u on both axes.  The defaults are the identity record."""
+    return JpTexSampler(int(wrap_u), int(wrap_u if wrap_v is None else wrap_v), int(filter), float(scale[0]), float(scale[1]), float(offset[0]), float(offset[1]))
+
+
+def texture_sampling(tex=None, maps=None):
+    """A JpTextureSampling: tex / maps a list of JpTexSampler (None entries: the identity), one per texture / per normal map of the next upload, or None for
+    none of that kind.  The arrays are kept alive on the returned object as ._keep."""
+    def arr(lst):
+        if lst is None:
+            return 0, None
+        a = (JpTexSampler * max(1, len(lst)))()
+        for i, s in enumerate(lst):
+            a[i] = tex_sampler() if s is None else s
+        return len(lst), a
+    nt, at = arr(tex); nm, am = arr(maps)
+    v = JpTextureSampling(C.sizeof(JpTextureSampling), nt, at if at is None else C.cast(at, C.POINTER(JpTexSampler)), nm, am if am is None else C.cast(am, C.POINTER(JpTexSampler)))
+    v._keep = (at, am)
+    return v
+
+
+def check_texture_sampling(sampling):
+    """jp_check_texture_sampling: the validation of jp_set_texture_sampling (pure host code, no GPU) -> (n_active_textures, n_active_maps); raises JetPbrtError
+    with its message"""
+    a = C.c_int32(0); b = C.c_int32(0)
+    L = hip_lib()
+    _hip_status(L, L.jp_check_texture_sampling(C.byref(sampling), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def texture_lookup(sampler, rgb8, uv):
+    """jp_texture_lookup: the bytes the device's lookup delivers (include/jp_tex_sampling.h) for n uv pairs on the (h, w, 3) uint8 image under `sampler` (None: the
+    lookup without records) -> (n, 3) uint8; the colour is (1 / 255) * byte.  Pure host code."""
+    import numpy as np
+    img = np.ascontiguousarray(rgb8, np.uint8)
+    c = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    out = np.zeros((c.shape[0], 3), np.uint8)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_texture_lookup(None if sampler is None else C.byref(sampler), img.shape[1], img.shape[0], q(img), c.shape[0], q(c), q(out)))
+    return out
+
+
+def perturb_normals_sampled(sampler, nb, ng, dpdu, dpdv, uv, rgb8, strength=1.0):
+    """jp_perturb_normals_sampled: perturb_normals with the map addressed through `sampler` (None: perturb_normals).  Pure host code."""
+    import numpy as np
+    a = [np.ascontiguousarray(x, np.float32) for x in (nb, ng, dpdu, dpdv, uv)]
+    img = np.ascontiguousarray(rgb8, np.uint8)
+    n = a[0].shape[0]
+    ns = np.zeros((n, 3), np.float32); on = np.zeros(n, np.int32)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_perturb_normals_sampled(None if sampler is None else C.byref(sampler), n, q(a[0]), q(a[1]), q(a[2]), q(a[3]), q(a[4]), img.shape[1], img.shape[0],
+                                                q(img), float(strength), q(ns), q(on)))
+    return ns, on
+
+
 def triangle_tangents(p0, p1, p2, uv6):
     """jp_triangle_tangents: dpdu, dpdv of n triangles from their corners (n, 3) and uvs (n, 6) -> (dpdu (n, 3), dpdv (n, 3), ok (n,) int32).  Pure host code."""
     import numpy as np
@@ -676,6 +753,11 @@ def host_lib():
         L.jp_host_mat_set_normal_map.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
         L.jp_host_flatten_normal_maps.restype = C.POINTER(JpNormalMaps)
         L.jp_host_flatten_normal_maps.argtypes = [C.c_void_p]
+        L.jp_host_texture_set_sampling.argtypes = [C.c_void_p, C.c_int, C.POINTER(JpTexSampler)]
+        L.jp_host_normal_map_set_sampling.argtypes = [C.c_void_p, C.c_int, C.POINTER(JpTexSampler)]
+        L.jp_host_scene_set_texture_sampling_default.argtypes = [C.c_void_p, C.POINTER(JpTexSampler)]
+        L.jp_host_flatten_texture_sampling.restype = C.POINTER(JpTextureSampling)
+        L.jp_host_flatten_texture_sampling.argtypes = [C.c_void_p]
         L.jp_host_flatten_envmap.restype = C.POINTER(JpEnvMap)
         L.jp_host_flatten_envmap.argtypes = [C.c_void_p]
         _host = L
@@ -743,6 +825,11 @@ def hip_lib():
         L.jp_check_normal_maps.argtypes = [C.POINTER(JpNormalMaps), C.POINTER(C.c_int32)]
         L.jp_get_normal_map_info.argtypes = [C.c_void_p, C.POINTER(JpNormalMapInfo)]
         L.jp_perturb_normals.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        L.jp_set_texture_sampling.argtypes = [C.c_void_p, C.POINTER(JpTextureSampling)]
+        L.jp_check_texture_sampling.argtypes = [C.POINTER(JpTextureSampling), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.jp_get_texture_sampling_info.argtypes = [C.c_void_p, C.POINTER(JpTexSamplingInfo)]
+        L.jp_texture_lookup.argtypes = [C.POINTER(JpTexSampler), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        L.jp_perturb_normals_sampled.argtypes = [C.POINTER(JpTexSampler), C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         L.jp_triangle_tangents.argtypes = [C.c_int32] + [C.c_void_p] * 7
         L.jp_set_lens.argtypes = [C.c_void_p, C.POINTER(JpLens)]
         L.jp_get_lens_info.argtypes = [C.c_void_p, C.POINTER(JpLensInfo)]
@@ -1110,6 +1197,16 @@ class Context:
         i = JpNormalMapInfo()
         i.struct_bytes = C.sizeof(JpNormalMapInfo)
         self._check(self.lib.jp_get_normal_map_info(self.h, C.byref(i)))
+        return i
+
+    def set_texture_sampling(self, sampling):
+        """jp_set_texture_sampling for the next upload: a JpTextureSampling (texture_sampling(...) builds one), or None for none"""
+        self._check(self.lib.jp_set_texture_sampling(self.h, None if sampling is None else C.byref(sampling)))
+
+    def texture_sampling_info(self):
+        i = JpTexSamplingInfo()
+        i.struct_bytes = C.sizeof(JpTexSamplingInfo)
+        self._check(self.lib.jp_get_texture_sampling_info(self.h, C.byref(i)))
         return i
 
     def shading_normal(self, origin, direction, tmin, tmax):

@@ -22,8 +22,10 @@ struct GuideConst
 // kernels keep their registers and their instruction streams
 // kMapped (k_guides_mapped, k_guides_mapped_lens, scenes with normal maps; jp_normal_map.h): the normal is the Ns the render uses there -- the smooth triangle's Ns where the scene has vertex
 // normals (nv.prim_vn may be null), then the material's map on top; instances of their own again
+// sm (jp_tex_sampling.h; both pointers null: no active record): the sampling records of the textures and the maps, a runtime branch in every form -- the albedo and the
+// normal guide describe the surface the render shades
 template <int kMode, bool kSmooth, bool kLens, bool kMapped = false>
-__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp, const NMapView* mp = nullptr)
+__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp, const SampView& sm, const NMapView* mp = nullptr)
 {
 	SceneAccess<kMode> acc(sc, depth);
 	const int npix = gc.width * gc.height;
@@ -53,7 +55,7 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 					else if (type == JP_SHAPE_RECTANGLE) n = dot(xyz(g3), rd) <= 0 ? xyz(g3) : -xyz(g3);
 					else if (type == JP_SHAPE_DISK) n = xyz(sc.prims[4 * h + 1]);
 					else n = normalize(p - xyz(sc.prims[4 * h]));
-					if constexpr (kMapped) n = mapped_shading_normal(sc.prims, nv, *mp, h, meta.x, meta.y, p, n);
+					if constexpr (kMapped) n = mapped_shading_normal(sc.prims, nv, *mp, h, meta.x, meta.y, p, n, sm.map);
 					else if (kSmooth) shading_normal(sc.prims, nv, h, meta.x, p, n);
 					t = tmax;
 					const int mat = meta.y;
@@ -61,7 +63,7 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 					{   // k_surface's colour; (1,1,1) stays where that is 0 by definition
 						const int mtype = sc.mat_type[mat];
 						const int tx = tv.mat_tex ? tv.mat_tex[mat] : -1;
-						if (tx >= 0) a = tex_color(tv, tex_sample(tv, tx, tex_uv(sc.prims, tv, h, meta.x, p), p));
+						if (tx >= 0) a = tex_color(tv, tex_sample_s(tv, sm.tex, tx, tex_uv(sc.prims, tv, h, meta.x, p), p));
 						else if (mtype == JP_MAT_MATTE || mtype == JP_MAT_MIRROR || mtype == JP_MAT_PLASTIC) a = xyz(sc.mats[4 * mat]);
 					}
 				}
@@ -75,35 +77,35 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 	}
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, SampView sm)
 {
-	guides_body<kMode, false, false>(sc, tv, depth, gc, albedo, normal, dist, NormView(), nullptr);
+	guides_body<kMode, false, false>(sc, tv, depth, gc, albedo, normal, dist, NormView(), nullptr, sm);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, SampView sm)
 {
-	guides_body<kMode, true, false>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr);
+	guides_body<kMode, true, false>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, JpLensPlan lp)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, JpLensPlan lp, SampView sm)
 {
-	guides_body<kMode, false, true>(sc, tv, depth, gc, albedo, normal, dist, NormView(), &lp);
+	guides_body<kMode, false, true>(sc, tv, depth, gc, albedo, normal, dist, NormView(), &lp, sm);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, JpLensPlan lp)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, JpLensPlan lp, SampView sm)
 {
-	guides_body<kMode, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp);
+	guides_body<kMode, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, sm);
 }
 
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, SampView sm)
 {
-	guides_body<kMode, false, false, true>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, &mp);
+	guides_body<kMode, false, false, true>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, &mp);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, JpLensPlan lp)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, JpLensPlan lp, SampView sm)
 {
-	guides_body<kMode, false, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, &mp);
+	guides_body<kMode, false, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, sm, &mp);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -201,12 +203,12 @@ namespace
 #define JP_DENOISE_SIGMA_NORMAL 0.1f
 #define JP_DENOISE_SIGMA_DEPTH  0.03f
 
-typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*);
-typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView);
-typedef void (*GuideLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, JpLensPlan);
-typedef void (*GuideSmoothLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, JpLensPlan);
-typedef void (*GuideMappedKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView);
-typedef void (*GuideMappedLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, JpLensPlan);
+typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, SampView);
+typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, SampView);
+typedef void (*GuideLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, JpLensPlan, SampView);
+typedef void (*GuideSmoothLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, JpLensPlan, SampView);
+typedef void (*GuideMappedKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, SampView);
+typedef void (*GuideMappedLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, JpLensPlan, SampView);
 struct GuideLaunch { GuideKernel k; size_t lds; int depth; GuideSmoothKernel smooth; GuideLensKernel lens; GuideSmoothLensKernel smooth_lens; GuideMappedKernel mapped; GuideMappedLensKernel mapped_lens; };   // smooth: the twin a scene with vertex normals runs; lens: the twins of jp_set_lens
 template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth, k_guides_smooth<M>, k_guides_lens<M>, k_guides_smooth_lens<M>, k_guides_mapped<M>, k_guides_mapped_lens<M> }; return g; }
 // the walk trace_kernel(p, 0) gives jp_surface
@@ -251,13 +253,13 @@ int guides_launch(JpContext* c, const GuideConst& gc, float* albedo, float* norm
 	HIP_TRY(hipEventRecord(c->gd_ev[0], c->stream));
 	if (c->lens_on)
 	{   // jp_set_lens: sample s stays the camera ray of sample s of the render
-		if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, lp);
-		else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, lp);
-		else hipLaunchKernelGGL(gk.lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, lp);
+		if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, lp, c->plan.sm);
+		else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, lp, c->plan.sm);
+		else hipLaunchKernelGGL(gk.lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, lp, c->plan.sm);
 	}
-	else if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp);
-	else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv);
-	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist);
+	else if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, c->plan.sm);
+	else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.sm);
+	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.sm);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->gd_ev[1], c->stream));
 	c->gd_timed = true; c->last_guide_spp = gc.spp;

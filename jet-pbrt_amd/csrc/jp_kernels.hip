@@ -1429,10 +1429,10 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shade_tex(SceneView sc, Queues q, 
 }
 
 // k_surface (jp_surface): the closest hit of k_trace's walk, then the uv k_texel computes and the colour k_shade_tex puts in the textured
-// slot (untextured matte / mirror / plastic: mat_params[0..2]; glass, metal, no material, no hit: 0)
+// slot (untextured matte / mirror / plastic: mat_params[0..2]; glass, metal, no material, no hit: 0); sm.tex (null: none): the textures' sampling records
 template <int kMode>
 __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, int depth, int n, const float* o, const float* d, const float* tmin, const float* tmax_in,
-                                                      int* prim, float* uv, float* albedo)
+                                                      int* prim, float* uv, float* albedo, SampView sm)
 {
 	SceneAccess<kMode> acc(sc, depth);
 	for (int i = blockIdx.x * JP_BLOCK + threadIdx.x; i < n; i += gridDim.x * JP_BLOCK)
@@ -1453,7 +1453,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 			{
 				const int mtype = sc.mat_type[mat];
 				const int t = tv.mat_tex ? tv.mat_tex[mat] : -1;
-				if (t >= 0) a = tex_color(tv, tex_sample(tv, t, st, p));
+				if (t >= 0) a = tex_color(tv, tex_sample_s(tv, sm.tex, t, st, p));
 				else if (mtype == JP_MAT_MATTE || mtype == JP_MAT_MIRROR || mtype == JP_MAT_PLASTIC) a = xyz(sc.mats[4 * mat]);
 			}
 		}
@@ -1461,6 +1461,9 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 		albedo[3 * i] = a.x; albedo[3 * i + 1] = a.y; albedo[3 * i + 2] = a.z;
 	}
 }
+
+#define JP_TEX_SAMPLING_KERNELS
+#include "jp_tex_sampling.h"     // texture sampling records, part 2: k_texel_s, k_normal_map_s (part 1 comes with jp_normal_map.h's, part 3 at the end)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host runtime (same translation unit: the code below launches the kernels above)
@@ -1477,6 +1480,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_mis.h"              // estimator, part 2: k_shade_mis*, k_light_pdf and their entry points (jp_render.h declares the selector)
 #define JP_NORMAL_MAP_RUNTIME
 #include "jp_normal_map.h"       // normal maps, part 2: k_normal_map, k_shading_normal_mapped and their entry points (before the vertex normals' part 2, whose selector and hook hand out its kernels)
+#define JP_TEX_SAMPLING_RUNTIME
+#include "jp_tex_sampling.h"     // texture sampling records, part 3: the upload's table steps and the entry points (after jp_normal_map.h's part 2: pack_rgb8, jp_perturb_normals)
 #define JP_NORMALS_RUNTIME
 #include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points (jp_render.h declares the selector)
 #include "jp_lens_runtime.h"     // thin-lens camera: k_camera_rays and the lens entry points (jp_render.h reads the context's lens state)

@@ -10,6 +10,7 @@
 #include "jp_tex.h"
 #include "jp_normals.h"
 #include "../../include/jp_normal_map.h"
+#include "jp_tex_sampling.h"      // part 1: SampView, SampSlot (texture sampling records: the map's addressing)
 
 // ---- part 1 -----------------------------------------------------------------------------------------------------------------------------
 // A separate kernel argument like NormView: the kernels of scenes without maps do not change.
@@ -34,8 +35,8 @@ __device__ __forceinline__ V3 hit_normal(const float4* prims, int h, V3 p, V3 rd
 }
 
 // Ns' at the point p of device primitive h (caller's primitive index prim, material mat): N the geometric normal there, Nb the base normal (Ns of a smooth
-// triangle, else N); false: unperturbed (Ns untouched)
-__device__ __forceinline__ bool mapped_normal(const float4* prims, const NMapView& mp, int h, int prim, int mat, V3 p, V3 N, V3 Nb, V3& Ns)
+// triangle, else N); false: unperturbed (Ns untouched).  slots (jp_tex_sampling.h; null: none): the maps' sampling records -- a map with an active one is addressed through it
+__device__ __forceinline__ bool mapped_normal(const float4* prims, const NMapView& mp, int h, int prim, int mat, V3 p, V3 N, V3 Nb, V3& Ns, const SampSlot* slots = nullptr)
 {
 	if (mat < 0) return false;
 	const float2 mm = mp.mat[mat];
@@ -76,18 +77,23 @@ __device__ __forceinline__ bool mapped_normal(const float4* prims, const NMapVie
 	const int4 md = mp.desc[k];
 	const float nb[3] = { Nb.x, Nb.y, Nb.z }, ng[3] = { N.x, N.y, N.z };
 	float ns[3];
-	if (!jp_perturb_normal(nb, ng, dpdu, dpdv, uv.x, uv.y, mp.texels + md.z, md.x, md.y, mm.y, ns)) return false;
+	if (slots)
+	{
+		const SampSlot sl = slots[k];
+		if (!jp_perturb_normal_sampled(sl.active ? &sl.s : nullptr, nb, ng, dpdu, dpdv, uv.x, uv.y, mp.texels + md.z, md.x, md.y, mm.y, ns)) return false;
+	}
+	else if (!jp_perturb_normal(nb, ng, dpdu, dpdv, uv.x, uv.y, mp.texels + md.z, md.x, md.y, mm.y, ns)) return false;
 	Ns = mk(ns[0], ns[1], ns[2]);
 	return true;
 }
 
 // the Ns the render uses at a hit of a mapped scene: the smooth triangle's Ns (nv.prim_vn may be null: no vertex normals), then the map on top; N where neither applies
-__device__ __forceinline__ V3 mapped_shading_normal(const float4* prims, const NormView& nv, const NMapView& mp, int h, int prim, int mat, V3 p, V3 N)
+__device__ __forceinline__ V3 mapped_shading_normal(const float4* prims, const NormView& nv, const NMapView& mp, int h, int prim, int mat, V3 p, V3 N, const SampSlot* slots = nullptr)
 {
 	V3 Nb = N;
 	if (nv.prim_vn) shading_normal(prims, nv, h, prim, p, Nb);
 	V3 Ns = Nb;
-	mapped_normal(prims, mp, h, prim, mat, p, N, Nb, Ns);
+	mapped_normal(prims, mp, h, prim, mat, p, N, Nb, Ns, slots);
 	return Ns;
 }
 } // namespace jp
@@ -131,9 +137,10 @@ __global__ void __launch_bounds__(JP_BLOCK, 8) k_normal_map(SceneView sc, Queues
 	}
 }
 
-// k_shading_normal_mapped (jp_shading_normal on a mapped scene): k_shading_normal with the map on top -- an instance of its own, k_shading_normal keeps its code
+// k_shading_normal_mapped (jp_shading_normal on a mapped scene): k_shading_normal with the map on top -- an instance of its own, k_shading_normal keeps its code.
+// sm.map (null: none): the maps' sampling records, a runtime branch -- the hook follows the records the render's k_normal_map_s follows
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_shading_normal_mapped(SceneView sc, NormView nv, NMapView mp, int depth, int n, const float* o, const float* d, const float* tmin, const float* tmax_in,
+__global__ void __launch_bounds__(JP_BLOCK) k_shading_normal_mapped(SceneView sc, NormView nv, NMapView mp, SampView sm, int depth, int n, const float* o, const float* d, const float* tmin, const float* tmax_in,
                                                                        int* prim, float* ng, float* ns)
 {
 	SceneAccess<kMode> acc(sc, depth);
@@ -149,7 +156,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shading_normal_mapped(SceneView sc
 			const V3 p = ro + tmax * rd;
 			pr = meta.x;
 			N = hit_normal(sc.prims, h, p, rd);
-			Ns = mapped_shading_normal(sc.prims, nv, mp, h, meta.x, meta.y, p, N);
+			Ns = mapped_shading_normal(sc.prims, nv, mp, h, meta.x, meta.y, p, N, sm.map);
 		}
 		prim[i] = pr;
 		ng[3 * i] = N.x; ng[3 * i + 1] = N.y; ng[3 * i + 2] = N.z;
@@ -159,7 +166,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shading_normal_mapped(SceneView sc
 
 namespace
 {
-typedef void (*ShadingNormalMappedKernel)(SceneView, NormView, NMapView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*);
+typedef void (*ShadingNormalMappedKernel)(SceneView, NormView, NMapView, SampView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*);
 ShadingNormalMappedKernel shading_normal_mapped_kernel(const TraceLaunch& t)
 {
 	if (t.trace == k_trace<6>) return k_shading_normal_mapped<6>;

@@ -267,7 +267,7 @@ int jp_shading_normal(JpContext* c, int32_t n, const float* origin, const float*
 	HIP_TRY(hipMemcpyAsync(d_o, origin, (size_t)n * 12, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_d, dir, (size_t)n * 12, hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
 	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-	if (km) hipLaunchKernelGGL(km, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.nv, c->plan.mp, tk.depth, n, (const float*)d_o, (const float*)d_d, (const float*)d_t0, (const float*)d_t1, d_prim, d_g, d_s);
+	if (km) hipLaunchKernelGGL(km, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.nv, c->plan.mp, c->plan.sm, tk.depth, n, (const float*)d_o, (const float*)d_d, (const float*)d_t0, (const float*)d_t1, d_prim, d_g, d_s);
 	else hipLaunchKernelGGL(k, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.nv, c->plan.smooth ? 1 : 0, tk.depth, n, (const float*)d_o, (const float*)d_d, (const float*)d_t0, (const float*)d_t1, d_prim, d_g, d_s);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(ng, d_g, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));

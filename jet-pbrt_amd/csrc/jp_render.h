@@ -5,7 +5,7 @@
 // ---- render ---------------------------------------------------------------------------------------------------------------
 namespace
 {
-enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4, CLS_NORMAL = 5, CLS_NMAP = 6 };   // (CLS_NORMAL: k_normal, stamped inside its CLS_SHADE pair -- a share of shade_ms, JpNormalInfo)
+enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4, CLS_NORMAL = 5, CLS_NMAP = 6, CLS_TEXEL = 7 };   // (CLS_NORMAL: k_normal, stamped inside its CLS_SHADE pair -- a share of shade_ms, JpNormalInfo)
 
 // the lens in force as the kernels take it (zeros while none is set: the kernels then do not read it); the camera is the uploaded scene's
 int lens_plan_of(const JpContext* c, JpLensPlan& lp)
@@ -70,6 +70,14 @@ struct Stamper
 	}
 	~Stamper() { if (!c->profiling) return; hipEventRecord(c->evpool[a + 1], c->stream); JpContext::Stamp s = { cls, a, a + 1 }; c->stamps.push_back(s); }
 };
+
+// k_texel, or its twin k_texel_s where a colour texture of the scene has an active sampling record (jp_tex_sampling.h); with profiling, timed inside the CLS_SHADE pair
+static void launch_texel(JpContext* c, const ScenePlan& p, int grid, int cur, const TexView& tv)
+{
+	Stamper t(c, CLS_TEXEL);
+	if (p.sm.tex) hipLaunchKernelGGL(k_texel_s, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm);
+	else hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
+}
 
 // ---- the shard: JpRenderParams checked, its bands' rows counted, a lane's share of them ----------------------------------
 struct Shard { int band, count, index, local_rows, lane_rows; };     // local_rows: rows of the shard's bands; lane_rows: the ones this lane renders
@@ -223,7 +231,7 @@ OtherKernel other_kernel(const ScenePlan& p) { return p.trav_mode == 5 ? k_other
 // jp_trace / jp_surface.  JpOptions::trace_walk (tests; jp_surface passes 0): 1 the binary tree, 2 the 8-wide tree, 3 the caller's tree verbatim; else what the
 // render's closest-hit rays walk.  The one-ray-per-lane kernels keep the whole stack in LDS: a 4-wide tree deeper than 64 KB of stack falls back to the binary / verbatim walk
 typedef void (*TraceKernel)(SceneView, int, int, const float*, const float*, const float*, const float*, int*, float*, int*, float*);
-typedef void (*SurfaceKernel)(SceneView, TexView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*);
+typedef void (*SurfaceKernel)(SceneView, TexView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*, SampView);
 struct TraceLaunch { TraceKernel trace; SurfaceKernel surface; size_t lds; int depth; };     // (surface: null for the 8-wide walk, which only trace_walk = 2 selects)
 template <int M> TraceLaunch trace_row(size_t lds, int depth) { TraceLaunch t = { k_trace<M>, k_surface<M>, lds, depth }; return t; }
 TraceLaunch trace_kernel(const ScenePlan& p, int tw, bool generic = true)   // generic false (jp_trace without JpOptions::reserved[0] == 1): a scene of flat shapes gets the lean closest-hit walk
@@ -376,8 +384,9 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 					Stamper t(c, CLS_SHADE);
 					if (smooth)
 					{   // scenes with vertex normals: k_texel as ever, k_normal leaves Ns for every hit on a smooth triangle, the family's smooth twin shades with it
-						if (tex) hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
-						if (p.mapped) { Stamper tn(c, CLS_NMAP); hipLaunchKernelGGL(nk.normal_map, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv, p.mp); }   // normal maps: one kernel leaves Ns or Ns'
+						if (tex) launch_texel(c, p, grid, cur, tv);
+						if (p.mapped && p.sm.map) { Stamper tn(c, CLS_NMAP); hipLaunchKernelGGL(k_normal_map_s, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv, p.mp, p.sm); }   // ... addressed through a sampling record: its twin
+						else if (p.mapped) { Stamper tn(c, CLS_NMAP); hipLaunchKernelGGL(nk.normal_map, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv, p.mp); }   // normal maps: one kernel leaves Ns or Ns'
 						else { Stamper tn(c, CLS_NORMAL); hipLaunchKernelGGL(nk.normal, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv); }
 						const size_t l = p.shade_lds_bytes;
 						if (tex)
@@ -396,7 +405,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 					}
 					else if (tex)
 					{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
-						hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
+						launch_texel(c, p, grid, cur, tv);
 						if (mis && p.env) hipLaunchKernelGGL(mk2.env_tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev, mv);
 						else if (mis) hipLaunchKernelGGL(mk2.pick_tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, mv);
 						else if (p.env) hipLaunchKernelGGL(vk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev);
@@ -615,7 +624,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
 	c->last_hdr = 0;
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0; c->last_sampled = 0;
 	if (c->plan.mapped && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with normal maps, jp_set_normal_maps)");
 	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
 	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
@@ -631,6 +640,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	c->last_mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_smooth = c->plan.smooth && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_nmapped = c->plan.mapped && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_sampled = ((c->plan.textured && c->plan.sm.tex) || (c->plan.mapped && c->plan.sm.map)) && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_lens = c->lens_on ? 1 : 0;                                    // (every integrator forms the lens ray)
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
@@ -693,7 +703,7 @@ int finish_one(JpContext* c, JpCounters& o)
 {
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	DevCounters h; HIP_TRY(hipMemcpy(&h, c->cnt.get<void>(), sizeof(h), hipMemcpyDeviceToHost));
-	c->normal_ms = 0.0; c->normal_map_ms = 0.0;
+	c->normal_ms = 0.0; c->normal_map_ms = 0.0; c->texel_ms = 0.0;
 	o.closest_rays += h.closest; o.closest_hits += h.closest_hit; o.shadow_rays += h.shadow; o.shadow_occluded += h.shadow_occ; o.certified_fallback_rays += h.cert_fallback;
 	for (const JpContext::Stamp& s : c->stamps)
 	{
@@ -704,6 +714,7 @@ int finish_one(JpContext* c, JpCounters& o)
 		else if (s.cls == CLS_PATH) { o.path_ms += t; o.path_launches++; }
 		else if (s.cls == CLS_NORMAL) c->normal_ms += t;
 		else if (s.cls == CLS_NMAP) c->normal_map_ms += t;
+		else if (s.cls == CLS_TEXEL) c->texel_ms += t;
 		else o.other_ms += t;
 	}
 	return JP_OK;
@@ -883,7 +894,7 @@ int jp_surface(JpContext* c, int32_t n, const float* origin, const float* dir, c
 	HIP_TRY(hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
 	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
 	const TraceLaunch tk = trace_kernel(c->plan, 0);                // the walk jp_trace takes by default (what the render's closest-hit rays walk)
-	hipLaunchKernelGGL(tk.surface, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.tv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a);
+	hipLaunchKernelGGL(tk.surface, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.tv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a, c->plan.sm);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(albedo, d_a, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));

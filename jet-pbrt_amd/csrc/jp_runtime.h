@@ -59,6 +59,7 @@ struct ScenePlan
 	NormView nv = {}; bool smooth = false;                                             // vertex normals (jp_normals.h): at least one smooth triangle; k_shade's row is then <false, false, false>
 	NMapView mp = {}; bool mapped = false;                                             // normal maps (jp_normal_map.h): at least one material whose map perturbs; smooth is then set too (the smooth row, k_normal_map in k_normal's place)
 	int nm_maps = 0, nm_mapped = 0; long long nm_texel_bytes = 0, nm_table_bytes = 0;   // ... and what jp_get_normal_map_info reports of the uploaded scene's maps
+	SampView sm = {}; int ts_active_textures = 0, ts_active_maps = 0; long long ts_table_bytes = 0;   // texture sampling records (jp_tex_sampling.h): the slots of the textures / maps where one is active (k_texel_s / k_normal_map_s then), and what jp_get_texture_sampling_info reports
 	EnvView ev = {}; bool env = false; double env_mean_sum = 0.0;                      // environment map (jp_env.h): the texel tables; the map light's weight in the light table is (env_mean_sum * pi) * R^2
 	int trav_mode = 0, stack_depth = 1, stack_depth_q4 = 0; bool scene_in_lds = false, shade_prims_in_lds = false; size_t lds_bytes = 0, lds_bytes_shadow = 0;
 	bool cert = false;                                                                 // reference semantics, certified walk (Walker<6>)
@@ -83,6 +84,7 @@ struct SceneTables
 	DevBuf env_texel, env_bins, env_rows;                            // environment map (jp_env.h)
 	DevBuf prim_vn;                                                  // vertex normals (jp_normals.h)
 	DevBuf nm_desc, nm_texels, nm_mat, nm_prim_uv;                   // normal maps (jp_normal_map.h)
+	DevBuf ts_tex, ts_map;                                           // texture sampling records (jp_tex_sampling.h)
 };
 // The arrays behind a Queues view (the fused schedule's region queues have no hit records and no per-block counts)
 struct QueueBufs { DevBuf ray_o[2], ray_d[2], beta[2], blk_q[2], hit, lacc, sh_o, sh_d, sh_c, blk_sh; };
@@ -95,6 +97,9 @@ struct VertexNormalsHost { bool set = false; int n_triangles = 0, n_smooth = 0; 
 // the maps jp_set_normal_maps copied, waiting for the next upload (set false: none); texels already one dword each, neutral: R == G == 128 everywhere
 struct NormalMapsHost { bool set = false; int n_materials = 0, n_triangles = 0, n_mapped = 0; std::vector<int> width, height, mat_map; std::vector<long long> first; std::vector<char> neutral;
                         std::vector<unsigned int> texels; std::vector<float> strength, tri_uv; };
+
+// the records jp_set_texture_sampling copied, waiting for the next upload (has_tex / has_map false: none of that kind)
+struct TexSamplingHost { bool has_tex = false, has_map = false; int n_textures = 0, n_maps = 0, n_active_textures = 0, n_active_maps = 0; std::vector<JpTexSampler> tex, map; };
 
 struct JpContext
 {
@@ -159,6 +164,10 @@ struct JpContext
 	// normal maps (jp_normal_map.h): the maps the next upload takes (jp_set_normal_maps) and what jp_get_normal_map_info reports; the side records are nside
 	NormalMapsHost nmaps;
 	int last_nmapped = 0; double normal_map_ms = 0.0;
+	// texture sampling records (jp_tex_sampling.h): the records the next upload takes (jp_set_texture_sampling), the texture count of the upload in progress
+	// (jp_upload_scene_textured tells jp_upload_scene; 0 else) and what jp_get_texture_sampling_info reports
+	TexSamplingHost tsamp;
+	int upload_n_textures = 0, last_sampled = 0; double texel_ms = 0.0;
 	// thin-lens camera (jp_lens_runtime.h): render-time state like the estimator (jp_set_lens; a lane takes its parent's before it renders) and what the last
 	// render ran.  The plan is a kernel argument made per launch from the uploaded camera: the lens owns no device memory.
 	JpLens lens = {}; bool lens_on = false; int last_lens = 0;
@@ -174,6 +183,10 @@ static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, con
 static int upload_environment_map(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, bool pick);
 static int upload_vertex_normals(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s);   // jp_normals.h
 static int upload_normal_maps(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s);      // jp_normal_map.h
+static int check_sampling_counts(const JpContext* c, int n_textures);                               // jp_tex_sampling.h
+static int check_sampling_textures(const JpContext* c, const JpTextures* t);
+static int upload_map_sampling(JpContext* c, SceneTables& T, ScenePlan& plan);
+static int upload_tex_sampling(JpContext* c, SceneTables& T, ScenePlan& plan);
 
 // a context buffer that kernels in flight may still use: grown only once the stream is idle (nothing happens when the capacity suffices)
 static int reserve_idle(JpContext* c, DevBuf& b, size_t bytes)
@@ -195,6 +208,7 @@ static void free_scene(JpContext* c)
 	c->side.reset();                                               // ... and the side array only textured frames use (callers synchronise first)
 	c->plan.nv = NormView(); c->plan.smooth = false; c->vn_triangles = c->vn_smooth = 0; c->vn_table_bytes = 0; c->nside.reset();
 	c->plan.mp = NMapView(); c->plan.mapped = false; c->plan.nm_maps = c->plan.nm_mapped = 0; c->plan.nm_texel_bytes = c->plan.nm_table_bytes = 0;
+	c->plan.sm = SampView(); c->plan.ts_active_textures = c->plan.ts_active_maps = 0; c->plan.ts_table_bytes = 0;
 }
 
 // Which build of glibc's sinf / cosf / sincosf does this host run (jp_shading.h, sincosf_libm)?  The reference computes its

@@ -82,7 +82,11 @@ __device__ __forceinline__ unsigned int tex_sample(const TexView& tv, int t, flo
 // the colour a side word stands for: (1 / 255) * byte (texture.cc), or a colour of the table
 __device__ __forceinline__ V3 tex_color(const TexView& tv, unsigned int w)
 {
-	if (w & JP_TEX_IMAGE_TAG)
+	// The image tag is the word's sign bit, and w is never 0 here (k_shade_tex tests the word first, tex_sample always tags it): written as the compare
+	// `(int)w < 1` the k_shade*_tex kernels have always been built with.  With `w & JP_TEX_IMAGE_TAG` the optimiser picks between that form and
+	// `(int)w > -1` depending on what else the translation unit holds, and the two orders of the branches below are different instruction streams
+	// (tools/asm_kernel_diff.py; DESIGN.md "Texture sampling").
+	if ((int)w < 1)
 	{
 		const float s = 1.0f / 255.0f;
 		return mk(s * (float)(w & 0xffu), s * (float)((w >> 8) & 0xffu), s * (float)((w >> 16) & 0xffu));

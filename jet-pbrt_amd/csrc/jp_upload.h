@@ -78,6 +78,8 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	const bool pick = c->light_mode == JP_LIGHTS_POWER_ONE;
 	SceneCheck k;
 	if (const int st = check_scene(s, pick, k); st != JP_OK) return st;
+	const int n_textures = c->upload_n_textures; c->upload_n_textures = 0;   // (jp_upload_scene_textured's count; a plain upload has none)
+	if (const int st = check_sampling_counts(c, n_textures); st != JP_OK) return st;   // jp_set_texture_sampling: refused while the old scene is still there
 	HIP_TRY(hipSetDevice(c->device));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	free_scene(c);                                                  // first: the old and the new scene are never resident together
@@ -95,6 +97,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	if (pick) if (const int st = upload_light_table(c, T, p, s, t.light_area); st != JP_OK) return st;
 	if (c->vnormals.set) if (const int st = upload_vertex_normals(c, T, p, s); st != JP_OK) return st;   // (a scene whose normals are all flat keeps its plan)
 	if (c->nmaps.set) if (const int st = upload_normal_maps(c, T, p, s); st != JP_OK) return st;          // (so does a scene whose maps perturb nothing)
+	if (const int st = upload_map_sampling(c, T, p); st != JP_OK) return st;                              // (... and a scene whose maps' sampling records are all the identity)
 
 	c->tab = std::move(T); c->plan = p; c->plan.have_scene = true;
 	c->build_on_device = k.device_build; c->build_ms = build_ms; c->bvh_height = t.height; c->bvh_nodes = k.ref_sem ? s->n_bvh_nodes : t.n_nodes;
@@ -291,7 +294,9 @@ extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const Jp
 	if (!t) return jp_upload_scene(c, s);
 	long long pool; int ntm;
 	if (const int st = check_textures(s, t, pool, ntm); st != JP_OK) return st;
-	const int st = jp_upload_scene(c, s);                              // (validates the scene; drops the textures of an earlier upload)
+	if (const int st = check_sampling_textures(c, t); st != JP_OK) return st;
+	c->upload_n_textures = t->n_textures;
+	const int st = jp_upload_scene(c, s); c->upload_n_textures = 0;                              // (validates the scene; drops the textures of an earlier upload)
 	if (st != JP_OK) return st;
 	if (ntm == 0) return JP_OK;                                        // no textures, or textures no material uses: the untextured scene, exactly
 	TexTables x; build_texture_tables(s, t, pool, x);
@@ -307,5 +312,6 @@ extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const Jp
 	tv.desc = T.tex_desc.get<int4>(); tv.col = T.tex_col.get<float4>(); tv.texels = T.texels.get<unsigned int>();
 	tv.mat_tex = T.mat_tex.get<int>(); tv.prim_uv = T.prim_uv.get<float2>();
 	c->plan.textured = true; c->n_textures = t->n_textures; c->n_tex_mats = ntm; c->texel_bytes = (long long)x.texels.size() * 4;
+	if (upload_tex_sampling(c, T, c->plan) != JP_OK) { free_scene(c); return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: out of device memory for the sampling records"); }
 	return JP_OK;
 }

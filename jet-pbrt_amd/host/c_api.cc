@@ -183,6 +183,37 @@ int jp_host_mat_set_normal_map(void* h, int mat, int map, float strength)
 	return 0;
 }
 
+// texture sampling: FImageTexture::SetSampling / FNormalMap::SetSampling / FScene::SetTextureSamplingDefault from a JpTexSampler (null: back to none of its own)
+static FTexSampling sampling_of(const JpTexSampler* r)
+{
+	FTexSampling s; s.wrapU = (EWrap)r->wrap_u; s.wrapV = (EWrap)r->wrap_v; s.filter = (EFilter)r->filter;
+	s.scaleU = r->scale_u; s.scaleV = r->scale_v; s.offsetU = r->offset_u; s.offsetV = r->offset_v;
+	return s;
+}
+int jp_host_texture_set_sampling(void* h, int tex, const JpTexSampler* r)
+{
+	HostScene* hs = (HostScene*)h;
+	FImageTexture* it = tex >= 0 && tex < (int)hs->texs.size() ? dynamic_cast<FImageTexture*>(hs->texs[tex].get()) : nullptr;
+	if (!it) { hs->error = "jp_host_texture_set_sampling: no such image texture"; return -1; }
+	if (r) it->SetSampling(sampling_of(r)); else { it->sampling = FTexSampling(); it->hasSampling = false; }
+	hs->flattened = false;
+	return 0;
+}
+int jp_host_normal_map_set_sampling(void* h, int map, const JpTexSampler* r)
+{
+	HostScene* hs = (HostScene*)h;
+	if (map < 0 || map >= (int)hs->nmaps.size()) { hs->error = "jp_host_normal_map_set_sampling: no such map"; return -1; }
+	if (r) hs->nmaps[map]->SetSampling(sampling_of(r)); else { hs->nmaps[map]->sampling = FTexSampling(); hs->nmaps[map]->hasSampling = false; }
+	hs->flattened = false;
+	return 0;
+}
+int jp_host_scene_set_texture_sampling_default(void* h, const JpTexSampler* r)
+{
+	HostScene* hs = (HostScene*)h;
+	if (r) hs->scene->SetTextureSamplingDefault(sampling_of(r)); else { hs->scene->textureSamplingDefault = FTexSampling(); hs->scene->hasTextureSamplingDefault = false; }
+	hs->flattened = false;
+	return 0;
+}
 void jp_host_scene_preprocess(void* h) { HostScene* hs = (HostScene*)h; hs->scene->Preprocess(); hs->flattened = false; }
 int  jp_host_num_primitives(void* h) { return (int)((HostScene*)h)->scene->primitives.size(); }
 int  jp_host_num_lights(void* h) { return ((HostScene*)h)->scene->LightNum(); }
@@ -217,6 +248,14 @@ const JpNormalMaps* jp_host_flatten_normal_maps(void* h)
 	HostScene* hs = (HostScene*)h;
 	if (!jp_host_flatten(h) || hs->flat.n_normal_mapped == 0) return nullptr;
 	return &hs->flat.normalMaps;
+}
+
+// the flattened sampling records (valid with jp_host_flatten's view; null: every record is the identity, or the flattening failed)
+const JpTextureSampling* jp_host_flatten_texture_sampling(void* h)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!jp_host_flatten(h) || hs->flat.n_sampled == 0) return nullptr;
+	return &hs->flat.sampling;
 }
 
 // FGpuPathIntegrator(maxdepth).Render(scene, FCounterSampler(spp, seed), film, numthreads) -> rgb (added onto zeros)

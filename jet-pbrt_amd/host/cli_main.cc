@@ -4,6 +4,9 @@
 //             [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]
 //             [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]
 //             [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]
+//             [--texture-wrap clamp|repeat|mirror] [--texture-filter nearest|bilinear] [--texture-tile SU SV] [--normal-wrap clamp|repeat] [--normal-tile SU SV]
+// --texture-wrap / --texture-filter / --texture-tile: the sampling record (FScene::SetTextureSamplingDefault) of every image texture without one of its own: the wrap mode of
+// both axes, the filter, the uv scale; --normal-wrap / --normal-tile: the same for the --normal-map map (FNormalMap::SetSampling; a normal map is always filtered bilinearly).
 // --hdr: the unclamped film (FFilm::SetHDR): --format hdr then writes radiance above 1.  --sample-clamp C: each sample's radiance is scaled down to a maximum channel of C
 // before it enters the pixel's sum (FFilm::SetSampleClamp): fireflies.  --tonemap: the display transform of BMP / PPM on the GPU (FFilm::SetToneMap; implies --hdr):
 // exposure, the curve, then the gamma table; --exposure EV: the scale 2^EV (default 0), auto: from the film's luminance histogram (key 0.18); --white W: Reinhard's
@@ -111,12 +114,14 @@ int main(int argc, char* argv[])
 	FSmoothing smoothing;
 	std::string normalMap; float normalStrength = 1.f, normalFromHeight = 0.f; bool fromHeight = false;
 	bool hdr = false, haveToneMap = false; float sampleClamp = 0.f; FToneMap toneMap;
+	FTexSampling texSampling, normalSampling; bool haveTexSampling = false, haveNormalSampling = false;
 	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
 	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
 	fprintf(stderr, "          [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]\n");
 	fprintf(stderr, "          [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]\n");
 	fprintf(stderr, "          [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]\n");
+	fprintf(stderr, "          [--texture-wrap clamp|repeat|mirror] [--texture-filter nearest|bilinear] [--texture-tile SU SV] [--normal-wrap clamp|repeat] [--normal-tile SU SV]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -165,6 +170,34 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--normal-map") && i + 1 < argc) normalMap = argv[++i];
 		else if (!strcmp(argv[i], "--normal-strength") && i + 1 < argc) { normalStrength = (float)atof(argv[++i]); if (!std::isfinite(normalStrength)) { fprintf(stderr, "--normal-strength must be a number\n"); return 5; } }
 		else if (!strcmp(argv[i], "--normal-from-height") && i + 1 < argc) { normalFromHeight = (float)atof(argv[++i]); fromHeight = true; if (!std::isfinite(normalFromHeight)) { fprintf(stderr, "--normal-from-height must be a number\n"); return 5; } }
+		else if (!strcmp(argv[i], "--texture-wrap") && i + 1 < argc)
+		{
+			const char* m = argv[++i]; haveTexSampling = true;
+			if (!strcmp(m, "clamp")) texSampling.wrapU = texSampling.wrapV = EWrap::Clamp; else if (!strcmp(m, "repeat")) texSampling.wrapU = texSampling.wrapV = EWrap::Repeat;
+			else if (!strcmp(m, "mirror")) texSampling.wrapU = texSampling.wrapV = EWrap::Mirror;
+			else { fprintf(stderr, "--texture-wrap must be clamp, repeat or mirror\n"); return 5; }
+		}
+		else if (!strcmp(argv[i], "--texture-filter") && i + 1 < argc)
+		{
+			const char* m = argv[++i]; haveTexSampling = true;
+			if (!strcmp(m, "nearest")) texSampling.filter = EFilter::Nearest; else if (!strcmp(m, "bilinear")) texSampling.filter = EFilter::Bilinear;
+			else { fprintf(stderr, "--texture-filter must be nearest or bilinear\n"); return 5; }
+		}
+		else if ((!strcmp(argv[i], "--texture-tile") || !strcmp(argv[i], "--normal-tile")) && i + 2 < argc)
+		{
+			const bool normal = !strcmp(argv[i], "--normal-tile");
+			char *e0 = nullptr, *e1 = nullptr; const float su = strtof(argv[i + 1], &e0), sv = strtof(argv[i + 2], &e1);
+			if (e0 == argv[i + 1] || *e0 || e1 == argv[i + 2] || *e1 || !(su > 0.f) || !(sv > 0.f) || !std::isfinite(su) || !std::isfinite(sv)) { fprintf(stderr, "%s takes two numbers > 0\n", argv[i]); return 5; }
+			FTexSampling& s = normal ? normalSampling : texSampling; s.scaleU = su; s.scaleV = sv; (normal ? haveNormalSampling : haveTexSampling) = true;
+			i += 2;
+		}
+		else if (!strcmp(argv[i], "--normal-wrap") && i + 1 < argc)
+		{
+			const char* m = argv[++i]; haveNormalSampling = true;
+			if (!strcmp(m, "clamp")) normalSampling.wrapU = normalSampling.wrapV = EWrap::Clamp; else if (!strcmp(m, "repeat")) normalSampling.wrapU = normalSampling.wrapV = EWrap::Repeat;
+			else { fprintf(stderr, "--normal-wrap must be clamp or repeat\n"); return 5; }
+		}
+		else if (!strncmp(argv[i], "--texture-", 10) || !strcmp(argv[i], "--normal-wrap") || !strcmp(argv[i], "--normal-tile")) { fprintf(stderr, "%s: missing value\n", argv[i]); return 5; }
 		else if (!strcmp(argv[i], "--hdr")) hdr = true;
 		else if (!strcmp(argv[i], "--sample-clamp") && i + 1 < argc) { sampleClamp = (float)atof(argv[++i]); if (!(sampleClamp >= 0.f) || !std::isfinite(sampleClamp)) { fprintf(stderr, "--sample-clamp must be a number >= 0\n"); return 5; } }
 		else if (!strcmp(argv[i], "--tonemap") && i + 1 < argc)
@@ -207,6 +240,7 @@ int main(int argc, char* argv[])
 			for (size_t k = 0; k < grey.size(); k++) grey[k] = nmap->data[3 * k];
 			nmap = FNormalMap::FromHeight(grey.data(), nmap->width, nmap->height, normalFromHeight);
 		}
+		if (haveNormalSampling) nmap->SetSampling(normalSampling);
 	}
 	bool floorHasUV = true;
 	const FColor tint(envScale, envScale, envScale);
@@ -219,6 +253,7 @@ int main(int argc, char* argv[])
 	}
 	if (nmap && !floorHasUV) { fprintf(stderr, "--normal-map: %s/cornellbox/floor.obj has no texture coordinates (vt), so nothing would be mapped\n", assets.c_str()); return 5; }
 	if (map) scene->SetEnvironmentMap(map, envUp);
+	if (haveTexSampling) scene->SetTextureSamplingDefault(texSampling);   // every image texture without a sampling of its own (the scene is flattened at Render)
 	fprintf(stderr, "current scene: %s\n", scene->NameStr());
 	scene->SetLightSampling(estimator == JP_ESTIMATOR_MIS ? JP_LIGHTS_POWER_ONE : lightSampling);
 	scene->SetEstimator(estimator);

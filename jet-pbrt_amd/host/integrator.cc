@@ -32,7 +32,8 @@ struct HipApi
 	int (*set_environment_map)(JpContext*, const JpEnvMap*) = nullptr;                       // (looked up, needed by FScene::SetEnvironmentMap only)
 	int (*set_vertex_normals)(JpContext*, const JpVertexNormals*) = nullptr;                 // (looked up, needed by scenes with smooth meshes only)
 	int (*set_normal_maps)(JpContext*, const JpNormalMaps*) = nullptr;                       // (looked up, needed by scenes with FMaterial::normalMap only)
-	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                          // (looked up, needed by FScene::SetEstimator only)
+	int (*set_texture_sampling)(JpContext*, const JpTextureSampling*) = nullptr;             // (looked up, needed by scenes with a sampling record only)
+	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                        // (looked up, needed by FScene::SetEstimator only)
 	int (*set_lens)(JpContext*, const JpLens*) = nullptr;                                    // (looked up, needed by FCamera::SetLens only)
 	int (*focus_distance)(JpContext*, float, float, float*) = nullptr;                       // (looked up, needed by FCamera::FocusAt only)
 	int (*set_film)(JpContext*, const JpFilm*) = nullptr;                                    // (looked up, needed by FFilm::SetHDR / SetSampleClamp / SetToneMap only)
@@ -71,6 +72,7 @@ HipApi& Api()
 		api.set_vertex_normals = (decltype(api.set_vertex_normals))dlsym(api.lib, "jp_set_vertex_normals");
 		api.set_lens = (decltype(api.set_lens))dlsym(api.lib, "jp_set_lens");
 		api.set_normal_maps = (decltype(api.set_normal_maps))dlsym(api.lib, "jp_set_normal_maps");
+		api.set_texture_sampling = (decltype(api.set_texture_sampling))dlsym(api.lib, "jp_set_texture_sampling");
 		api.focus_distance = (decltype(api.focus_distance))dlsym(api.lib, "jp_focus_distance");
 		api.set_film = (decltype(api.set_film))dlsym(api.lib, "jp_set_film");
 		api.set_tonemap = (decltype(api.set_tonemap))dlsym(api.lib, "jp_set_tonemap");
@@ -181,6 +183,14 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			lastStatus = api.set_normal_maps(ctx, flat.n_normal_mapped > 0 ? &flat.normalMaps : nullptr);
 			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
 			ctxNormalMaps = flat.n_normal_mapped > 0;
+		}
+		if (flat.n_sampled > 0 || ctxSampling)
+		{   // FImageTexture / FNormalMap::SetSampling: the records go to the context before the upload they are to affect; a scene whose records are all the identity removes
+			// what an earlier scene left (NULL), and a context that never held any makes no such call
+			if (!api.set_texture_sampling) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_texture_sampling\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_texture_sampling(ctx, flat.n_sampled > 0 ? &flat.sampling : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxSampling = flat.n_sampled > 0;
 		}
 		// a scene with a textured material goes through jp_upload_scene_textured; any other makes exactly the calls it always made
 		const bool textured = flat.textures.n_textures > 0;

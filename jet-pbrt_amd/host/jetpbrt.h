@@ -163,6 +163,17 @@ public:
 	int Kind() const override { return JP_TEXTURE_CHECKER; }
 	FColor odd, even;
 };
+// ---- texture sampling (include/jetpbrt_amd.h "Texture sampling"): how an image texture or a normal map is addressed; the default is the identity record ----
+enum class EWrap { Clamp = JP_WRAP_CLAMP, Repeat = JP_WRAP_REPEAT, Mirror = JP_WRAP_MIRROR };
+enum class EFilter { Default = JP_FILTER_DEFAULT, Nearest = JP_FILTER_NEAREST, Bilinear = JP_FILTER_BILINEAR };   // Default: nearest for an image texture, bilinear for a normal map
+struct FTexSampling
+{
+	EWrap wrapU = EWrap::Clamp, wrapV = EWrap::Clamp;
+	EFilter filter = EFilter::Default;
+	Float scaleU = 1, scaleV = 1, offsetU = 0, offsetV = 0;      // t = c * scale + offset per axis
+	JpTexSampler Record() const { JpTexSampler r = { (int32_t)wrapU, (int32_t)wrapV, (int32_t)filter, scaleU, scaleV, offsetU, offsetV }; return r; }
+};
+
 class FImageTexture : public FTexture                            // texture.h, texture.cc (constructor, Sample)
 {
 public:
@@ -175,6 +186,9 @@ public:
 	int Kind() const override { return data.empty() ? JP_TEXTURE_SOLID : JP_TEXTURE_IMAGE; }
 	std::vector<uint8_t> data;                                   // empty: no image (solid cyan)
 	int width, height;
+	// the texture's own sampling record (jp_set_texture_sampling); unset: the command line's defaults where given, else the identity
+	void SetSampling(const FTexSampling& s) { sampling = s; hasSampling = true; }
+	FTexSampling sampling; bool hasSampling = false;
 };
 // image readers of film_io.cc: RGB8, top row first; false for any other format or a file that cannot be read
 bool ReadImageRGB8(const char* filename, std::vector<uint8_t>& rgb, int& width, int& height);
@@ -211,6 +225,9 @@ public:
 	bool Valid() const { return width >= 1 && width <= 16384 && height >= 1 && height <= 16384 && data.size() == (size_t)width * height * 3; }
 	std::vector<uint8_t> data;
 	int width = 0, height = 0;
+	// the map's sampling record (jp_set_texture_sampling): Clamp or Repeat, the bilinear filter, scales > 0
+	void SetSampling(const FTexSampling& s) { sampling = s; hasSampling = true; }
+	FTexSampling sampling; bool hasSampling = false;
 };
 
 // ---- materials: parameter holders with a flatten hook -------------------------------------------------------
@@ -495,6 +512,9 @@ public:
 	// power -- what a scene lit by CreateAreaLights(mesh) needs.  Read by FGpuPathIntegrator::Render at its next upload of this scene.
 	int lightSampling = JP_LIGHTS_ALL;
 	void SetLightSampling(int mode) { lightSampling = mode; }
+	// The sampling record of every FImageTexture without one of its own (FImageTexture::SetSampling); unset: the identity.  Read by FlattenScene.
+	FTexSampling textureSamplingDefault; bool hasTextureSamplingDefault = false;
+	void SetTextureSamplingDefault(const FTexSampling& s) { textureSamplingDefault = s; hasTextureSamplingDefault = true; }
 	// JP_ESTIMATOR_NEE (default: the reference's estimator) or JP_ESTIMATOR_MIS: next-event estimation and the BSDF sample weighted against each other (power
 	// heuristic).  Render-time state, sent before every render; a scene that asks for MIS is uploaded with JP_LIGHTS_POWER_ONE whatever lightSampling says.
 	int estimator = JP_ESTIMATOR_NEE;
@@ -535,6 +555,11 @@ struct FlatScene
 	JpNormalMaps normalMaps;
 	std::vector<int32_t> nm_width, nm_height, mat_normal_map; std::vector<int64_t> nm_offset; std::vector<uint8_t> nm_texels; std::vector<float> mat_normal_strength;
 	int n_normal_mapped = 0;
+	// texture sampling (jp_set_texture_sampling): one record per flattened texture and per flattened map, in their order; n_sampled == 0: every record is
+	// the identity and the scene sets no sampling state
+	JpTextureSampling sampling;
+	std::vector<JpTexSampler> tex_sampler, nm_sampler;
+	int n_sampled = 0;
 };
 bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error = nullptr);
 
@@ -578,6 +603,7 @@ protected:
 	mutable JpLens ctxLens = {};                                    // the lens the context was last told (FCamera::SetLens; radius 0: none)
 	mutable JpFilm ctxFilm = {}; mutable JpToneMap ctxToneMap = {};   // the film state and tone map the context was last told (FFilm::SetHDR / SetSampleClamp / SetToneMap; zeros: none)
 	mutable bool ctxNormalMaps = false;                            // ... or normal maps (jp_set_normal_maps)
+	mutable bool ctxSampling = false;                              // ... or texture sampling records (jp_set_texture_sampling)
 	mutable bool ctxNormals = false;                                // the context holds vertex normals of an earlier upload (jp_set_vertex_normals)
 	mutable int lastStatus = 0;
 	mutable JpCounters counters;

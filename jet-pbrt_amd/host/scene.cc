@@ -1,6 +1,7 @@
 // jet-pbrt_amd/host/scene.cc -- host scene description: bounds, shapes, materials, camera, FScene, OBJ ingest,
 // and the flattener that produces the JpScene SoA view.  No ray is traced on the host.
 #include "jetpbrt.h"
+#include "jp_tex_sampling.h"     // jp_tsamp_identity: which records FlattenScene counts as set
 
 #include <algorithm>
 #include <cstdlib>
@@ -435,6 +436,10 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 			else return fail("FlattenScene: unknown texture class");
 			out.tex_type.push_back(kind); out.tex_color.insert(out.tex_color.end(), col, col + 6);
 			out.tex_width.push_back(w); out.tex_height.push_back(h); out.tex_offset.push_back(off);
+			// the sampling record: an image's own, else the scene's default for images, else the identity (solid and checker textures have no addressing)
+			FTexSampling smp;
+			if (kind == JP_TEXTURE_IMAGE) { const FImageTexture* it = static_cast<const FImageTexture*>(T); if (it->hasSampling) smp = it->sampling; else if (scene.hasTextureSamplingDefault) smp = scene.textureSamplingDefault; }
+			out.tex_sampler.push_back(smp.Record());
 			ti = texRef.insert(std::make_pair(T, k)).first;
 		}
 		out.mat_texture.back() = ti->second;
@@ -456,6 +461,7 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 			const int k = (int)out.nm_width.size();
 			out.nm_width.push_back(N->width); out.nm_height.push_back(N->height); out.nm_offset.push_back((int64_t)out.nm_texels.size());
 			out.nm_texels.insert(out.nm_texels.end(), N->data.begin(), N->data.end());
+			out.nm_sampler.push_back((N->hasSampling ? N->sampling : FTexSampling()).Record());
 			ni = nmRef.insert(std::make_pair(N, k)).first;
 		}
 		out.mat_normal_map.back() = ni->second; out.n_normal_mapped++;
@@ -544,6 +550,13 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 	nm.n_texel_bytes = (int64_t)out.nm_texels.size(); nm.texels = out.nm_texels.data();
 	nm.n_materials = v.n_materials; nm.mat_map = out.mat_normal_map.data(); nm.mat_strength = out.mat_normal_strength.data();
 	nm.n_triangles = v.n_triangles; nm.tri_uv = out.tri_uv.data();
+	// the sampling records, in texture / map order; n_sampled counts the ones that are not the identity of their kind
+	JpTextureSampling& ts = out.sampling; std::memset(&ts, 0, sizeof(ts));
+	ts.struct_bytes = (int32_t)sizeof(JpTextureSampling);
+	ts.n_textures = t.n_textures; ts.tex = t.n_textures > 0 ? out.tex_sampler.data() : nullptr;
+	if (out.n_normal_mapped > 0) { ts.n_maps = nm.n_maps; ts.map = out.nm_sampler.data(); }
+	for (const JpTexSampler& r : out.tex_sampler) if (!jp_tsamp_identity(&r, JP_TSAMP_COLOR)) out.n_sampled++;
+	if (out.n_normal_mapped > 0) for (const JpTexSampler& r : out.nm_sampler) if (!jp_tsamp_identity(&r, JP_TSAMP_NORMAL)) out.n_sampled++;
 	return true;
 }
 

@@ -220,10 +220,32 @@ class HostBackend:
     def texture_checker(self, odd, even):
         a, _a = _fa(odd); b, _b = _fa(even); return self._f("texture_checker")(self.h, a, b)
 
-    def texture_image(self, rgb8):
-        """rgb8: (H, W, 3) uint8, top row first"""
+    def texture_image(self, rgb8, sampling=None):
+        """rgb8: (H, W, 3) uint8, top row first; sampling: a JpTexSampler (jet_pbrt_amd.tex_sampler), FImageTexture::SetSampling"""
         img = np.ascontiguousarray(rgb8, np.uint8)
-        return self._f("texture_image")(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0])
+        k = self._f("texture_image")(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0])
+        if sampling is not None:
+            self.texture_set_sampling(k, sampling)
+        return k
+
+    def texture_set_sampling(self, tex, sampling):
+        """FImageTexture::SetSampling (None: no record of its own)"""
+        if self._f("texture_set_sampling")(self.h, tex, None if sampling is None else C.byref(sampling)) != 0:
+            raise RuntimeError("texture_set_sampling failed: %s" % self.L.jp_host_last_error(self.h).decode())
+
+    def normal_map_set_sampling(self, nmap, sampling):
+        """FNormalMap::SetSampling (None: no record of its own)"""
+        if self._f("normal_map_set_sampling")(self.h, nmap, None if sampling is None else C.byref(sampling)) != 0:
+            raise RuntimeError("normal_map_set_sampling failed: %s" % self.L.jp_host_last_error(self.h).decode())
+
+    def set_texture_sampling_default(self, sampling):
+        """FScene::SetTextureSamplingDefault: the record of every image texture without one of its own (None: the identity)"""
+        self._f("scene_set_texture_sampling_default")(self.h, None if sampling is None else C.byref(sampling))
+
+    def flatten_texture_sampling(self):
+        """the scene's sampling records as a JpTextureSampling for Context.set_texture_sampling (None: every record is the identity); valid until the next preprocess"""
+        p = self.L.jp_host_flatten_texture_sampling(self.h)
+        return p.contents if p else None
 
     def texture_image_file(self, path):
         """FImageTexture(filename): binary PPM or uncompressed BMP; anything else is the reference's solid cyan"""
@@ -336,14 +358,19 @@ class HostBackend:
             raise RuntimeError("%s failed: %s" % (what, self.L.jp_host_last_error(self.h).decode()))
         return k
 
-    def normal_map(self, rgb8):
-        """FNormalMap from memory: (H, W, 3) uint8, top row first; or the path of a binary PPM / BMP file (FNormalMap::FromFile)"""
+    def normal_map(self, rgb8, sampling=None):
+        """FNormalMap from memory: (H, W, 3) uint8, top row first; or the path of a binary PPM / BMP file (FNormalMap::FromFile); sampling: a JpTexSampler
+        (FNormalMap::SetSampling)"""
         if isinstance(rgb8, (str, bytes, os.PathLike)):
-            return self._nmap(self._f("normal_map_file")(self.h, os.fsencode(rgb8)), "normal_map")
-        img = np.ascontiguousarray(rgb8, np.uint8)
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise RuntimeError("a normal map is an (H, W, 3) uint8 array")
-        return self._nmap(self._f("normal_map")(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0]), "normal_map")
+            k = self._nmap(self._f("normal_map_file")(self.h, os.fsencode(rgb8)), "normal_map")
+        else:
+            img = np.ascontiguousarray(rgb8, np.uint8)
+            if img.ndim != 3 or img.shape[2] != 3:
+                raise RuntimeError("a normal map is an (H, W, 3) uint8 array")
+            k = self._nmap(self._f("normal_map")(self.h, img.ctypes.data_as(C.c_void_p), img.shape[1], img.shape[0]), "normal_map")
+        if sampling is not None:
+            self.normal_map_set_sampling(k, sampling)
+        return k
 
     def normal_map_from_height(self, grey, scale):
         """FNormalMap::FromHeight: (H, W) uint8 heights, top row first -> the map of their slopes times `scale`"""
