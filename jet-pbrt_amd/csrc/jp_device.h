@@ -418,6 +418,99 @@ __device__ __forceinline__ int traverse_flat(const float4* flat_g, int n_flat, i
 	return flat_prims<kAnyHit, false, kS, F>(flat_boxes<false>(flat_g, n_flat, o, d, tmin, tmax), prims, o, d, tmin, tmax);
 }
 
+// ---- two shadow rays of one entry in one pass (k_shadow_pair; DESIGN.md section 5, "Shadow pairs") ------------------------------------
+// The rays of a shadow entry leave one origin, so everything of the flat walk that depends on the origin and the leaf / primitive only
+// is the same value for both: it is computed once here, the per-direction arithmetic is flat_boxes_lean<false>'s and tri_hit's /
+// rect_hit's own, operation for operation.  Flat shapes and <= 32 primitives (the 32-bit mask) only.
+// flat_boxes_lean_pair: one sweep over the leaves, the six (plane - o) once per leaf; per ray the reciprocal, multiplications, min / max,
+// clamp against its own tmax, slack multiply and or_bits_if_le of flat_boxes_lean<false>.  mA / mB: bit for bit that function's masks.
+__device__ __forceinline__ void flat_boxes_lean_pair(const float4* flat_g, int n_flat, V3 o, V3 dA, V3 dB, float tmin, float tmaxA, float tmaxB, unsigned int& mA, unsigned int& mB)
+{
+	ConstFPtr flat = (ConstFPtr)flat_g;
+	const float ixA = __builtin_amdgcn_rcpf(dA.x), iyA = __builtin_amdgcn_rcpf(dA.y), izA = __builtin_amdgcn_rcpf(dA.z);
+	const float ixB = __builtin_amdgcn_rcpf(dB.x), iyB = __builtin_amdgcn_rcpf(dB.y), izB = __builtin_amdgcn_rcpf(dB.z);
+	unsigned int maskA = 0, maskB = 0;
+	#define JP_FLAT_BOX_RAY(mask, ix, iy, iz, tmax) \
+	{ \
+		const float x0 = sx0 * ix, x1 = sx1 * ix, y0 = sy0 * iy, y1 = sy1 * iy, z0 = sz0 * iz, z1 = sz1 * iz; \
+		const float tn = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), tmin)); \
+		const float fxy = fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fz = fmaxf(z0, z1); \
+		const float tf = fminf(fxy, fminf(fz, tmax)); \
+		or_bits_if_le(mask, tn, tf * 1.000002f, bits); \
+	}
+	#define JP_FLAT_BOX(i) \
+	{ \
+		const float sx0 = flat[8 * (i) + 0] - o.x, sx1 = flat[8 * (i) + 4] - o.x; \
+		const float sy0 = flat[8 * (i) + 1] - o.y, sy1 = flat[8 * (i) + 5] - o.y; \
+		const float sz0 = flat[8 * (i) + 2] - o.z, sz1 = flat[8 * (i) + 6] - o.z; \
+		const unsigned int bits = __float_as_uint(flat[8 * (i) + 3]); \
+		JP_FLAT_BOX_RAY(maskA, ixA, iyA, izA, tmaxA) \
+		JP_FLAT_BOX_RAY(maskB, ixB, iyB, izB, tmaxB) \
+	}
+	int i0 = 0;
+	for (; i0 + 4 <= n_flat; i0 += 4)
+	{
+		#pragma unroll
+		for (int u = 0; u < 4; u++) JP_FLAT_BOX(i0 + u)
+	}
+	for (; i0 < n_flat; i0++) JP_FLAT_BOX(i0)
+	#undef JP_FLAT_BOX
+	#undef JP_FLAT_BOX_RAY
+	mA = maskA; mB = maskB;
+}
+
+// flat_prims_pair: the any-hit verdicts of both rays from one loop over the set bits of mA | mB in __ffs order.  An any-hit walk never
+// shrinks tmax before it returns, so a ray's verdict is the OR over ITS OWN mask of accept(primitive, ray, tmin, tmax) in any order; a
+// bit only the other ray's mask holds is never counted for this ray (a primitive outside a ray's box mask can still accept in the fp32
+// noise in front of its box).  Per candidate: the record, oa and dot(n, oa) once; per ray dot(n, d), the division and the interval test
+// against its own tmax; if either ray passes, ob, oc (od) and the cross products once, then each ray's dot products and sign test.  A
+// ray whose verdict is closed drops its mask; the lane leaves when no open ray has a candidate left.
+template <int kS, typename PrimPtr>
+__device__ __forceinline__ void flat_prims_pair(unsigned int mA, unsigned int mB, PrimPtr prims, V3 o, V3 dA, V3 dB, float tmin, float tmaxA, float tmaxB, bool& hitA, bool& hitB)
+{
+	bool hA = false, hB = false;
+	unsigned int todo = mA | mB;
+	while (todo)
+	{
+		const int p = __ffs((int)todo) - 1;
+		const unsigned int bit = todo & (0u - todo);
+		todo &= todo - 1;
+		const float4 g0 = prims[kS * p + 0], g1 = prims[kS * p + 1], g2 = prims[kS * p + 2], g3 = prims[kS * p + 3];
+		const V3 n = xyz(g3);
+		const V3 oa = xyz(g0) - o;
+		const float noa = dot(n, oa);
+		const float distA = noa / dot(n, dA), distB = noa / dot(n, dB);
+		const bool passA = (mA & bit) && (distA > tmin) && (distA < tmaxA);
+		const bool passB = (mB & bit) && (distB > tmin) && (distB < tmaxB);
+		if (passA || passB)
+		{
+			const V3 ob = xyz(g1) - o, oc = xyz(g2) - o;
+			const V3 v0 = cross(oc, ob), v1 = cross(ob, oa);
+			const float v0A = dot(v0, dA), v1A = dot(v1, dA), v0B = dot(v0, dB), v1B = dot(v1, dB);
+			bool inA, inB;
+			if (__float_as_int(g3.w) == JP_SHAPE_TRIANGLE)
+			{
+				const V3 v2 = cross(oa, oc);
+				const float v2A = dot(v2, dA), v2B = dot(v2, dB);
+				inA = ((v0A < 0) && (v1A < 0) && (v2A < 0)) || ((v0A >= 0) && (v1A >= 0) && (v2A >= 0));
+				inB = ((v0B < 0) && (v1B < 0) && (v2B < 0)) || ((v0B >= 0) && (v1B >= 0) && (v2B >= 0));
+			}
+			else
+			{
+				const V3 od = mk(g0.w, g1.w, g2.w) - o;
+				const V3 v2 = cross(oa, od), v3 = cross(od, oc);
+				const float v2A = dot(v2, dA), v3A = dot(v3, dA), v2B = dot(v2, dB), v3B = dot(v3, dB);
+				inA = ((v0A < 0) && (v1A < 0) && (v2A < 0) && (v3A < 0)) || ((v0A >= 0) && (v1A >= 0) && (v2A >= 0) && (v3A >= 0));
+				inB = ((v0B < 0) && (v1B < 0) && (v2B < 0) && (v3B < 0)) || ((v0B >= 0) && (v1B >= 0) && (v2B >= 0) && (v3B >= 0));
+			}
+			if (passA && inA) { hA = true; mA = 0; }
+			if (passB && inB) { hB = true; mB = 0; }
+			todo &= mA | mB;
+		}
+	}
+	hitA = hA; hitB = hB;
+}
+
 // Large scenes: 8-wide BVH with quantised child boxes (after Ylitie, Karras, Laine: "Efficient Incoherent Ray Traversal
 // on GPUs Through Compressed Wide BVHs", HPG 2017), 80 bytes per node.  Incoherent rays on a 280k-triangle scene are
 // bound by the number of distinct cache lines a wave's loads touch (every lane walks its own node): the binary tree

@@ -886,6 +886,76 @@ __global__ void __launch_bounds__(JP_BLOCK, 4) k_shadow(SceneView sc, Queues q, 
 	if ((threadIdx.x & 63) == 0) { if (rays) atomicAdd(&cnt->shadow, (unsigned long long)rays); if (occ) atomicAdd(&cnt->shadow_occ, (unsigned long long)occ); }
 }
 
+// k_shadow_pair: k_shadow<2, FeatFlat> for scenes of <= 32 primitives with two or more shadow planes, a kernel of its own name.  Region
+// walk, prefetch and radiance handling are k_shadow's; an entry's rays are traced two at a time, (0, 1), (2, 3), ..., through
+// flat_boxes_lean_pair / flat_prims_pair (jp_device.h: what depends on the shared origin only is computed once).  A last odd ray and
+// a one-ray entry take the same pass with ray B switched off (an empty mask: the loop then is ray A's own any-hit walk): a separate
+// single walk behind the pair loop would be run by every wave that holds ONE such lane, which on the Cornell box is most of them
+// (measured: +5 % vector instructions instead of fewer).  Verdicts are the single walk's, contributions are
+// added in light order, rays and occ count per ray.  The prefetch also requests the next entry's plane-1 direction (rc.n_planes >= 2:
+// the plane exists; a one-ray entry never looks at what was read).
+// Launch bounds: six waves per SIMD, k_shadow<2, FeatFlat>'s occupancy.  Left at four the compiler spends 113 VGPRs on the pass (four waves) and the
+// frame is SLOWER than the parent's although the kernel runs 10 % fewer vector instructions; held to six it needs 77 and no scratch.
+// -DJP_NO_PAIR_BOXES: the box phase stays one flat_boxes_lean<false> per ray (primitive-loop sharing only); -DJP_NO_PAIR_PRIMS: the primitive
+// phase stays one flat_prims per ray (box sharing only) -- the two pieces, for A/B measurements.
+__global__ void __launch_bounds__(JP_BLOCK, 6) k_shadow_pair(SceneView sc, Queues q, RenderConst rc, int depth, DevCounters* cnt)
+{
+	typedef FeatFlat F;
+	SceneAccess<2, F> acc(sc, depth);
+	const unsigned int b = blockIdx.x, E = q.blk_sh[b], rbase = b * q.R;
+	unsigned int rays = 0, occ = 0;
+	float4 so_n = make_float4(0, 0, 0, 0), sd_n = make_float4(0, 0, 1, 0), sd1_n = make_float4(0, 0, 1, 0);
+	if (threadIdx.x < E) { so_n = q.sh_o[rbase + threadIdx.x]; sd_n = q.sh_d[rbase + threadIdx.x]; sd1_n = q.sh_d[(size_t)q.cap + rbase + threadIdx.x]; }
+	for (unsigned int j = threadIdx.x; j < E; j += JP_BLOCK)
+	{
+		const unsigned int e = rbase + j;
+		const float4 so = so_n; float4 sd = sd_n, sd1 = sd1_n;
+		if (j + JP_BLOCK < E) { so_n = q.sh_o[e + JP_BLOCK]; sd_n = q.sh_d[e + JP_BLOCK]; sd1_n = q.sh_d[(size_t)q.cap + e + JP_BLOCK]; }
+		const int packed = __float_as_int(so.w);
+		const int slot = packed & ((1 << rc.slot_bits) - 1), n = (int)((unsigned int)packed >> rc.slot_bits);
+		if (n == 0) continue;
+		bool any = false;
+		const float4 L = q.lacc[slot];                               // issued up front: its latency hides behind the traversal
+		V3 a = mk(L.x, L.y, L.z);
+		for (int k = 0; k < n; k += 2)
+		{
+			const bool two = k + 1 < n;                                // false: the last odd ray, a one-ray entry -- ray B repeats ray A with an empty mask
+			const float4 cA = q.sh_c[(size_t)k * q.cap + e];             // needed only after the traversal
+			float4 cB = make_float4(0, 0, 0, 0);
+			if (two) cB = q.sh_c[(size_t)(k + 1) * q.cap + e];
+			const float tmaxA = sd.w, tmaxB = two ? sd1.w : sd.w;
+			const V3 dA = xyz(sd), dB = two ? xyz(sd1) : xyz(sd);
+			if (k + 2 < n) sd = q.sh_d[(size_t)(k + 2) * q.cap + e];
+			if (k + 3 < n) sd1 = q.sh_d[(size_t)(k + 3) * q.cap + e];
+			unsigned int mA, mB;
+#ifdef JP_NO_PAIR_BOXES
+			mA = flat_boxes_lean<false>(sc.flat, sc.n_flat, xyz(so), dA, 0.001f, tmaxA);
+			mB = flat_boxes_lean<false>(sc.flat, sc.n_flat, xyz(so), dB, 0.001f, tmaxB);
+#else
+			flat_boxes_lean_pair(sc.flat, sc.n_flat, xyz(so), dA, dB, 0.001f, tmaxA, tmaxB, mA, mB);
+#endif
+			if (!two) mB = 0;
+			bool hitA, hitB;
+#ifdef JP_NO_PAIR_PRIMS
+			{ float tA = tmaxA, tB = tmaxB; hitA = flat_prims<true, false, 5, F>(mA, acc.prims, xyz(so), dA, 0.001f, tA) >= 0; hitB = flat_prims<true, false, 5, F>(mB, acc.prims, xyz(so), dB, 0.001f, tB) >= 0; }
+#else
+			flat_prims_pair<5>(mA, mB, acc.prims, xyz(so), dA, dB, 0.001f, tmaxA, tmaxB, hitA, hitB);
+#endif
+			rays += two ? 2u : 1u;
+			if (hitA) occ++;
+			else { a = a + xyz(cA); any = true; }
+			if (two)
+			{
+				if (hitB) occ++;
+				else { a = a + xyz(cB); any = true; }
+			}
+		}
+		if (any) q.lacc[slot] = make_float4(a.x, a.y, a.z, 0.f);
+	}
+	for (int off = 32; off > 0; off >>= 1) { rays += __shfl_down(rays, off); occ += __shfl_down(occ, off); }
+	if ((threadIdx.x & 63) == 0) { if (rays) atomicAdd(&cnt->shadow, (unsigned long long)rays); if (occ) atomicAdd(&cnt->shadow_occ, (unsigned long long)occ); }
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // k_extend_persist / k_shadow_persist: the traversal kernels of large scenes with LANE REFILL.  There the rays of a wave differ
 // wildly in length (most leave the scene after a few nodes, some walk 60+ nodes through a mesh), and a wave that traces one ray

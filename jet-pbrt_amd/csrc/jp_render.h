@@ -151,6 +151,10 @@ ShadowLaunch shadow_kernel(const ScenePlan& p, unsigned int R, bool generic)   /
 {
 	const int words = std::min(shadow_depth(p), p.stack_lds_words);
 	const size_t plds = (size_t)words * JP_BLOCK * sizeof(int) + (((size_t)R * p.n_planes + 31) / 32) * 4 * (p.cert ? 2 : 1);   // (certified walk: a second bitmap, the rays without a certificate)
+#ifndef JP_NO_SHADOW_PAIR
+	// two rays of an entry in one pass (k_shadow_pair): the 32-bit-mask scenes whose entries can hold two rays
+	if (lean_traversal(p, generic) && p.sv.n_prims <= 32 && p.n_planes >= 2) return { nullptr, k_shadow_pair, p.lds_bytes, p.stack_depth, p.cert };
+#endif
 	if (lean_traversal(p, generic)) return { nullptr, k_shadow<2, FeatFlat>, p.lds_bytes, p.stack_depth, p.cert };
 	if (!refill_walks(p) || plds > 64 * 1024)                         // one ray per lane: these kernels walk a certified scene's caller's tree verbatim
 		return { nullptr, p.trav_mode == 3 ? k_shadow<3> : (p.trav_mode == 5 ? k_shadow<5> : (p.trav_mode == 2 ? k_shadow<2> : (p.trav_mode == 1 ? k_shadow<1> : k_shadow<0>))), p.trav_mode == 3 ? p.lds_bytes_shadow : p.lds_bytes, p.stack_depth, p.cert };
@@ -903,6 +907,17 @@ int jp_surface(JpContext* c, int32_t n, const float* origin, const float* dir, c
 }
 
 } // extern "C"
+
+// Diagnostic, outside the ABI structs: which shadow kernel shadow_kernel picks for the uploaded scene under the options in force.
+// 0: a lane-refill kernel, 1: k_shadow<mode> with every feature in it, 2: k_shadow<2, FeatFlat>, 3: k_shadow_pair
+extern "C" int jp_dbg_shadow_kernel(JpContext* c, int* which_out)
+{
+	if (!c || !which_out) return fail(JP_ERR_INVALID_ARGUMENT, "jp_dbg_shadow_kernel: null argument");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_dbg_shadow_kernel: no scene uploaded");
+	const ShadowLaunch sk = shadow_kernel(c->plan, c->q.R ? c->q.R : JP_BLOCK, c->opt.reserved[0] == 1);
+	*which_out = sk.refill ? 0 : (sk.plain == (ShadowKernel)k_shadow_pair ? 3 : (sk.plain == (ShadowKernel)k_shadow<2, FeatFlat> ? 2 : 1));
+	return JP_OK;
+}
 
 #if defined(JP_SHADE_TIMING) || defined(JP_TRAV_TIMING)
 extern "C" int jp_dbg_shade_timing(unsigned long long* out16)

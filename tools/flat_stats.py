@@ -72,12 +72,39 @@ def main(name="cornell_lambert", n=20000):
     lp = np.stack([rng.uniform(213, 343, n), np.full(n, 548.7), -rng.uniform(227, 332, n)], 1).astype(np.float32)
     sd = lp - pos; dist = np.linalg.norm(sd, axis=1); sd = (sd / dist[:, None]).astype(np.float32)
     sets["shadow"] = (pos[hit > 0], sd[hit > 0], (dist - 0.001).astype(np.float32)[hit > 0])
+    # shadow pairs: origins of the first and the second bounce, one sample on each lamp triangle (cornellbox/light.obj: (343, 227) (343, 332) (213, 332) | (343, 227) (213, 332) (213, 227) in x, z)
+    hit2, pos2, _ = otrace(pos[hit > 0], d1[hit > 0])
+    po = np.concatenate([pos[hit > 0], pos2[hit2 > 0]]).astype(np.float32)
+    def lamp_sample(c0, c1, c2):
+        u = rng.random(len(po)); v = rng.random(len(po)); f = u + v > 1; u = np.where(f, 1 - u, u); v = np.where(f, 1 - v, v)
+        xz = np.array(c0)[None, :] + u[:, None] * (np.array(c1) - np.array(c0))[None, :] + v[:, None] * (np.array(c2) - np.array(c0))[None, :]
+        t = np.stack([xz[:, 0], np.full(len(po), 548.7), -xz[:, 1]], 1).astype(np.float32) - po
+        dl = np.linalg.norm(t, axis=1)
+        return (t / dl[:, None]).astype(np.float32), (dl - 0.001).astype(np.float32)
+    pair = (po,) + lamp_sample((343, 227), (343, 332), (213, 332)) + lamp_sample((343, 227), (213, 332), (213, 227))
     for gname, g in groupings.items():
         print("== %s: %d entries, sizes %s" % (gname, len(g), np.bincount([len(c[0]) for c in g])))
         B = np.stack([c[1] for c in g]).astype(np.float32)
         e = np.maximum(np.abs(B[:, :3]), np.abs(B[:, 3:])) * 1e-6 + 1e-6
         B = np.concatenate([B[:, :3] - e, B[:, 3:] + e], 1)
         cnt = np.array([len(c[0]) for c in g])
+        def entered(ro, rd, tmx):
+            with np.errstate(divide="ignore", invalid="ignore"):
+                idr = 1.0 / rd
+                t0 = (B[None, :, :3] - ro[:, None, :]) * idr[:, None, :]; t1 = (B[None, :, 3:] - ro[:, None, :]) * idr[:, None, :]
+                tn_ = np.maximum(np.fmax(np.fmin(t0, t1), -np.inf).max(2), 0.001); tf = np.minimum(np.fmin(np.fmax(t0, t1), np.inf).min(2), tmx[:, None])
+            return tn_ <= tf * 1.000002
+        if len(tb) <= 64:
+            # shadow pairs: the candidate primitives of a ray are the members of the boxes it enters (one bit per primitive, as the device mask)
+            member = np.zeros((len(g), len(tb)), bool)
+            for k, c in enumerate(g): member[k, c[0]] = True
+            pa = (entered(pair[0], pair[1], pair[2]).astype(np.int32) @ member.astype(np.int32)) > 0
+            pb = (entered(pair[0], pair[3], pair[4]).astype(np.int32) @ member.astype(np.int32)) > 0
+            m = (len(pa) // 64) * 64
+            cols = {"ray A": pa.sum(1), "ray B": pb.sum(1), "A | B": (pa | pb).sum(1), "A + B pooled": pa.sum(1) + pb.sum(1)}
+            print("   shadow pairs (%d origins): candidate primitives per entry  %s" % (len(pa), "  ".join("%s %.2f" % (k, v.mean()) for k, v in cols.items())))
+            print("   shadow pairs: per 64-entry wave, largest lane            %s   (two loops: %.2f)" % ("  ".join("%s %.2f" % (k, v[:m].reshape(-1, 64).max(1).mean()) for k, v in cols.items()),
+                  cols["ray A"][:m].reshape(-1, 64).max(1).mean() + cols["ray B"][:m].reshape(-1, 64).max(1).mean()))
         for sname, (ro, rd, tmx) in sets.items():
             with np.errstate(divide="ignore", invalid="ignore"):
                 idr = 1.0 / rd
