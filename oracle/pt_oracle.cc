@@ -1342,6 +1342,8 @@ void render_rows(const Scene& sc, const JpRenderParams& rp, Sampler& smp, int y0
 
 } // namespace
 
+// oracle/pt_features.cc includes this file for the restated functions above and defines JP_ORACLE_NO_ENTRY_POINTS: the entry points below exist once.
+#ifndef JP_ORACLE_NO_ENTRY_POINTS
 extern "C" {
 
 // FIntegrator::Render integrator.cc:35-80: nthreads < 1 -> serial whole-frame path with ONE sampler stream;
@@ -1534,3 +1536,4 @@ void jp_oracle_li_scripted(void* h, int count, int maxdepth, const float* pxy, c
 void jp_oracle_stock_stream(int n, float* out) { Sampler s(JP_SAMPLER_STOCK_MT19937, 0, 1); for (int i = 0; i < n; i++) out[i] = s.stock(); }
 
 } // extern "C"
+#endif // JP_ORACLE_NO_ENTRY_POINTS

@@ -44,8 +44,140 @@ def oracle_lib():
         L.jp_oracle_li_scripted.argtypes = [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int, _vp]
         L.jp_oracle_stock_stream.argtypes = [C.c_int, _vp]
         L.jp_oracle_bsdf_direct.argtypes = [C.POINTER(jp.JpBsdfDesc), C.c_int] + [_vp] * 10
+        L.jp_oracle_render_features.argtypes = [C.POINTER(jp.JpScene), C.POINTER(jp.JpRenderParams), C.POINTER(JpOracleFeatures), C.c_int, _vp, C.POINTER(jp.JpCounters), _vp]
+        L.jp_oracle_path_features.argtypes = [C.POINTER(jp.JpScene), C.POINTER(jp.JpRenderParams), C.POINTER(JpOracleFeatures), C.c_int, C.c_int, C.c_int, _vp]
         _oracle = L
     return _oracle
+
+
+class JpOracleFeatures(C.Structure):
+    """oracle/pt_features.h: the feature state of jp_oracle_render_features; every field optional"""
+    _ip = C.POINTER(C.c_int32)
+    _fields_ = [("struct_bytes", C.c_int32), ("light_mode", C.c_int32), ("n_lights", C.c_int32), ("n_env", C.c_int32),
+                ("q", _fp), ("alias", _ip), ("pmf", _fp), ("env_lights", _ip),
+                ("env_w", C.c_int32), ("env_h", C.c_int32), ("env_up", C.c_int32), ("env_light", C.c_int32),
+                ("env_texel", _fp), ("env_q", _fp), ("env_alias", _ip), ("env_row_cos", _fp),
+                ("estimator", C.c_int32), ("watertight", C.c_int32),
+                ("normals", C.POINTER(jp.JpVertexNormals)), ("textures", C.POINTER(jp.JpTextures)), ("sampling", C.POINTER(jp.JpTextureSampling)),
+                ("normal_maps", C.POINTER(jp.JpNormalMaps)), ("lens", C.POINTER(jp.JpLens)), ("film", C.POINTER(jp.JpFilm))]
+
+
+def _scene_arr(p, n, dt=np.float32):
+    return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(n,)).copy() if n else np.zeros(0, dt)
+
+
+def light_weights(s, env_mean_sum=None):
+    """INTEGRATION.md section 9 "Weights": one double per light of the JpScene `s`, from the fp32 scene values; areas in fp32 with the upload's expressions
+    (shape.h:351, 457, 546, 253).  env_mean_sum: the scene's one environment light carries a map, whose mean_sum takes the radiance sum's place (section 10)."""
+    f32 = np.float32
+    n = s.n_lights
+    ty = _scene_arr(s.light_type, n, np.int32); rad = _scene_arr(s.light_radiance, 3 * n).reshape(n, 3).astype(np.float64); lp = _scene_arr(s.light_prim, n, np.int32)
+    st, si = _scene_arr(s.prim_shape_type, s.n_primitives, np.int32), _scene_arr(s.prim_shape_index, s.n_primitives, np.int32)
+    T = [_scene_arr(getattr(s, "tri_p%d" % k), 3 * s.n_triangles).reshape(-1, 3) for k in range(3)]
+    Q = [_scene_arr(getattr(s, "rect_p%d" % k), 3 * s.n_rectangles).reshape(-1, 3) for k in range(3)]
+    sr = _scene_arr(s.sph_radius, s.n_spheres); dr = _scene_arr(s.disk_radius, s.n_disks)
+    kpi = f32(3.14159265358979323846)
+
+    def cross_len(a, b):
+        a = a.astype(f32); b = b.astype(f32)
+        c = [f32(a[1] * b[2]) - f32(a[2] * b[1]), f32(a[2] * b[0]) - f32(a[0] * b[2]), f32(a[0] * b[1]) - f32(a[1] * b[0])]
+        return np.sqrt(f32(f32(c[0] * c[0]) + f32(c[1] * c[1])) + f32(c[2] * c[2]), dtype=f32)
+    R2 = float(s.world_radius) * float(s.world_radius)
+    w = np.zeros(n)
+    for i in range(n):
+        ssum = (rad[i, 0] + rad[i, 1]) + rad[i, 2]
+        if ty[i] == 1:                                                  # JP_LIGHT_AREA
+            p = lp[i]; k = si[p]
+            if st[p] == 0:
+                area = f32(0.5) * cross_len(T[1][k] - T[0][k], T[2][k] - T[0][k])
+            elif st[p] == 1:
+                area = cross_len(Q[0][k] - Q[1][k], Q[2][k] - Q[1][k])
+            elif st[p] == 3:                                            # JP_SHAPE_DISK
+                area = f32(f32(kpi * dr[k]) * dr[k])
+            else:
+                area = f32(f32(f32(4) * kpi) * f32(sr[k] * sr[k]))
+            w[i] = (ssum * float(area)) * np.pi
+        elif ty[i] == 2:                                                # JP_LIGHT_POINT
+            w[i] = ssum * (4.0 * np.pi)
+        elif ty[i] == 0 and env_mean_sum is not None:                   # the map light
+            w[i] = (env_mean_sum * np.pi) * R2
+        else:
+            w[i] = (ssum * np.pi) * R2
+    return w
+
+
+def _as_ptr(x, ty):
+    """a ctypes pointer to `x`: None, an instance of ty, or already a pointer (what HostBackend.flatten_* return)"""
+    if x is None:
+        return None, None
+    if isinstance(x, C._Pointer):
+        return x, x
+    return C.pointer(x), x
+
+
+def oracle_features(scene_ptr, light_mode=None, env_rgb=None, env_up="z", env_importance=0, estimator=None, normals=None, textures=None, sampling=None,
+                    normal_maps=None, lens=None, film=None, watertight=False):
+    """The JpOracleFeatures of a feature set, built the way the library builds its state: light_mode "power" takes the light table from
+    jp_build_light_table over light_weights(); env_rgb (an (H, W, 3) array) the map tables from jp_build_environment_table with the scene's one environment
+    light as the tint.  The other arguments are the structs the Context setters take (or pointers to them).  Everything is kept alive on the result."""
+    s = scene_ptr.contents
+    f = JpOracleFeatures()
+    f.struct_bytes = C.sizeof(JpOracleFeatures)
+    keep = []
+    ip = C.POINTER(C.c_int32)
+    mean_sum = None
+    if env_rgb is not None:
+        ty = _scene_arr(s.light_type, s.n_lights, np.int32); rad = _scene_arr(s.light_radiance, 3 * s.n_lights).reshape(-1, 3)
+        at = [i for i in range(s.n_lights) if ty[i] == 0]
+        assert len(at) == 1, "a map needs exactly one environment light"
+        e = jp.build_environment_table(env_rgb, tuple(rad[at[0]]), env_up, env_importance)
+        f.env_h, f.env_w = np.asarray(env_rgb).shape[:2]; f.env_up = jp.ENV_UP_AXES[env_up]; f.env_light = at[0]
+        f.env_texel = e["texel"].ctypes.data_as(_fp); f.env_q = e["q"].ctypes.data_as(_fp); f.env_alias = e["alias"].ctypes.data_as(ip); f.env_row_cos = e["row_cos"].ctypes.data_as(_fp)
+        keep.append(e); mean_sum = e["mean_sum"]
+    f.light_mode = jp.LIGHT_SAMPLING_MODES[light_mode]
+    if f.light_mode == jp.JP_LIGHTS_POWER_ONE:
+        w = light_weights(s, mean_sum)
+        q, alias, pmf = jp.build_light_table(w)
+        ty = _scene_arr(s.light_type, s.n_lights, np.int32); rad = _scene_arr(s.light_radiance, 3 * s.n_lights).reshape(-1, 3)
+        envl = np.array([i for i in range(s.n_lights) if ty[i] == 0 and (rad[i] != 0).any()], np.int32)
+        f.n_lights = s.n_lights; f.q = q.ctypes.data_as(_fp); f.alias = alias.ctypes.data_as(ip); f.pmf = pmf.ctypes.data_as(_fp)
+        f.n_env = len(envl); f.env_lights = envl.ctypes.data_as(ip) if len(envl) else None
+        keep += [w, q, alias, pmf, envl]
+        f.table = (w, q, alias, pmf)
+    f.estimator = jp.ESTIMATOR_MODES[estimator]
+    f.watertight = 1 if watertight else 0
+    for name, val, ty in (("normals", normals, jp.JpVertexNormals), ("textures", textures, jp.JpTextures), ("sampling", sampling, jp.JpTextureSampling),
+                          ("normal_maps", normal_maps, jp.JpNormalMaps), ("lens", lens, jp.JpLens), ("film", film, jp.JpFilm)):
+        p, k = _as_ptr(val, ty)
+        if p is not None:
+            setattr(f, name, C.cast(p, C.POINTER(ty))); keep.append((p, k))
+    f._keep = keep
+    return f
+
+
+def oracle_render_features(scene_ptr, params, features=None, nthreads=8, rand_seed=1):
+    """jp_oracle_render_features -> (film, JpCounters, undecided (H, W) bool).  features: oracle_features(...) or None.  rand_seed: as oracle_render."""
+    film = np.zeros((params.height, params.width, 3), np.float32)
+    und = np.zeros((params.height, params.width), np.uint8)
+    cnt = jp.JpCounters()
+    L = oracle_lib()
+    if rand_seed is not None:
+        libc_srand(rand_seed)
+    st = L.jp_oracle_render_features(scene_ptr, C.byref(params), None if features is None else C.byref(features), nthreads, ptr(film), C.byref(cnt), ptr(und))
+    if st != 0:
+        raise jp.JetPbrtError("jp_oracle_render_features: status %d" % st)
+    return film, cnt, und.astype(bool)
+
+
+def oracle_path_features(scene_ptr, params, features, x, y, s, rand_seed=1):
+    """jp_oracle_path_features: sample s of pixel (x, y) alone, its draws, decisions and contributions printed to stdout -> the sample's radiance"""
+    out = np.zeros(3, np.float32)
+    if rand_seed is not None:
+        libc_srand(rand_seed)
+    st = oracle_lib().jp_oracle_path_features(scene_ptr, C.byref(params), None if features is None else C.byref(features), x, y, s, ptr(out))
+    if st != 0:
+        raise jp.JetPbrtError("jp_oracle_path_features: status %d" % st)
+    return out
 
 
 def have_ref():
