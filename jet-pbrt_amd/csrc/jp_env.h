@@ -4,6 +4,7 @@
 //   part 1 (included by jp_kernels.hip before the kernels): EnvView, env_lookup, env_sample;
 //   part 2 (JP_ENV_RUNTIME, included after jp_pick.h): k_shade_env / k_shade_env_tex (shade_body<..., kPick, kEnv>), the test hook k_env_probe, the upload's
 //   table step and the entry points jp_set_environment_map / jp_get_env_info / jp_env_lookup / jp_env_sample / jp_build_environment_table.
+// The kernels are selected and launched with every other k_shade family (shade_choice, jp_render.h; shade_launch, jp_shade_launch.h).
 // A context that never binds a map runs nothing of this file.
 #ifndef JP_ENV_DEVICE_PART
 #define JP_ENV_DEVICE_PART
@@ -94,21 +95,6 @@ __global__ void __launch_bounds__(JP_BLOCK) k_env_probe(EnvView ev, int mode, in
 			index[i] = j; wi[3 * i] = w.x; wi[3 * i + 1] = w.y; wi[3 * i + 2] = w.z; Li[3 * i] = L.x; Li[3 * i + 1] = L.y; Li[3 * i + 2] = L.z; pdf[i] = p;
 		}
 	}
-}
-
-namespace
-{
-template <bool kTab, bool kPrims, bool kStage> ShadeEnvKernels shade_env_row(bool sort)
-{
-	ShadeEnvKernels k = { sort ? k_shade_env<kTab, kPrims, kStage, true> : k_shade_env<kTab, kPrims, kStage, false>, sort ? k_shade_env_tex<kTab, kPrims, kStage, true> : k_shade_env_tex<kTab, kPrims, kStage, false> };
-	return k;
-}
-ShadeEnvKernels shade_env_kernels(const ScenePlan& p)                // the rows of shade_pick_kernels
-{
-	if (p.shade_prims_in_lds) return p.stage_nee ? shade_env_row<true, true, true>(p.shade_sort) : shade_env_row<true, true, false>(p.shade_sort);
-	if (p.tables_in_lds) return p.stage_nee ? shade_env_row<true, false, true>(p.shade_sort) : shade_env_row<true, false, false>(p.shade_sort);
-	return shade_env_row<false, false, false>(p.shade_sort);
-}
 }
 
 // the upload's map step (jp_upload_scene with a map bound, before upload_light_table): the refusals, the tables (build_environment_table, jp_scene_host.h),

@@ -37,6 +37,9 @@
 #include <cmath>
 #include <mutex>
 #include <thread>
+#include <tuple>
+#include <functional>
+#include <type_traits>
 #include "jp_devmem.h"           // DevBuf / PinnedBuf: who owns device memory
 #include "jp_lbvh.h"
 #include "jp_ploc.h"
@@ -1544,16 +1547,17 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_render.h"           // jp_render*: queues, launch sequence, stream lanes, fused schedule; counters, jp_trace, jp_bsdf
 #include "jp_denoise.h"          // guides and denoising: k_guides, k_atrous and their entry points (additive: nothing above refers to it)
 #define JP_ENV_RUNTIME
-#include "jp_env.h"              // environment maps, part 2: k_shade_env / k_shade_env_tex, k_env_probe and their entry points (jp_render.h declares the selector)
-#include "jp_pick.h"             // light selection: the alias table, k_shade_pick / k_shade_pick_tex, k_light_pick and their entry points (jp_render.h declares its two hooks)
+#include "jp_env.h"              // environment maps, part 2: k_shade_env / k_shade_env_tex, k_env_probe and their entry points
+#include "jp_pick.h"             // light selection: the alias table, k_shade_pick / k_shade_pick_tex, k_light_pick and their entry points
 #define JP_MIS_RUNTIME
-#include "jp_mis.h"              // estimator, part 2: k_shade_mis*, k_light_pdf and their entry points (jp_render.h declares the selector)
+#include "jp_mis.h"              // estimator, part 2: k_shade_mis*, k_light_pdf and their entry points
 #define JP_NORMAL_MAP_RUNTIME
-#include "jp_normal_map.h"       // normal maps, part 2: k_normal_map, k_shading_normal_mapped and their entry points (before the vertex normals' part 2, whose selector and hook hand out its kernels)
+#include "jp_normal_map.h"       // normal maps, part 2: k_normal_map, k_shading_normal_mapped and their entry points (before the vertex normals' part 2, whose hook hands out its kernel)
 #define JP_TEX_SAMPLING_RUNTIME
 #include "jp_tex_sampling.h"     // texture sampling records, part 3: the upload's table steps and the entry points (after jp_normal_map.h's part 2: pack_rgb8, jp_perturb_normals)
 #define JP_NORMALS_RUNTIME
-#include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points (jp_render.h declares the selector)
+#include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points
+#include "jp_shade_launch.h"     // shade_launch and launch_normal, which jp_render.h declares: after the last of the k_shade families and normal kernels above
 #include "jp_lens_runtime.h"     // thin-lens camera: k_camera_rays and the lens entry points (jp_render.h reads the context's lens state)
 #define JP_FILM_RUNTIME
 #include "jp_film.h"             // film, part 2: k_film_hist, k_display and the film / tone map entry points (jp_render.h declares film_to_rgb8 and reads the context's film state)

@@ -5,6 +5,7 @@
 //   part 1 (included by jp_kernels.hip before the kernels): MisView, mis_weight, pdf_local, light_weighed, light_pdf;
 //   part 2 (JP_MIS_RUNTIME, included last): k_shade_mis / _tex / _env / _env_tex (shade_body<..., kPick, kEnv, kMis>), the test hook k_light_pdf and the
 //   entry points jp_set_estimator / jp_get_estimator_info / jp_light_pdf.
+// The kernels are selected and launched with every other k_shade family (shade_choice, jp_render.h; shade_launch, jp_shade_launch.h).
 // A context that never switches the estimator on runs nothing of this file.
 #ifndef JP_MIS_DEVICE_PART
 #define JP_MIS_DEVICE_PART
@@ -154,30 +155,9 @@ __global__ void __launch_bounds__(JP_BLOCK) k_light_pdf(SceneView sc, PickView p
 
 namespace
 {
-template <bool kTab, bool kPrims, bool kStage> ShadeMisKernels shade_mis_row(bool sort)
-{
-	ShadeMisKernels k = { sort ? k_shade_mis<kTab, kPrims, kStage, true> : k_shade_mis<kTab, kPrims, kStage, false>, sort ? k_shade_mis_tex<kTab, kPrims, kStage, true> : k_shade_mis_tex<kTab, kPrims, kStage, false>,
-	                      sort ? k_shade_mis_env<kTab, kPrims, kStage, true> : k_shade_mis_env<kTab, kPrims, kStage, false>, sort ? k_shade_mis_env_tex<kTab, kPrims, kStage, true> : k_shade_mis_env_tex<kTab, kPrims, kStage, false> };
-	return k;
-}
-ShadeMisKernels shade_mis_kernels(const ScenePlan& p)                // the rows of shade_pick_kernels
-{
-	if (p.shade_prims_in_lds) return p.stage_nee ? shade_mis_row<true, true, true>(p.shade_sort) : shade_mis_row<true, true, false>(p.shade_sort);
-	if (p.tables_in_lds) return p.stage_nee ? shade_mis_row<true, false, true>(p.shade_sort) : shade_mis_row<true, false, false>(p.shade_sort);
-	return shade_mis_row<false, false, false>(p.shade_sort);
-}
-
 // k_light_pdf for the walk jp_trace takes by default: the instance that belongs to the k_trace trace_kernel selects
 typedef void (*LightPdfKernel)(SceneView, PickView, EnvView, int, int, int, const float*, const float*, const float*, const float*, int*, float*);
-LightPdfKernel light_pdf_kernel(const TraceLaunch& t)
-{
-	if (t.trace == k_trace<6>) return k_light_pdf<6>;
-	if (t.trace == k_trace<5>) return k_light_pdf<5>;
-	if (t.trace == k_trace<4>) return k_light_pdf<4>;
-	if (t.trace == k_trace<2>) return k_light_pdf<2>;
-	if (t.trace == k_trace<1>) return k_light_pdf<1>;
-	return t.trace == k_trace<0> ? k_light_pdf<0> : nullptr;
-}
+LightPdfKernel light_pdf_kernel(const TraceLaunch& t) { return by_trace_mode(t.mode, [](auto m) -> LightPdfKernel { return k_light_pdf<decltype(m)::value>; }); }
 }
 
 // the side records of a context's queue set (render_one, first MIS render: cap positions per queue)

@@ -1,6 +1,6 @@
 // jet-pbrt_amd/csrc/jp_normal_map.h -- tangent-space normal maps (INTEGRATION.md "Normal maps", DESIGN.md "Normal maps"), in two parts like jp_normals.h:
 //   part 1 (included before the kernels): NMapView and mapped_normal, the device side of include/jp_normal_map.h
-//   part 2 (JP_NORMAL_MAP_RUNTIME, included before jp_normals.h's part 2, whose selector and hook hand out these kernels): k_normal_map, the test hook k_shading_normal_mapped, the upload's table step and the
+//   part 2 (JP_NORMAL_MAP_RUNTIME, included before jp_normals.h's part 2, whose hook hands out k_shading_normal_mapped; launch_normal, jp_shade_launch.h, launches k_normal_map): k_normal_map, the test hook k_shading_normal_mapped, the upload's table step and the
 //     entry points jp_set_normal_maps / jp_check_normal_maps / jp_get_normal_map_info / jp_perturb_normals / jp_triangle_tangents.
 // A normal map is one more producer of the side record (Ns, 1) that k_shade_smooth* read: k_shade and the ten smooth families stay as they are.
 // A context that never sets a normal map runs nothing of this file.
@@ -167,15 +167,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shading_normal_mapped(SceneView sc
 namespace
 {
 typedef void (*ShadingNormalMappedKernel)(SceneView, NormView, NMapView, SampView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*);
-ShadingNormalMappedKernel shading_normal_mapped_kernel(const TraceLaunch& t)
-{
-	if (t.trace == k_trace<6>) return k_shading_normal_mapped<6>;
-	if (t.trace == k_trace<5>) return k_shading_normal_mapped<5>;
-	if (t.trace == k_trace<4>) return k_shading_normal_mapped<4>;
-	if (t.trace == k_trace<2>) return k_shading_normal_mapped<2>;
-	if (t.trace == k_trace<1>) return k_shading_normal_mapped<1>;
-	return t.trace == k_trace<0> ? k_shading_normal_mapped<0> : nullptr;
-}
+ShadingNormalMappedKernel shading_normal_mapped_kernel(const TraceLaunch& t) { return by_trace_mode(t.mode, [](auto m) -> ShadingNormalMappedKernel { return k_shading_normal_mapped<decltype(m)::value>; }); }
 
 // everything of a JpNormalMaps that does not need the scene; n_mapped: materials with a map index >= 0
 int check_normal_maps(const JpNormalMaps* m, long long& pool, int& n_mapped)

@@ -2,6 +2,7 @@
 //   part 1 (included before the kernels): NormView and shading_normal, the device side of include/jp_normals.h
 //   part 2 (JP_NORMALS_RUNTIME, included after jp_render.h and jp_denoise.h): k_normal, the smooth twins of the ten k_shade families (shade_body<..., kSmooth>), the test
 //     hook k_shading_normal, the upload's table step and the entry points jp_set_vertex_normals / jp_get_normal_info / jp_shading_normal / jp_interpolate_normals.
+// k_normal is launched by launch_normal, the smooth twins by shade_launch with every other k_shade family (jp_shade_launch.h, included after this part).
 // A context that never sets vertex normals runs nothing of this file.
 #ifndef JP_NORMALS_DEVICE_PART
 #define JP_NORMALS_DEVICE_PART
@@ -119,35 +120,9 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shading_normal(SceneView sc, NormV
 
 namespace
 {
-SmoothKernels shade_smooth_kernels(const ScenePlan& p)
-{
-	SmoothKernels k;
-	k.normal = k_normal; k.normal_map = k_normal_map;
-	if (p.shade_sort)
-	{
-		k.plain = k_shade_smooth<true>; k.tex = k_shade_smooth_tex<true>; k.pick = k_shade_smooth_pick<true>; k.pick_tex = k_shade_smooth_pick_tex<true>;
-		k.env = k_shade_smooth_env<true>; k.env_tex = k_shade_smooth_env_tex<true>; k.mis = k_shade_smooth_mis<true>; k.mis_tex = k_shade_smooth_mis_tex<true>;
-		k.mis_env = k_shade_smooth_mis_env<true>; k.mis_env_tex = k_shade_smooth_mis_env_tex<true>;
-	}
-	else
-	{
-		k.plain = k_shade_smooth<false>; k.tex = k_shade_smooth_tex<false>; k.pick = k_shade_smooth_pick<false>; k.pick_tex = k_shade_smooth_pick_tex<false>;
-		k.env = k_shade_smooth_env<false>; k.env_tex = k_shade_smooth_env_tex<false>; k.mis = k_shade_smooth_mis<false>; k.mis_tex = k_shade_smooth_mis_tex<false>;
-		k.mis_env = k_shade_smooth_mis_env<false>; k.mis_env_tex = k_shade_smooth_mis_env_tex<false>;
-	}
-	return k;
-}
-
 typedef void (*ShadingNormalKernel)(SceneView, NormView, int, int, int, const float*, const float*, const float*, const float*, int*, float*, float*);
-ShadingNormalKernel shading_normal_kernel(const TraceLaunch& t)       // the instance that belongs to the k_trace trace_kernel selects
-{
-	if (t.trace == k_trace<6>) return k_shading_normal<6>;
-	if (t.trace == k_trace<5>) return k_shading_normal<5>;
-	if (t.trace == k_trace<4>) return k_shading_normal<4>;
-	if (t.trace == k_trace<2>) return k_shading_normal<2>;
-	if (t.trace == k_trace<1>) return k_shading_normal<1>;
-	return t.trace == k_trace<0> ? k_shading_normal<0> : nullptr;
-}
+// the instance that belongs to the k_trace trace_kernel selects
+ShadingNormalKernel shading_normal_kernel(const TraceLaunch& t) { return by_trace_mode(t.mode, [](auto m) -> ShadingNormalKernel { return k_shading_normal<decltype(m)::value>; }); }
 
 // nine values per triangle as the ABI takes them; which: the first offending triangle
 int check_vertex_normals(int n, const float* vn, int& n_smooth)

@@ -1,7 +1,7 @@
 // jet-pbrt_amd/csrc/jp_pick.h -- light selection (JP_LIGHTS_POWER_ONE; INTEGRATION.md "Light selection", DESIGN.md "Light selection"): the alias table
 // builder's entry point (the builder itself: build_light_table, jp_scene_host.h), the upload's table step, k_shade_pick / k_shade_pick_tex (shade_body<..., kPick>), the test hook k_light_pick and the entry points
 // jp_set_light_sampling / jp_get_light_info / jp_get_light_table / jp_light_pick / jp_build_light_table.  Included last by jp_kernels.hip: a context that
-// never switches the mode on runs nothing of this file.
+// never switches the mode on runs nothing of this file.  The kernels are selected and launched with every other k_shade family (shade_choice, jp_render.h; shade_launch, jp_shade_launch.h).
 #pragma once
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------------
@@ -27,22 +27,6 @@ __global__ void __launch_bounds__(JP_BLOCK) k_light_pick(PickView pv, int n, con
 		if (pv.n > 0) j = light_pick(pv, u0[i], u1[i], pm);
 		index[i] = j; pmf[i] = pm;
 	}
-}
-
-namespace
-{
-template <bool kTab, bool kPrims, bool kStage> ShadePickKernels shade_pick_row(bool sort)
-{
-	ShadePickKernels k = { sort ? k_shade_pick<kTab, kPrims, kStage, true> : k_shade_pick<kTab, kPrims, kStage, false>, sort ? k_shade_pick_tex<kTab, kPrims, kStage, true> : k_shade_pick_tex<kTab, kPrims, kStage, false> };
-	return k;
-}
-ShadePickKernels shade_pick_kernels(const ScenePlan& p)               // the rows of shade_kernels
-{
-	if (p.shade_prims_in_lds) return p.stage_nee ? shade_pick_row<true, true, true>(p.shade_sort) : shade_pick_row<true, true, false>(p.shade_sort);
-	if (p.tables_in_lds) return p.stage_nee ? shade_pick_row<true, false, true>(p.shade_sort) : shade_pick_row<true, false, false>(p.shade_sort);
-	return shade_pick_row<false, false, false>(p.shade_sort);
-}
-
 }
 
 // the upload's table step (jp_upload_scene, mode JP_LIGHTS_POWER_ONE): weights, table, the environment list, the device copies into the upload's

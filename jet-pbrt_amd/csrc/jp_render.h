@@ -1,4 +1,4 @@
-// jet-pbrt_amd/csrc/jp_render.h -- host runtime, part 3 of 3: jp_render* -- the shard helper, the kernel selectors, queue budget, the per-bounce launch sequence, stream lanes, the fused schedule,
+// jet-pbrt_amd/csrc/jp_render.h -- host runtime, part 3 of 3: jp_render* -- the shard helper, the kernel selectors (k_shade's launcher: jp_shade_launch.h), queue budget, the per-bounce launch sequence, stream lanes, the fused schedule,
 // and the rest of the C ABI (counters, build info, jp_trace, jp_bsdf, tone map).  Every buffer is a DevBuf of the context (grown through reserve_idle, jp_runtime.h, when
 // kernels in flight may use it) or a local DevBuf of the call; ensure_queues regrows a queue set as a whole.  Included by jp_kernels.hip after jp_upload.h.
 #pragma once
@@ -78,6 +78,8 @@ static void launch_texel(JpContext* c, const ScenePlan& p, int grid, int cur, co
 	if (p.sm.tex) hipLaunchKernelGGL(k_texel_s, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm);
 	else hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
 }
+// k_normal, or a mapped scene's k_normal_map / k_normal_map_s, timed likewise (defined in jp_shade_launch.h: the kernels come after this file)
+static void launch_normal(JpContext* c, const ScenePlan& p, int grid, int cur, const NormView& nv);
 
 // ---- the shard: JpRenderParams checked, its bands' rows counted, a lane's share of them ----------------------------------
 struct Shard { int band, count, index, local_rows, lane_rows; };     // local_rows: rows of the shard's bands; lane_rows: the ones this lane renders
@@ -101,6 +103,7 @@ int shard_of(const JpRenderParams* rp, Shard& s, int lane_index = 0, int lane_co
 
 // ---- kernel selectors: one function per kernel family (path_kernel below is k_path's), the only place of the host code that names the family's instantiations.
 // Each returns the kernel with the dynamic LDS and the stack words it is launched with: a pure function of the plan (shadow: and the region size), called once per render.
+// (k_shade's families are defined after this file: shade_choice picks here, shade_launch names the instances in jp_shade_launch.h.)
 inline bool refill_walks(const ScenePlan& p) { return p.persist && (p.trav_mode == 0 || p.trav_mode == 3 || p.trav_mode == 5); }   // the lane refill kernels exist for these walks
 inline int refill_row(const ScenePlan& p) { return p.persist >= 32 ? 2 : (p.persist >= 16 ? 1 : 0); }   // refill threshold 8 / 16 / 32: the row of a walk's table
 // stack words a thread's walk may need: closest-hit rays, shadow rays, and the deepest walk of all (the spill area's size)
@@ -162,64 +165,31 @@ ShadowLaunch shadow_kernel(const ScenePlan& p, unsigned int R, bool generic)   /
 	return { k, nullptr, plds, words, false };
 }
 
-typedef void (*ShadeKernel)(SceneView, Queues, RenderConst, int, DevCounters*);
-typedef void (*ShadeTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView);
-struct ShadeKernels { ShadeKernel plain; ShadeTexKernel tex; };        // k_shade and its textured twin (after k_texel); both take plan.shade_lds_bytes
-template <bool kTab, bool kPrims, bool kStage> ShadeKernels shade_row(bool sort)
+// k_shade and its families (shade_body<...>: jp_kernels.hip, jp_pick.h, jp_env.h, jp_mis.h, jp_normals.h).  shade_choice says which instance a render runs: a pure function of
+// the plan and of what the render switches on.  shade_launch (jp_shade_launch.h, included after the last family) binds that instance to the render's views: the only place
+// of the host code that names the instantiations.  Every instance takes plan.shade_lds_bytes.
+enum { SHADE_PLAIN = 0, SHADE_LEAN, SHADE_LEAN_ONE, SHADE_PICK, SHADE_ENV, SHADE_MIS, SHADE_MIS_ENV };
+enum { ROW_TTT = 0, ROW_TTF, ROW_TFT, ROW_TFF, ROW_FFF };            // <kTab, kPrims, kStage>
+struct ShadeChoice { int family; bool tex, smooth; int row; bool sort; };   // (smooth: the family's twin with kSmooth, which exists for sort alone -- the upload plans a smooth scene onto ROW_FFF)
+ShadeChoice shade_choice(const ScenePlan& p, bool tex, bool mis, bool smooth, bool generic)
 {
-	ShadeKernels k = { sort ? k_shade<kTab, kPrims, kStage, true> : k_shade<kTab, kPrims, kStage, false>, sort ? k_shade_tex<kTab, kPrims, kStage, true> : k_shade_tex<kTab, kPrims, kStage, false> };
-	return k;
-}
-ShadeKernels shade_kernels(const ScenePlan& p, bool generic)
-{
-	if (lean_shading(p, generic))
-	{   // the textured twin stays generic (a textured scene is outside the lean sets' measurements)
-		ShadeKernels k = shade_row<true, true, true>(p.shade_sort);
-		k.plain = p.shade_sort ? k_shade<true, true, true, true, FeatLean> : k_shade<true, true, true, false, FeatLean>;
+	ShadeChoice c;
+	c.family = mis ? (p.env ? SHADE_MIS_ENV : SHADE_MIS) : (p.env ? SHADE_ENV : (p.pick ? SHADE_PICK : SHADE_PLAIN));
+	c.tex = tex; c.smooth = smooth; c.sort = p.shade_sort;
+	c.row = p.shade_prims_in_lds ? (p.stage_nee ? ROW_TTT : ROW_TTF) : (p.tables_in_lds ? (p.stage_nee ? ROW_TFT : ROW_TFF) : ROW_FFF);
+	if (c.family == SHADE_PLAIN && !tex && !smooth && lean_shading(p, generic))
+	{   // FeatLean (its row is ROW_TTT); the textured twin stays generic (a textured scene is outside the lean sets' measurements)
+		c.family = SHADE_LEAN;
 #ifndef JP_NO_ONE_SWEEP
-		if (p.shade_sort && !p.has_null_material) k.plain = k_shade_lean_one;   // one-sweep partition: a miss does nothing in this instance only while no primitive is without a material
+		if (p.shade_sort && !p.has_null_material) c.family = SHADE_LEAN_ONE;   // one-sweep partition: a miss does nothing in this instance only while no primitive is without a material
 #endif
-		return k;
 	}
-	if (p.shade_prims_in_lds) return p.stage_nee ? shade_row<true, true, true>(p.shade_sort) : shade_row<true, true, false>(p.shade_sort);
-	if (p.tables_in_lds) return p.stage_nee ? shade_row<true, false, true>(p.shade_sort) : shade_row<true, false, false>(p.shade_sort);
-	return shade_row<false, false, false>(p.shade_sort);
+	return c;
 }
-
-// JP_LIGHTS_POWER_ONE: k_shade_pick and its textured twin, same rows (selector in jp_pick.h, next to the kernels)
-typedef void (*ShadePickKernel)(SceneView, Queues, RenderConst, int, DevCounters*, PickView);
-typedef void (*ShadePickTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView);
-struct ShadePickKernels { ShadePickKernel plain; ShadePickTexKernel tex; };
-ShadePickKernels shade_pick_kernels(const ScenePlan& p);
-// ... with an environment map: k_shade_env and its textured twin, same rows again (selector in jp_env.h)
-typedef void (*ShadeEnvKernel)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, EnvView);
-typedef void (*ShadeEnvTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView);
-struct ShadeEnvKernels { ShadeEnvKernel plain; ShadeEnvTexKernel tex; };
-ShadeEnvKernels shade_env_kernels(const ScenePlan& p);
-// JP_ESTIMATOR_MIS: the pick and map kernels with both strategies weighted, same rows once more (selector and side records in jp_mis.h)
-typedef void (*ShadeMisKernel)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, MisView);
-typedef void (*ShadeMisTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, MisView);
-typedef void (*ShadeMisEnvKernel)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, EnvView, MisView);
-typedef void (*ShadeMisEnvTexKernel)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView, MisView);
-struct ShadeMisKernels { ShadeMisKernel pick; ShadeMisTexKernel pick_tex; ShadeMisEnvKernel env; ShadeMisEnvTexKernel env_tex; };
-ShadeMisKernels shade_mis_kernels(const ScenePlan& p);
-// scenes with vertex normals: k_normal after k_texel, then the smooth twin of the family the scene would take (selector and side records in jp_normals.h)
-struct SmoothKernels
-{
-	void (*normal)(SceneView, Queues, int, NormView);
-	void (*normal_map)(SceneView, Queues, int, NormView, NMapView);          // k_normal's twin of a mapped scene (jp_normal_map.h)
-	void (*plain)(SceneView, Queues, RenderConst, int, DevCounters*, NormView);
-	void (*tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, NormView);
-	void (*pick)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, NormView);
-	void (*pick_tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, NormView);
-	void (*env)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, EnvView, NormView);
-	void (*env_tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView, NormView);
-	void (*mis)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, MisView, NormView);
-	void (*mis_tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, MisView, NormView);
-	void (*mis_env)(SceneView, Queues, RenderConst, int, DevCounters*, PickView, EnvView, MisView, NormView);
-	void (*mis_env_tex)(SceneView, Queues, RenderConst, int, DevCounters*, TexView, PickView, EnvView, MisView, NormView);
-};
-SmoothKernels shade_smooth_kernels(const ScenePlan& p);
+// the views of one render, in the order the kernels append them; each kernel takes the ones its signature names (TexView::side, MisView and NormView::side are the queue set's)
+typedef std::tuple<TexView, PickView, EnvView, MisView, NormView> ShadeViews;
+typedef std::function<void(hipStream_t, int, size_t, const SceneView&, const Queues&, const RenderConst&, int, DevCounters*)> ShadeLaunch;   // (stream, grid, lds, sv, q, rc, cur, cnt)
+ShadeLaunch shade_launch(const ShadeChoice& c, const ShadeViews& views);
 }
 // the bytes of jp_render_rgb8 / jp_render_denoised, after ensure_rgb8: k_tonemap8, or the display transform while a tone map is in force (jp_film.h, part 2)
 static int film_to_rgb8(JpContext* c, const float* src, int width, int height);
@@ -236,16 +206,31 @@ OtherKernel other_kernel(const ScenePlan& p) { return p.trav_mode == 5 ? k_other
 // render's closest-hit rays walk.  The one-ray-per-lane kernels keep the whole stack in LDS: a 4-wide tree deeper than 64 KB of stack falls back to the binary / verbatim walk
 typedef void (*TraceKernel)(SceneView, int, int, const float*, const float*, const float*, const float*, int*, float*, int*, float*);
 typedef void (*SurfaceKernel)(SceneView, TexView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*, SampView);
-struct TraceLaunch { TraceKernel trace; SurfaceKernel surface; size_t lds; int depth; };     // (surface: null for the 8-wide walk, which only trace_walk = 2 selects)
-template <int M> TraceLaunch trace_row(size_t lds, int depth) { TraceLaunch t = { k_trace<M>, k_surface<M>, lds, depth }; return t; }
+struct TraceLaunch { TraceKernel trace; SurfaceKernel surface; size_t lds; int depth; int mode; };   // (surface: null for the 8-wide walk, which only trace_walk = 2 selects; mode: the kMode that runs, + 16 for the lean flat instance)
+template <int M> TraceLaunch trace_row(size_t lds, int depth) { TraceLaunch t = { k_trace<M>, k_surface<M>, lds, depth, M }; return t; }
+// the hooks that ride on k_trace's walk (k_light_pdf, k_shading_normal, k_shading_normal_mapped): f(integral_constant<int, kMode>) for the mode trace_kernel chose; null
+// for the 8-wide walk (mode 3) and the lean flat instance, of which these hooks have no instance
+template <class F> auto by_trace_mode(int mode, F f) -> decltype(f(std::integral_constant<int, 0>()))
+{
+	switch (mode)
+	{
+	case 0: return f(std::integral_constant<int, 0>());
+	case 1: return f(std::integral_constant<int, 1>());
+	case 2: return f(std::integral_constant<int, 2>());
+	case 4: return f(std::integral_constant<int, 4>());
+	case 5: return f(std::integral_constant<int, 5>());
+	case 6: return f(std::integral_constant<int, 6>());
+	default: return nullptr;
+	}
+}
 TraceLaunch trace_kernel(const ScenePlan& p, int tw, bool generic = true)   // generic false (jp_trace without JpOptions::reserved[0] == 1): a scene of flat shapes gets the lean closest-hit walk
 {
 	const size_t q4lds = (size_t)p.stack_depth_q4 * JP_BLOCK * sizeof(int);
-	if (p.trav_mode == 3 && tw == 2) { TraceLaunch t = { k_trace<3>, nullptr, p.lds_bytes_shadow, p.stack_depth }; return t; }
+	if (p.trav_mode == 3 && tw == 2) { TraceLaunch t = { k_trace<3>, nullptr, p.lds_bytes_shadow, p.stack_depth, 3 }; return t; }
 	if (p.trav_mode == 5 && p.cert && q4lds <= 64 * 1024 && tw != 3) return trace_row<6>(q4lds, p.stack_depth_q4);
 	if (p.trav_mode == 5) return trace_row<5>(p.lds_bytes, p.stack_depth);
 	if (p.use_q4 && q4lds <= 64 * 1024 && tw != 1) return trace_row<4>(q4lds, p.stack_depth_q4);
-	if (lean_traversal(p, generic)) { TraceLaunch t = { k_trace_flat, k_surface<2>, p.lds_bytes, p.stack_depth }; return t; }
+	if (lean_traversal(p, generic)) { TraceLaunch t = { k_trace_flat, k_surface<2>, p.lds_bytes, p.stack_depth, 2 + 16 }; return t; }
 	return p.trav_mode == 2 ? trace_row<2>(p.lds_bytes, p.stack_depth) : (p.trav_mode == 1 ? trace_row<1>(p.lds_bytes, p.stack_depth) : trace_row<0>(p.lds_bytes, p.stack_depth));
 }
 
@@ -347,11 +332,8 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		if (c->opt.compact_regions != 0) rc.compact = (c->opt.compact_regions > 0 && npix % JP_BLOCK == 0) ? 1 : 0;
 		const int grid = (int)G;
 		const bool generic = c->opt.reserved[0] == 1;                // JpOptions::reserved[0]: the kernels with every feature in them, whatever the scene holds
-		const ExtendLaunch ek = extend_kernel(p, generic); const ShadowLaunch sk = shadow_kernel(p, R, generic); const ShadeKernels hk = shade_kernels(p, generic); const OtherKernel ok = other_kernel(p);
-		const ShadePickKernels pk = p.pick ? shade_pick_kernels(p) : ShadePickKernels{ nullptr, nullptr };
-		const ShadeEnvKernels vk = p.env ? shade_env_kernels(p) : ShadeEnvKernels{ nullptr, nullptr };
-		const ShadeMisKernels mk2 = mis ? shade_mis_kernels(p) : ShadeMisKernels{ nullptr, nullptr, nullptr, nullptr };
-		const SmoothKernels nk = smooth ? shade_smooth_kernels(p) : SmoothKernels{};
+		const ExtendLaunch ek = extend_kernel(p, generic); const ShadowLaunch sk = shadow_kernel(p, R, generic); const OtherKernel ok = other_kernel(p);
+		const ShadeLaunch shade = shade_launch(shade_choice(p, tex, mis, smooth, generic), ShadeViews(tv, p.pv, p.ev, mv, nv));
 		JpLensPlan lp;                                                 // jp_set_lens: k_raygen<true> / k_other form the lens ray; the bounces never know
 		if (const int e = lens_plan_of(c, lp); e != JP_OK) return e;
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
@@ -386,41 +368,9 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 				}
 				{
 					Stamper t(c, CLS_SHADE);
-					if (smooth)
-					{   // scenes with vertex normals: k_texel as ever, k_normal leaves Ns for every hit on a smooth triangle, the family's smooth twin shades with it
-						if (tex) launch_texel(c, p, grid, cur, tv);
-						if (p.mapped && p.sm.map) { Stamper tn(c, CLS_NMAP); hipLaunchKernelGGL(k_normal_map_s, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv, p.mp, p.sm); }   // ... addressed through a sampling record: its twin
-						else if (p.mapped) { Stamper tn(c, CLS_NMAP); hipLaunchKernelGGL(nk.normal_map, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv, p.mp); }   // normal maps: one kernel leaves Ns or Ns'
-						else { Stamper tn(c, CLS_NORMAL); hipLaunchKernelGGL(nk.normal, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, nv); }
-						const size_t l = p.shade_lds_bytes;
-						if (tex)
-						{
-							if (mis && p.env) hipLaunchKernelGGL(nk.mis_env_tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev, mv, nv);
-							else if (mis) hipLaunchKernelGGL(nk.mis_tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, mv, nv);
-							else if (p.env) hipLaunchKernelGGL(nk.env_tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev, nv);
-							else if (p.pick) hipLaunchKernelGGL(nk.pick_tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, nv);
-							else hipLaunchKernelGGL(nk.tex, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, nv);
-						}
-						else if (mis && p.env) hipLaunchKernelGGL(nk.mis_env, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev, mv, nv);
-						else if (mis) hipLaunchKernelGGL(nk.mis, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, mv, nv);
-						else if (p.env) hipLaunchKernelGGL(nk.env, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev, nv);
-						else if (p.pick) hipLaunchKernelGGL(nk.pick, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, nv);
-						else hipLaunchKernelGGL(nk.plain, dim3(grid), dim3(JP_BLOCK), l, c->stream, p.sv, c->q, rc, cur, d_cnt, nv);
-					}
-					else if (tex)
-					{   // textured scenes: k_texel leaves the texture's answer for every hit, k_shade_tex shades with it (same schedule otherwise)
-						launch_texel(c, p, grid, cur, tv);
-						if (mis && p.env) hipLaunchKernelGGL(mk2.env_tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev, mv);
-						else if (mis) hipLaunchKernelGGL(mk2.pick_tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, mv);
-						else if (p.env) hipLaunchKernelGGL(vk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv, p.ev);
-						else if (p.pick) hipLaunchKernelGGL(pk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv, p.pv);
-						else hipLaunchKernelGGL(hk.tex, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, tv);
-					}
-					else if (mis && p.env) hipLaunchKernelGGL(mk2.env, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev, mv);
-					else if (mis) hipLaunchKernelGGL(mk2.pick, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, mv);
-					else if (p.env) hipLaunchKernelGGL(vk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv, p.ev);
-					else if (p.pick) hipLaunchKernelGGL(pk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt, p.pv);
-					else hipLaunchKernelGGL(hk.plain, dim3(grid), dim3(JP_BLOCK), p.shade_lds_bytes, c->stream, p.sv, c->q, rc, cur, d_cnt);
+					if (tex) launch_texel(c, p, grid, cur, tv);              // textured scenes: k_texel leaves the texture's answer for every hit, the textured twin shades with it
+					if (smooth) launch_normal(c, p, grid, cur, nv);         // scenes with vertex normals or normal maps: Ns for every hit it applies to, the smooth twin shades with it
+					shade(c->stream, grid, p.shade_lds_bytes, p.sv, c->q, rc, cur, d_cnt);
 				}
 				HIP_TRY(hipGetLastError());                               // a failed launch (k_extend / k_shade) is reported where it happens, not at the end of the frame
 				if (it < rp->max_depth || p.has_null_material)                 // at bounce == maxDepth Li() breaks before the NEE (integrator.cc:340-343)

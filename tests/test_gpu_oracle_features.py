@@ -11,7 +11,7 @@ cell is one render of at most 48 x 32 pixels at 16 spp, depth 6, counter sampler
 Scenes with a mesh -- all of them -- are rendered on the reference tree, so both sides walk the same tree; one cell runs on the library's own tree under the rule of
 test_gpu_parity.assert_film.
 
-The shade_body instantiations the library can launch for these feature sets (jp_render.h shade_kernels, jp_pick.h, jp_env.h, jp_mis.h, jp_normals.h), by
+The shade_body instantiations the library can launch for these feature sets (jp_render.h shade_choice, jp_shade_launch.h shade_launch), by
 <kTab, kPrims, kStage> = (tables in LDS, primitive records in LDS, next-event entries staged), each with kSort on and off:
 
   family                          TTT        TTF        TFT           TFF        FFF        covered by

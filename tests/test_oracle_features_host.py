@@ -248,7 +248,7 @@ def _cells():
     return cells
 
 
-# the row of the kernel selectors (jp_render.h shade_kernels, jp_pick.h, jp_env.h, jp_mis.h, jp_normals.h) each variant reaches: (tables in LDS, primitive records in
+# the row of the kernel selector (jp_render.h shade_choice) each variant reaches: (tables in LDS, primitive records in
 # LDS, next-event entries staged) in JP_LIGHTS_ALL and in JP_LIGHTS_POWER_ONE; a scene with smooth triangles or normal maps: (0, 0, 0) whatever its size
 ROWS = {"zoo": ((1, 1, 0), (1, 1, 1)), "zoo_few": ((1, 1, 1), (1, 1, 1)), "zoo_bulk": ((1, 0, 0), (1, 0, 1)), "zoo_bulk_few": ((1, 0, 1), (1, 0, 1)), "zoo_mats": ((0, 0, 0), (0, 0, 0)),
         "cornell": ((1, 1, 1), (1, 1, 1)), "cornell_null": ((1, 1, 1), (1, 1, 1))}
