@@ -1245,6 +1245,15 @@ class Context:
         self._check(fn(self.h, C.byref(which)))
         return ("refill", "generic", "flat", "pair")[which.value]
 
+    def extend_kernel(self):
+        """jp_dbg_extend_kernel (diagnostic, outside the ABI structs): the closest-hit kernel the selector picks for the uploaded scene under the options in
+        force -> "refill" (a lane-refill kernel), "generic" (k_extend<mode>), "flat" (k_extend<2, FeatFlat>) or "pool" (k_extend_pool)"""
+        fn = self.lib.jp_dbg_extend_kernel
+        fn.argtypes = [C.c_void_p, C.POINTER(C.c_int)]; fn.restype = C.c_int
+        which = C.c_int(-1)
+        self._check(fn(self.h, C.byref(which)))
+        return ("refill", "generic", "flat", "pool")[which.value]
+
     def read_table(self, which):
         """jp_read_scene_table: one hierarchy table of the uploaded scene ("nodes", "prims", "meta", "wide", "q4", "flat"), copied from the device -> uint8 array"""
         return _read_table(lambda out, cap, n: self.lib.jp_read_scene_table(self.h, _table_index(which), out, cap, n))

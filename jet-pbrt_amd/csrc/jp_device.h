@@ -511,6 +511,66 @@ __device__ __forceinline__ void flat_prims_pair(unsigned int mA, unsigned int mB
 	hitA = hA; hitB = hB;
 }
 
+// ---- the closest hits of a wave's rays from one pooled list (k_extend_pool, k_trace_pool; DESIGN.md section 5, "Pooled closest hits") ------
+// flat_prims runs as many trips as the lane with the most candidates has set bits, every trip with the lanes that still hold one.  Here the
+// wave's (owner lane, primitive) pairs go through a ring of 16-bit entries in LDS and are tested 64 at a time, one pair per lane, whoever owns it.
+//   list   per trip every lane that holds a candidate appends its next one in __ffs order; room is taken by ballot rank.  The ring holds
+//          JP_POOL_RING = 128 entries: fewer than 64 wait when a trip starts, a trip adds at most 64, and a dense round runs as soon as 64 wait.
+//   round  prim_hit itself (tri_hit / rect_hit: the interval half, then the inside test under the execution mask) on the owner's ray, read
+//          from LDS, against the owner's ORIGINAL tmax; an accepted pair does one 64-bit LDS atomic min on (distance bits << 32 | primitive)
+//          into the owner's slot.
+//   result the lane's own slot after the last round.
+// The sequential loop returns the accepted candidate of least distance, among equal distances the first in __ffs order (`distance < tmax`
+// is strict): the minimum of (distance, primitive) over the accepted set of the ray's mask.  Testing against the original tmax instead of
+// the shrinking one only adds candidates farther than that minimum.  Accepted distances are > tmin >= 0, so positive and no NaN: their bit
+// patterns order as the floats do (the callers send a wave whose tmin may be negative through flat_prims).
+// All LDS traffic is the wave's own and LDS serves a wave's instructions in order: no barrier; the wavefront-scope fences only keep the
+// compiler from moving an access across the point where another lane's access answers it.  Every lane of the wave must call this
+// (a lane without a ray: mask 0).  kUniform: (tmin, tmax) is the same for every ray of the wave (k_extend), so the rays carry none.
+#define JP_POOL_RING 128
+#define JP_POOL_WAVE_BYTES (64 * 32 + 64 * 8 + JP_POOL_RING * 2)      // rays (2 x float4), slots (u64), ring (u16) of one wave
+template <bool kUniform, int kS, typename PrimPtr>
+__device__ __forceinline__ void pool_round(PrimPtr prims, const float4* rays, u64* slots, const unsigned short* ring, unsigned int head, unsigned int n_valid,
+                                           unsigned int lane, float tmin_u, float tmax_u)
+{
+	if (lane < n_valid)
+	{
+		const unsigned int e = ring[(head + lane) & (JP_POOL_RING - 1)];
+		const unsigned int owner = e >> 8, p = e & 0xffu;
+		const float4 r0 = rays[2 * owner], r1 = rays[2 * owner + 1];
+		float t = kUniform ? tmax_u : r1.w;
+		if (prim_hit<kS, FeatFlat>(prims, (int)p, xyz(r0), mk(r0.w, r1.x, r1.y), kUniform ? tmin_u : r1.z, t))
+			__hip_atomic_fetch_min(&slots[owner], ((u64)__float_as_uint(t) << 32) | (u64)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+	}
+}
+
+template <bool kUniform, int kS, typename PrimPtr>
+__device__ __forceinline__ int flat_prims_pool(unsigned int mask, PrimPtr prims, V3 o, V3 d, float tmin, float& tmax, float4* rays, u64* slots, unsigned short* ring)
+{
+	const unsigned int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+	rays[2 * lane] = make_float4(o.x, o.y, o.z, d.x); rays[2 * lane + 1] = make_float4(d.y, d.z, tmin, tmax);
+	slots[lane] = ~(u64)0;
+	__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+	unsigned int head = 0, tail = 0;                                  // wave-uniform; tail - head entries wait in the ring
+	for (u64 live = __ballot(mask != 0); live; live = __ballot(mask != 0))   // one trip per set bit of the fullest mask: at most 32
+	{
+		const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(live >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)live, 0u));
+		const unsigned int entry = (lane << 8) | (unsigned int)(__ffs((int)mask) - 1);   // (an empty mask: no store)
+		if (mask) ring[(tail + rank) & (JP_POOL_RING - 1)] = (unsigned short)entry;
+		mask &= mask - 1;                                             // (0 stays 0)
+		tail += (unsigned int)__popcll(live);
+		__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+		if (tail - head >= 64u) { pool_round<kUniform, kS>(prims, rays, slots, ring, head, 64u, lane, tmin, tmax); head += 64u; }
+	}
+	if (tail != head) pool_round<kUniform, kS>(prims, rays, slots, ring, head, tail - head, lane, tmin, tmax);
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+	const u64 best = slots[lane];
+	__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");             // (the next pass's stores stay behind this read)
+	if (best == ~(u64)0) return -1;
+	tmax = __uint_as_float((unsigned int)(best >> 32));
+	return (int)(unsigned int)best;
+}
+
 // Large scenes: 8-wide BVH with quantised child boxes (after Ylitie, Karras, Laine: "Efficient Incoherent Ray Traversal
 // on GPUs Through Compressed Wide BVHs", HPG 2017), 80 bytes per node.  Incoherent rays on a 280k-triangle scene are
 // bound by the number of distinct cache lines a wave's loads touch (every lane walks its own node): the binary tree

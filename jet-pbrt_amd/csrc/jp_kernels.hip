@@ -244,6 +244,44 @@ __global__ void __launch_bounds__(JP_BLOCK) k_extend(SceneView sc, Queues q, int
 	if ((threadIdx.x & 63) == 0 && h) atomicAdd(&cnt->closest_hit, (unsigned long long)h);
 }
 
+// the pooled pass's LDS behind the primitive table: JP_POOL_WAVE_BYTES per wave (jp_device.h: rays, slots, ring)
+struct PoolLds
+{
+	float4* rays; u64* slots; unsigned short* ring;
+	__device__ __forceinline__ PoolLds(int n_prims)
+	{
+		char* base = (char*)(s_dyn + 5 * n_prims) + (threadIdx.x >> 6) * JP_POOL_WAVE_BYTES;
+		rays = (float4*)base; slots = (u64*)(base + 64 * 32); ring = (unsigned short*)(base + 64 * 32 + 64 * 8);
+	}
+};
+
+// k_extend_pool: k_extend<2, FeatFlat> for scenes of <= 32 primitives, a kernel of its own name (extend_kernel, jp_render.h).  The box phase is
+// flat_boxes_lean<true> per lane, the primitive phase flat_prims_pool (jp_device.h; DESIGN.md section 5, "Pooled closest hits"): the wave's candidates
+// from one list, 64 per round.  A wave takes 64 consecutive rays of the region per pass as in k_extend, but walks the region with a wave-uniform
+// loop: the lanes behind the region's end carry an empty mask through the pass, because every lane serves the list.
+__global__ void __launch_bounds__(JP_BLOCK, 8) k_extend_pool(SceneView sc, Queues q, int cur, int depth, DevCounters* cnt)
+{
+	SceneAccess<2, FeatFlat> acc(sc, depth);
+	const PoolLds pool(sc.n_prims);
+	const unsigned int b = blockIdx.x, n = q.blk_q[cur][b], rbase = b * q.R;
+	if (b == 0 && threadIdx.x == 0) { cnt->closest += cnt->n_queue[cur]; cnt->n_queue[cur ^ 1] = 0; cnt->n_shadow = 0; }
+	unsigned int h = 0;
+	float4 ro = make_float4(0, 0, 0, 0), rd = make_float4(0, 0, 1, 0);
+	if (threadIdx.x < n) { ro = q.ray_o[cur][rbase + threadIdx.x]; rd = q.ray_d[cur][rbase + threadIdx.x]; }
+	for (unsigned int j0 = threadIdx.x & ~63u; j0 < n; j0 += JP_BLOCK)          // j0: the wave's first ray of the pass, wave-uniform
+	{
+		const unsigned int j = j0 + (threadIdx.x & 63u), i = rbase + j;
+		const float4 co = ro, cd = rd;
+		if (j + JP_BLOCK < n) { ro = q.ray_o[cur][i + JP_BLOCK]; rd = q.ray_d[cur][i + JP_BLOCK]; }
+		float tmax = JP_INF;
+		const unsigned int m = flat_boxes_lean<true>(sc.flat, sc.n_flat, xyz(co), xyz(cd), 0.001f, tmax);
+		const int hit = flat_prims_pool<true, 5>(j < n ? m : 0u, acc.prims, xyz(co), xyz(cd), 0.001f, tmax, pool.rays, pool.slots, pool.ring);
+		if (j < n) { q.hit[i] = make_float2(tmax, __int_as_float(hit)); h += hit >= 0 ? 1u : 0u; }
+	}
+	for (int off = 32; off > 0; off >>= 1) h += __shfl_down(h, off);
+	if ((threadIdx.x & 63) == 0 && h) atomicAdd(&cnt->closest_hit, (unsigned long long)h);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // k_shade: the body of FPathIntegratorIteration::Li after the intersection (integrator.cc:328-399)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1448,6 +1486,37 @@ __global__ void __launch_bounds__(JP_BLOCK) k_trace_flat(SceneView sc, int depth
 			N = (__float_as_int(g3.w) == JP_SHAPE_TRIANGLE || dot(xyz(g3), rd) <= 0) ? xyz(g3) : -xyz(g3);
 		}
 		nrm[3 * i] = N.x; nrm[3 * i + 1] = N.y; nrm[3 * i + 2] = N.z;
+	}
+}
+
+// k_trace_flat for scenes of <= 32 primitives: the walk of k_extend_pool with the caller's (tmin, tmax) per ray (flat_boxes_lean<false>, flat_prims_pool<false>).
+// The pooled pass orders distances by their bit patterns, which needs tmin >= 0: a wave that holds a ray with any other tmin (negative, NaN) takes flat_prims.
+__global__ void __launch_bounds__(JP_BLOCK, 8) k_trace_pool(SceneView sc, int depth, int n, const float* o, const float* d, const float* tmin, const float* tmax_in,
+                                                            int* hit, float* t, int* prim, float* nrm)
+{
+	SceneAccess<2, FeatFlat> acc(sc, depth);
+	const PoolLds pool(sc.n_prims);
+	for (int i0 = blockIdx.x * JP_BLOCK + (threadIdx.x & ~63); i0 < n; i0 += gridDim.x * JP_BLOCK)   // i0: the wave's first ray of the pass, wave-uniform
+	{
+		const int i = i0 + (threadIdx.x & 63);
+		const bool live = i < n;
+		V3 ro = mk(0, 0, 0), rd = mk(0, 0, 1); float t0 = 0.001f, tmax = JP_INF;
+		if (live) { ro = mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]); rd = mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]); t0 = tmin[i]; tmax = tmax_in[i]; }
+		const unsigned int m0 = flat_boxes_lean<false>(sc.flat, sc.n_flat, ro, rd, t0, tmax), m = live ? m0 : 0u;
+		int h;
+		if (__ballot(!(t0 >= 0.f)) == 0) h = flat_prims_pool<false, 5>(m, acc.prims, ro, rd, t0, tmax, pool.rays, pool.slots, pool.ring);
+		else h = flat_prims<false, false, 5, FeatFlat>(m, acc.prims, ro, rd, t0, tmax);
+		if (live)
+		{
+			hit[i] = h >= 0; t[i] = tmax; prim[i] = h >= 0 ? sc.meta[h].x : -1;
+			V3 N = mk(0, 0, 0);
+			if (h >= 0)
+			{
+				const float4 g3 = sc.prims[4 * h + 3];
+				N = (__float_as_int(g3.w) == JP_SHAPE_TRIANGLE || dot(xyz(g3), rd) <= 0) ? xyz(g3) : -xyz(g3);
+			}
+			nrm[3 * i] = N.x; nrm[3 * i + 1] = N.y; nrm[3 * i + 2] = N.z;
+		}
 	}
 }
 

@@ -126,6 +126,7 @@ inline bool lean_shading(const ScenePlan& p, bool generic)
 }
 
 typedef void (*ExtendKernel)(SceneView, Queues, int, int, DevCounters*);
+inline size_t pool_lds_bytes() { return (size_t)(JP_BLOCK / 64) * JP_POOL_WAVE_BYTES; }   // k_extend_pool / k_trace_pool: the pooled pass's LDS of a workgroup (jp_device.h)
 typedef void (*ExtendRefillKernel)(SceneView, Queues, int, int, int*, DevCounters*);
 struct ExtendLaunch { ExtendRefillKernel refill; ExtendKernel plain; size_t lds; int words; };   // one of the two kernels; words: of the stack, kept in LDS (refill) / in all (plain)
 template <int M> ExtendRefillKernel extend_refill(const ScenePlan& p)
@@ -135,6 +136,10 @@ template <int M> ExtendRefillKernel extend_refill(const ScenePlan& p)
 }
 ExtendLaunch extend_kernel(const ScenePlan& p, bool generic)
 {
+#ifndef JP_NO_EXTEND_POOL
+	// the wave's primitive tests from one pooled list (k_extend_pool): the 32-bit-mask scenes; its per-wave rays, slots and ring lie behind the primitive table
+	if (lean_traversal(p, generic) && p.sv.n_prims <= 32) return { nullptr, k_extend_pool, p.lds_bytes + pool_lds_bytes(), p.stack_depth };
+#endif
 	if (lean_traversal(p, generic)) return { nullptr, k_extend<2, FeatFlat>, p.lds_bytes, p.stack_depth };
 	if (!refill_walks(p)) return { nullptr, p.trav_mode == 5 ? k_extend<5> : (p.trav_mode == 2 ? k_extend<2> : (p.trav_mode == 1 ? k_extend<1> : k_extend<0>)), p.lds_bytes, p.stack_depth };
 	const int words = std::min(extend_depth(p), p.stack_lds_words);
@@ -230,6 +235,9 @@ TraceLaunch trace_kernel(const ScenePlan& p, int tw, bool generic = true)   // g
 	if (p.trav_mode == 5 && p.cert && q4lds <= 64 * 1024 && tw != 3) return trace_row<6>(q4lds, p.stack_depth_q4);
 	if (p.trav_mode == 5) return trace_row<5>(p.lds_bytes, p.stack_depth);
 	if (p.use_q4 && q4lds <= 64 * 1024 && tw != 1) return trace_row<4>(q4lds, p.stack_depth_q4);
+#ifndef JP_NO_EXTEND_POOL
+	if (lean_traversal(p, generic) && p.sv.n_prims <= 32) { TraceLaunch t = { k_trace_pool, k_surface<2>, p.lds_bytes + pool_lds_bytes(), p.stack_depth, 2 + 16 }; return t; }   // (k_surface<2> takes less LDS than it is given)
+#endif
 	if (lean_traversal(p, generic)) { TraceLaunch t = { k_trace_flat, k_surface<2>, p.lds_bytes, p.stack_depth, 2 + 16 }; return t; }
 	return p.trav_mode == 2 ? trace_row<2>(p.lds_bytes, p.stack_depth) : (p.trav_mode == 1 ? trace_row<1>(p.lds_bytes, p.stack_depth) : trace_row<0>(p.lds_bytes, p.stack_depth));
 }
@@ -866,6 +874,16 @@ extern "C" int jp_dbg_shadow_kernel(JpContext* c, int* which_out)
 	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_dbg_shadow_kernel: no scene uploaded");
 	const ShadowLaunch sk = shadow_kernel(c->plan, c->q.R ? c->q.R : JP_BLOCK, c->opt.reserved[0] == 1);
 	*which_out = sk.refill ? 0 : (sk.plain == (ShadowKernel)k_shadow_pair ? 3 : (sk.plain == (ShadowKernel)k_shadow<2, FeatFlat> ? 2 : 1));
+	return JP_OK;
+}
+
+// The same for the closest-hit kernel extend_kernel picks.  0: a lane-refill kernel, 1: k_extend<mode> with every feature in it, 2: k_extend<2, FeatFlat>, 3: k_extend_pool
+extern "C" int jp_dbg_extend_kernel(JpContext* c, int* which_out)
+{
+	if (!c || !which_out) return fail(JP_ERR_INVALID_ARGUMENT, "jp_dbg_extend_kernel: null argument");
+	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_dbg_extend_kernel: no scene uploaded");
+	const ExtendLaunch ek = extend_kernel(c->plan, c->opt.reserved[0] == 1);
+	*which_out = ek.refill ? 0 : (ek.plain == (ExtendKernel)k_extend_pool ? 3 : (ek.plain == (ExtendKernel)k_extend<2, FeatFlat> ? 2 : 1));
 	return JP_OK;
 }
 
