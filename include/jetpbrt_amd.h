@@ -578,6 +578,50 @@ int  jp_texture_lookup(const JpTexSampler* s_or_null, int32_t w, int32_t h, cons
 int  jp_perturb_normals_sampled(const JpTexSampler* s_or_null, int32_t n, const float* nb, const float* ng, const float* dpdu, const float* dpdv, const float* uv,
                                 int32_t width, int32_t height, const uint8_t* rgb8, float strength, float* ns_out, int32_t* perturbed_out);
 
+/* Mip maps (additive to ABI 7; INTEGRATION.md "Mip maps" has the definition, include/jp_mipmap.h the code).  A mode per image texture: with JP_MIP_TRILINEAR the
+ * upload builds the texture's pyramid on the device (box filter, integers) behind the texel pool, and the path integrator carries a ray cone per path slot
+ * (width, spread: 8 bytes) from which the side kernel k_texel_m -- in k_texel / k_texel_s's place -- takes the footprint rho of every textured hit in texels and
+ * filters trilinearly between levels floor(log2 rho) and the next.  rho <= 1 is exactly the lookup without mipmaps.  footprint_scale multiplies rho (0: 1);
+ * bounce_spread (radians; 0: 0.125, a design choice) is the least spread of the cone after a bounce that is not specular.  Context state like the sampling
+ * records: validated and copied here, read by the next jp_upload_scene*, whose JpTextures.n_textures must equal n_textures (a plain jp_upload_scene counts as 0):
+ * else JP_ERR_INVALID_ARGUMENT, and the context keeps the scene it had.  JP_MIP_TRILINEAR on a SOLID or CHECKER texture is refused at the upload.  No state, all
+ * modes OFF, or mipmaps only on textures no material uses: exactly the upload without them -- the same kernels, mip_last_render 0, no device bytes.  The guides'
+ * albedo follows the mip at the first hit (width = gamma0 * t); jp_surface has no cone and reads level 0.  Normal maps are not mip-mapped. */
+enum { JP_MIP_OFF = 0, JP_MIP_TRILINEAR = 1 };
+typedef struct JpTextureMipmaps { int32_t struct_bytes, n_textures; const int32_t* mode; float footprint_scale, bounce_spread; } JpTextureMipmaps;   /* mode NULL: all OFF */
+typedef struct JpTextureMipmapInfo {
+    int32_t struct_bytes, n_on;                       /* textures of the uploaded scene whose pyramid was built (mode TRILINEAR, used by a material)          */
+    int32_t n_levels;                                 /* their levels in all, level 0 included                                                               */
+    int32_t mip_last_render;                          /* the last jp_render* ran k_texel_m                                                                   */
+    int64_t pyramid_bytes_device;                     /* levels >= 1, 4 bytes per texel, plus the level tables                                               */
+    int64_t cone_bytes_device;                        /* 8 bytes per path slot, over all lanes (0 until a render needs it)                                   */
+    double  build_ms;                                 /* the k_mip_level launches of the upload (HIP events)                                                 */
+    double  texel_ms;                                 /* with jp_set_profiling: the side kernel's launches of the last render (JpTexSamplingInfo.texel_ms)  */
+    float   footprint_scale, bounce_spread, gamma0;   /* the values in force (defaults resolved); gamma0 = 2 |cam.up| / res_y of the uploaded camera         */
+} JpTextureMipmapInfo;
+int  jp_set_texture_mipmaps(JpContext* ctx, const JpTextureMipmaps* mipmaps);      /* read by the next upload; NULL removes */
+int  jp_check_texture_mipmaps(const JpTextureMipmaps* mipmaps, int32_t* n_on);     /* pure host: the same validation, status and message (n_on may be NULL) */
+int  jp_get_texture_mipmap_info(JpContext* ctx, JpTextureMipmapInfo* out);
+/* the uploaded pyramid of one texture, copied from the device: levels in order, 3 bytes per texel; capacity in bytes (JP_ERR_INVALID_ARGUMENT when too small or
+ * the texture has no pyramid) */
+int  jp_read_mip_chain(JpContext* ctx, int32_t texture, uint8_t* rgb8_out, int64_t capacity);
+/* pure host: the pyramid of a w x h image, levels in order into rgb8_out (3 bytes per texel; level 0 is the image); level_w / level_h: 15 entries at least.
+ * rgb8_out NULL: only the sizes */
+int  jp_build_mip_chain(int32_t w, int32_t h, const uint8_t* rgb8, uint8_t* rgb8_out, int32_t* level_w, int32_t* level_h, int32_t* n_levels);
+/* pure host: one hit for each of n independent cones: state_inout[2k .. 2k+1] = (width, spread) of cone k before the hit at distance t[k] of a ray with the
+ * flags word flags[k] (bounce in bits 0-7, bit 8: the ray left a specular closure), overwritten with the state after it; a path is a chain of calls */
+int  jp_mip_cone_step(float gamma0, float bounce_spread, int32_t n, const int32_t* flags, const float* t, float* state_inout /*2n*/);
+/* pure host: rho of n hits from the cone's width and the world area per unit uv area A at the hit (include/jp_mipmap.h has A per shape) */
+int  jp_mip_footprint(int32_t n, const float* width, const float* area, int32_t w, int32_t h, float scale_u, float scale_v, float footprint_scale, float* rho_out);
+/* pure host: jp_texture_lookup at a footprint of rho texels per lookup, on the image's pyramid */
+int  jp_texture_lookup_mip(const JpTexSampler* s_or_null, int32_t w, int32_t h, const uint8_t* rgb8, int32_t n, const float* uv, const float* rho, uint8_t* rgb8_out);
+/* test hook like jp_surface: the closest hit of the same walk, then the very device function k_texel_m calls on the caller's flags and (width, spread) state:
+ * state_inout 2 floats per ray, updated as at a hit; prim -1 (state untouched, rho 0, colour 0) on a miss; rho 0 and the bytes of the lookup without mipmaps where the
+ * hit's image has no pyramid; colour 0 for an untextured hit and for a SOLID or CHECKER texture (their side word is no texel).  Needs a scene uploaded with at least
+ * one pyramid */
+int  jp_mip_probe(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, const int32_t* flags, float* state_inout,
+                  int32_t* prim, float* rho, uint8_t* rgb8);
+
 /* Lens (additive to ABI 7; INTEGRATION.md "Lens" has the definition).  The reference's camera is a pinhole: every camera ray starts at JpCamera.pos.  A lens of
  * radius > 0 gives depth of field: the camera ray of a sample starts at a point of the aperture -- a disk (blades 0) or a regular polygon of 3 .. 16 blades with
  * circumradius `radius`, its first vertex rotation_deg from the camera's right axis toward its up axis -- and passes through the point where the pinhole ray meets

@@ -340,6 +340,102 @@ def perturb_normals_sampled(sampler, nb, ng, dpdu, dpdv, uv, rgb8, strength=1.0)
     return ns, on
 
 
+JP_MIP_OFF, JP_MIP_TRILINEAR = 0, 1
+
+
+class JpTextureMipmaps(C.Structure):
+    """include/jetpbrt_amd.h: JpTextureMipmaps (jp_set_texture_mipmaps); struct_bytes = sizeof(JpTextureMipmaps)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_textures", C.c_int32), ("mode", C.POINTER(C.c_int32)), ("footprint_scale", C.c_float), ("bounce_spread", C.c_float)]
+
+
+class JpTextureMipmapInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_on", C.c_int32), ("n_levels", C.c_int32), ("mip_last_render", C.c_int32), ("pyramid_bytes_device", C.c_int64),
+                ("cone_bytes_device", C.c_int64), ("build_ms", C.c_double), ("texel_ms", C.c_double), ("footprint_scale", C.c_float), ("bounce_spread", C.c_float),
+                ("gamma0", C.c_float)]
+
+
+def texture_mipmaps(modes, footprint_scale=0.0, bounce_spread=0.0):
+    """A JpTextureMipmaps: modes a list of JP_MIP_OFF / JP_MIP_TRILINEAR (or booleans), one per texture of the next upload.  footprint_scale 0: 1;
+    bounce_spread 0: 0.125 rad.  The array is kept alive on the returned object as ._keep."""
+    a = (C.c_int32 * max(1, len(modes)))(*[int(m) for m in modes])
+    v = JpTextureMipmaps(C.sizeof(JpTextureMipmaps), len(modes), C.cast(a, C.POINTER(C.c_int32)), float(footprint_scale), float(bounce_spread))
+    v._keep = a
+    return v
+
+
+def check_texture_mipmaps(mipmaps):
+    """jp_check_texture_mipmaps: the validation of jp_set_texture_mipmaps (pure host code, no GPU) -> n_on; raises JetPbrtError with its message"""
+    a = C.c_int32(0)
+    L = hip_lib()
+    _hip_status(L, L.jp_check_texture_mipmaps(C.byref(mipmaps), C.byref(a)))
+    return a.value
+
+
+def build_mip_chain(rgb8):
+    """jp_build_mip_chain: the pyramid of an (h, w, 3) uint8 image -> list of (h_k, w_k, 3) uint8 levels, level 0 first.  Pure host code."""
+    import numpy as np
+    img = np.ascontiguousarray(rgb8, np.uint8)
+    h, w = img.shape[0], img.shape[1]
+    lw = (C.c_int32 * 16)(); lh = (C.c_int32 * 16)(); n = C.c_int32(0)
+    L = hip_lib()
+    _hip_status(L, L.jp_build_mip_chain(w, h, None, None, lw, lh, C.byref(n)))
+    total = sum(lw[k] * lh[k] for k in range(n.value))
+    out = np.zeros(3 * total, np.uint8)
+    _hip_status(L, L.jp_build_mip_chain(w, h, img.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), lw, lh, C.byref(n)))
+    return _split_chain(out, [(lw[k], lh[k]) for k in range(n.value)])
+
+
+def _split_chain(flat, sizes):
+    levels, at = [], 0
+    for w, h in sizes:
+        levels.append(flat[3 * at:3 * (at + w * h)].reshape(h, w, 3).copy())
+        at += w * h
+    return levels
+
+
+def mip_level_sizes(w, h):
+    """The (w_k, h_k) of every level of a w x h image's pyramid (jp_build_mip_chain without an image)."""
+    lw = (C.c_int32 * 16)(); lh = (C.c_int32 * 16)(); n = C.c_int32(0)
+    L = hip_lib()
+    _hip_status(L, L.jp_build_mip_chain(int(w), int(h), None, None, lw, lh, C.byref(n)))
+    return [(lw[k], lh[k]) for k in range(n.value)]
+
+
+def mip_cone_step(gamma0, bounce_spread, flags, t, state):
+    """jp_mip_cone_step: one hit for each of n independent cones; state (n, 2) float32 (width, spread) before the hit -> the state after it (a new array).  Pure host code."""
+    import numpy as np
+    f = np.ascontiguousarray(flags, np.int32); tt = np.ascontiguousarray(t, np.float32)
+    st = np.array(state, np.float32).reshape(-1, 2).copy()
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_mip_cone_step(float(gamma0), float(bounce_spread), f.shape[0], q(f), q(tt), q(st)))
+    return st
+
+
+def mip_footprint(width, area, w, h, scale=(1.0, 1.0), footprint_scale=1.0):
+    """jp_mip_footprint: rho in texels from the cone's width and the world area per unit uv area at the hit -> (n,) float32.  Pure host code."""
+    import numpy as np
+    a = np.ascontiguousarray(width, np.float32); b = np.ascontiguousarray(area, np.float32)
+    out = np.zeros(a.shape[0], np.float32)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_mip_footprint(a.shape[0], q(a), q(b), int(w), int(h), float(scale[0]), float(scale[1]), float(footprint_scale), q(out)))
+    return out
+
+
+def texture_lookup_mip(sampler, rgb8, uv, rho):
+    """jp_texture_lookup_mip: texture_lookup at a footprint of rho texels per lookup, on the image's pyramid -> (n, 3) uint8.  Pure host code."""
+    import numpy as np
+    img = np.ascontiguousarray(rgb8, np.uint8)
+    c = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    r = np.ascontiguousarray(rho, np.float32)
+    out = np.zeros((c.shape[0], 3), np.uint8)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_texture_lookup_mip(None if sampler is None else C.byref(sampler), img.shape[1], img.shape[0], q(img), c.shape[0], q(c), q(r), q(out)))
+    return out
+
+
 def triangle_tangents(p0, p1, p2, uv6):
     """jp_triangle_tangents: dpdu, dpdv of n triangles from their corners (n, 3) and uvs (n, 6) -> (dpdu (n, 3), dpdv (n, 3), ok (n,) int32).  Pure host code."""
     import numpy as np
@@ -758,6 +854,10 @@ def host_lib():
         L.jp_host_scene_set_texture_sampling_default.argtypes = [C.c_void_p, C.POINTER(JpTexSampler)]
         L.jp_host_flatten_texture_sampling.restype = C.POINTER(JpTextureSampling)
         L.jp_host_flatten_texture_sampling.argtypes = [C.c_void_p]
+        L.jp_host_texture_set_mipmaps.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.jp_host_scene_set_texture_mipmap_default.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+        L.jp_host_flatten_texture_mipmaps.restype = C.POINTER(JpTextureMipmaps)
+        L.jp_host_flatten_texture_mipmaps.argtypes = [C.c_void_p]
         L.jp_host_flatten_envmap.restype = C.POINTER(JpEnvMap)
         L.jp_host_flatten_envmap.argtypes = [C.c_void_p]
         _host = L
@@ -831,6 +931,15 @@ def hip_lib():
         L.jp_texture_lookup.argtypes = [C.POINTER(JpTexSampler), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         L.jp_perturb_normals_sampled.argtypes = [C.POINTER(JpTexSampler), C.c_int32] + [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
         L.jp_triangle_tangents.argtypes = [C.c_int32] + [C.c_void_p] * 7
+        L.jp_set_texture_mipmaps.argtypes = [C.c_void_p, C.POINTER(JpTextureMipmaps)]
+        L.jp_check_texture_mipmaps.argtypes = [C.POINTER(JpTextureMipmaps), C.POINTER(C.c_int32)]
+        L.jp_get_texture_mipmap_info.argtypes = [C.c_void_p, C.POINTER(JpTextureMipmapInfo)]
+        L.jp_read_mip_chain.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64]
+        L.jp_build_mip_chain.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.jp_mip_cone_step.argtypes = [C.c_float, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.jp_mip_footprint.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        L.jp_texture_lookup_mip.argtypes = [C.POINTER(JpTexSampler), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.jp_mip_probe.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
         L.jp_set_lens.argtypes = [C.c_void_p, C.POINTER(JpLens)]
         L.jp_get_lens_info.argtypes = [C.c_void_p, C.POINTER(JpLensInfo)]
         L.jp_check_lens.argtypes = [C.POINTER(JpLens)]
@@ -1208,6 +1317,37 @@ class Context:
         i.struct_bytes = C.sizeof(JpTexSamplingInfo)
         self._check(self.lib.jp_get_texture_sampling_info(self.h, C.byref(i)))
         return i
+
+    def set_texture_mipmaps(self, mipmaps):
+        """jp_set_texture_mipmaps for the next upload: a JpTextureMipmaps (texture_mipmaps(...) builds one), or None for none"""
+        self._check(self.lib.jp_set_texture_mipmaps(self.h, None if mipmaps is None else C.byref(mipmaps)))
+
+    def texture_mipmap_info(self):
+        i = JpTextureMipmapInfo()
+        i.struct_bytes = C.sizeof(JpTextureMipmapInfo)
+        self._check(self.lib.jp_get_texture_mipmap_info(self.h, C.byref(i)))
+        return i
+
+    def read_mip_chain(self, texture, w, h):
+        """jp_read_mip_chain: the uploaded pyramid of texture `texture` (a w x h image) -> list of (h_k, w_k, 3) uint8 levels, level 0 first"""
+        import numpy as np
+        sizes = mip_level_sizes(w, h)
+        out = np.zeros(3 * sum(a * b for a, b in sizes), np.uint8)
+        self._check(self.lib.jp_read_mip_chain(self.h, int(texture), out.ctypes.data_as(C.c_void_p), out.size))
+        return _split_chain(out, sizes)
+
+    def mip_probe(self, origin, direction, tmin, tmax, flags, state):
+        """jp_mip_probe: closest hit of jp_surface's walk, then k_texel_m's device function on the caller's flags and (n, 2) (width, spread) state
+        -> (state after (n, 2), prim (n,), rho (n,), rgb8 (n, 3))"""
+        import numpy as np
+        n = origin.shape[0]
+        o = np.ascontiguousarray(origin, np.float32); d = np.ascontiguousarray(direction, np.float32)
+        t0 = np.ascontiguousarray(tmin, np.float32); t1 = np.ascontiguousarray(tmax, np.float32)
+        f = np.ascontiguousarray(flags, np.int32); st = np.array(state, np.float32).reshape(n, 2).copy()
+        prim = np.zeros(n, np.int32); rho = np.zeros(n, np.float32); rgb = np.zeros((n, 3), np.uint8)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_mip_probe(self.h, n, p(o), p(d), p(t0), p(t1), p(f), p(st), p(prim), p(rho), p(rgb)))
+        return st, prim, rho, rgb
 
     def shading_normal(self, origin, direction, tmin, tmax):
         """jp_shading_normal: closest hit of jp_trace's walk -> (prim (n,), ng (n, 3), ns (n, 3)): the geometric normal and the shading normal the render uses"""

@@ -1572,6 +1572,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_shade_tex(SceneView sc, Queues q, 
 
 // k_surface (jp_surface): the closest hit of k_trace's walk, then the uv k_texel computes and the colour k_shade_tex puts in the textured
 // slot (untextured matte / mirror / plastic: mat_params[0..2]; glass, metal, no material, no hit: 0); sm.tex (null: none): the textures' sampling records
+// (mip maps, jp_mipmap.h: jp_surface has no cone, so it reads level 0 under the record whatever the texture's mode; jp_mip_probe is the hook with a cone)
 template <int kMode>
 __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, int depth, int n, const float* o, const float* d, const float* tmin, const float* tmax_in,
                                                       int* prim, float* uv, float* albedo, SampView sm)
@@ -1606,6 +1607,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 
 #define JP_TEX_SAMPLING_KERNELS
 #include "jp_tex_sampling.h"     // texture sampling records, part 2: k_texel_s, k_normal_map_s (part 1 comes with jp_normal_map.h's, part 3 at the end)
+#define JP_MIPMAP_KERNELS
+#include "jp_mipmap.h"           // mip maps, parts 1 and 2: MipView, k_mip_level, k_texel_m, k_mip_probe (after every kernel above: none of them refers to it; part 3 at the end)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host runtime (same translation unit: the code below launches the kernels above)
@@ -1624,6 +1627,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_normal_map.h"       // normal maps, part 2: k_normal_map, k_shading_normal_mapped and their entry points (before the vertex normals' part 2, whose hook hands out its kernel)
 #define JP_TEX_SAMPLING_RUNTIME
 #include "jp_tex_sampling.h"     // texture sampling records, part 3: the upload's table steps and the entry points (after jp_normal_map.h's part 2: pack_rgb8, jp_perturb_normals)
+#define JP_MIPMAP_RUNTIME
+#include "jp_mipmap.h"           // mip maps, part 3: the upload's steps and the entry points (after jp_normal_map.h's part 2: pack_rgb8)
 #define JP_NORMALS_RUNTIME
 #include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points
 #include "jp_shade_launch.h"     // shade_launch and launch_normal, which jp_render.h declares: after the last of the k_shade families and normal kernels above

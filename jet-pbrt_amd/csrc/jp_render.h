@@ -72,10 +72,12 @@ struct Stamper
 };
 
 // k_texel, or its twin k_texel_s where a colour texture of the scene has an active sampling record (jp_tex_sampling.h); with profiling, timed inside the CLS_SHADE pair
-static void launch_texel(JpContext* c, const ScenePlan& p, int grid, int cur, const TexView& tv)
+// ... or k_texel_m where one has a pyramid (jp_mipmap.h; mv.cone: this context's cone array)
+static void launch_texel(JpContext* c, const ScenePlan& p, int grid, int cur, const TexView& tv, const MipView& mv)
 {
 	Stamper t(c, CLS_TEXEL);
-	if (p.sm.tex) hipLaunchKernelGGL(k_texel_s, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm);
+	if (mv.tex) hipLaunchKernelGGL(k_texel_m, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm, mv);
+	else if (p.sm.tex) hipLaunchKernelGGL(k_texel_s, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm);
 	else hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
 }
 // k_normal, or a mapped scene's k_normal_map / k_normal_map_s, timed likewise (defined in jp_shade_launch.h: the kernels come after this file)
@@ -316,6 +318,8 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		// the side words of k_texel: one per queue position, allocated for textured scenes only
 		if (tex) if (const int e = reserve_idle(c, c->side, (size_t)cap * sizeof(unsigned int)); e != JP_OK) return e;
 		TexView tv = p.tv; tv.side = c->side.get<unsigned int>();
+		MipView mv_cone = {};                                         // mip maps (jp_mipmap.h): k_texel_m and the cones of this queue set, allocated for scenes with a pyramid only
+		if (tex && p.mip_on > 0) { mv_cone = p.mv; if (const int e = ensure_cone(c, cap, mv_cone); e != JP_OK) return e; }
 		// JP_ESTIMATOR_MIS (render_impl refused a scene without the light table): the side records of this queue set
 		const bool mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH;
 		MisView mv = {};
@@ -376,7 +380,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 				}
 				{
 					Stamper t(c, CLS_SHADE);
-					if (tex) launch_texel(c, p, grid, cur, tv);              // textured scenes: k_texel leaves the texture's answer for every hit, the textured twin shades with it
+					if (tex) launch_texel(c, p, grid, cur, tv, mv_cone);             // textured scenes: k_texel leaves the texture's answer for every hit, the textured twin shades with it
 					if (smooth) launch_normal(c, p, grid, cur, nv);         // scenes with vertex normals or normal maps: Ns for every hit it applies to, the smooth twin shades with it
 					shade(c->stream, grid, p.shade_lds_bytes, p.sv, c->q, rc, cur, d_cnt);
 				}
@@ -430,6 +434,7 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 {
 	l->plan = c->plan;                                               // (the lane's side array is its own, allocated with its queues)
 	if (!l->plan.textured && l->side) { hipStreamSynchronize(l->stream); l->side.reset(); }   // untextured scene: not kept
+	if (l->plan.mip_on == 0 && l->cone) { hipStreamSynchronize(l->stream); l->cone.reset(); }   // (and the cones of k_texel_m)
 	if (!l->plan.smooth && l->nside) { hipStreamSynchronize(l->stream); l->nside.reset(); }   // (the same for the side records of k_normal)
 	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
 	l->estimator = c->estimator;                                     // ... and the estimator (its side records are its own, like its queues)
@@ -586,7 +591,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
 	c->last_hdr = 0;
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0; c->last_sampled = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0; c->last_sampled = 0; c->last_mip = 0;
 	if (c->plan.mapped && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with normal maps, jp_set_normal_maps)");
 	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
 	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
@@ -603,6 +608,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	c->last_smooth = c->plan.smooth && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_nmapped = c->plan.mapped && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_sampled = ((c->plan.textured && c->plan.sm.tex) || (c->plan.mapped && c->plan.sm.map)) && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_mip = c->plan.textured && c->plan.mip_on > 0 && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_lens = c->lens_on ? 1 : 0;                                    // (every integrator forms the lens ray)
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38

@@ -80,6 +80,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	if (const int st = check_scene(s, pick, k); st != JP_OK) return st;
 	const int n_textures = c->upload_n_textures; c->upload_n_textures = 0;   // (jp_upload_scene_textured's count; a plain upload has none)
 	if (const int st = check_sampling_counts(c, n_textures); st != JP_OK) return st;   // jp_set_texture_sampling: refused while the old scene is still there
+	if (const int st = check_mipmap_counts(c, n_textures); st != JP_OK) return st;     // jp_set_texture_mipmaps: likewise
 	HIP_TRY(hipSetDevice(c->device));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	free_scene(c);                                                  // first: the old and the new scene are never resident together
@@ -295,12 +296,15 @@ extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const Jp
 	long long pool; int ntm;
 	if (const int st = check_textures(s, t, pool, ntm); st != JP_OK) return st;
 	if (const int st = check_sampling_textures(c, t); st != JP_OK) return st;
+	if (const int st = check_mipmap_textures(c, t, pool); st != JP_OK) return st;
 	c->upload_n_textures = t->n_textures;
 	const int st = jp_upload_scene(c, s); c->upload_n_textures = 0;                              // (validates the scene; drops the textures of an earlier upload)
 	if (st != JP_OK) return st;
 	if (ntm == 0) return JP_OK;                                        // no textures, or textures no material uses: the untextured scene, exactly
 	TexTables x; build_texture_tables(s, t, pool, x);
 	SceneTables& T = c->tab;
+	const long long pool_mip = mip_pool_texels(c, t, pool);             // jp_set_texture_mipmaps: the pool's allocation grows by the pyramids (equal to pool without them)
+	if (pool_mip > pool && T.texels.reserve((size_t)pool_mip * sizeof(unsigned int)) != hipSuccess) { free_scene(c); return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: out of device memory for the pyramids"); }
 	if (upload(T.tex_desc, x.desc.data(), x.desc.size() * sizeof(int4)) != hipSuccess || upload(T.tex_col, x.col.data(), x.col.size() * sizeof(float4)) != hipSuccess
 	    || upload(T.texels, x.texels.data(), x.texels.size() * sizeof(unsigned int)) != hipSuccess || upload(T.mat_tex, x.mat_tex.data(), x.mat_tex.size() * sizeof(int)) != hipSuccess
 	    || upload(T.prim_uv, x.prim_uv.data(), x.prim_uv.size() * sizeof(float2)) != hipSuccess)
@@ -313,5 +317,6 @@ extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const Jp
 	tv.mat_tex = T.mat_tex.get<int>(); tv.prim_uv = T.prim_uv.get<float2>();
 	c->plan.textured = true; c->n_textures = t->n_textures; c->n_tex_mats = ntm; c->texel_bytes = (long long)x.texels.size() * 4;
 	if (upload_tex_sampling(c, T, c->plan) != JP_OK) { free_scene(c); return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: out of device memory for the sampling records"); }
+	if (pool_mip > pool && upload_mipmaps(c, T, c->plan, s, t, x.desc, pool) != JP_OK) { free_scene(c); return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: building the pyramids failed"); }
 	return JP_OK;
 }

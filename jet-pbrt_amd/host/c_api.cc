@@ -214,6 +214,23 @@ int jp_host_scene_set_texture_sampling_default(void* h, const JpTexSampler* r)
 	hs->flattened = false;
 	return 0;
 }
+// mip maps: FImageTexture::SetMipmaps (on < 0: back to the scene's default) and FScene::SetTextureMipmapDefault with the scene's footprint scale and bounce spread
+int jp_host_texture_set_mipmaps(void* h, int tex, int on)
+{
+	HostScene* hs = (HostScene*)h;
+	FImageTexture* it = tex >= 0 && tex < (int)hs->texs.size() ? dynamic_cast<FImageTexture*>(hs->texs[tex].get()) : nullptr;
+	if (!it) { hs->error = "jp_host_texture_set_mipmaps: no such image texture"; return -1; }
+	if (on >= 0) it->SetMipmaps(on != 0); else { it->mipmaps = false; it->hasMipmaps = false; }
+	hs->flattened = false;
+	return 0;
+}
+int jp_host_scene_set_texture_mipmap_default(void* h, int on, float footprint_scale, float bounce_spread)
+{
+	HostScene* hs = (HostScene*)h;
+	hs->scene->SetTextureMipmapDefault(on != 0); hs->scene->mipFootprintScale = footprint_scale; hs->scene->mipBounceSpread = bounce_spread;
+	hs->flattened = false;
+	return 0;
+}
 void jp_host_scene_preprocess(void* h) { HostScene* hs = (HostScene*)h; hs->scene->Preprocess(); hs->flattened = false; }
 int  jp_host_num_primitives(void* h) { return (int)((HostScene*)h)->scene->primitives.size(); }
 int  jp_host_num_lights(void* h) { return ((HostScene*)h)->scene->LightNum(); }
@@ -256,6 +273,14 @@ const JpTextureSampling* jp_host_flatten_texture_sampling(void* h)
 	HostScene* hs = (HostScene*)h;
 	if (!jp_host_flatten(h) || hs->flat.n_sampled == 0) return nullptr;
 	return &hs->flat.sampling;
+}
+
+// the flattened mipmap modes (valid with jp_host_flatten's view; null: every mode is OFF, or the flattening failed)
+const JpTextureMipmaps* jp_host_flatten_texture_mipmaps(void* h)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!jp_host_flatten(h) || hs->flat.n_mipmapped == 0) return nullptr;
+	return &hs->flat.mipmaps;
 }
 
 // FGpuPathIntegrator(maxdepth).Render(scene, FCounterSampler(spp, seed), film, numthreads) -> rgb (added onto zeros)

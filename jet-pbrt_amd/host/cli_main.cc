@@ -5,6 +5,9 @@
 //             [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]
 //             [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]
 //             [--texture-wrap clamp|repeat|mirror] [--texture-filter nearest|bilinear] [--texture-tile SU SV] [--normal-wrap clamp|repeat] [--normal-tile SU SV]
+//             [--texture-mip [--mip-footprint S] [--mip-bounce-spread RAD]]
+// --texture-mip: mip maps for every image texture (FScene::SetTextureMipmapDefault): trilinear filtering at the footprint of the path's ray cone; --mip-footprint S scales
+// the footprint (default 1); --mip-bounce-spread RAD: the least spread of the cone after a bounce that is not specular (default 0.125, a design choice).
 // --texture-wrap / --texture-filter / --texture-tile: the sampling record (FScene::SetTextureSamplingDefault) of every image texture without one of its own: the wrap mode of
 // both axes, the filter, the uv scale; --normal-wrap / --normal-tile: the same for the --normal-map map (FNormalMap::SetSampling; a normal map is always filtered bilinearly).
 // --hdr: the unclamped film (FFilm::SetHDR): --format hdr then writes radiance above 1.  --sample-clamp C: each sample's radiance is scaled down to a maximum channel of C
@@ -115,6 +118,7 @@ int main(int argc, char* argv[])
 	std::string normalMap; float normalStrength = 1.f, normalFromHeight = 0.f; bool fromHeight = false;
 	bool hdr = false, haveToneMap = false; float sampleClamp = 0.f; FToneMap toneMap;
 	FTexSampling texSampling, normalSampling; bool haveTexSampling = false, haveNormalSampling = false;
+	bool textureMip = false; float mipFootprint = 0.f, mipBounceSpread = 0.f;
 	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
 	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
@@ -122,6 +126,7 @@ int main(int argc, char* argv[])
 	fprintf(stderr, "          [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]\n");
 	fprintf(stderr, "          [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]\n");
 	fprintf(stderr, "          [--texture-wrap clamp|repeat|mirror] [--texture-filter nearest|bilinear] [--texture-tile SU SV] [--normal-wrap clamp|repeat] [--normal-tile SU SV]\n");
+	fprintf(stderr, "          [--texture-mip [--mip-footprint S] [--mip-bounce-spread RAD]]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -197,6 +202,14 @@ int main(int argc, char* argv[])
 			if (!strcmp(m, "clamp")) normalSampling.wrapU = normalSampling.wrapV = EWrap::Clamp; else if (!strcmp(m, "repeat")) normalSampling.wrapU = normalSampling.wrapV = EWrap::Repeat;
 			else { fprintf(stderr, "--normal-wrap must be clamp or repeat\n"); return 5; }
 		}
+		else if (!strcmp(argv[i], "--texture-mip")) textureMip = true;
+		else if ((!strcmp(argv[i], "--mip-footprint") || !strcmp(argv[i], "--mip-bounce-spread")) && i + 1 < argc)
+		{
+			char* e = nullptr; const float v = strtof(argv[i + 1], &e);
+			if (e == argv[i + 1] || *e || !(v > 0.f) || !std::isfinite(v)) { fprintf(stderr, "%s takes a number > 0\n", argv[i]); return 5; }
+			(!strcmp(argv[i], "--mip-footprint") ? mipFootprint : mipBounceSpread) = v; i++;
+		}
+		else if (!strcmp(argv[i], "--mip-footprint") || !strcmp(argv[i], "--mip-bounce-spread")) { fprintf(stderr, "%s: missing value\n", argv[i]); return 5; }
 		else if (!strncmp(argv[i], "--texture-", 10) || !strcmp(argv[i], "--normal-wrap") || !strcmp(argv[i], "--normal-tile")) { fprintf(stderr, "%s: missing value\n", argv[i]); return 5; }
 		else if (!strcmp(argv[i], "--hdr")) hdr = true;
 		else if (!strcmp(argv[i], "--sample-clamp") && i + 1 < argc) { sampleClamp = (float)atof(argv[++i]); if (!(sampleClamp >= 0.f) || !std::isfinite(sampleClamp)) { fprintf(stderr, "--sample-clamp must be a number >= 0\n"); return 5; } }
@@ -253,6 +266,8 @@ int main(int argc, char* argv[])
 	}
 	if (nmap && !floorHasUV) { fprintf(stderr, "--normal-map: %s/cornellbox/floor.obj has no texture coordinates (vt), so nothing would be mapped\n", assets.c_str()); return 5; }
 	if (map) scene->SetEnvironmentMap(map, envUp);
+	if ((mipFootprint != 0.f || mipBounceSpread != 0.f) && !textureMip) { fprintf(stderr, "--mip-footprint / --mip-bounce-spread need --texture-mip\n"); return 5; }
+	if (textureMip) { scene->SetTextureMipmapDefault(true); scene->mipFootprintScale = mipFootprint; scene->mipBounceSpread = mipBounceSpread; }
 	if (haveTexSampling) scene->SetTextureSamplingDefault(texSampling);   // every image texture without a sampling of its own (the scene is flattened at Render)
 	fprintf(stderr, "current scene: %s\n", scene->NameStr());
 	scene->SetLightSampling(estimator == JP_ESTIMATOR_MIS ? JP_LIGHTS_POWER_ONE : lightSampling);

@@ -33,6 +33,7 @@ struct HipApi
 	int (*set_vertex_normals)(JpContext*, const JpVertexNormals*) = nullptr;                 // (looked up, needed by scenes with smooth meshes only)
 	int (*set_normal_maps)(JpContext*, const JpNormalMaps*) = nullptr;                       // (looked up, needed by scenes with FMaterial::normalMap only)
 	int (*set_texture_sampling)(JpContext*, const JpTextureSampling*) = nullptr;             // (looked up, needed by scenes with a sampling record only)
+	int (*set_texture_mipmaps)(JpContext*, const JpTextureMipmaps*) = nullptr;               // (looked up, needed by scenes with FImageTexture::SetMipmaps only)
 	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                        // (looked up, needed by FScene::SetEstimator only)
 	int (*set_lens)(JpContext*, const JpLens*) = nullptr;                                    // (looked up, needed by FCamera::SetLens only)
 	int (*focus_distance)(JpContext*, float, float, float*) = nullptr;                       // (looked up, needed by FCamera::FocusAt only)
@@ -73,6 +74,7 @@ HipApi& Api()
 		api.set_lens = (decltype(api.set_lens))dlsym(api.lib, "jp_set_lens");
 		api.set_normal_maps = (decltype(api.set_normal_maps))dlsym(api.lib, "jp_set_normal_maps");
 		api.set_texture_sampling = (decltype(api.set_texture_sampling))dlsym(api.lib, "jp_set_texture_sampling");
+		api.set_texture_mipmaps = (decltype(api.set_texture_mipmaps))dlsym(api.lib, "jp_set_texture_mipmaps");
 		api.focus_distance = (decltype(api.focus_distance))dlsym(api.lib, "jp_focus_distance");
 		api.set_film = (decltype(api.set_film))dlsym(api.lib, "jp_set_film");
 		api.set_tonemap = (decltype(api.set_tonemap))dlsym(api.lib, "jp_set_tonemap");
@@ -191,6 +193,14 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			lastStatus = api.set_texture_sampling(ctx, flat.n_sampled > 0 ? &flat.sampling : nullptr);
 			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
 			ctxSampling = flat.n_sampled > 0;
+		}
+		if (flat.n_mipmapped > 0 || ctxMipmaps)
+		{   // FImageTexture::SetMipmaps / FScene::SetTextureMipmapDefault: the modes go to the context before the upload they are to affect; a scene without them removes what an
+			// earlier scene left (NULL), and a context that never held any makes no such call
+			if (!api.set_texture_mipmaps) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_texture_mipmaps\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_texture_mipmaps(ctx, flat.n_mipmapped > 0 ? &flat.mipmaps : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxMipmaps = flat.n_mipmapped > 0;
 		}
 		// a scene with a textured material goes through jp_upload_scene_textured; any other makes exactly the calls it always made
 		const bool textured = flat.textures.n_textures > 0;

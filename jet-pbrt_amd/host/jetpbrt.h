@@ -189,6 +189,9 @@ public:
 	// the texture's own sampling record (jp_set_texture_sampling); unset: the command line's defaults where given, else the identity
 	void SetSampling(const FTexSampling& s) { sampling = s; hasSampling = true; }
 	FTexSampling sampling; bool hasSampling = false;
+	// mip maps (jp_set_texture_mipmaps): trilinear filtering at the footprint of the path's ray cone; unset: the scene's default (FScene::SetTextureMipmapDefault), else off
+	void SetMipmaps(bool on) { mipmaps = on; hasMipmaps = true; }
+	bool mipmaps = false, hasMipmaps = false;
 };
 // image readers of film_io.cc: RGB8, top row first; false for any other format or a file that cannot be read
 bool ReadImageRGB8(const char* filename, std::vector<uint8_t>& rgb, int& width, int& height);
@@ -515,6 +518,10 @@ public:
 	// The sampling record of every FImageTexture without one of its own (FImageTexture::SetSampling); unset: the identity.  Read by FlattenScene.
 	FTexSampling textureSamplingDefault; bool hasTextureSamplingDefault = false;
 	void SetTextureSamplingDefault(const FTexSampling& s) { textureSamplingDefault = s; hasTextureSamplingDefault = true; }
+	// Mip maps of every FImageTexture without a choice of its own (FImageTexture::SetMipmaps); the footprint's scale (0: 1) and the least spread of the ray cone after a bounce
+	// that is not specular (radians; 0: 0.125, a design choice) hold for the whole scene.  Read by FlattenScene.
+	bool textureMipmapDefault = false; Float mipFootprintScale = 0, mipBounceSpread = 0;
+	void SetTextureMipmapDefault(bool on = true) { textureMipmapDefault = on; }
 	// JP_ESTIMATOR_NEE (default: the reference's estimator) or JP_ESTIMATOR_MIS: next-event estimation and the BSDF sample weighted against each other (power
 	// heuristic).  Render-time state, sent before every render; a scene that asks for MIS is uploaded with JP_LIGHTS_POWER_ONE whatever lightSampling says.
 	int estimator = JP_ESTIMATOR_NEE;
@@ -560,6 +567,10 @@ struct FlatScene
 	JpTextureSampling sampling;
 	std::vector<JpTexSampler> tex_sampler, nm_sampler;
 	int n_sampled = 0;
+	// mip maps (jp_set_texture_mipmaps): one mode per flattened texture; n_mipmapped == 0: every mode is OFF and the scene sets no mipmap state
+	JpTextureMipmaps mipmaps;
+	std::vector<int32_t> tex_mip_mode;
+	int n_mipmapped = 0;
 };
 bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error = nullptr);
 
@@ -603,6 +614,7 @@ protected:
 	mutable JpLens ctxLens = {};                                    // the lens the context was last told (FCamera::SetLens; radius 0: none)
 	mutable JpFilm ctxFilm = {}; mutable JpToneMap ctxToneMap = {};   // the film state and tone map the context was last told (FFilm::SetHDR / SetSampleClamp / SetToneMap; zeros: none)
 	mutable bool ctxNormalMaps = false;                            // ... or normal maps (jp_set_normal_maps)
+	mutable bool ctxMipmaps = false;                               // ... or mipmap modes (jp_set_texture_mipmaps)
 	mutable bool ctxSampling = false;                              // ... or texture sampling records (jp_set_texture_sampling)
 	mutable bool ctxNormals = false;                                // the context holds vertex normals of an earlier upload (jp_set_vertex_normals)
 	mutable int lastStatus = 0;

@@ -440,6 +440,10 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 			FTexSampling smp;
 			if (kind == JP_TEXTURE_IMAGE) { const FImageTexture* it = static_cast<const FImageTexture*>(T); if (it->hasSampling) smp = it->sampling; else if (scene.hasTextureSamplingDefault) smp = scene.textureSamplingDefault; }
 			out.tex_sampler.push_back(smp.Record());
+			// the mipmap mode: an image's own choice, else the scene's default for images
+			bool mip = false;
+			if (kind == JP_TEXTURE_IMAGE) { const FImageTexture* it = static_cast<const FImageTexture*>(T); mip = it->hasMipmaps ? it->mipmaps : scene.textureMipmapDefault; }
+			out.tex_mip_mode.push_back(mip ? JP_MIP_TRILINEAR : JP_MIP_OFF);
 			ti = texRef.insert(std::make_pair(T, k)).first;
 		}
 		out.mat_texture.back() = ti->second;
@@ -556,6 +560,11 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 	ts.n_textures = t.n_textures; ts.tex = t.n_textures > 0 ? out.tex_sampler.data() : nullptr;
 	if (out.n_normal_mapped > 0) { ts.n_maps = nm.n_maps; ts.map = out.nm_sampler.data(); }
 	for (const JpTexSampler& r : out.tex_sampler) if (!jp_tsamp_identity(&r, JP_TSAMP_COLOR)) out.n_sampled++;
+	// the mipmap modes, in texture order
+	JpTextureMipmaps& mm = out.mipmaps; std::memset(&mm, 0, sizeof(mm));
+	mm.struct_bytes = (int32_t)sizeof(JpTextureMipmaps); mm.n_textures = t.n_textures; mm.mode = t.n_textures > 0 ? out.tex_mip_mode.data() : nullptr;
+	mm.footprint_scale = scene.mipFootprintScale; mm.bounce_spread = scene.mipBounceSpread;
+	for (const int32_t m : out.tex_mip_mode) if (m != JP_MIP_OFF) out.n_mipmapped++;
 	if (out.n_normal_mapped > 0) for (const JpTexSampler& r : out.nm_sampler) if (!jp_tsamp_identity(&r, JP_TSAMP_NORMAL)) out.n_sampled++;
 	return true;
 }

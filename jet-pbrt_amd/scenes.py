@@ -247,6 +247,20 @@ class HostBackend:
         p = self.L.jp_host_flatten_texture_sampling(self.h)
         return p.contents if p else None
 
+    def texture_set_mipmaps(self, tex, on):
+        """FImageTexture::SetMipmaps (None: the scene's default)"""
+        if self._f("texture_set_mipmaps")(self.h, tex, -1 if on is None else int(bool(on))) != 0:
+            raise RuntimeError("texture_set_mipmaps failed: %s" % self.L.jp_host_last_error(self.h).decode())
+
+    def set_texture_mipmap_default(self, on=True, footprint_scale=0.0, bounce_spread=0.0):
+        """FScene::SetTextureMipmapDefault: mip maps for every image texture without a choice of its own, and the scene's footprint scale and bounce spread (0: defaults)"""
+        self._f("scene_set_texture_mipmap_default")(self.h, int(bool(on)), C.c_float(footprint_scale), C.c_float(bounce_spread))
+
+    def flatten_texture_mipmaps(self):
+        """the scene's mipmap modes as a JpTextureMipmaps for Context.set_texture_mipmaps (None: every mode is OFF); valid until the next preprocess"""
+        p = self.L.jp_host_flatten_texture_mipmaps(self.h)
+        return p.contents if p else None
+
     def texture_image_file(self, path):
         """FImageTexture(filename): binary PPM or uncompressed BMP; anything else is the reference's solid cyan"""
         return self._f("texture_image_file")(self.h, path.encode())
