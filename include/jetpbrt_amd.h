@@ -622,6 +622,46 @@ int  jp_texture_lookup_mip(const JpTexSampler* s_or_null, int32_t w, int32_t h, 
 int  jp_mip_probe(JpContext* ctx, int32_t n, const float* origin, const float* dir, const float* tmin, const float* tmax, const int32_t* flags, float* state_inout,
                   int32_t* prim, float* rho, uint8_t* rgb8);
 
+/* Procedural textures (additive to ABI 7; INTEGRATION.md "Procedural textures" has the definition, include/jp_procedural.h the code).  A record per texture
+ * turns a JP_TEXTURE_CHECKER texture into gradient noise, fBm, turbulence, marble or the box-filtered checker between the texture's two colours
+ * (c_even = tex_color[3..5] at t = 0, c_odd = tex_color[0..2] at t = 1; both in [0, 1]: the result is an RGB8 side word).  The lookup point is q = M x + t with
+ * x the hit point (SPACE_WORLD) or (u, v, 0) (SPACE_UV) and m the row-major 3 x 4 map.  With antialias on (the default) the side kernel k_texel_p -- in
+ * k_texel / k_texel_s / k_texel_m's place -- band-limits the texture by the footprint of the path's ray cone (the cone of the mip maps: 8 bytes per path
+ * slot): octaves whose wavelength falls below the footprint fade out and the loop over them ends early.  Context state like the mipmap modes: validated and
+ * copied here, read by the next jp_upload_scene*, whose JpTextures.n_textures must equal n_textures.  The rules that need the textures (a record on a texture
+ * that is not CHECKER, colours outside [0, 1], SPACE_UV without tri_uv) are checked at the upload: JP_ERR_INVALID_ARGUMENT, and the context keeps the scene it
+ * had.  No state, all kinds NONE, or records only on textures no material uses: exactly the upload without them -- the same kernels, procedural_last_render 0,
+ * no device bytes.  The guides' albedo follows the procedural colour at the first hit (width = gamma0 * t). */
+enum { JP_PROC_NONE = 0, JP_PROC_NOISE = 1, JP_PROC_FBM = 2, JP_PROC_TURBULENCE = 3, JP_PROC_MARBLE = 4, JP_PROC_CHECKER_AA = 5 };
+enum { JP_PROC_SPACE_WORLD = 0, JP_PROC_SPACE_UV = 1 };
+typedef struct JpProcedural {
+    int32_t kind, space;                              /* JP_PROC_*, JP_PROC_SPACE_*                                                                          */
+    float   m[12];                                    /* row-major 3 x 4: q = M x + t; finite, linear part not singular                                      */
+    int32_t octaves;                                  /* 1 .. 12; 0: 6 (NOISE has one octave whatever this says)                                             */
+    float   gain;                                     /* amplitude ratio between octaves, (0, 1]; 0: 0.5                                                     */
+    float   variation;                                /* MARBLE: the weight of the fBm in the stripe coordinate; 0: 1                                        */
+    int32_t antialias;                                /* 0: default (on), 1: on, -1: off                                                                     */
+} JpProcedural;
+typedef struct JpTextureProcedurals { int32_t struct_bytes, n_textures; const JpProcedural* rec; } JpTextureProcedurals;   /* rec NULL: all NONE */
+typedef struct JpProceduralInfo {
+    int32_t struct_bytes, n_procedural;               /* textures of the uploaded scene with a record (kind not NONE, used by a material)                    */
+    int32_t n_antialiased;                            /* ... of them with antialias on                                                                       */
+    int32_t procedural_last_render;                   /* the last jp_render* ran k_texel_p                                                                   */
+    int64_t table_bytes_device;                       /* the records and the per-texture index                                                               */
+} JpProceduralInfo;
+int  jp_set_texture_procedurals(JpContext* ctx, const JpTextureProcedurals* procedurals);   /* read by the next upload; NULL removes */
+/* pure host: the same validation, status and message; textures_or_null: also the rules of the upload against these textures (n_textures must match).
+ * n_procedural counts the records that are not NONE, n_antialiased those of them with antialias on (either may be NULL) */
+int  jp_check_texture_procedurals(const JpTextureProcedurals* procedurals, const JpTextures* textures_or_null, int32_t* n_procedural, int32_t* n_antialiased);
+int  jp_get_procedural_info(JpContext* ctx, JpProceduralInfo* out);
+/* pure host: the lookup of one record (kind not NONE) as texture index `texture` at n points: p 3n floats, uv 2n, width n (the cone's width at the hit; 0: no
+ * cone) -> word_out n side words (the colour's RGB8 under the image tag, or the plain checker's colour index 2 * texture + parity under the colour tag) and
+ * t_out n blend parameters (either may be NULL) */
+int  jp_procedural_lookup(const JpProcedural* rec, const float* c_even, const float* c_odd, int32_t texture, int32_t n, const float* p, const float* uv, const float* width,
+                          uint32_t* word_out, float* t_out);
+/* test hook: the device twin of jp_procedural_lookup on the uploaded record and colours of texture `texture` (kernel k_proc_probe, no traversal) */
+int  jp_procedural_probe(JpContext* ctx, int32_t texture, int32_t n, const float* p, const float* uv, const float* width, uint32_t* word_out);
+
 /* Lens (additive to ABI 7; INTEGRATION.md "Lens" has the definition).  The reference's camera is a pinhole: every camera ray starts at JpCamera.pos.  A lens of
  * radius > 0 gives depth of field: the camera ray of a sample starts at a point of the aperture -- a disk (blades 0) or a regular polygon of 3 .. 16 blades with
  * circumradius `radius`, its first vertex rotation_deg from the camera's right axis toward its up axis -- and passes through the point where the pinhole ray meets

@@ -436,6 +436,68 @@ def texture_lookup_mip(sampler, rgb8, uv, rho):
     return out
 
 
+JP_PROC_NONE, JP_PROC_NOISE, JP_PROC_FBM, JP_PROC_TURBULENCE, JP_PROC_MARBLE, JP_PROC_CHECKER_AA = 0, 1, 2, 3, 4, 5
+JP_PROC_SPACE_WORLD, JP_PROC_SPACE_UV = 0, 1
+PROC_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+class JpProcedural(C.Structure):
+    """include/jetpbrt_amd.h: JpProcedural (one record of jp_set_texture_procedurals)"""
+    _fields_ = [("kind", C.c_int32), ("space", C.c_int32), ("m", C.c_float * 12), ("octaves", C.c_int32), ("gain", C.c_float), ("variation", C.c_float),
+                ("antialias", C.c_int32)]
+
+
+class JpTextureProcedurals(C.Structure):
+    """include/jetpbrt_amd.h: JpTextureProcedurals (jp_set_texture_procedurals); struct_bytes = sizeof(JpTextureProcedurals)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("n_textures", C.c_int32), ("rec", C.POINTER(JpProcedural))]
+
+
+class JpProceduralInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("n_procedural", C.c_int32), ("n_antialiased", C.c_int32), ("procedural_last_render", C.c_int32),
+                ("table_bytes_device", C.c_int64)]
+
+
+def procedural(kind, space=JP_PROC_SPACE_WORLD, m=PROC_IDENTITY, octaves=0, gain=0.0, variation=0.0, antialias=0):
+    """A JpProcedural: kind JP_PROC_*, m the row-major 3 x 4 map into texture space; octaves 0: 6, gain 0: 0.5, variation 0: 1, antialias 0 / 1: on, -1: off"""
+    return JpProcedural(int(kind), int(space), (C.c_float * 12)(*[float(x) for x in m]), int(octaves), float(gain), float(variation), int(antialias))
+
+
+def texture_procedurals(records):
+    """A JpTextureProcedurals: one JpProcedural (or None: JP_PROC_NONE) per texture of the next upload.  The array is kept alive on the returned object as ._keep."""
+    a = (JpProcedural * max(1, len(records)))()
+    for i, r in enumerate(records):
+        if r is not None:
+            a[i] = r
+    v = JpTextureProcedurals(C.sizeof(JpTextureProcedurals), len(records), C.cast(a, C.POINTER(JpProcedural)))
+    v._keep = a
+    return v
+
+
+def check_texture_procedurals(procedurals, textures=None):
+    """jp_check_texture_procedurals: the validation of jp_set_texture_procedurals and, with a JpTextures, of the upload (pure host code, no GPU)
+    -> (n_procedural, n_antialiased); raises JetPbrtError with its message"""
+    a = C.c_int32(0); b = C.c_int32(0)
+    L = hip_lib()
+    _hip_status(L, L.jp_check_texture_procedurals(C.byref(procedurals), None if textures is None else C.byref(textures), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def procedural_lookup(record, c_even, c_odd, p, uv, width, texture=0):
+    """jp_procedural_lookup: the side words (n,) uint32 and blend parameters t (n,) float32 of one record at n points: p (n, 3), uv (n, 2), width (n,).
+    Pure host code."""
+    import numpy as np
+    pp = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+    n = pp.shape[0]
+    u = np.ascontiguousarray(np.broadcast_to(np.asarray(uv, np.float32), (n, 2)))
+    w = np.ascontiguousarray(np.broadcast_to(np.asarray(width, np.float32), (n,)))
+    ce = (C.c_float * 3)(*[float(x) for x in c_even]); co = (C.c_float * 3)(*[float(x) for x in c_odd])
+    word = np.zeros(n, np.uint32); t = np.zeros(n, np.float32)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    _hip_status(L, L.jp_procedural_lookup(C.byref(record), ce, co, int(texture), n, q(pp), q(u), q(w), q(word), q(t)))
+    return word, t
+
+
 def triangle_tangents(p0, p1, p2, uv6):
     """jp_triangle_tangents: dpdu, dpdv of n triangles from their corners (n, 3) and uvs (n, 6) -> (dpdu (n, 3), dpdv (n, 3), ok (n,) int32).  Pure host code."""
     import numpy as np
@@ -857,6 +919,10 @@ def host_lib():
         L.jp_host_texture_set_mipmaps.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.jp_host_scene_set_texture_mipmap_default.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
         L.jp_host_flatten_texture_mipmaps.restype = C.POINTER(JpTextureMipmaps)
+        L.jp_host_flatten_texture_procedurals.restype = C.POINTER(JpTextureProcedurals)
+        L.jp_host_flatten_texture_procedurals.argtypes = [C.c_void_p]
+        L.jp_host_texture_procedural.argtypes = [C.c_void_p, C.POINTER(JpProcedural), C.c_void_p, C.c_void_p]
+        L.jp_host_normal_map_from_procedural.argtypes = [C.c_void_p, C.POINTER(JpProcedural), C.c_int, C.c_int, C.c_float]
         L.jp_host_flatten_texture_mipmaps.argtypes = [C.c_void_p]
         L.jp_host_flatten_envmap.restype = C.POINTER(JpEnvMap)
         L.jp_host_flatten_envmap.argtypes = [C.c_void_p]
@@ -940,6 +1006,11 @@ def hip_lib():
         L.jp_mip_footprint.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
         L.jp_texture_lookup_mip.argtypes = [C.POINTER(JpTexSampler), C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.jp_mip_probe.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 9
+        L.jp_set_texture_procedurals.argtypes = [C.c_void_p, C.POINTER(JpTextureProcedurals)]
+        L.jp_check_texture_procedurals.argtypes = [C.POINTER(JpTextureProcedurals), C.POINTER(JpTextures), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        L.jp_get_procedural_info.argtypes = [C.c_void_p, C.POINTER(JpProceduralInfo)]
+        L.jp_procedural_lookup.argtypes = [C.POINTER(JpProcedural), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.c_int32] + [C.c_void_p] * 5
+        L.jp_procedural_probe.argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4
         L.jp_set_lens.argtypes = [C.c_void_p, C.POINTER(JpLens)]
         L.jp_get_lens_info.argtypes = [C.c_void_p, C.POINTER(JpLensInfo)]
         L.jp_check_lens.argtypes = [C.POINTER(JpLens)]
@@ -1348,6 +1419,28 @@ class Context:
         p = lambda a: a.ctypes.data_as(C.c_void_p)
         self._check(self.lib.jp_mip_probe(self.h, n, p(o), p(d), p(t0), p(t1), p(f), p(st), p(prim), p(rho), p(rgb)))
         return st, prim, rho, rgb
+
+    def set_texture_procedurals(self, procedurals):
+        """jp_set_texture_procedurals for the next upload: a JpTextureProcedurals (texture_procedurals(...) builds one), or None for none"""
+        self._check(self.lib.jp_set_texture_procedurals(self.h, None if procedurals is None else C.byref(procedurals)))
+
+    def procedural_info(self):
+        i = JpProceduralInfo()
+        i.struct_bytes = C.sizeof(JpProceduralInfo)
+        self._check(self.lib.jp_get_procedural_info(self.h, C.byref(i)))
+        return i
+
+    def procedural_probe(self, texture, p, uv, width):
+        """jp_procedural_probe: the device twin of procedural_lookup on the uploaded record and colours of texture `texture` -> side words (n,) uint32"""
+        import numpy as np
+        pp = np.ascontiguousarray(p, np.float32).reshape(-1, 3)
+        n = pp.shape[0]
+        u = np.ascontiguousarray(np.broadcast_to(np.asarray(uv, np.float32), (n, 2)))
+        w = np.ascontiguousarray(np.broadcast_to(np.asarray(width, np.float32), (n,)))
+        word = np.zeros(n, np.uint32)
+        q = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_procedural_probe(self.h, int(texture), n, q(pp), q(u), q(w), q(word)))
+        return word
 
     def shading_normal(self, origin, direction, tmin, tmax):
         """jp_shading_normal: closest hit of jp_trace's walk -> (prim (n,), ng (n, 3), ns (n, 3)): the geometric normal and the shading normal the render uses"""

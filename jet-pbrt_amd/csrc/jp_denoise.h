@@ -25,8 +25,9 @@ struct GuideConst
 // sm (jp_tex_sampling.h; both pointers null: no active record): the sampling records of the textures and the maps, a runtime branch in every form -- the albedo and the
 // normal guide describe the surface the render shades
 // mv (jp_mipmap.h; mv.tex null: no pyramid): the albedo follows the mip the render's camera ray reads at the first hit, one runtime branch again
+// pv (jp_procedural.h; pv.tex null: no procedural record): likewise the procedural colour at the first hit's footprint
 template <int kMode, bool kSmooth, bool kLens, bool kMapped = false>
-__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp, const SampView& sm, const MipView& mv, const NMapView* mp = nullptr)
+__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp, const SampView& sm, const MipView& mv, const ProcView& pv, const NMapView* mp = nullptr)
 {
 	SceneAccess<kMode> acc(sc, depth);
 	const int npix = gc.width * gc.height;
@@ -64,7 +65,8 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 					{   // k_surface's colour; (1,1,1) stays where that is 0 by definition
 						const int mtype = sc.mat_type[mat];
 						const int tx = tv.mat_tex ? tv.mat_tex[mat] : -1;
-						if (tx >= 0 && mv.tex) { float rho; a = tex_color(tv, tex_sample_m(sc.prims, tv, sm, mv, h, meta.x, tx, p, mv.gamma0 * tmax, rho)); }   // the first hit's cone: width = gamma0 * t
+						if (tx >= 0 && pv.tex) a = tex_color(tv, proc_sample(sc.prims, tv, sm, mv, pv, h, meta.x, tx, p, mv.gamma0 * tmax));   // a scene with a procedural record: its colour at the first hit's cone (and the mip's, where mv.tex)
+						else if (tx >= 0 && mv.tex) { float rho; a = tex_color(tv, tex_sample_m(sc.prims, tv, sm, mv, h, meta.x, tx, p, mv.gamma0 * tmax, rho)); }   // the first hit's cone: width = gamma0 * t
 						else if (tx >= 0) a = tex_color(tv, tex_sample_s(tv, sm.tex, tx, tex_uv(sc.prims, tv, h, meta.x, p), p));
 						else if (mtype == JP_MAT_MATTE || mtype == JP_MAT_MIRROR || mtype == JP_MAT_PLASTIC) a = xyz(sc.mats[4 * mat]);
 					}
@@ -79,35 +81,35 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 	}
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, SampView sm, MipView mv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, SampView sm, MipView mv, ProcView pv)
 {
-	guides_body<kMode, false, false>(sc, tv, depth, gc, albedo, normal, dist, NormView(), nullptr, sm, mv);
+	guides_body<kMode, false, false>(sc, tv, depth, gc, albedo, normal, dist, NormView(), nullptr, sm, mv, pv);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, SampView sm, MipView mv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, SampView sm, MipView mv, ProcView pv)
 {
-	guides_body<kMode, true, false>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, mv);
+	guides_body<kMode, true, false>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, mv, pv);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, JpLensPlan lp, SampView sm, MipView mv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, JpLensPlan lp, SampView sm, MipView mv, ProcView pv)
 {
-	guides_body<kMode, false, true>(sc, tv, depth, gc, albedo, normal, dist, NormView(), &lp, sm, mv);
+	guides_body<kMode, false, true>(sc, tv, depth, gc, albedo, normal, dist, NormView(), &lp, sm, mv, pv);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, JpLensPlan lp, SampView sm, MipView mv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, JpLensPlan lp, SampView sm, MipView mv, ProcView pv)
 {
-	guides_body<kMode, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, sm, mv);
+	guides_body<kMode, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, sm, mv, pv);
 }
 
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, SampView sm, MipView mv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, SampView sm, MipView mv, ProcView pv)
 {
-	guides_body<kMode, false, false, true>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, mv, &mp);
+	guides_body<kMode, false, false, true>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, mv, pv, &mp);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, JpLensPlan lp, SampView sm, MipView mv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, JpLensPlan lp, SampView sm, MipView mv, ProcView pv)
 {
-	guides_body<kMode, false, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, sm, mv, &mp);
+	guides_body<kMode, false, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, sm, mv, pv, &mp);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -205,12 +207,12 @@ namespace
 #define JP_DENOISE_SIGMA_NORMAL 0.1f
 #define JP_DENOISE_SIGMA_DEPTH  0.03f
 
-typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, SampView, MipView);
-typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, SampView, MipView);
-typedef void (*GuideLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, JpLensPlan, SampView, MipView);
-typedef void (*GuideSmoothLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, JpLensPlan, SampView, MipView);
-typedef void (*GuideMappedKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, SampView, MipView);
-typedef void (*GuideMappedLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, JpLensPlan, SampView, MipView);
+typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, SampView, MipView, ProcView);
+typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, SampView, MipView, ProcView);
+typedef void (*GuideLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, JpLensPlan, SampView, MipView, ProcView);
+typedef void (*GuideSmoothLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, JpLensPlan, SampView, MipView, ProcView);
+typedef void (*GuideMappedKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, SampView, MipView, ProcView);
+typedef void (*GuideMappedLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, JpLensPlan, SampView, MipView, ProcView);
 struct GuideLaunch { GuideKernel k; size_t lds; int depth; GuideSmoothKernel smooth; GuideLensKernel lens; GuideSmoothLensKernel smooth_lens; GuideMappedKernel mapped; GuideMappedLensKernel mapped_lens; };   // smooth: the twin a scene with vertex normals runs; lens: the twins of jp_set_lens
 template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth, k_guides_smooth<M>, k_guides_lens<M>, k_guides_smooth_lens<M>, k_guides_mapped<M>, k_guides_mapped_lens<M> }; return g; }
 // the walk trace_kernel(p, 0) gives jp_surface
@@ -255,13 +257,13 @@ int guides_launch(JpContext* c, const GuideConst& gc, float* albedo, float* norm
 	HIP_TRY(hipEventRecord(c->gd_ev[0], c->stream));
 	if (c->lens_on)
 	{   // jp_set_lens: sample s stays the camera ray of sample s of the render
-		if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, lp, c->plan.sm, c->plan.mv);
-		else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, lp, c->plan.sm, c->plan.mv);
-		else hipLaunchKernelGGL(gk.lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, lp, c->plan.sm, c->plan.mv);
+		if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, lp, c->plan.sm, c->plan.mv, c->plan.proc);
+		else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, lp, c->plan.sm, c->plan.mv, c->plan.proc);
+		else hipLaunchKernelGGL(gk.lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, lp, c->plan.sm, c->plan.mv, c->plan.proc);
 	}
-	else if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, c->plan.sm, c->plan.mv);
-	else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.sm, c->plan.mv);
-	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.sm, c->plan.mv);
+	else if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, c->plan.sm, c->plan.mv, c->plan.proc);
+	else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.sm, c->plan.mv, c->plan.proc);
+	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.sm, c->plan.mv, c->plan.proc);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->gd_ev[1], c->stream));
 	c->gd_timed = true; c->last_guide_spp = gc.spp;

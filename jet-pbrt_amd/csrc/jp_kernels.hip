@@ -1609,6 +1609,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_tex_sampling.h"     // texture sampling records, part 2: k_texel_s, k_normal_map_s (part 1 comes with jp_normal_map.h's, part 3 at the end)
 #define JP_MIPMAP_KERNELS
 #include "jp_mipmap.h"           // mip maps, parts 1 and 2: MipView, k_mip_level, k_texel_m, k_mip_probe (after every kernel above: none of them refers to it; part 3 at the end)
+#define JP_PROCEDURAL_KERNELS
+#include "jp_procedural.h"       // procedural textures, parts 1 and 2: ProcView, k_texel_p, k_proc_probe (after jp_mipmap.h: the cone is its; part 3 at the end)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // host runtime (same translation unit: the code below launches the kernels above)
@@ -1629,6 +1631,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_tex_sampling.h"     // texture sampling records, part 3: the upload's table steps and the entry points (after jp_normal_map.h's part 2: pack_rgb8, jp_perturb_normals)
 #define JP_MIPMAP_RUNTIME
 #include "jp_mipmap.h"           // mip maps, part 3: the upload's steps and the entry points (after jp_normal_map.h's part 2: pack_rgb8)
+#define JP_PROCEDURAL_RUNTIME
+#include "jp_procedural.h"       // procedural textures, part 3: the upload's steps and the entry points
 #define JP_NORMALS_RUNTIME
 #include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points
 #include "jp_shade_launch.h"     // shade_launch and launch_normal, which jp_render.h declares: after the last of the k_shade families and normal kernels above

@@ -230,6 +230,18 @@ static long long mip_pool_texels(const JpContext* c, const JpTextures* t, long l
 	for (int i = 0; i < t->n_textures; i++) if (on[i]) pool += mip_chain_layout(t->tex_width[i], t->tex_height[i], lev) - (long long)t->tex_width[i] * t->tex_height[i];
 	return pool;
 }
+// the cone's constants of an upload, defaults resolved: what upload_mipmaps and upload_procedurals (jp_procedural.h: an antialiased record on a scene without
+// pyramids carries cones too) put into the plan's MipView; tex / lev / cone stay null
+static MipView mip_cone_constants(const JpContext* c, const JpScene* s)
+{
+	const MipmapsHost& h = c->mipmaps;
+	MipView mv = MipView();
+	mv.footprint_scale = h.set && h.footprint_scale != 0.f ? h.footprint_scale : 1.f;
+	mv.bounce_spread = h.set && h.bounce_spread != 0.f ? h.bounce_spread : JP_MIP_DEFAULT_BOUNCE_SPREAD;
+	const float* up = s->camera.up;
+	mv.gamma0 = 2.f * sqrtf((up[0] * up[0] + up[1] * up[1]) + up[2] * up[2]) / s->camera.res_y;
+	return mv;
+}
 static int upload_mipmaps(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const JpTextures* t, const std::vector<int4>& desc, long long pool)
 {
 	const MipmapsHost& h = c->mipmaps;
@@ -270,12 +282,8 @@ static int upload_mipmaps(JpContext* c, SceneTables& T, ScenePlan& plan, const J
 	float ms = 0.f; if (le == hipSuccess && se == hipSuccess) hipEventElapsedTime(&ms, e0, e1);
 	hipEventDestroy(e0); hipEventDestroy(e1);
 	HIP_TRY(le); HIP_TRY(se);
-	MipView& mv = plan.mv; mv = MipView();
+	MipView& mv = plan.mv; mv = mip_cone_constants(c, s);
 	mv.tex = T.mip_tex.get<int2>(); mv.lev = T.mip_lev.get<JpMipLevel>();
-	mv.footprint_scale = h.footprint_scale != 0.f ? h.footprint_scale : 1.f;
-	mv.bounce_spread = h.bounce_spread != 0.f ? h.bounce_spread : JP_MIP_DEFAULT_BOUNCE_SPREAD;
-	const float* up = s->camera.up;
-	mv.gamma0 = 2.f * sqrtf((up[0] * up[0] + up[1] * up[1]) + up[2] * up[2]) / s->camera.res_y;
 	plan.mip_on = n_on; plan.mip_levels = (int)all.size();
 	plan.mip_bytes = (at - pool) * 4 + (long long)(tex.size() * sizeof(int2) + all.size() * sizeof(JpMipLevel));
 	c->mip_build_ms = ms; c->mip_host_tex = std::move(tex); c->mip_host_lev = std::move(all);

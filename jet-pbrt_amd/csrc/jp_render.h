@@ -76,7 +76,8 @@ struct Stamper
 static void launch_texel(JpContext* c, const ScenePlan& p, int grid, int cur, const TexView& tv, const MipView& mv)
 {
 	Stamper t(c, CLS_TEXEL);
-	if (mv.tex) hipLaunchKernelGGL(k_texel_m, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm, mv);
+	if (p.proc_on > 0) hipLaunchKernelGGL(k_texel_p, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm, mv, p.proc);   // a procedural record (jp_procedural.h): first; mv.cone and mv.tex may each be null
+	else if (mv.tex) hipLaunchKernelGGL(k_texel_m, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm, mv);
 	else if (p.sm.tex) hipLaunchKernelGGL(k_texel_s, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv, p.sm);
 	else hipLaunchKernelGGL(k_texel, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, cur, tv);
 }
@@ -213,6 +214,7 @@ OtherKernel other_kernel(const ScenePlan& p) { return p.trav_mode == 5 ? k_other
 // render's closest-hit rays walk.  The one-ray-per-lane kernels keep the whole stack in LDS: a 4-wide tree deeper than 64 KB of stack falls back to the binary / verbatim walk
 typedef void (*TraceKernel)(SceneView, int, int, const float*, const float*, const float*, const float*, int*, float*, int*, float*);
 typedef void (*SurfaceKernel)(SceneView, TexView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*, SampView);
+typedef void (*SurfaceProcKernel)(SceneView, TexView, int, int, const float*, const float*, const float*, const float*, int*, float*, float*, SampView, ProcView);
 struct TraceLaunch { TraceKernel trace; SurfaceKernel surface; size_t lds; int depth; int mode; };   // (surface: null for the 8-wide walk, which only trace_walk = 2 selects; mode: the kMode that runs, + 16 for the lean flat instance)
 template <int M> TraceLaunch trace_row(size_t lds, int depth) { TraceLaunch t = { k_trace<M>, k_surface<M>, lds, depth, M }; return t; }
 // the hooks that ride on k_trace's walk (k_light_pdf, k_shading_normal, k_shading_normal_mapped): f(integral_constant<int, kMode>) for the mode trace_kernel chose; null
@@ -318,8 +320,8 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		// the side words of k_texel: one per queue position, allocated for textured scenes only
 		if (tex) if (const int e = reserve_idle(c, c->side, (size_t)cap * sizeof(unsigned int)); e != JP_OK) return e;
 		TexView tv = p.tv; tv.side = c->side.get<unsigned int>();
-		MipView mv_cone = {};                                         // mip maps (jp_mipmap.h): k_texel_m and the cones of this queue set, allocated for scenes with a pyramid only
-		if (tex && p.mip_on > 0) { mv_cone = p.mv; if (const int e = ensure_cone(c, cap, mv_cone); e != JP_OK) return e; }
+		MipView mv_cone = {};                                         // mip maps (jp_mipmap.h): k_texel_m / k_texel_p and the cones of this queue set, allocated for scenes with a pyramid or an antialiased procedural only
+		if (tex && (p.mip_on > 0 || p.proc_aa > 0)) { mv_cone = p.mv; if (const int e = ensure_cone(c, cap, mv_cone); e != JP_OK) return e; }
 		// JP_ESTIMATOR_MIS (render_impl refused a scene without the light table): the side records of this queue set
 		const bool mis = c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH;
 		MisView mv = {};
@@ -434,7 +436,7 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 {
 	l->plan = c->plan;                                               // (the lane's side array is its own, allocated with its queues)
 	if (!l->plan.textured && l->side) { hipStreamSynchronize(l->stream); l->side.reset(); }   // untextured scene: not kept
-	if (l->plan.mip_on == 0 && l->cone) { hipStreamSynchronize(l->stream); l->cone.reset(); }   // (and the cones of k_texel_m)
+	if (l->plan.mip_on == 0 && l->plan.proc_aa == 0 && l->cone) { hipStreamSynchronize(l->stream); l->cone.reset(); }   // (and the cones of k_texel_m)
 	if (!l->plan.smooth && l->nside) { hipStreamSynchronize(l->stream); l->nside.reset(); }   // (the same for the side records of k_normal)
 	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
 	l->estimator = c->estimator;                                     // ... and the estimator (its side records are its own, like its queues)
@@ -591,7 +593,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
 	c->last_hdr = 0;
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0; c->last_sampled = 0; c->last_mip = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0; c->last_sampled = 0; c->last_mip = 0; c->last_proc = 0;
 	if (c->plan.mapped && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with normal maps, jp_set_normal_maps)");
 	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
 	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
@@ -609,6 +611,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	c->last_nmapped = c->plan.mapped && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_sampled = ((c->plan.textured && c->plan.sm.tex) || (c->plan.mapped && c->plan.sm.map)) && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_mip = c->plan.textured && c->plan.mip_on > 0 && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
+	c->last_proc = c->plan.textured && c->plan.proc_on > 0 && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_lens = c->lens_on ? 1 : 0;                                    // (every integrator forms the lens ray)
 	// lanes: the shard's rows in groups of 4 dealt round-robin to L contexts.  Default: 3 lanes when each gets >= 16 groups and
 	// full-size batches, else 2, else 1 (measured on the benchmark frame: 1 lane 2.19, 2 lanes 2.70, 3 lanes 2.82, 4 lanes 2.38
@@ -862,7 +865,13 @@ int jp_surface(JpContext* c, int32_t n, const float* origin, const float* dir, c
 	HIP_TRY(hipMemcpyAsync(d_t0, tmin, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_t1, tmax, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
 	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
 	const TraceLaunch tk = trace_kernel(c->plan, 0);                // the walk jp_trace takes by default (what the render's closest-hit rays walk)
-	hipLaunchKernelGGL(tk.surface, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.tv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a, c->plan.sm);
+	if (c->plan.proc_on > 0)
+	{   // a scene with a procedural record (jp_procedural.h): k_surface's twin reports the record's colour at width 0
+		const SurfaceProcKernel sk = by_trace_mode(tk.mode & 15, [](auto m) -> SurfaceProcKernel { return k_surface_p<decltype(m)::value>; });
+		if (!sk) return fail(JP_ERR_UNSUPPORTED, "jp_surface: no instance for this walk on a scene with procedural textures");
+		hipLaunchKernelGGL(sk, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.tv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a, c->plan.sm, c->plan.proc);
+	}
+	else hipLaunchKernelGGL(tk.surface, dim3(grid), dim3(JP_BLOCK), tk.lds, c->stream, c->plan.sv, c->plan.tv, tk.depth, n, d_o, d_d, d_t0, d_t1, d_prim, d_uv, d_a, c->plan.sm);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(prim, d_prim, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipMemcpyAsync(uv, d_uv, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(albedo, d_a, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));

@@ -61,6 +61,7 @@ struct ScenePlan
 	int nm_maps = 0, nm_mapped = 0; long long nm_texel_bytes = 0, nm_table_bytes = 0;   // ... and what jp_get_normal_map_info reports of the uploaded scene's maps
 	SampView sm = {}; int ts_active_textures = 0, ts_active_maps = 0; long long ts_table_bytes = 0;   // texture sampling records (jp_tex_sampling.h): the slots of the textures / maps where one is active (k_texel_s / k_normal_map_s then), and what jp_get_texture_sampling_info reports
 	MipView mv = {}; int mip_on = 0, mip_levels = 0; long long mip_bytes = 0;           // mip maps (jp_mipmap.h): the level tables where a pyramid was built (k_texel_m then; mv.cone is set per launch), and what jp_get_texture_mipmap_info reports
+	ProcView proc = {}; int proc_on = 0, proc_aa = 0; long long proc_bytes = 0;        // procedural textures (jp_procedural.h): the records and the per-texture index where a used texture has one (k_texel_p then), how many of them are antialiased (the cone array then), and what jp_get_procedural_info reports
 	EnvView ev = {}; bool env = false; double env_mean_sum = 0.0;                      // environment map (jp_env.h): the texel tables; the map light's weight in the light table is (env_mean_sum * pi) * R^2
 	int trav_mode = 0, stack_depth = 1, stack_depth_q4 = 0; bool scene_in_lds = false, shade_prims_in_lds = false; size_t lds_bytes = 0, lds_bytes_shadow = 0;
 	bool cert = false;                                                                 // reference semantics, certified walk (Walker<6>)
@@ -86,6 +87,7 @@ struct SceneTables
 	DevBuf prim_vn;                                                  // vertex normals (jp_normals.h)
 	DevBuf nm_desc, nm_texels, nm_mat, nm_prim_uv;                   // normal maps (jp_normal_map.h)
 	DevBuf ts_tex, ts_map;                                           // texture sampling records (jp_tex_sampling.h)
+	DevBuf proc_rec, proc_tex;                                       // procedural textures (jp_procedural.h): the records and the per-texture index
 	DevBuf mip_tex, mip_lev;                                         // mip maps (jp_mipmap.h): the level tables; the pyramids' texels follow level 0 in `texels`
 };
 // The arrays behind a Queues view (the fused schedule's region queues have no hit records and no per-block counts)
@@ -105,6 +107,9 @@ struct TexSamplingHost { bool has_tex = false, has_map = false; int n_textures =
 
 // the modes jp_set_texture_mipmaps copied, waiting for the next upload (set false: none)
 struct MipmapsHost { bool set = false; int n_textures = 0, n_on = 0; float footprint_scale = 0.f, bounce_spread = 0.f; std::vector<int32_t> mode; };
+
+// the records jp_set_texture_procedurals copied, waiting for the next upload (set false: none)
+struct ProceduralsHost { bool set = false; int n_textures = 0, n_on = 0, n_aa = 0; std::vector<JpProcedural> rec; };
 
 struct JpContext
 {
@@ -178,6 +183,8 @@ struct JpContext
 	MipmapsHost mipmaps;
 	std::vector<int2> mip_host_tex; std::vector<JpMipLevel> mip_host_lev; double mip_build_ms = 0.0; int last_mip = 0;
 	DevBuf cone;
+	// procedural textures (jp_procedural.h): the records the next upload takes (jp_set_texture_procedurals) and what the last render ran
+	ProceduralsHost procedurals; int last_proc = 0;
 	// thin-lens camera (jp_lens_runtime.h): render-time state like the estimator (jp_set_lens; a lane takes its parent's before it renders) and what the last
 	// render ran.  The plan is a kernel argument made per launch from the uploaded camera: the lens owns no device memory.
 	JpLens lens = {}; bool lens_on = false; int last_lens = 0;
@@ -202,6 +209,9 @@ static int check_mipmap_textures(const JpContext* c, const JpTextures* t, long l
 static long long mip_pool_texels(const JpContext* c, const JpTextures* t, long long pool);
 static int upload_mipmaps(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const JpTextures* t, const std::vector<int4>& desc, long long pool);
 static int ensure_cone(JpContext* c, unsigned int cap, MipView& mv);
+static int check_procedural_counts(const JpContext* c, int n_textures);                             // jp_procedural.h
+static int check_procedural_textures(const JpContext* c, const JpTextures* t);
+static int upload_procedurals(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const JpTextures* t);
 
 // a context buffer that kernels in flight may still use: grown only once the stream is idle (nothing happens when the capacity suffices)
 static int reserve_idle(JpContext* c, DevBuf& b, size_t bytes)
@@ -225,6 +235,7 @@ static void free_scene(JpContext* c)
 	c->plan.mp = NMapView(); c->plan.mapped = false; c->plan.nm_maps = c->plan.nm_mapped = 0; c->plan.nm_texel_bytes = c->plan.nm_table_bytes = 0;
 	c->plan.sm = SampView(); c->plan.ts_active_textures = c->plan.ts_active_maps = 0; c->plan.ts_table_bytes = 0;
 	c->plan.mv = MipView(); c->plan.mip_on = c->plan.mip_levels = 0; c->plan.mip_bytes = 0; c->mip_host_tex.clear(); c->mip_host_lev.clear(); c->mip_build_ms = 0.0; c->cone.reset();
+	c->plan.proc = ProcView(); c->plan.proc_on = c->plan.proc_aa = 0; c->plan.proc_bytes = 0;
 }
 
 // Which build of glibc's sinf / cosf / sincosf does this host run (jp_shading.h, sincosf_libm)?  The reference computes its

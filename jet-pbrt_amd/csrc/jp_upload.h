@@ -81,6 +81,7 @@ extern "C" int jp_upload_scene(JpContext* c, const JpScene* s)
 	const int n_textures = c->upload_n_textures; c->upload_n_textures = 0;   // (jp_upload_scene_textured's count; a plain upload has none)
 	if (const int st = check_sampling_counts(c, n_textures); st != JP_OK) return st;   // jp_set_texture_sampling: refused while the old scene is still there
 	if (const int st = check_mipmap_counts(c, n_textures); st != JP_OK) return st;     // jp_set_texture_mipmaps: likewise
+	if (const int st = check_procedural_counts(c, n_textures); st != JP_OK) return st; // jp_set_texture_procedurals: likewise
 	HIP_TRY(hipSetDevice(c->device));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	free_scene(c);                                                  // first: the old and the new scene are never resident together
@@ -297,6 +298,7 @@ extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const Jp
 	if (const int st = check_textures(s, t, pool, ntm); st != JP_OK) return st;
 	if (const int st = check_sampling_textures(c, t); st != JP_OK) return st;
 	if (const int st = check_mipmap_textures(c, t, pool); st != JP_OK) return st;
+	if (const int st = check_procedural_textures(c, t); st != JP_OK) return st;
 	c->upload_n_textures = t->n_textures;
 	const int st = jp_upload_scene(c, s); c->upload_n_textures = 0;                              // (validates the scene; drops the textures of an earlier upload)
 	if (st != JP_OK) return st;
@@ -318,5 +320,6 @@ extern "C" int jp_upload_scene_textured(JpContext* c, const JpScene* s, const Jp
 	c->plan.textured = true; c->n_textures = t->n_textures; c->n_tex_mats = ntm; c->texel_bytes = (long long)x.texels.size() * 4;
 	if (upload_tex_sampling(c, T, c->plan) != JP_OK) { free_scene(c); return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: out of device memory for the sampling records"); }
 	if (pool_mip > pool && upload_mipmaps(c, T, c->plan, s, t, x.desc, pool) != JP_OK) { free_scene(c); return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: building the pyramids failed"); }
+	if (upload_procedurals(c, T, c->plan, s, t) != JP_OK) { free_scene(c); return fail(JP_ERR_DEVICE, "jp_upload_scene_textured: out of device memory for the procedural records"); }
 	return JP_OK;
 }

@@ -2,6 +2,7 @@
 // (tests, bench.py, __graft_entry__) can build scenes through the SAME call sequence they use on the compiled
 // reference (oracle/ref_build/ref_driver.cc: ref_*), i.e. the calls of main.cc:13-111.
 #include "jetpbrt.h"
+#include "jp_procedural.h"       // jp_procedural_check: what jp_host_texture_procedural accepts
 
 #include <cstring>
 
@@ -56,6 +57,15 @@ int jp_host_mat_metal(void* h, const float* eta, const float* k, float ur, float
 // textures (FSolidColor / FCheckerTexture / FImageTexture) -> handle index; materials that take one (-1: none)
 int jp_host_texture_solid(void* h, const float* rgb) { HostScene* hs = (HostScene*)h; hs->texs.push_back(std::make_shared<FSolidColor>(C3(rgb))); return (int)hs->texs.size() - 1; }
 int jp_host_texture_checker(void* h, const float* odd, const float* even) { HostScene* hs = (HostScene*)h; hs->texs.push_back(std::make_shared<FCheckerTexture>(C3(odd), C3(even))); return (int)hs->texs.size() - 1; }
+// FProceduralTexture from a JpProcedural (kind not NONE): the texture flattens as the CHECKER of the two colours plus the record
+int jp_host_texture_procedural(void* h, const JpProcedural* rec, const float* odd, const float* even)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!rec || rec->kind == JP_PROC_NONE || jp_procedural_check(rec)) { hs->error = std::string("jp_host_texture_procedural: ") + (rec ? jp_procedural_rule(jp_procedural_check(rec)) : "null record"); return -1; }
+	auto t = std::make_shared<FProceduralTexture>(rec->kind, C3(odd), C3(even), rec->m, rec->octaves, rec->gain, rec->antialias >= 0, rec->variation, rec->space == JP_PROC_SPACE_UV);
+	hs->texs.push_back(t);
+	return (int)hs->texs.size() - 1;
+}
 int jp_host_texture_image(void* h, const unsigned char* rgb8, int w, int hgt) { HostScene* hs = (HostScene*)h; hs->texs.push_back(std::make_shared<FImageTexture>(rgb8, w, hgt)); return (int)hs->texs.size() - 1; }
 int jp_host_texture_image_file(void* h, const char* path) { HostScene* hs = (HostScene*)h; hs->texs.push_back(std::make_shared<FImageTexture>(path)); return (int)hs->texs.size() - 1; }
 int jp_host_mat_matte_tex(void* h, int tex) { HostScene* hs = (HostScene*)h; if (tex < 0 || tex >= (int)hs->texs.size()) return -1; hs->mats.push_back(hs->scene->CreateMaterial<FMatteMaterial>(hs->texs[tex])); return (int)hs->mats.size() - 1; }
@@ -162,6 +172,12 @@ static int add_normal_map(HostScene* hs, const std::shared_ptr<FNormalMap>& m, c
 }
 int jp_host_normal_map(void* h, const unsigned char* rgb8, int w, int hgt) { return add_normal_map((HostScene*)h, std::make_shared<FNormalMap>(rgb8, w, hgt), "jp_host_normal_map"); }
 int jp_host_normal_map_file(void* h, const char* path) { return add_normal_map((HostScene*)h, FNormalMap::FromFile(path), "jp_host_normal_map_file"); }
+int jp_host_normal_map_from_procedural(void* h, const JpProcedural* rec, int w, int hgt, float scale)
+{
+	std::shared_ptr<FNormalMap> m = rec ? FNormalMap::FromProcedural(*rec, w, hgt, scale) : nullptr;
+	if (!m) { ((HostScene*)h)->error = "jp_host_normal_map_from_procedural: a record the validation refuses, or a size out of range"; return -1; }
+	return add_normal_map((HostScene*)h, m, "jp_host_normal_map_from_procedural");
+}
 int jp_host_normal_map_from_height(void* h, const unsigned char* grey, int w, int hgt, float scale) { return add_normal_map((HostScene*)h, FNormalMap::FromHeight(grey, w, hgt, scale), "jp_host_normal_map_from_height"); }
 // the map's size (either pointer may be null) and, with rgb8_out, its 3 * w * hgt bytes
 int jp_host_normal_map_read(void* h, int map, int* w, int* hgt, unsigned char* rgb8_out)
@@ -273,6 +289,14 @@ const JpTextureSampling* jp_host_flatten_texture_sampling(void* h)
 	HostScene* hs = (HostScene*)h;
 	if (!jp_host_flatten(h) || hs->flat.n_sampled == 0) return nullptr;
 	return &hs->flat.sampling;
+}
+
+// the flattened procedural records (valid with jp_host_flatten's view; null: every kind is NONE, or the flattening failed)
+const JpTextureProcedurals* jp_host_flatten_texture_procedurals(void* h)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!jp_host_flatten(h) || hs->flat.n_procedural == 0) return nullptr;
+	return &hs->flat.procedurals;
 }
 
 // the flattened mipmap modes (valid with jp_host_flatten's view; null: every mode is OFF, or the flattening failed)

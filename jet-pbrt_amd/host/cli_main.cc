@@ -6,6 +6,10 @@
 //             [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]
 //             [--texture-wrap clamp|repeat|mirror] [--texture-filter nearest|bilinear] [--texture-tile SU SV] [--normal-wrap clamp|repeat] [--normal-tile SU SV]
 //             [--texture-mip [--mip-footprint S] [--mip-bounce-spread RAD]]
+//             [--floor-texture noise|fbm|turbulence|marble|checker [--floor-texture-scale S] [--floor-texture-octaves N] [--no-texture-antialias]]
+// --floor-texture KIND: a procedural texture (FProceduralTexture) in world space on the floor of either scene, which gets a material of its own as with --normal-map;
+// --floor-texture-scale S: texture-space units per world unit (default 0.02: one noise cell is 50 units wide); --floor-texture-octaves N: 1 .. 12 (default 6);
+// --no-texture-antialias: point-sample it instead of band-limiting it by the footprint of the path's ray cone.
 // --texture-mip: mip maps for every image texture (FScene::SetTextureMipmapDefault): trilinear filtering at the footprint of the path's ray cone; --mip-footprint S scales
 // the footprint (default 1); --mip-bounce-spread RAD: the least spread of the cone after a bounce that is not specular (default 0.125, a design choice).
 // --texture-wrap / --texture-filter / --texture-tile: the sampling record (FScene::SetTextureSamplingDefault) of every image texture without one of its own: the wrap mode of
@@ -49,7 +53,7 @@ static FColor LightRadiance()                                    // main.cc:35
 
 // nmap (--normal-map): the floor gets a material of its own that carries it; *floorHasUV tells whether the floor mesh has texture coordinates at all
 static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr, const FSmoothing& sm = FSmoothing(),
-                                                       const std::shared_ptr<FNormalMap>& nmap = nullptr, float nstrength = 1.f, bool* floorHasUV = nullptr)   // main.cc:13-62; background: --envmap's tint; sm: --smooth
+                                                       const std::shared_ptr<FNormalMap>& nmap = nullptr, float nstrength = 1.f, bool* floorHasUV = nullptr, const std::shared_ptr<FTexture>& floorTex = nullptr)   // main.cc:13-62; background: --envmap's tint; sm: --smooth
 {
 	const FPoint3 lookfrom(278, 273, 960), lookat(278, 273, 0);
 	std::shared_ptr<FScene> scene = std::make_shared<FScene>("cornell_box_scene");
@@ -64,9 +68,11 @@ static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize,
 	scene->CreateAreaLights(1, LightRadiance(), scene->CreateTriangleMesh((d + "light.obj").c_str(), true, true), mat_light);
 	const std::vector<std::shared_ptr<FShape>> floorMesh = scene->CreateTriangleMesh((d + "floor.obj").c_str(), true, true, FVector3(0, 0, 0), 1.f, sm);
 	std::shared_ptr<FMaterial> floorMat = white;
+	if (floorTex) floorMat = scene->CreateMaterial<FMatteMaterial>(floorTex);     // --floor-texture: a material of the floor's own
 	if (nmap)
 	{
-		floorMat = scene->CreateMaterial<FMatteMaterial>(FColor(0.725f, 0.71f, 0.68f)); floorMat->normalMap = nmap; floorMat->normalStrength = nstrength;
+		if (!floorTex) floorMat = scene->CreateMaterial<FMatteMaterial>(FColor(0.725f, 0.71f, 0.68f));
+		floorMat->normalMap = nmap; floorMat->normalStrength = nstrength;
 		bool uv = floorMesh.empty();                                  // (a mesh that did not load is reported as such, below)
 		for (auto& sh : floorMesh) { const FTriangle* t = static_cast<const FTriangle*>(sh.get()); if (t->uv0.x != t->uv1.x || t->uv0.y != t->uv1.y || t->uv0.x != t->uv2.x || t->uv0.y != t->uv2.y) uv = true; }
 		if (floorHasUV) *floorHasUV = uv;
@@ -81,7 +87,7 @@ static std::shared_ptr<FScene> create_cornellbox_scene(const FVector2& filmsize,
 }
 
 static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, const std::string& dir, const FColor* background = nullptr, const FSmoothing& sm = FSmoothing(),
-                                                  const std::shared_ptr<FNormalMap>& nmap = nullptr, float nstrength = 1.f)        // main.cc:64-111
+                                                  const std::shared_ptr<FNormalMap>& nmap = nullptr, float nstrength = 1.f, const std::shared_ptr<FTexture>& floorTex = nullptr)        // main.cc:64-111
 {
 	const FPoint3 lookfrom(-300, 300, -300), lookat(0, 0, 0);
 	std::shared_ptr<FScene> scene = std::make_shared<FScene>("bunny_scene");
@@ -95,6 +101,7 @@ static std::shared_ptr<FScene> create_bunny_scene(const FVector2& filmsize, cons
 	scene->CreateAreaLight(1, LightRadiance(), light, mat_light);
 	std::shared_ptr<FShape> floor = scene->CreateShape<FRectangle>(FRectangle::FromXZ(-200, 200, -200, 200, 0));
 	if (nmap) { green->normalMap = nmap; green->normalStrength = nstrength; }     // (green is the floor's alone)
+	if (floorTex) green->texture = floorTex;
 	scene->CreatePrimitive(floor.get(), green.get(), (const FAreaLight*)nullptr);
 	const std::string obj = dir + "/bunny/bunny.obj";
 	scene->CreatePrimitives(scene->CreateTriangleMesh(obj.c_str(), true, true, FVector3(0, 0, 0), 500.f, sm), red);
@@ -119,6 +126,7 @@ int main(int argc, char* argv[])
 	bool hdr = false, haveToneMap = false; float sampleClamp = 0.f; FToneMap toneMap;
 	FTexSampling texSampling, normalSampling; bool haveTexSampling = false, haveNormalSampling = false;
 	bool textureMip = false; float mipFootprint = 0.f, mipBounceSpread = 0.f;
+	int floorTexture = JP_PROC_NONE, floorOctaves = 0; float floorScale = 0.02f; bool floorAntialias = true, floorOptions = false;
 	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
 	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
@@ -127,6 +135,7 @@ int main(int argc, char* argv[])
 	fprintf(stderr, "          [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]\n");
 	fprintf(stderr, "          [--texture-wrap clamp|repeat|mirror] [--texture-filter nearest|bilinear] [--texture-tile SU SV] [--normal-wrap clamp|repeat] [--normal-tile SU SV]\n");
 	fprintf(stderr, "          [--texture-mip [--mip-footprint S] [--mip-bounce-spread RAD]]\n");
+	fprintf(stderr, "          [--floor-texture noise|fbm|turbulence|marble|checker [--floor-texture-scale S] [--floor-texture-octaves N] [--no-texture-antialias]]\n");
 	std::vector<const char*> pos;
 	for (int i = 1; i < argc; i++)
 	{
@@ -203,6 +212,27 @@ int main(int argc, char* argv[])
 			else { fprintf(stderr, "--normal-wrap must be clamp or repeat\n"); return 5; }
 		}
 		else if (!strcmp(argv[i], "--texture-mip")) textureMip = true;
+		else if (!strcmp(argv[i], "--floor-texture") && i + 1 < argc)
+		{
+			const char* m = argv[++i];
+			if (!strcmp(m, "noise")) floorTexture = JP_PROC_NOISE; else if (!strcmp(m, "fbm")) floorTexture = JP_PROC_FBM; else if (!strcmp(m, "turbulence")) floorTexture = JP_PROC_TURBULENCE;
+			else if (!strcmp(m, "marble")) floorTexture = JP_PROC_MARBLE; else if (!strcmp(m, "checker")) floorTexture = JP_PROC_CHECKER_AA;
+			else { fprintf(stderr, "--floor-texture must be noise, fbm, turbulence, marble or checker\n"); return 5; }
+		}
+		else if (!strcmp(argv[i], "--floor-texture-scale") && i + 1 < argc)
+		{
+			char* e = nullptr; floorScale = strtof(argv[i + 1], &e); floorOptions = true;
+			if (e == argv[i + 1] || *e || !(floorScale > 0.f) || !std::isfinite(floorScale)) { fprintf(stderr, "--floor-texture-scale takes a number > 0\n"); return 5; }
+			i++;
+		}
+		else if (!strcmp(argv[i], "--floor-texture-octaves") && i + 1 < argc)
+		{
+			char* e = nullptr; const long v = strtol(argv[i + 1], &e, 10); floorOptions = true;
+			if (e == argv[i + 1] || *e || v < 1 || v > 12) { fprintf(stderr, "--floor-texture-octaves takes 1 .. 12\n"); return 5; }
+			floorOctaves = (int)v; i++;
+		}
+		else if (!strcmp(argv[i], "--no-texture-antialias")) { floorAntialias = false; floorOptions = true; }
+		else if (!strncmp(argv[i], "--floor-texture", 15)) { fprintf(stderr, "%s: missing value\n", argv[i]); return 5; }
 		else if ((!strcmp(argv[i], "--mip-footprint") || !strcmp(argv[i], "--mip-bounce-spread")) && i + 1 < argc)
 		{
 			char* e = nullptr; const float v = strtof(argv[i + 1], &e);
@@ -257,11 +287,18 @@ int main(int argc, char* argv[])
 	}
 	bool floorHasUV = true;
 	const FColor tint(envScale, envScale, envScale);
+	if (floorOptions && floorTexture == JP_PROC_NONE) { fprintf(stderr, "--floor-texture-scale / --floor-texture-octaves / --no-texture-antialias need --floor-texture\n"); return 5; }
+	std::shared_ptr<FTexture> floorTex;
+	if (floorTexture != JP_PROC_NONE)
+	{   // world space, the same scale on every axis; the floor's own colour at t = 0, a dark slate at t = 1
+		const float m[12] = { floorScale, 0, 0, 0, 0, floorScale, 0, 0, 0, 0, floorScale, 0 };
+		floorTex = std::make_shared<FProceduralTexture>(floorTexture, FColor(0.2f, 0.2f, 0.25f), FColor(0.725f, 0.71f, 0.68f), m, floorOctaves, 0.f, floorAntialias);
+	}
 	std::shared_ptr<FScene> scene;
 	switch (sceneId)
 	{
-	case 0: scene = create_cornellbox_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing, nmap, normalStrength, &floorHasUV); break;
-	case 1: scene = create_bunny_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing, nmap, normalStrength); break;
+	case 0: scene = create_cornellbox_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing, nmap, normalStrength, &floorHasUV, floorTex); break;
+	case 1: scene = create_bunny_scene(film.GetResolution(), assets, map ? &tint : nullptr, smoothing, nmap, normalStrength, floorTex); break;
 	default: return 0;
 	}
 	if (nmap && !floorHasUV) { fprintf(stderr, "--normal-map: %s/cornellbox/floor.obj has no texture coordinates (vt), so nothing would be mapped\n", assets.c_str()); return 5; }

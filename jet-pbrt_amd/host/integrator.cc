@@ -33,6 +33,7 @@ struct HipApi
 	int (*set_vertex_normals)(JpContext*, const JpVertexNormals*) = nullptr;                 // (looked up, needed by scenes with smooth meshes only)
 	int (*set_normal_maps)(JpContext*, const JpNormalMaps*) = nullptr;                       // (looked up, needed by scenes with FMaterial::normalMap only)
 	int (*set_texture_sampling)(JpContext*, const JpTextureSampling*) = nullptr;             // (looked up, needed by scenes with a sampling record only)
+	int (*set_texture_procedurals)(JpContext*, const JpTextureProcedurals*) = nullptr;       // (looked up, needed by scenes with an FProceduralTexture only)
 	int (*set_texture_mipmaps)(JpContext*, const JpTextureMipmaps*) = nullptr;               // (looked up, needed by scenes with FImageTexture::SetMipmaps only)
 	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                        // (looked up, needed by FScene::SetEstimator only)
 	int (*set_lens)(JpContext*, const JpLens*) = nullptr;                                    // (looked up, needed by FCamera::SetLens only)
@@ -75,6 +76,7 @@ HipApi& Api()
 		api.set_normal_maps = (decltype(api.set_normal_maps))dlsym(api.lib, "jp_set_normal_maps");
 		api.set_texture_sampling = (decltype(api.set_texture_sampling))dlsym(api.lib, "jp_set_texture_sampling");
 		api.set_texture_mipmaps = (decltype(api.set_texture_mipmaps))dlsym(api.lib, "jp_set_texture_mipmaps");
+		api.set_texture_procedurals = (decltype(api.set_texture_procedurals))dlsym(api.lib, "jp_set_texture_procedurals");
 		api.focus_distance = (decltype(api.focus_distance))dlsym(api.lib, "jp_focus_distance");
 		api.set_film = (decltype(api.set_film))dlsym(api.lib, "jp_set_film");
 		api.set_tonemap = (decltype(api.set_tonemap))dlsym(api.lib, "jp_set_tonemap");
@@ -201,6 +203,13 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			lastStatus = api.set_texture_mipmaps(ctx, flat.n_mipmapped > 0 ? &flat.mipmaps : nullptr);
 			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
 			ctxMipmaps = flat.n_mipmapped > 0;
+		}
+		if (flat.n_procedural > 0 || ctxProcedurals)
+		{   // FProceduralTexture: the records go to the context before the upload they are to affect, like the mipmap modes
+			if (!api.set_texture_procedurals) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_texture_procedurals\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_texture_procedurals(ctx, flat.n_procedural > 0 ? &flat.procedurals : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxProcedurals = flat.n_procedural > 0;
 		}
 		// a scene with a textured material goes through jp_upload_scene_textured; any other makes exactly the calls it always made
 		const bool textured = flat.textures.n_textures > 0;

@@ -163,6 +163,34 @@ public:
 	int Kind() const override { return JP_TEXTURE_CHECKER; }
 	FColor odd, even;
 };
+// ---- procedural textures (include/jetpbrt_amd.h "Procedural textures", include/jp_procedural.h): gradient noise, fBm, turbulence, marble and the box-filtered
+// checker between two colours (even at t = 0, odd at t = 1, both in [0, 1]); flattened as a CHECKER texture plus its record (jp_set_texture_procedurals).
+// transform: the row-major 3 x 4 map of the hit point (or of (u, v, 0) with uvSpace) into texture space, null: the identity; octaves 0: 6; gain 0: 0.5;
+// antialias: band-limit by the footprint of the path's ray cone.
+class FProceduralTexture : public FCheckerTexture
+{
+public:
+	FProceduralTexture(int kind, const FColor& odd, const FColor& even, const float* transform, int octaves, Float gain, bool antialias, Float variation = 0, bool uvSpace = false)
+		: FCheckerTexture(odd, even)
+	{
+		static const float identity[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
+		record.kind = kind; record.space = uvSpace ? JP_PROC_SPACE_UV : JP_PROC_SPACE_WORLD;
+		for (int k = 0; k < 12; k++) record.m[k] = transform ? transform[k] : identity[k];
+		record.octaves = octaves; record.gain = gain; record.variation = variation; record.antialias = antialias ? 1 : -1;
+	}
+	// every factory takes the colours in the constructor's (and FCheckerTexture's) order: odd (t = 1) first, then even (t = 0)
+	static std::shared_ptr<FProceduralTexture> Noise(const FColor& odd, const FColor& even, const float* transform = nullptr, int octaves = 0, Float gain = 0, bool antialias = true)
+	{ return std::make_shared<FProceduralTexture>(JP_PROC_NOISE, odd, even, transform, octaves, gain, antialias); }
+	static std::shared_ptr<FProceduralTexture> FBm(const FColor& odd, const FColor& even, const float* transform = nullptr, int octaves = 0, Float gain = 0, bool antialias = true)
+	{ return std::make_shared<FProceduralTexture>(JP_PROC_FBM, odd, even, transform, octaves, gain, antialias); }
+	static std::shared_ptr<FProceduralTexture> Turbulence(const FColor& odd, const FColor& even, const float* transform = nullptr, int octaves = 0, Float gain = 0, bool antialias = true)
+	{ return std::make_shared<FProceduralTexture>(JP_PROC_TURBULENCE, odd, even, transform, octaves, gain, antialias); }
+	static std::shared_ptr<FProceduralTexture> Marble(const FColor& odd, const FColor& even, const float* transform = nullptr, int octaves = 0, Float gain = 0, bool antialias = true, Float variation = 0)
+	{ return std::make_shared<FProceduralTexture>(JP_PROC_MARBLE, odd, even, transform, octaves, gain, antialias, variation); }
+	static std::shared_ptr<FProceduralTexture> FilteredChecker(const FColor& odd, const FColor& even, const float* transform = nullptr, bool antialias = true)   // (a checker has no octaves)
+	{ return std::make_shared<FProceduralTexture>(JP_PROC_CHECKER_AA, odd, even, transform, 0, 0, antialias); }
+	JpProcedural record;
+};
 // ---- texture sampling (include/jetpbrt_amd.h "Texture sampling"): how an image texture or a normal map is addressed; the default is the identity record ----
 enum class EWrap { Clamp = JP_WRAP_CLAMP, Repeat = JP_WRAP_REPEAT, Mirror = JP_WRAP_MIRROR };
 enum class EFilter { Default = JP_FILTER_DEFAULT, Nearest = JP_FILTER_NEAREST, Bilinear = JP_FILTER_BILINEAR };   // Default: nearest for an image texture, bilinear for a normal map
@@ -225,6 +253,9 @@ public:
 	// a height map (w * h grey bytes, top row first) as a normal map: central differences with clamped neighbours, heights in 0 .. 1,
 	// n = normalize(-scale * dh/dx, -scale * dh/dy_up, 1) per texel, each component encoded as round(127 * c) + 128 (the inverse of the decode)
 	static std::shared_ptr<FNormalMap> FromHeight(const uint8_t* grey, int w, int h, float scale);
+	// a w x h height image baked from a procedural record with the host lookup (include/jp_procedural.h; t over uv in [0, 1)^2 at z = 0, width 0: q = M (u, v, 0) + t,
+	// whatever the record's space), then FromHeight: a marble floor can be bumpy too.  Null for a record the validation refuses or a size out of range.
+	static std::shared_ptr<FNormalMap> FromProcedural(const JpProcedural& record, int w, int h, float scale);
 	bool Valid() const { return width >= 1 && width <= 16384 && height >= 1 && height <= 16384 && data.size() == (size_t)width * height * 3; }
 	std::vector<uint8_t> data;
 	int width = 0, height = 0;
@@ -571,6 +602,10 @@ struct FlatScene
 	JpTextureMipmaps mipmaps;
 	std::vector<int32_t> tex_mip_mode;
 	int n_mipmapped = 0;
+	// procedural textures (jp_set_texture_procedurals): one record per flattened texture; n_procedural == 0: every kind is NONE and the scene sets no such state
+	JpTextureProcedurals procedurals;
+	std::vector<JpProcedural> tex_procedural;
+	int n_procedural = 0;
 };
 bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error = nullptr);
 
@@ -614,6 +649,7 @@ protected:
 	mutable JpLens ctxLens = {};                                    // the lens the context was last told (FCamera::SetLens; radius 0: none)
 	mutable JpFilm ctxFilm = {}; mutable JpToneMap ctxToneMap = {};   // the film state and tone map the context was last told (FFilm::SetHDR / SetSampleClamp / SetToneMap; zeros: none)
 	mutable bool ctxNormalMaps = false;                            // ... or normal maps (jp_set_normal_maps)
+	mutable bool ctxProcedurals = false;                           // ... or procedural records (jp_set_texture_procedurals)
 	mutable bool ctxMipmaps = false;                               // ... or mipmap modes (jp_set_texture_mipmaps)
 	mutable bool ctxSampling = false;                              // ... or texture sampling records (jp_set_texture_sampling)
 	mutable bool ctxNormals = false;                                // the context holds vertex normals of an earlier upload (jp_set_vertex_normals)

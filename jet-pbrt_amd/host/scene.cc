@@ -2,6 +2,7 @@
 // and the flattener that produces the JpScene SoA view.  No ray is traced on the host.
 #include "jetpbrt.h"
 #include "jp_tex_sampling.h"     // jp_tsamp_identity: which records FlattenScene counts as set
+#include "jp_procedural.h"       // the host lookup FNormalMap::FromProcedural bakes with
 
 #include <algorithm>
 #include <cstdlib>
@@ -374,6 +375,23 @@ std::shared_ptr<FNormalMap> FNormalMap::FromFile(const char* filename)
 	auto m = std::make_shared<FNormalMap>(rgb.data(), w, h);
 	return m->Valid() ? m : nullptr;
 }
+std::shared_ptr<FNormalMap> FNormalMap::FromProcedural(const JpProcedural& record, int w, int h, float scale)
+{
+	if (w < 1 || w > 16384 || h < 1 || h > 16384 || record.kind == JP_PROC_NONE || jp_procedural_check(&record)) return nullptr;
+	JpProcedural r = record; r.space = JP_PROC_SPACE_UV;
+	const JpProcDev d = jp_proc_resolve(&r);
+	const float black[3] = { 0, 0, 0 }, white[3] = { 1, 1, 1 }, origin[3] = { 0, 0, 0 };
+	std::vector<uint8_t> grey((size_t)w * h);
+	for (int j = 0; j < h; j++)
+		for (int i = 0; i < w; i++)
+		{   // the texel's centre; row 0 is the top row, v = 1 at the top as for every image
+			float t = 0.f;
+			jp_proc_lookup(&d, black, white, 0, origin, ((float)i + 0.5f) / (float)w, 1.f - ((float)j + 0.5f) / (float)h, 0.f, &t);
+			grey[(size_t)j * w + i] = (uint8_t)jp_proc_byte(t);
+		}
+	return FromHeight(grey.data(), w, h, scale);
+}
+
 std::shared_ptr<FNormalMap> FNormalMap::FromHeight(const uint8_t* grey, int w, int h, float scale)
 {
 	if (!grey || w < 1 || w > 16384 || h < 1 || h > 16384 || !std::isfinite(scale)) return nullptr;
@@ -444,6 +462,10 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 			bool mip = false;
 			if (kind == JP_TEXTURE_IMAGE) { const FImageTexture* it = static_cast<const FImageTexture*>(T); mip = it->hasMipmaps ? it->mipmaps : scene.textureMipmapDefault; }
 			out.tex_mip_mode.push_back(mip ? JP_MIP_TRILINEAR : JP_MIP_OFF);
+			// the procedural record: an FProceduralTexture's own (it flattens as the CHECKER of its two colours), NONE else
+			JpProcedural pr; std::memset(&pr, 0, sizeof(pr));
+			if (const FProceduralTexture* pt = dynamic_cast<const FProceduralTexture*>(T)) pr = pt->record;
+			out.tex_procedural.push_back(pr);
 			ti = texRef.insert(std::make_pair(T, k)).first;
 		}
 		out.mat_texture.back() = ti->second;
@@ -565,6 +587,10 @@ bool FlattenScene(const FScene& scene, FlatScene& out, std::string* error)
 	mm.struct_bytes = (int32_t)sizeof(JpTextureMipmaps); mm.n_textures = t.n_textures; mm.mode = t.n_textures > 0 ? out.tex_mip_mode.data() : nullptr;
 	mm.footprint_scale = scene.mipFootprintScale; mm.bounce_spread = scene.mipBounceSpread;
 	for (const int32_t m : out.tex_mip_mode) if (m != JP_MIP_OFF) out.n_mipmapped++;
+	// the procedural records, in texture order
+	JpTextureProcedurals& pp = out.procedurals; std::memset(&pp, 0, sizeof(pp));
+	pp.struct_bytes = (int32_t)sizeof(JpTextureProcedurals); pp.n_textures = t.n_textures; pp.rec = t.n_textures > 0 ? out.tex_procedural.data() : nullptr;
+	for (const JpProcedural& r : out.tex_procedural) if (r.kind != JP_PROC_NONE) out.n_procedural++;
 	if (out.n_normal_mapped > 0) for (const JpTexSampler& r : out.nm_sampler) if (!jp_tsamp_identity(&r, JP_TSAMP_NORMAL)) out.n_sampled++;
 	return true;
 }

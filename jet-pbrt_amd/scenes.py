@@ -261,6 +261,26 @@ class HostBackend:
         p = self.L.jp_host_flatten_texture_mipmaps(self.h)
         return p.contents if p else None
 
+    def texture_procedural(self, record, odd, even):
+        """FProceduralTexture from a JpProcedural (jp.procedural(...)): the colour at t = 1 (odd) and at t = 0 (even); flattens as their CHECKER plus the record"""
+        a, _a = _fa(odd); b, _b = _fa(even)
+        k = self._f("texture_procedural")(self.h, C.byref(record), a, b)
+        if k < 0:
+            raise RuntimeError("texture_procedural failed: %s" % self.L.jp_host_last_error(self.h).decode())
+        return k
+
+    def flatten_texture_procedurals(self):
+        """the scene's procedural records as a JpTextureProcedurals for Context.set_texture_procedurals (None: no record); valid until the next preprocess"""
+        p = self.L.jp_host_flatten_texture_procedurals(self.h)
+        return p.contents if p else None
+
+    def normal_map_from_procedural(self, record, w, h, scale):
+        """FNormalMap::FromProcedural: a w x h height image baked from the record with the host lookup, then FromHeight -> normal map index"""
+        k = self._f("normal_map_from_procedural")(self.h, C.byref(record), int(w), int(h), C.c_float(scale))
+        if k < 0:
+            raise RuntimeError("normal_map_from_procedural failed: %s" % self.L.jp_host_last_error(self.h).decode())
+        return k
+
     def texture_image_file(self, path):
         """FImageTexture(filename): binary PPM or uncompressed BMP; anything else is the reference's solid cyan"""
         return self._f("texture_image_file")(self.h, path.encode())
@@ -657,6 +677,22 @@ def build_disks(be, width, height):
         b.disk((1.0, 274, -280), (1.0, 0.0, 0.0), 100.0, m["white"], None)                        # just in front of the left wall
         b.disk((300, 1.5, -100), (0.0, 1.0, 0.0), 3.0, metal, None)
     return build_cornell(be, width, height, lambert_only=False, extras=extras, env=(0.03, 0.03, 0.03))
+
+
+PROCEDURAL_VIEWS = {"near": ((0, 3, 0), (0.0, -1.0, -0.35), (0, 0, -1)), "far": ((0, 3, 0), (0.0, -0.06, -1.0), (0, 1, 0))}
+
+
+def build_procedural_floor(be, width, height, record=None, view="far"):
+    """A floor to the horizon under a white sky, for the tools: `record` (a JpProcedural; None: the plain checker) on the floor's texture, seen from 3 units above --
+    "near": looking down, every octave in reach; "far": looking along it, the ray cone's footprint swallowing octave after octave."""
+    pos, front, up = PROCEDURAL_VIEWS[view]
+    be.camera(pos, _normalize(np.array(front, np.float32)), up, 50.0, width, height)
+    be.envlight((1, 1, 1))
+    odd, even = (0.2, 0.2, 0.25), (0.725, 0.71, 0.68)
+    tex = be.texture_checker(odd, even) if record is None else be.texture_procedural(record, odd, even)
+    be.rect(AXIS_XZ, -400, 400, -800, 100, 0, False, be.mat_matte(tex=tex), None)
+    be.preprocess()
+    return be
 
 
 def export_reference_layout(root, n_lon=187, n_lat=188):
