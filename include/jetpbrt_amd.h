@@ -756,6 +756,50 @@ int  jp_tonemap_host(const JpToneMap* tonemap, float scale, int64_t n_values, co
 typedef struct JpToneMapInfo { int32_t struct_bytes, curve, exposure_mode; float scale_last; int32_t mapped_last_render; double histogram_ms, tonemap_ms; } JpToneMapInfo;
 int  jp_get_tonemap_info(JpContext* ctx, JpToneMapInfo* out);  /* curve / mode in force (0 0: none); scale and kernel times of the last transform; synchronises the stream */
 
+/* ---- Variance (additive to ABI 7; INTEGRATION.md "Variance") --------------------------------------------------------------------------------------
+ * A render that also delivers the per-pixel variance of its own mean, and a variance-guided variant of the a-trous filter.  All of it is fp32, operation by
+ * operation, no contraction (include/jp_variance.h: the text the kernels and jp_variance_samples both compile).  With none of these calls made, every kernel,
+ * film, guide and byte is what it is without this section.
+ *
+ * The estimate.  Per pixel, over its samples in sample-index order k = 1 .. spp, with l the sample's radiance as it enters the film's sum (after the sample clamp
+ * of jp_set_film where one is in force):
+ *     y = (0.2126f*l.r + 0.7152f*l.g) + 0.0722f*l.b                       (y not finite -> 0)
+ *     d = y - mean;  mean = mean + d / (float)k;  m2 = m2 + d * (y - mean)           (mean = m2 = 0 before k = 1)
+ *     variance = (m2 / (float)(spp - 1)) / (float)spp                     (the variance of the pixel's mean luminance)
+ *   jp_render_variance*: jp_render* with that plane next to the film (W*H floats, the film's pixel layout; pixels outside the band shard are 0, so shards sum to
+ *   the full plane).  The film is jp_render's bit for bit under the same state; every schedule, lane count and integrator.  spp < 2: JP_ERR_INVALID_ARGUMENT.
+ *   (mean, m2) live in 8 bytes per pixel on the device while the call runs (a call with sync = 0: until the next jp_render*).  A jp_render after it runs the
+ *   kernels it always ran; variance_last_render is then 0. */
+int  jp_render_variance(JpContext* ctx, const JpRenderParams* params, float* film_rgb_host, float* variance_host);          /* either may be NULL, not both */
+int  jp_render_variance_device(JpContext* ctx, const JpRenderParams* params, void* film_dev, void* variance_dev, int sync);
+/* pure host, the very function the device runs: samples_rgb [spp][n_pixels][3]; film NULL or sample_clamp 0: no clamp; variance_out / mean_out: n_pixels floats, either may be NULL */
+int  jp_variance_samples(const JpFilm* film_or_null, int32_t spp, int64_t n_pixels, const float* samples_rgb, float* variance_out, float* mean_out);
+/* test hook: the device twin of jp_variance_samples on caller-supplied samples, split into batches of batch_spp (>= 1) so the carried state is exercised; needs no scene */
+int  jp_variance_probe(JpContext* ctx, const JpFilm* film_or_null, int32_t spp, int32_t batch_spp, int64_t n_pixels, const float* samples_rgb, float* variance_out);
+/* The variance-guided filter: jp_denoise's inputs, taps, guides, validation and no-overlap rule (extended to the two new buffers), with the colour edge-stop scaled
+ * per pixel by a locally filtered variance that is carried through the iterations.  Only + - * / max min, in the order written:
+ *   set-up   a = max(albedo, 0.001f) per channel (1 without demodulation); c0 = film / a; aY = (0.2126f*a.r + 0.7152f*a.g) + 0.0722f*a.b;
+ *            vin = v > 0 ? min(v, 1e30f) : 0 (NaN and negatives: 0); v0 = vin / (aY*aY); kn, kz as in jp_denoise; sc2 = sigma_color*sigma_color
+ *   iteration i = 0 .. n-1, step 2^i:
+ *            g_p = (sum k3*v_q) / (sum k3) over q = p + (dx, dy), dx, dy in -1 .. 1 (distance 1 whatever the step; dy outer, dx inner; taps outside the image
+ *                  skipped in both sums), k3 = {1/4, 1/2, 1/4}[dy+1] * {1/4, 1/2, 1/4}[dx+1]
+ *            kc_p = 1.0f / (sc2 * g_p + 1e-8f)                              (no 4^i factor: the propagated variance does that job)
+ *            the 25 taps of jp_denoise, dc, dn, dz, hh unchanged: w = hh / (((1 + dc*kc_p) * (1 + dn*kn)) * (1 + dz*kz));
+ *                  num += w*c_q; den += w; vnum += (w*w)*v_q;   c_next_p = num / den;  v_next_p = vnum / (den*den)
+ *   output   out = Clamp01(c_n * a) (max(c_n * a, 0) while the film state has hdr = 1); variance_out = v_n * (aY*aY) (may be NULL)
+ * Defaults (fields left 0): as jp_denoise, but sigma_color 8.0 (DESIGN.md "Variance": the grid). */
+int  jp_denoise_variance(JpContext* ctx, const JpDenoiseParams* params, const float* film_rgb, const float* albedo, const float* normal, const float* depth,
+                         const float* variance, float* out_rgb, float* variance_out);
+int  jp_denoise_variance_device(JpContext* ctx, const JpDenoiseParams* params, const void* film_dev, const void* albedo_dev, const void* normal_dev, const void* depth_dev,
+                                const void* variance_dev, void* out_dev, void* variance_out_dev, int sync);
+/* as jp_render_denoised, with jp_render_variance and jp_denoise_variance as its stages; `variance` (may be NULL) receives the render's variance plane */
+int  jp_render_denoised_variance(JpContext* ctx, const JpRenderParams* render, int32_t guide_spp, const JpDenoiseParams* params, float* film_host, uint8_t* rgb8_host,
+                                 float* albedo, float* normal, float* depth, float* variance);
+/* variance_last_render: the last jp_render* kept the moments; moment_bytes_device: what they took (all lanes); the rest: the last jp_denoise_variance* (kernel time
+ * from HIP events on the context stream; synchronises the stream) */
+typedef struct JpVarianceInfo { int32_t struct_bytes, variance_last_render; int64_t moment_bytes_device; int32_t iterations; float sigma_color, sigma_normal, sigma_depth; int32_t demodulated; double denoise_ms; } JpVarianceInfo;
+int  jp_get_variance_info(JpContext* ctx, JpVarianceInfo* out);
+
 /* What jp_upload_scene would do with `scene` (additive to ABI 7; INTEGRATION.md "Describing an upload"): the scalars of the plan every later launch
  * reads, and for each table the host builds the byte count and the 64-bit FNV-1a of exactly the bytes the upload copies to the device.  Pure host code, no GPU
  * needed: the same validation (same status codes and jp_last_error texts), table builders and plan function the upload runs, nothing decided twice.

@@ -605,6 +605,12 @@ class JpToneMapInfo(C.Structure):
                 ("histogram_ms", C.c_double), ("tonemap_ms", C.c_double)]
 
 
+class JpVarianceInfo(C.Structure):
+    """include/jetpbrt_amd.h: JpVarianceInfo (jp_get_variance_info)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("variance_last_render", C.c_int32), ("moment_bytes_device", C.c_int64), ("iterations", C.c_int32),
+                ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("demodulated", C.c_int32), ("denoise_ms", C.c_double)]
+
+
 def film(hdr=1, sample_clamp=0.0):
     """A JpFilm (or pass one through)"""
     return hdr if isinstance(hdr, JpFilm) else JpFilm(C.sizeof(JpFilm), int(hdr), sample_clamp)
@@ -642,6 +648,20 @@ def film_samples(f, rgb):
     L = hip_lib()
     _hip_status(L, L.jp_film_samples(_ptr(f), a.shape[0], a.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+def variance_samples(f, samples, want_mean=False):
+    """jp_variance_samples: the per-pixel variance of the mean luminance of (spp, n, 3) float32 samples under JpFilm `f` (or None) -> (n,) float32
+    [, the running mean (n,)].  Pure host code, the function the device runs."""
+    import numpy as np
+    a = np.ascontiguousarray(samples, np.float32)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise JetPbrtError("variance_samples: samples must be (spp, n, 3)")
+    spp, n = a.shape[:2]
+    var = np.zeros(n, np.float32); mean = np.zeros(n, np.float32)
+    L = hip_lib()
+    _hip_status(L, L.jp_variance_samples(_ptr(f), spp, n, a.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p), mean.ctypes.data_as(C.c_void_p)))
+    return (var, mean) if want_mean else var
 
 
 def exposure_from_histogram(t, hist):
@@ -892,6 +912,7 @@ def host_lib():
         L.jp_host_flatten_textures.argtypes = [C.c_void_p]
         L.jp_host_render_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.jp_host_render_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.jp_host_render_variance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint] + [C.c_int] * 5 + [C.c_void_p] * 5
         L.jp_host_render_film.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                           C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_char_p, C.c_int]
         L.jp_host_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
@@ -1032,6 +1053,14 @@ def hip_lib():
         L.jp_tonemap_device.argtypes = [C.c_void_p, C.POINTER(JpToneMap), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int]
         L.jp_tonemap_host.argtypes = [C.POINTER(JpToneMap), C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         L.jp_get_tonemap_info.argtypes = [C.c_void_p, C.POINTER(JpToneMapInfo)]
+        L.jp_render_variance.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_void_p, C.c_void_p]
+        L.jp_render_variance_device.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_void_p, C.c_void_p, C.c_int]
+        L.jp_variance_samples.argtypes = [C.POINTER(JpFilm), C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.jp_variance_probe.argtypes = [C.c_void_p, C.POINTER(JpFilm), C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+        L.jp_denoise_variance.argtypes = [C.c_void_p, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 7
+        L.jp_denoise_variance_device.argtypes = [C.c_void_p, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 7 + [C.c_int]
+        L.jp_render_denoised_variance.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 6
+        L.jp_get_variance_info.argtypes = [C.c_void_p, C.POINTER(JpVarianceInfo)]
         _hip = L
     return _hip
 
@@ -1329,6 +1358,64 @@ class Context:
         dp = denoise_params(w, h, **kw) if denoise else None
         self._check(self.lib.jp_render_denoised(self.h, C.byref(params), guide_spp, _ptr(dp), q(f), q(b), q(alb), q(nrm), q(dep)))
         return f, b, alb, nrm, dep
+
+    def render_variance(self, params, want_film=True):
+        """jp_render_variance: the film of render() and the per-pixel variance of its mean luminance -> (film (H, W, 3) or None, variance (H, W))"""
+        import numpy as np
+        film = np.zeros((params.height, params.width, 3), np.float32) if want_film else None
+        var = np.zeros((params.height, params.width), np.float32)
+        self._check(self.lib.jp_render_variance(self.h, C.byref(params), film.ctypes.data_as(C.c_void_p) if want_film else None, var.ctypes.data_as(C.c_void_p)))
+        return film, var
+
+    def render_variance_device(self, params, film_ptr, variance_ptr, sync=False):
+        """jp_render_variance_device: device pointers, as render_device takes its film"""
+        self._check(self.lib.jp_render_variance_device(self.h, C.byref(params), C.c_void_p(film_ptr or None), C.c_void_p(variance_ptr or None), 1 if sync else 0))
+
+    def variance_probe(self, samples, batch_spp, f=None):
+        """jp_variance_probe: the device twin of variance_samples on (spp, n, 3) float32 samples, in batches of batch_spp -> (n,) float32"""
+        import numpy as np
+        a = np.ascontiguousarray(samples, np.float32)
+        spp, n = a.shape[:2]
+        var = np.zeros(n, np.float32)
+        self._check(self.lib.jp_variance_probe(self.h, _ptr(f), spp, batch_spp, n, a.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p)))
+        return var
+
+    def denoise_variance(self, film, albedo, normal, depth, variance, want_variance=True, **kw):
+        """jp_denoise_variance: the variance-guided a-trous filter on a (H, W, 3) film with its guides and its (H, W) variance plane ->
+        (the denoised (H, W, 3) film, the filtered variance (H, W) or None).  kw: the fields of denoise_params (0 = the library's default)"""
+        import numpy as np
+        h, w = film.shape[:2]
+        a = [None if x is None else np.ascontiguousarray(x, np.float32) for x in (film, albedo, normal, depth, variance)]
+        out = np.zeros((h, w, 3), np.float32); vout = np.zeros((h, w), np.float32) if want_variance else None
+        p = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        dp = denoise_params(w, h, **kw)
+        self._check(self.lib.jp_denoise_variance(self.h, C.byref(dp), p(a[0]), p(a[1]), p(a[2]), p(a[3]), p(a[4]), p(out), p(vout)))
+        return out, vout
+
+    def denoise_variance_device(self, width, height, film_ptr, albedo_ptr, normal_ptr, depth_ptr, variance_ptr, out_ptr, variance_out_ptr=None, sync=False, **kw):
+        """jp_denoise_variance_device: device pointers in the layouts the *_device renders write"""
+        dp = denoise_params(width, height, **kw)
+        v = lambda x: C.c_void_p(x or None)
+        self._check(self.lib.jp_denoise_variance_device(self.h, C.byref(dp), v(film_ptr), v(albedo_ptr), v(normal_ptr), v(depth_ptr), v(variance_ptr), v(out_ptr),
+                                                        v(variance_out_ptr), 1 if sync else 0))
+
+    def render_denoised_variance(self, params, guide_spp=8, denoise=True, want_bytes=True, **kw):
+        """jp_render_denoised_variance: the variance render, guides, the variance-guided filter (denoise False: guides only) and the bytes of render_rgb8 in
+        one call -> (film (H, W, 3), rgb8 (H, W, 3) or None, albedo, normal, depth, variance (H, W)).  kw: the fields of denoise_params"""
+        import numpy as np
+        h, w = params.height, params.width
+        f = np.zeros((h, w, 3), np.float32); b = np.zeros((h, w, 3), np.uint8) if want_bytes else None
+        alb = np.zeros((h, w, 3), np.float32); nrm = np.zeros((h, w, 3), np.float32); dep = np.zeros((h, w), np.float32); var = np.zeros((h, w), np.float32)
+        q = lambda x: None if x is None else x.ctypes.data_as(C.c_void_p)
+        dp = denoise_params(w, h, **kw) if denoise else None
+        self._check(self.lib.jp_render_denoised_variance(self.h, C.byref(params), guide_spp, _ptr(dp), q(f), q(b), q(alb), q(nrm), q(dep), q(var)))
+        return f, b, alb, nrm, dep, var
+
+    def variance_info(self):
+        i = JpVarianceInfo()
+        i.struct_bytes = C.sizeof(JpVarianceInfo)
+        self._check(self.lib.jp_get_variance_info(self.h, C.byref(i)))
+        return i
 
     def lens_info(self):
         i = JpLensInfo()

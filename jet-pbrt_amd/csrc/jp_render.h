@@ -51,10 +51,24 @@ void tonemap8(JpContext* c, const float* src, size_t n)
 }
 
 // k_resolve of one batch, for both schedules: the film instance while a film state is in force (jp_set_film), else the kernel that always ran
+// a variance render's per-frame state: the (zero) variance plane and the moments of this context's npix pixels (nothing while none runs)
+int variance_begin(JpContext* c, const JpRenderParams* rp, long long npix)
+{
+	if (!c->var_on) return JP_OK;
+	HIP_TRY(hipMemsetAsync(c->var_dev, 0, sizeof(float) * (size_t)rp->width * rp->height, c->stream));
+	return reserve_idle(c, c->var_mom, (size_t)std::max<long long>(npix, 1) * sizeof(float2));
+}
+
 void launch_resolve(JpContext* c, const Queues& q, const RenderConst& rc, long long npix, float4* pix_acc, float* film_dev, int first, int last)
 {
 	const dim3 grid((unsigned int)std::min<long long>(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK));
-	if (c->film_on) { hipLaunchKernelGGL(k_resolve_film, grid, dim3(JP_BLOCK), 0, c->stream, q, rc, pix_acc, film_dev, first, last, c->film_state.hdr, c->film_state.sample_clamp); c->last_hdr = 1; }
+	if (c->var_on)
+	{   // a variance render (jp_variance.h): the twin that also keeps the moments; without a film state it writes k_resolve's film (hdr 0, no clamp)
+		hipLaunchKernelGGL(k_resolve_var, grid, dim3(JP_BLOCK), 0, c->stream, q, rc, pix_acc, film_dev, c->var_mom.get<float2>(), c->var_dev, first, last,
+		                   c->film_on ? c->film_state.hdr : 0, c->film_on ? c->film_state.sample_clamp : 0.f);
+		if (c->film_on) c->last_hdr = 1;
+	}
+	else if (c->film_on) { hipLaunchKernelGGL(k_resolve_film, grid, dim3(JP_BLOCK), 0, c->stream, q, rc, pix_acc, film_dev, first, last, c->film_state.hdr, c->film_state.sample_clamp); c->last_hdr = 1; }
 	else hipLaunchKernelGGL(k_resolve, grid, dim3(JP_BLOCK), 0, c->stream, q, rc, pix_acc, film_dev, first, last);
 }
 
@@ -275,6 +289,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 	if (!ev0_recorded) HIP_TRY(hipEventRecord(c->ev0, c->stream));          // (with several lanes render_impl records it before the first lane is enqueued)
 	HIP_TRY(hipMemsetAsync(film_dev, 0, sizeof(float) * 3 * (size_t)rp->width * rp->height, c->stream));
 	HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(DevCounters), c->stream));
+	if (const int e = variance_begin(c, rp, npix); e != JP_OK) return e;
 	c->evused = 0; c->stamps.clear();
 	unsigned long long samples = 0;
 	if (npix > 0)
@@ -442,6 +457,7 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 	l->estimator = c->estimator;                                     // ... and the estimator (its side records are its own, like its queues)
 	l->lens = c->lens; l->lens_on = c->lens_on;                      // ... and the lens
 	l->film_state = c->film_state; l->film_on = c->film_on;          // ... and the film state (a lane resolves its own bands)
+	l->var_on = c->var_on;                                           // ... and whether it keeps the moments (render_impl gives it a variance plane of its own)
 }
 
 // ---- fused schedule: one k_path launch per batch (jp_path.h) --------------------------------------------------------------
@@ -493,6 +509,7 @@ int render_fused(JpContext* c, const JpRenderParams* rp, float* film_dev, bool s
 	HIP_TRY(hipEventRecord(c->ev0, c->stream));
 	HIP_TRY(hipMemsetAsync(film_dev, 0, sizeof(float) * 3 * (size_t)rp->width * rp->height, c->stream));
 	HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(DevCounters), c->stream));
+	if (const int e = variance_begin(c, rp, npix); e != JP_OK) return e;
 	c->evused = 0; c->stamps.clear();
 	unsigned long long samples = 0;
 	c->last_fused = 1; c->last_lanes = 1;
@@ -593,6 +610,8 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 {
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
 	c->last_hdr = 0;
+	c->last_var = c->var_on ? 1 : 0;
+	if (!c->var_on && (c->var_mom || (!c->lanes.empty() && c->lanes[0]->var_mom))) { c->var_mom.reset(); for (JpContext* l : c->lanes) l->var_mom.reset(); }   // (left by a variance render that did not wait for its stream)
 	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0; c->last_sampled = 0; c->last_mip = 0; c->last_proc = 0;
 	if (c->plan.mapped && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with normal maps, jp_set_normal_maps)");
 	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
@@ -651,6 +670,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 		sync_lane_scene(c, l);
 		if (l->film.bytes() < n * sizeof(float)) c->added_valid = false;
 		if (const int e = reserve_idle(c, l->film, n * sizeof(float)); e != JP_OK) return e;   // (waits for the PARENT's stream: its merge of the previous frame reads the lane film)
+		if (c->var_on) { if (const int e = reserve_idle(c, l->var_plane, n / 3 * sizeof(float)); e != JP_OK) return e; l->var_dev = l->var_plane.get<float>(); }   // (likewise the lane's variance plane)
 		if (c->added_valid) HIP_TRY(hipStreamWaitEvent(l->stream, c->ev_added, 0));   // the previous frame's merge still reads the lane film
 		l->blocks_per_cu = bpc_lane;
 		st = render_one(l, rp, l->film.get<float>(), false, k, L, group);
@@ -662,6 +682,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 		JpContext* l = c->lanes[k - 1];
 		HIP_TRY(hipStreamWaitEvent(c->stream, l->ev1, 0));                           // recorded at the end of the lane's render_one
 		hipLaunchKernelGGL(k_add_film, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, film_dev, l->film.get<const float>(), n);
+		if (c->var_on) hipLaunchKernelGGL(k_add_film, dim3((unsigned int)std::min<size_t>((size_t)c->n_cus * 8, (n / 3 + JP_BLOCK - 1) / JP_BLOCK)), dim3(JP_BLOCK), 0, c->stream, c->var_dev, l->var_plane.get<const float>(), n / 3);   // the variance planes are disjoint like the films
 	}
 	HIP_TRY(hipEventRecord(c->ev_added, c->stream)); c->added_valid = true;
 	HIP_TRY(hipEventRecord(c->ev1, c->stream));                                       // render_ms: all lanes and the merge

@@ -194,6 +194,13 @@ struct JpContext
 	JpToneMap tonemap = {}; bool tonemap_on = false; int last_tonemapped = 0; float last_scale = 0.f;
 	DevBuf film_hist, film_stage;
 	hipEvent_t fh_ev[2] = { nullptr, nullptr }, tm_ev[2] = { nullptr, nullptr }; bool fh_timed = false, tm_timed = false;
+	// variance (jp_variance.h): set for the length of a variance render (jp_render_variance*; a lane takes its parent's flag and gets a plane of its own) -- launch_resolve
+	// then picks k_resolve_var, which keeps (mean, m2) per pixel in var_mom across batches and writes var_dev; var_plane: the staging plane of the host variants / a lane's
+	// plane; the variance-guided filter's second normal + variance buffer (the first is dn_nr), its event pair and what the last calls did (jp_get_variance_info)
+	bool var_on = false; float* var_dev = nullptr; int last_var = 0; long long last_mom_bytes = 0;
+	DevBuf var_mom, var_plane, dn_nv;
+	hipEvent_t dv_ev[2] = { nullptr, nullptr }; bool dv_timed = false;
+	int last_dv = 0, last_dv_demod = 0; float last_dv_sigma[3] = { 0.f, 0.f, 0.f };
 };
 // jp_pick.h / jp_env.h (included last) define the upload's table steps
 static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area);
@@ -453,7 +460,7 @@ int jp_destroy_context(JpContext* c)
 	if (c->stream) hipStreamSynchronize(c->stream);
 	for (JpContext* l : c->lanes) jp_destroy_context(l);
 	c->lanes.clear();
-	for (hipEvent_t e : { c->ev_added, c->dn_ev[0], c->dn_ev[1], c->gd_ev[0], c->gd_ev[1], c->fh_ev[0], c->fh_ev[1], c->tm_ev[0], c->tm_ev[1], c->ev0, c->ev1 }) if (e) hipEventDestroy(e);
+	for (hipEvent_t e : { c->ev_added, c->dn_ev[0], c->dn_ev[1], c->gd_ev[0], c->gd_ev[1], c->fh_ev[0], c->fh_ev[1], c->tm_ev[0], c->tm_ev[1], c->dv_ev[0], c->dv_ev[1], c->ev0, c->ev1 }) if (e) hipEventDestroy(e);
 	for (hipEvent_t e : c->evpool) hipEventDestroy(e);
 	if (c->stream) hipStreamDestroy(c->stream);
 	delete c;                                                      // every DevBuf / PinnedBuf member frees its memory

@@ -384,6 +384,36 @@ int jp_host_render_denoised(void* h, int W, int H, int spp, int maxdepth, unsign
 	return JP_OK;
 }
 
+// FFilm::RequestVariance() (variance 1) and / or RequestGuides(guide_spp) (guide_spp > 0, denoise 0) / RequestDenoise(guide_spp, { varianceGuided }) (denoise 1) [+ SetHDR] -> Render -> the
+// film, the variance plane and the guides; any output may be null
+int jp_host_render_variance(void* h, int W, int H, int spp, int maxdepth, unsigned seed, int device, int variance, int guide_spp, int denoise, int hdr,
+                            float* film_out, float* variance_out, float* albedo_out, float* normal_out, float* depth_out)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!hs->integ || hs->integDepth != maxdepth) { hs->integ.reset(new FGpuPathIntegrator(maxdepth, device)); hs->integDepth = maxdepth; }
+	hs->integ->SetShard(0, 1);
+	FFilm film(W, H);
+	if (hdr) film.SetHDR();
+	if (variance) film.RequestVariance();
+	if (denoise) { FDenoiseOptions o; o.varianceGuided = true; film.RequestDenoise(guide_spp, o); } else if (guide_spp > 0) film.RequestGuides(guide_spp);
+	FCounterSampler sampler(spp, seed);
+	hs->integ->Render(hs->scene.get(), &sampler, &film, 16);
+	if (hs->integ->LastStatus() != JP_OK) return hs->integ->LastStatus();
+	const size_t n = (size_t)W * H;
+	const bool guides = denoise || guide_spp > 0;
+	if ((variance || denoise) && film.Variance().size() != n) return JP_ERR_DEVICE;
+	if (guides && (film.Albedo().size() != n || film.Normal().size() != n || film.Depth().size() != n)) return JP_ERR_DEVICE;
+	if (film_out) for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) { const FColor& c = static_cast<const FFilm&>(film)(x, y); float* o = film_out + 3 * ((size_t)y * W + x); o[0] = c.r; o[1] = c.g; o[2] = c.b; }
+	if (variance_out && film.Variance().size() == n) std::memcpy(variance_out, film.Variance().data(), n * sizeof(float));
+	for (size_t i = 0; guides && i < n; i++)
+	{
+		if (albedo_out) { albedo_out[3 * i] = film.Albedo()[i].r; albedo_out[3 * i + 1] = film.Albedo()[i].g; albedo_out[3 * i + 2] = film.Albedo()[i].b; }
+		if (normal_out) { normal_out[3 * i] = film.Normal()[i].x; normal_out[3 * i + 1] = film.Normal()[i].y; normal_out[3 * i + 2] = film.Normal()[i].z; }
+		if (depth_out) depth_out[i] = film.Depth()[i];
+	}
+	return JP_OK;
+}
+
 // The linear-light film: FFilm::SetHDR(hdr) / SetSampleClamp(sample_clamp) / SetToneMap(curve, auto_exposure, ev, white) when tonemap != 0 [+ RequestDeviceLDR(true) when
 // ldr_only] -> Render -> the fp32 film (unless ldr_only), the 8-bit pixels (with a tone map or ldr_only), FFilm::ToneMapScale() -> optionally SaveAsImage(filename, type).
 // Any output may be null.

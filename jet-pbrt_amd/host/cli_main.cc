@@ -1,6 +1,6 @@
 // jet-pbrt_amd/host/cli_main.cc -- the reference's command line (main.cc:113-163) on the GPU integrator:
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
-//             [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
+//             [--denoise [variance]] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
 //             [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]
 //             [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]
 //             [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]
@@ -32,6 +32,8 @@
 // --light-sampling power: one light per bounce, picked by power (FScene::SetLightSampling(JP_LIGHTS_POWER_ONE)); all (default): every light at every bounce.
 // --denoise: the edge-avoiding filter on the rendered film (FFilm::RequestDenoise); --guide-spp: camera samples per pixel of its guides (default 8,
 // 1 .. 1024); --aov: the guides as images PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5), PREFIX_depth (t / max t) in the chosen format.
+// --denoise variance: the variance-guided filter on a variance render instead (FDenoiseOptions::varianceGuided; needs spp >= 2); --aov then, and without --denoise
+// at spp >= 2, also writes PREFIX_variance (v / max v), the per-pixel variance of the film's mean luminance (FFilm::RequestVariance).
 // sceneid 0 = Cornell box, 1 = bunny scene; spp defaults to 50, the film to 1024 x 1024, the output to
 // <scene name>_<spp>.bmp, as in the reference.  The scene scripts are the calls of main.cc:13-111; the meshes are
 // read from DIR/cornellbox/{light,floor,shortbox,tallbox,left,right}.obj and DIR/bunny/bunny.obj (the reference
@@ -119,7 +121,7 @@ int main(int argc, char* argv[])
 {
 	int width = 1024, height = 1024, samples_per_pixel = 50;     // main.cc:115,119
 	std::string assets = "scene", out, format = "bmp", integratorName = "path";
-	bool denoise = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL, estimator = JP_ESTIMATOR_NEE;
+	bool denoise = false, denoiseVariance = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL, estimator = JP_ESTIMATOR_NEE;
 	std::string envmap; int envUp = JP_ENV_UP_Y; float envScale = 1.f;
 	FSmoothing smoothing;
 	std::string normalMap; float normalStrength = 1.f, normalFromHeight = 0.f; bool fromHeight = false;
@@ -129,7 +131,7 @@ int main(int argc, char* argv[])
 	int floorTexture = JP_PROC_NONE, floorOctaves = 0; float floorScale = 0.02f; bool floorAntialias = true, floorOptions = false;
 	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
-	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
+	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise [variance]] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
 	fprintf(stderr, "          [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]\n");
 	fprintf(stderr, "          [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]\n");
 	fprintf(stderr, "          [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]\n");
@@ -146,7 +148,7 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--integrator") && i + 1 < argc) integratorName = argv[++i];
 		else if (!strcmp(argv[i], "--reference-tree")) setenv("JETPBRT_REFERENCE_TREE", "1", 1);   // FScene::referenceTree: the reference's own BVH and traversal semantics
 		else if (!strcmp(argv[i], "--reference-tree=certified")) setenv("JETPBRT_REFERENCE_TREE", "2", 1);   // ... with the certified walk (FScene::certifiedWalk)
-		else if (!strcmp(argv[i], "--denoise")) denoise = true;
+		else if (!strcmp(argv[i], "--denoise")) { denoise = true; if (i + 1 < argc && !strcmp(argv[i + 1], "variance")) { denoiseVariance = true; i++; } }
 		else if (!strcmp(argv[i], "--guide-spp") && i + 1 < argc) { guideSpp = atoi(argv[++i]); if (guideSpp < 1 || guideSpp > 1024) { fprintf(stderr, "--guide-spp must be 1 .. 1024\n"); return 5; } }
 		else if (!strcmp(argv[i], "--aov") && i + 1 < argc) aov = argv[++i];
 		else if (!strcmp(argv[i], "--light-sampling") && i + 1 < argc)
@@ -326,7 +328,9 @@ int main(int argc, char* argv[])
 	if (hdr) film.SetHDR();
 	if (sampleClamp > 0.f) film.SetSampleClamp(sampleClamp);
 	if (haveToneMap) film.SetToneMap(toneMap);                    // (turns HDR on)
-	if (denoise) film.RequestDenoise(guideSpp); else if (!aov.empty()) film.RequestGuides(guideSpp);
+	if (denoiseVariance) { FDenoiseOptions o; o.varianceGuided = true; film.RequestDenoise(guideSpp, o); }
+	else if (denoise) film.RequestDenoise(guideSpp);
+	else if (!aov.empty()) { film.RequestGuides(guideSpp); if (samples_per_pixel >= 2) film.RequestVariance(); }
 	integrator->Render(scene.get(), sampler.get(), &film, 16);    // main.cc:156
 	if (integrator->LastStatus() != JP_OK) return 3;              // no GPU / no library: fail loudly, nothing is written
 	if (aperture > 0.f && scene->camera) fprintf(stderr, "lens: aperture %g, focus distance %g%s\n", aperture, scene->camera->LastFocus(), focusPixel ? " (found at the focus pixel)" : "");
@@ -348,6 +352,13 @@ int main(int argc, char* argv[])
 			const Float z = zmax > 0 ? film.Depth()[i] / zmax : 0; fz(x, y) = FColor(z, z, z);
 		}
 		if (!fa.SaveAsImage(aov + "_albedo", t) || !fn.SaveAsImage(aov + "_normal", t) || !fz.SaveAsImage(aov + "_depth", t)) return 4;
+		if (film.Variance().size() == n)
+		{   // the variance plane, v / max v
+			Float vmax = 0; for (Float v : film.Variance()) vmax = v > vmax ? v : vmax;
+			FFilm fv(width, height);
+			for (size_t i = 0; i < n; i++) { const Float v = vmax > 0 ? film.Variance()[i] / vmax : 0; fv((int)(i % width), (int)(i / width)) = FColor(v, v, v); }
+			if (!fv.SaveAsImage(aov + "_variance", t)) return 4;
+		}
 	}
 	return film.SaveAsImage(name, t) ? 0 : 4;                     // main.cc:160
 }

@@ -27,6 +27,8 @@ struct HipApi
 	int (*abi_version)() = nullptr;
 	int (*set_options)(JpContext*, const JpOptions*) = nullptr;
 	int (*upload_scene_textured)(JpContext*, const JpScene*, const JpTextures*) = nullptr;   // (looked up, needed by textured scenes only)
+	int (*render_variance)(JpContext*, const JpRenderParams*, float*, float*) = nullptr;                                                              // (FFilm::RequestVariance)
+	int (*render_denoised_variance)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*, float*) = nullptr;   // (... with guides, the variance-guided filter or 8-bit bytes)
 	int (*render_denoised)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*) = nullptr;   // (looked up, needed by FFilm::RequestGuides / RequestDenoise only)
 	int (*set_light_sampling)(JpContext*, const JpLightSampling*) = nullptr;                 // (looked up, needed by FScene::SetLightSampling only)
 	int (*set_environment_map)(JpContext*, const JpEnvMap*) = nullptr;                       // (looked up, needed by FScene::SetEnvironmentMap only)
@@ -68,6 +70,8 @@ HipApi& Api()
 		api.set_options = (int (*)(JpContext*, const JpOptions*))dlsym(api.lib, "jp_set_options");
 		api.upload_scene_textured = (int (*)(JpContext*, const JpScene*, const JpTextures*))dlsym(api.lib, "jp_upload_scene_textured");
 		api.render_denoised = (decltype(api.render_denoised))dlsym(api.lib, "jp_render_denoised");
+		api.render_variance = (decltype(api.render_variance))dlsym(api.lib, "jp_render_variance");
+		api.render_denoised_variance = (decltype(api.render_denoised_variance))dlsym(api.lib, "jp_render_denoised_variance");
 		api.set_light_sampling = (decltype(api.set_light_sampling))dlsym(api.lib, "jp_set_light_sampling");
 		api.set_environment_map = (decltype(api.set_environment_map))dlsym(api.lib, "jp_set_environment_map");
 		api.set_estimator = (decltype(api.set_estimator))dlsym(api.lib, "jp_set_estimator");
@@ -289,8 +293,30 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 	const bool floatFilm = !(film->wantLDR && film->ldrOnly);
 	std::vector<float> rgb(floatFilm ? (size_t)rp.width * rp.height * 3 : 0);
 	std::vector<uint8_t> ldr;
-	std::vector<float> galb, gnrm, gdep;
-	if (film->wantGuides)
+	std::vector<float> galb, gnrm, gdep, gvar;
+	const bool varFilter = film->wantDenoise && film->denoise.varianceGuided, wantVar = film->wantVariance || varFilter;
+	if (wantVar && film->wantDenoise && !varFilter)
+	{ fprintf(stderr, "FGpuPathIntegrator::Render: RequestVariance with RequestDenoise needs the variance-guided filter (FDenoiseOptions::varianceGuided)\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+	if (wantVar && (film->wantGuides || wantLDR))
+	{   // FFilm::RequestVariance / the variance-guided RequestDenoise: the variance render, guides, filter and tone map in one call (no guides asked for: one camera sample of them, dropped)
+		if (!api.render_denoised_variance) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_render_denoised_variance\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+		const size_t n = (size_t)rp.width * rp.height;
+		gvar.assign(n, 0.f);
+		if (film->wantGuides) { galb.assign(3 * n, 0.f); gnrm.assign(3 * n, 0.f); gdep.assign(n, 0.f); }
+		if (wantLDR) ldr.assign(3 * n, 0);
+		JpDenoiseParams dp; std::memset(&dp, 0, sizeof(dp));
+		dp.struct_bytes = (int32_t)sizeof(dp); dp.width = rp.width; dp.height = rp.height; dp.iterations = film->denoise.iterations;
+		dp.sigma_color = film->denoise.sigmaColor; dp.sigma_normal = film->denoise.sigmaNormal; dp.sigma_depth = film->denoise.sigmaDepth; dp.demodulate = film->denoise.demodulate ? 1 : -1;
+		lastStatus = api.render_denoised_variance(ctx, &rp, film->wantGuides ? film->guideSpp_ : 1, varFilter ? &dp : nullptr, floatFilm ? rgb.data() : nullptr, wantLDR ? ldr.data() : nullptr,
+		                                          film->wantGuides ? galb.data() : nullptr, film->wantGuides ? gnrm.data() : nullptr, film->wantGuides ? gdep.data() : nullptr, gvar.data());
+	}
+	else if (wantVar)
+	{
+		if (!api.render_variance) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_render_variance\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+		gvar.assign((size_t)rp.width * rp.height, 0.f);
+		lastStatus = api.render_variance(ctx, &rp, rgb.data(), gvar.data());
+	}
+	else if (film->wantGuides)
 	{   // FFilm::RequestGuides / RequestDenoise: render, guides, filter and tone map in one call -- the film stays on the device in between
 		if (!api.render_denoised) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_render_denoised\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
 		const size_t n = (size_t)rp.width * rp.height;
@@ -320,6 +346,7 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 		film->albedo.resize(n); film->normal.resize(n); film->depth.swap(gdep);
 		for (size_t i = 0; i < n; i++) { film->albedo[i] = FColor(galb[3 * i], galb[3 * i + 1], galb[3 * i + 2]); film->normal[i] = FVector3(gnrm[3 * i], gnrm[3 * i + 1], gnrm[3 * i + 2]); }
 	}
+	if (wantVar) film->variance.swap(gvar);
 	if (wantLDR) { film->ldr8.swap(ldr); film->floatValid = floatFilm; }   // (after AddColor: any later change of a pixel drops the bytes again)
 	if (film->haveToneMap)
 	{   // FFilm::ToneMapScale: the exposure scale the transform used

@@ -386,7 +386,8 @@ inline Float Clamp01(Float x) { return x < 0 ? 0 : (x > 1 ? 1 : x); }           
 inline uint8_t gamma_encoding(Float x) { return (uint8_t)(std::pow(Clamp01(x), (Float)(1 / 2.2)) * 255.0); }   // film.h:24
 
 // FFilm::RequestDenoise: the fields of JpDenoiseParams (0: the library's default; INTEGRATION.md "Guides and denoising")
-struct FDenoiseOptions { int iterations = 0; Float sigmaColor = 0, sigmaNormal = 0, sigmaDepth = 0; bool demodulate = true; };
+// varianceGuided: the variance-guided filter (jp_denoise_variance; INTEGRATION.md "Variance") on a variance render instead of jp_denoise on a plain one
+struct FDenoiseOptions { int iterations = 0; Float sigmaColor = 0, sigmaNormal = 0, sigmaDepth = 0; bool demodulate = true; bool varianceGuided = false; };
 // FFilm::SetToneMap: the fields of JpToneMap (curve: JP_CURVE_*; 0: the library's default; INTEGRATION.md "Film")
 struct FToneMap { int curve = JP_CURVE_CLAMP; bool autoExposure = false; Float ev = 0, key = 0, white = 0, pctLow = 0, pctHigh = 0; };
 
@@ -417,6 +418,11 @@ public:
 	const std::vector<FColor>& Albedo() const { return albedo; }
 	const std::vector<FVector3>& Normal() const { return normal; }
 	const std::vector<Float>& Depth() const { return depth; }
+	// Variance (INTEGRATION.md "Variance"): ask the integrator for the per-pixel variance of the film's mean luminance (jp_render_variance; needs spp >= 2): after
+	// Render Variance() holds the plane, row-major, top row first; the film is the one a plain Render delivers.  Together with RequestDenoise it needs the
+	// variance-guided filter (FDenoiseOptions::varianceGuided), which reads that plane; that filter asks for the variance render by itself.
+	void RequestVariance() { wantVariance = true; }
+	const std::vector<Float>& Variance() const { return variance; }
 	// The linear-light film (INTEGRATION.md "Film"): SetHDR keeps radiance above 1 (SaveAsImage(HDR) then writes the unclamped film, and a denoise request filters
 	// it unclamped), SetSampleClamp tames fireflies sample by sample, SetToneMap -- which turns HDR on: highlights above 1 are what the curves compress -- has the
 	// integrator deliver the 8-bit bytes of BMP / PPM through exposure and a tone curve on the GPU (next to the fp32 film, or instead of it with RequestDeviceLDR).
@@ -428,6 +434,7 @@ public:
 	bool hdr = false, haveToneMap = false; Float sampleClamp = 0, toneMapScale = 0; FToneMap toneMap;
 	bool wantGuides = false, wantDenoise = false; int guideSpp_ = 8; FDenoiseOptions denoise;
 	std::vector<FColor> albedo; std::vector<FVector3> normal; std::vector<Float> depth;
+	bool wantVariance = false; std::vector<Float> variance;
 	int width, height; std::vector<FColor> pixels;
 	bool wantLDR = false, ldrOnly = false; std::vector<uint8_t> ldr8;   // R G B per pixel, top row first
 	bool floatValid = true;                                            // false after an LDR-only render: the fp32 pixels were not downloaded
