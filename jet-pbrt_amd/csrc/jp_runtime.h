@@ -242,6 +242,9 @@ static void free_scene(JpContext* c)
 	c->plan.mp = NMapView(); c->plan.mapped = false; c->plan.nm_maps = c->plan.nm_mapped = 0; c->plan.nm_texel_bytes = c->plan.nm_table_bytes = 0;
 	c->plan.sm = SampView(); c->plan.ts_active_textures = c->plan.ts_active_maps = 0; c->plan.ts_table_bytes = 0;
 	c->plan.mv = MipView(); c->plan.mip_on = c->plan.mip_levels = 0; c->plan.mip_bytes = 0; c->mip_host_tex.clear(); c->mip_host_lev.clear(); c->mip_build_ms = 0.0; c->cone.reset();
+	// ... and the lanes' cone arrays: sync_lane_scene drops a lane's only when that lane renders again, so a scene rendered in fewer lanes than the one before it
+	// would keep -- and jp_get_texture_mipmap_info would report -- cones no render of it needs
+	for (JpContext* l : c->lanes) if (l->cone) { hipStreamSynchronize(l->stream); l->cone.reset(); }
 	c->plan.proc = ProcView(); c->plan.proc_on = c->plan.proc_aa = 0; c->plan.proc_bytes = 0;
 }
 

@@ -1,17 +1,22 @@
 // oracle/pt_features.cc -- TEST INFRASTRUCTURE ONLY (see pt_oracle.cc).  The second translation unit of libjp_oracle.so: the path integrator of pt_oracle.cc with the
 // features the library added on top of the reference -- light selection, environment maps, the MIS estimator, vertex normals, textures, texture sampling records,
-// normal maps, the lens and the film state -- restated from their written definitions (INTEGRATION.md sections 7 and 9 - 16), one path at a time.  The reference has
+// normal maps, the lens, the film state, the ray cone with mip-mapped and procedural textures -- restated from their written definitions (INTEGRATION.md sections 7,
+// 9 - 16, 18 and 19), one path at a time.  The reference has
 // none of these features; nothing here follows reference code that pt_oracle.cc does not already restate.
 //
 // What is shared and what is restated:
 //   - the restated reference functions of pt_oracle.cc (shapes, tree, BSDFs, sample_li, occluded, the sampler) are used as they are: this file includes that one
 //     with its entry points compiled out, so there is one text of them and no symbol is defined twice;
-//   - the definition headers under include/ that the device kernels compile too (jp_normals.h, jp_normal_map.h, jp_tex_sampling.h, jp_lens.h, jp_film.h) are
-//     included: each has a Python restatement and host tests of its own;
+//   - the definition headers under include/ that the device kernels compile too (jp_normals.h, jp_normal_map.h, jp_tex_sampling.h, jp_lens.h, jp_film.h, and of
+//     jp_mipmap.h and jp_procedural.h the lookups: jp_mip_lookup_above with its level and fraction, jp_proc_lookup) are included: each has a Python restatement
+//     and host tests of its own;
+//   - the pyramids arrive as data from jp_build_mip_chain, like the tables;
 //   - the tables (light table, map tables) arrive as data from jp_build_light_table / jp_build_environment_table, which have tests of their own;
 //   - everything else -- which draw feeds which decision, the pick, the map lookup and its five-draw sample, the strategy pdfs, the power heuristic and where it
 //     applies, the carried record behind null-material primitives, which normal enters which product, the geometric-side guard, the uv of each shape, the
-//     texture lookups -- is written here from the document.
+//     texture lookups; the path's cone (gamma0, the reset at bounce 0, the step at every hit, which flag and which bounce number a segment carries), the footprint
+//     area of each shape and rho with their guards, which lookup a footprint selects, the identity record above level 0, a record's resolved form (defaults, norm,
+//     s, antialias off), its precedence on a checker texture and the colour its side word stands for -- is written here from the document.
 // Same build as pt_oracle.cc: baseline x86-64, -O2, no contraction.
 #define JP_ORACLE_NO_ENTRY_POINTS
 #include "pt_oracle.cc"
@@ -21,6 +26,8 @@
 #include "jp_tex_sampling.h"
 #include "jp_lens.h"
 #include "jp_film.h"
+#include "jp_mipmap.h"
+#include "jp_procedural.h"
 
 namespace {
 
@@ -54,6 +61,28 @@ inline Image load_rgb8(const uint8_t* base, int64_t off, int w, int h)
 	return im;
 }
 
+// a pyramid as include/jp_mipmap.h's lookup addresses it: every level in one dword pool, level 0 first
+struct Pyramid { std::vector<unsigned int> px; std::vector<JpMipLevel> lev; };
+
+// section 19, the record as the lookup reads it: octaves 0 -> 6 (NOISE: 1), gain 0 -> 0.5, variation 0 -> 1; norm = 1 / sum of gain^i over the record's octaves, fp32
+// in octave order; s = the square root of the largest squared column norm of M's linear part, 0 with antialias off
+inline JpProcDev resolve_record(const JpProcedural& r)
+{
+	JpProcDev d;
+	d.kind = r.kind; d.space = r.space; d.pad = 0;
+	d.octaves = r.kind == JP_PROC_NOISE ? 1 : (r.octaves == 0 ? 6 : r.octaves);
+	for (int k = 0; k < 12; k++) d.m[k] = r.m[k];
+	d.gain = r.gain == 0.f ? 0.5f : r.gain;
+	d.variation = r.variation == 0.f ? 1.f : r.variation;
+	float sum = 0.f, amp = 1.f;
+	for (int i = 0; i < d.octaves; i++) { sum = sum + amp; amp = amp * d.gain; }
+	d.norm = 1.f / sum;
+	float best = 0.f;
+	for (int c = 0; c < 3; c++) { const float n2 = (r.m[c] * r.m[c] + r.m[4 + c] * r.m[4 + c]) + r.m[8 + c] * r.m[8 + c]; if (n2 > best) best = n2; }
+	d.s = r.antialias < 0 ? 0.f : std::sqrt(best);
+	return d;
+}
+
 struct FState
 {
 	JpOracleFeatures f;
@@ -63,6 +92,11 @@ struct FState
 	std::vector<char> tri_smooth;
 	bool lens_on; JpLensPlan lens;
 	bool film_on;
+	// sections 18, 19
+	std::vector<Pyramid> pyr;                 // per texture; no levels: no pyramid
+	std::vector<JpProcDev> proc;              // per texture; kind JP_PROC_NONE: no record
+	bool cone;                                // the paths carry a cone: a pyramid or an antialiased record exists
+	float gamma0, bounce_spread, footprint_scale;
 	const JpTexSampler* tex_rec(int t) const
 	{
 		if (!f.sampling || !f.sampling->tex || t >= f.sampling->n_textures) return nullptr;
@@ -118,11 +152,69 @@ int prepare(const JpScene* js, const JpOracleFeatures* in, FState& fs)
 	}
 	fs.film_on = f.film && (f.film->hdr != 0 || f.film->sample_clamp != 0.f);
 	if (fs.film_on && jp_film_check(f.film) != 0) return JP_ERR_INVALID_ARGUMENT;
+	// sections 18, 19.  A pyramid exists for a texture whose mode is TRILINEAR and that a material uses; a record counts where a material uses its texture.
+	const JpTextures* T = (f.textures && f.textures->n_textures > 0) ? f.textures : nullptr;
+	const int nt = T ? T->n_textures : 0;
+	std::vector<char> used((size_t)nt, 0);
+	if (T) for (int m = 0; m < T->n_materials; m++) { const int k = T->mat_texture[m]; if (k >= 0 && k < nt) used[k] = 1; }
+	fs.pyr.assign((size_t)nt, Pyramid());
+	JpProcDev none; std::memset(&none, 0, sizeof(none));
+	fs.proc.assign((size_t)nt, none);
+	bool any_pyramid = false, any_antialiased = false;
+	if (f.mipmaps)
+	{
+		const JpTextureMipmaps* M = f.mipmaps;
+		int bad, n_on;
+		if (jp_mipmaps_check(M, &bad, &n_on) != 0 || M->n_textures != nt) return JP_ERR_INVALID_ARGUMENT;
+		for (int t = 0; M->mode && t < nt; t++)
+		{
+			if (M->mode[t] != JP_MIP_TRILINEAR) continue;
+			if (T->tex_type[t] != JP_TEXTURE_IMAGE) return JP_ERR_INVALID_ARGUMENT;          // mipmaps on a solid or checker texture: refused at the upload
+			if (!used[t]) continue;
+			if (!f.mip_chains || t >= f.n_mip_chains) return JP_ERR_INVALID_ARGUMENT;
+			const JpOracleMipChain& c = f.mip_chains[t];
+			int w = T->tex_width[t], h = T->tex_height[t], levels = 1;
+			for (int m = w > h ? w : h; m > 1; m >>= 1) levels++;                              // L = 1 + floor(log2(max(w, h)))
+			if (c.n_levels != levels || !c.level_w || !c.level_h || !c.rgb8) return JP_ERR_INVALID_ARGUMENT;
+			Pyramid& P = fs.pyr[t];
+			size_t at = 0;
+			for (int k = 0; k < levels; k++)
+			{
+				if (c.level_w[k] != w || c.level_h[k] != h) return JP_ERR_INVALID_ARGUMENT;      // level k + 1: max(1, w_k >> 1) x max(1, h_k >> 1)
+				const JpMipLevel l = { w, h, (int32_t)at, 0 }; P.lev.push_back(l);
+				at += (size_t)w * h; w = std::max(1, w >> 1); h = std::max(1, h >> 1);
+			}
+			P.px = load_rgb8(c.rgb8, 0, (int)at, 1).px;
+			for (size_t k = 0; k < (size_t)T->tex_width[t] * T->tex_height[t]; k++) if (P.px[k] != fs.tex_img[t].px[k]) return JP_ERR_INVALID_ARGUMENT;   // level 0 is the image
+			any_pyramid = true;
+		}
+	}
+	if (f.procedurals && f.procedurals->rec)
+	{
+		if (f.procedurals->n_textures != nt) return JP_ERR_INVALID_ARGUMENT;
+		for (int t = 0; t < nt; t++)
+		{
+			const JpProcedural& r = f.procedurals->rec[t];
+			if (jp_procedural_check(&r) != 0) return JP_ERR_INVALID_ARGUMENT;
+			if (r.kind == JP_PROC_NONE) continue;
+			if (T->tex_type[t] != JP_TEXTURE_CHECKER) return JP_ERR_INVALID_ARGUMENT;
+			for (int k = 0; k < 6; k++) { const float c = T->tex_color[6 * (size_t)t + k]; if (!(c >= 0.f && c <= 1.f)) return JP_ERR_INVALID_ARGUMENT; }
+			if (r.space == JP_PROC_SPACE_UV && T->n_triangles > 0 && !T->tri_uv) return JP_ERR_INVALID_ARGUMENT;
+			if (!used[t]) continue;
+			fs.proc[t] = resolve_record(r);
+			if (r.antialias >= 0) any_antialiased = true;
+		}
+	}
+	fs.cone = any_pyramid || any_antialiased;
+	fs.footprint_scale = (f.mipmaps && f.mipmaps->footprint_scale != 0.f) ? f.mipmaps->footprint_scale : 1.f;
+	fs.bounce_spread = (f.mipmaps && f.mipmaps->bounce_spread != 0.f) ? f.mipmaps->bounce_spread : 0.125f;
+	const float* up = js->camera.up;
+	fs.gamma0 = 2.f * std::sqrt((up[0] * up[0] + up[1] * up[1]) + up[2] * up[2]) / js->camera.res_y;
 	return JP_OK;
 }
 
 // what a path reports besides its radiance
-struct PathOut { bool undecided; bool log; };
+struct PathOut { bool undecided; bool log; JpOracleBranchStats* stats; };
 #define PLOG(po, ...) do { if ((po).log) std::printf(__VA_ARGS__); } while (0)
 
 // ---------------------------------------------------------------------------------------------
@@ -307,8 +399,78 @@ inline void shape_uv(const Scene& sc, int prim, V3 p, const float* tri_uv, float
 	}
 }
 
-// the colour of the textured slot at the hit; false: the material carries no texture
-inline bool textured_color(const FState& fs, const Scene& sc, const Isect& is, V3& kd, PathOut& po)
+// ---------------------------------------------------------------------------------------------
+// section 18: the cone of a path, the footprint of the cone at a hit
+// ---------------------------------------------------------------------------------------------
+struct Cone { float width, spread; };
+
+// the step at a hit at distance t of the segment the path is on: `bounce` is the number of scattering events behind the segment (a null-material primitive
+// does not count), `specular` the flag of the BSDF sample that made the last of them
+inline void cone_step(const FState& fs, int bounce, bool specular, float t, Cone& c)
+{
+	if (bounce == 0) { c.spread = fs.gamma0; c.width = c.spread * t; return; }      // whatever the cone held: after a null-material primitive at bounce 0 it starts again
+	if (!specular) c.spread = c.spread > fs.bounce_spread ? c.spread : fs.bounce_spread;
+	c.width = c.width + c.spread * t;
+}
+
+inline float cross_len(V3 a, V3 b)
+{
+	const float x = a.y * b.z - a.z * b.y, y = a.z * b.x - a.x * b.z, z = a.x * b.y - a.y * b.x;
+	return std::sqrt((x * x + y * y) + z * z);
+}
+// A = |dpdu x dpdv|, the world area per unit of uv area at p; 0: none (a triangle without a uv set or with a degenerate one, a pole, a disk's centre)
+inline float footprint_area(const Scene& sc, int prim, V3 p, const float* tri_uv)
+{
+	const JpScene* js = sc.js;
+	const int type = js->prim_shape_type[prim], i = js->prim_shape_index[prim];
+	if (type == JP_SHAPE_TRIANGLE)
+	{
+		if (!tri_uv) return 0.f;
+		const Tri& T = sc.tris[i];
+		const float* t = tri_uv + 6 * (size_t)i;
+		const float du1 = t[2] - t[0], dv1 = t[3] - t[1], du2 = t[4] - t[0], dv2 = t[5] - t[1];
+		const float det = du1 * dv2 - dv1 * du2;
+		if (det == 0.f || !(det - det == 0.f)) return 0.f;
+		return cross_len(T.p1 - T.p0, T.p2 - T.p0) / std::fabs(det);
+	}
+	if (type == JP_SHAPE_RECTANGLE) { const Rect& R = sc.rects[i]; return cross_len(R.p1 - R.p0, R.p3 - R.p0); }
+	if (type == JP_SHAPE_DISK) { const Disk& D = sc.disks[i]; const V3 v = p - D.c; return (6.2831855f * D.r) * std::sqrt((v.x * v.x + v.y * v.y) + v.z * v.z); }
+	const Sph& S = sc.sphs[i];
+	const V3 d = p - S.c;
+	return (19.739209f * S.r) * std::sqrt(d.x * d.x + d.z * d.z);                   // 2 pi^2 r sqrt(d.x^2 + d.z^2)
+}
+// rho in texels of level 0; su, sv: the active record's uv scale, 1 without one
+inline float footprint_rho(float width, float A, int w, int h, float su, float sv, float footprint_scale)
+{
+	if (!(A > 0.f) || !(A - A == 0.f)) return 0.f;
+	const float rho = width * std::sqrt((((float)w * su) * ((float)h * sv)) / A) * footprint_scale;
+	return rho - rho == 0.f ? rho : 0.f;
+}
+
+// section 19: which octaves a lookup of footprint fw evaluates (k_i = fw 2^i; a_i = 1 for k_i <= 0.25, 0 for k_i >= 0.5, else (0.5 - k_i) 4) -- for the branch
+// statistics and the debug print; the value itself is jp_proc_lookup's
+inline void octave_classes(float fw, int octaves, bool& all_one, bool& partial, bool& early, PathOut& po)
+{
+	all_one = true; partial = early = false;
+	float k = fw;
+	for (int i = 0; i < octaves; i++)
+	{
+		const float a = k <= 0.25f ? 1.f : (k >= 0.5f ? 0.f : (0.5f - k) * 4.f);
+		PLOG(po, " a_%d = %.9g", i, a);
+		if (a == 0.f) { early = true; all_one = false; break; }
+		if (a < 1.f) { partial = true; all_one = false; }
+		k = k * 2.f;
+	}
+}
+
+inline V3 word_rgb(unsigned int w)
+{
+	const float s = 1.0f / 255.0f;
+	return mk(s * (float)(w & 0xffu), s * (float)((w >> 8) & 0xffu), s * (float)((w >> 16) & 0xffu));
+}
+
+// the colour of the textured slot at the hit; false: the material carries no texture.  width: the cone's width at the hit (0: the paths carry none); bounce: of the segment
+inline bool textured_color(const FState& fs, const Scene& sc, const Isect& is, float width, int bounce, V3& kd, PathOut& po)
 {
 	const JpTextures* T = fs.f.textures;
 	if (!T || T->n_textures <= 0) return false;
@@ -317,7 +479,39 @@ inline bool textured_color(const FState& fs, const Scene& sc, const Isect& is, V
 	const int t = T->mat_texture[mat];
 	if (t < 0) return false;
 	const float* col = T->tex_color + 6 * (size_t)t;
+	const int b1 = bounce > 0 ? 1 : 0;
 	if (T->tex_type[t] == JP_TEXTURE_SOLID) { kd = ld3(col); return true; }
+	if (T->tex_type[t] == JP_TEXTURE_CHECKER && fs.proc[t].kind != JP_PROC_NONE)
+	{   // section 19: a record takes the plain checker's place, between its two colours
+		const JpProcDev& r = fs.proc[t];
+		float u = 0.f, v = 0.f; bool libm = false;
+		if (r.space == JP_PROC_SPACE_UV) shape_uv(sc, is.prim, is.p, T->tri_uv, u, v, libm);
+		if (libm) { po.undecided = true; PLOG(po, "      [undecided: a uv-space procedural on a sphere or disk uv]\n"); }   // every coordinate matters
+		const float pp[3] = { is.p.x, is.p.y, is.p.z }, c_odd[3] = { col[0], col[1], col[2] }, c_even[3] = { col[3], col[4], col[5] };
+		float tt;
+		const unsigned int w = jp_proc_lookup(&r, c_even, c_odd, t, pp, u, v, width, &tt);
+		float fw = width * r.s; if (!(fw > 0.f)) fw = 0.f;
+		PLOG(po, "    procedural kind %d on texture %d: width %.9g, fw %.9g, t %.9g, word %08x;", r.kind, t, width, fw, tt, w);
+		if (r.kind == JP_PROC_CHECKER_AA)
+		{
+			const bool plain = (w & JP_PROC_TAG_COLOR) != 0 && (w & JP_PROC_TAG_IMAGE) == 0;
+			float q[3]; jp_proc_point(&r, pp, u, v, q);
+			const bool half = !plain && (!jp_proc_in_range(q[0]) || !jp_proc_in_range(q[1]) || !jp_proc_in_range(q[2]) || !(fw * JP_PROC_10_OVER_PI < JP_PROC_CHECKER_MAX));
+			PLOG(po, " fy %.9g: %s\n", fw * JP_PROC_10_OVER_PI, plain ? "the plain checker's word" : (half ? "exactly 0.5" : "filtered"));
+			if (po.stats) { if (plain) po.stats->checker_plain[b1]++; else if (half) po.stats->checker_half[b1]++; else po.stats->checker_filtered[b1]++; }
+		}
+		else
+		{
+			bool all_one, partial, early; octave_classes(fw, r.octaves, all_one, partial, early, po);
+			PLOG(po, "\n");
+			if (po.stats) { if (all_one) po.stats->proc_all_one[r.kind][b1]++; if (partial) po.stats->proc_partial[r.kind][b1]++; if (early) po.stats->proc_early[r.kind][b1]++; }
+		}
+		if (po.stats) po.stats->word_sum[b1] += w;
+		// the word: the colour's RGB8 under the image tag, or -- the plain checker's own word -- an entry of the colour table, 2 texture + parity: odd [0..2], even [3..5]
+		if (w & JP_PROC_TAG_IMAGE) kd = word_rgb(w);
+		else kd = ((w & 0x3fffffffu) - 2u * (unsigned int)t) == 0u ? ld3(col) : ld3(col + 3);
+		return true;
+	}
 	if (T->tex_type[t] == JP_TEXTURE_CHECKER)
 	{
 		const float sx = std::sin(10 * is.p.x), sy = std::sin(10 * is.p.y), sz = std::sin(10 * is.p.z);
@@ -327,7 +521,27 @@ inline bool textured_color(const FState& fs, const Scene& sc, const Isect& is, V
 	const Image& im = fs.tex_img[t];
 	float u, v; bool libm; shape_uv(sc, is.prim, is.p, T->tri_uv, u, v, libm);
 	unsigned int w;
-	if (const JpTexSampler* rec = fs.tex_rec(t))
+	const JpTexSampler* rec = fs.tex_rec(t);
+	const Pyramid& P = fs.pyr[t];
+	float rho = 0.f;
+	if (!P.lev.empty())
+	{   // section 18: the footprint in texels; above one texel the trilinear lookup, else the lookup the texture has without mipmaps
+		const float A = footprint_area(sc, is.prim, is.p, T->tri_uv);
+		rho = footprint_rho(width, A, im.w, im.h, rec ? rec->scale_u : 1.f, rec ? rec->scale_v : 1.f, fs.footprint_scale);
+		PLOG(po, "    mip on texture %d: width %.9g, A %.9g, rho %.9g", t, width, A, rho);
+		if (po.stats) { if (rho == 0.f) po.stats->mip_rho_zero[b1]++; else if (rho <= 1.f) po.stats->mip_rho_le1[b1]++; }
+	}
+	if (rho > 1.f)
+	{
+		const int levels = (int)P.lev.size();
+		const int l = jp_mip_level_of(rho);
+		const JpTexSampler ident = jp_mip_identity_sampler();                  // a texture without an active record is addressed through the identity record here
+		w = jp_mip_lookup_above(rec ? rec : &ident, P.px.data(), P.lev.data(), levels, u, v, rho);
+		if (l >= levels - 1) { PLOG(po, ", l %d: level %d alone", l, levels - 1); if (po.stats) po.stats->mip_last_level[b1]++; }
+		else { PLOG(po, ", l %d, f %.9g", l, jp_mip_fraction(rho, l)); if (po.stats) po.stats->mip_two_level[b1][l < 15 ? l : 15]++; }
+		if (libm) { po.undecided = true; PLOG(po, " [undecided: a trilinear lookup on a sphere or disk uv]"); }   // bilinear weights on two levels: every coordinate matters
+	}
+	else if (rec)
 	{
 		w = jp_tex_lookup_sampled(rec, im.px.data(), im.w, im.h, u, v);
 		if (libm) { po.undecided = true; PLOG(po, "      [undecided: a texture under a sampling record on a sphere or disk uv]\n"); }   // wraps and bilinear weights: every coordinate matters
@@ -343,8 +557,8 @@ inline bool textured_color(const FState& fs, const Scene& sc, const Isect& is, V
 		w = im.px[(size_t)j * im.w + i];
 		if (libm && (near_border(fi, im.w) || near_border(fj, im.h))) { po.undecided = true; PLOG(po, "      [undecided image lookup: texel coordinates %.9g, %.9g]\n", fi, fj); }
 	}
-	const float s = 1.0f / 255.0f;
-	kd = mk(s * (float)(w & 0xffu), s * (float)((w >> 8) & 0xffu), s * (float)((w >> 16) & 0xffu));
+	if (!P.lev.empty()) { PLOG(po, ", texel %06x\n", w & 0xffffffu); if (po.stats) po.stats->word_sum[b1] += w & 0xffffffu; }
+	kd = word_rgb(w);
 	return true;
 }
 
@@ -441,6 +655,7 @@ V3 LiFeatures(const FState& fs, const Scene& sc, const Ray& inRay, Draw& rnd, in
 	V3 L = mk(0, 0, 0), beta = mk(1, 1, 1);
 	Ray ray = inRay;
 	bool specular = false;
+	Cone cone = { 0.f, 0.f };                         // section 18
 	float carried_pdf = 0.f, carried_dist = 0.f;      // section 11 "Carried state": the pdf the BSDF sample that produced the ray was drawn with, the distance since that shading point
 	for (int bounces = 0;; ++bounces)
 	{
@@ -495,10 +710,15 @@ V3 LiFeatures(const FState& fs, const Scene& sc, const Ray& inRay, Draw& rnd, in
 				PLOG(po, "    miss, environment light %d: a = %.9g, b = %.9g, weight %.9g -> L (%.9g %.9g %.9g)\n", l2, a, carried_pdf, w, L.x, L.y, L.z);
 			}
 		}
+		if (found)
+		{   // section 18: the cone is stepped at every hit -- textured, untextured or without a material -- with the flag of the BSDF sample that made the segment
+			cone_step(fs, bounces, specular, t_hit, cone);
+			if (fs.cone) PLOG(po, "    cone: width %.9g, spread %.9g\n", cone.width, cone.spread);
+		}
 		if (!found || bounces >= maxDepth) break;
 		const int mat = js->prim_material[is.prim];
 		if (mat < 0)
-		{   // null material: the path passes through, same bounce, the carried record goes along
+		{   // null material: the path passes through, same bounce (and the same specular flag), the carried record goes along
 			carried_dist = carried_dist + t_hit;
 			ray = mkray(is.p, ray.d);
 			--bounces;
@@ -513,7 +733,7 @@ V3 LiFeatures(const FState& fs, const Scene& sc, const Ray& inRay, Draw& rnd, in
 		Closure c;
 		V3 kd;
 		const unsigned dim0 = rnd.s ? rnd.s->dim : 0u;
-		if (textured_color(fs, sc, is, kd, po)) { PLOG(po, "    texture colour (%.9g %.9g %.9g)\n", kd.x, kd.y, kd.z); scattering_textured(js, mat, Ns, kd, rnd, c); }
+		if (textured_color(fs, sc, is, fs.cone ? cone.width : 0.f, bounces, kd, po)) { PLOG(po, "    texture colour (%.9g %.9g %.9g)\n", kd.x, kd.y, kd.z); scattering_textured(js, mat, Ns, kd, rnd, c); }
 		else scattering(js, mat, Ns, rnd, c);
 		PLOG(po, "    material %d (type %d), closure kind %d, draws from dim %u\n", mat, js->mat_type[mat], c.kind, dim0);
 		if (!c.delta())
@@ -600,13 +820,13 @@ inline V3 sample_radiance(const FState& fs, const Scene& sc, const JpRenderParam
 	return l;
 }
 
-void render_rows_features(const FState& fs, const Scene& sc, const JpRenderParams& rp, Sampler& smp, int y0, int y1, float* film, uint8_t* undecided, Counts& cn)
+void render_rows_features(const FState& fs, const Scene& sc, const JpRenderParams& rp, Sampler& smp, int y0, int y1, float* film, uint8_t* undecided, Counts& cn, JpOracleBranchStats* stats)
 {
 	const float ratio = (float)1 / rp.spp;
 	for (int y = y0; y < y1; y++) for (int x = 0; x < rp.width; x++)
 	{
 		V3 L = mk(0, 0, 0);
-		PathOut po = { false, false };
+		PathOut po = { false, false, stats };
 		smp.start_pixel();
 		do
 		{
@@ -636,6 +856,12 @@ extern "C" {
 
 int jp_oracle_render_features(const JpScene* js, const JpRenderParams* rp, const JpOracleFeatures* feat, int nthreads, float* film, JpCounters* out, uint8_t* undecided)
 {
+	return jp_oracle_render_features_stats(js, rp, feat, nthreads, film, out, undecided, nullptr);
+}
+
+int jp_oracle_render_features_stats(const JpScene* js, const JpRenderParams* rp, const JpOracleFeatures* feat, int nthreads, float* film, JpCounters* out, uint8_t* undecided,
+                                    JpOracleBranchStats* stats)
+{
 	if (!js || !rp || !film) return JP_ERR_INVALID_ARGUMENT;
 	FState fs;
 	if (const int st = prepare(js, feat, fs); st != JP_OK) return st;
@@ -649,16 +875,18 @@ int jp_oracle_render_features(const JpScene* js, const JpRenderParams* rp, const
 	const int rows = rp->band_rows > 0 ? rp->band_rows : 20;
 	const int nbands = (H + rows - 1) / rows;
 	unsigned long long bands_done = 0;
+	JpOracleBranchStats sum; std::memset(&sum, 0, sizeof(sum));
 	if (nthreads < 1)
 	{
 		Sampler smp(rp->sampler_mode, rp->seed, rp->spp);
-		render_rows_features(fs, sc, *rp, smp, 0, H, film, undecided, total);
+		render_rows_features(fs, sc, *rp, smp, 0, H, film, undecided, total, stats ? &sum : nullptr);
 		bands_done = (unsigned long long)H;
 	}
 	else
 	{
 		std::atomic<int> next(0);
 		std::vector<Counts> per(nthreads, total);
+		std::vector<JpOracleBranchStats> per_stats(nthreads, sum);
 		std::vector<unsigned long long> rows_done(nthreads, 0);
 		std::vector<std::thread> pool;
 		for (int t = 0; t < nthreads; t++) pool.push_back(std::thread([&, t]() {
@@ -669,14 +897,25 @@ int jp_oracle_render_features(const JpScene* js, const JpRenderParams* rp, const
 				if (rp->shard_count > 1 && (b % rp->shard_count) != rp->shard_index) continue;
 				Sampler smp(rp->sampler_mode, rp->seed, rp->spp);
 				int y0 = b * rows, y1 = y0 + rows; if (y1 > H) y1 = H;
-				render_rows_features(fs, sc, *rp, smp, y0, y1, film, undecided, per[t]);
+				render_rows_features(fs, sc, *rp, smp, y0, y1, film, undecided, per[t], stats ? &per_stats[t] : nullptr);
 				rows_done[t] += (unsigned long long)(y1 - y0);
 			}
 		}));
 		for (size_t t = 0; t < pool.size(); t++) pool[t].join();
 		for (int t = 0; t < nthreads; t++) { total.closest += per[t].closest; total.closest_hit += per[t].closest_hit; total.shadow += per[t].shadow; total.shadow_occ += per[t].shadow_occ; bands_done += rows_done[t]; }
+		for (int t = 0; t < nthreads; t++)
+		{   // every field after the header is a uint64_t count
+			const uint64_t* a = per_stats[t].mip_rho_zero; uint64_t* b = sum.mip_rho_zero;
+			for (size_t k = 0; k < (sizeof(sum) - offsetof(JpOracleBranchStats, mip_rho_zero)) / sizeof(uint64_t); k++) b[k] += a[k];
+		}
 	}
 	g_watertight = false;
+	if (stats)
+	{
+		const int32_t n = std::min((size_t)stats->struct_bytes, sizeof(sum));
+		sum.struct_bytes = n; sum.pad = 0;
+		if (n >= (int32_t)sizeof(int32_t)) std::memcpy(stats, &sum, (size_t)n);
+	}
 	if (out)
 	{
 		std::memset(out, 0, sizeof(*out));
@@ -698,7 +937,7 @@ int jp_oracle_path_features(const JpScene* js, const JpRenderParams* rp, const J
 	Sampler smp(rp->sampler_mode, rp->seed, rp->spp);
 	smp.start_pixel(); smp.sample_index = s;
 	Counts cn = { 0, 0, 0, 0 };
-	PathOut po = { false, true };
+	PathOut po = { false, true, nullptr };
 	std::printf("pixel (%d, %d) sample %d\n", x, y, s);
 	const V3 l = sample_radiance(fs, sc, *rp, smp, x, y, cn, po);
 	std::printf("  radiance (%.9g %.9g %.9g)%s; closest rays %llu, hits %llu, shadow rays %llu, occluded %llu\n", l.x, l.y, l.z, po.undecided ? " [undecided]" : "",

@@ -45,9 +45,28 @@ def oracle_lib():
         L.jp_oracle_stock_stream.argtypes = [C.c_int, _vp]
         L.jp_oracle_bsdf_direct.argtypes = [C.POINTER(jp.JpBsdfDesc), C.c_int] + [_vp] * 10
         L.jp_oracle_render_features.argtypes = [C.POINTER(jp.JpScene), C.POINTER(jp.JpRenderParams), C.POINTER(JpOracleFeatures), C.c_int, _vp, C.POINTER(jp.JpCounters), _vp]
+        L.jp_oracle_render_features_stats.argtypes = L.jp_oracle_render_features.argtypes + [C.POINTER(JpOracleBranchStats)]
         L.jp_oracle_path_features.argtypes = [C.POINTER(jp.JpScene), C.POINTER(jp.JpRenderParams), C.POINTER(JpOracleFeatures), C.c_int, C.c_int, C.c_int, _vp]
         _oracle = L
     return _oracle
+
+
+class JpOracleMipChain(C.Structure):
+    """oracle/pt_features.h: the pyramid of one image as jp_build_mip_chain returns it"""
+    _fields_ = [("n_levels", C.c_int32), ("pad", C.c_int32), ("level_w", C.POINTER(C.c_int32)), ("level_h", C.POINTER(C.c_int32)), ("rgb8", C.POINTER(C.c_uint8))]
+
+
+class JpOracleBranchStats(C.Structure):
+    """oracle/pt_features.h: the lookups of a render per branch of sections 18 and 19; the last index is 0: bounce 0, 1: bounce >= 1"""
+    _u2 = C.c_uint64 * 2
+    _fields_ = [("struct_bytes", C.c_int32), ("pad", C.c_int32),
+                ("mip_rho_zero", _u2), ("mip_rho_le1", _u2), ("mip_two_level", (C.c_uint64 * 16) * 2), ("mip_last_level", _u2),
+                ("proc_all_one", _u2 * 6), ("proc_partial", _u2 * 6), ("proc_early", _u2 * 6),
+                ("checker_plain", _u2), ("checker_filtered", _u2), ("checker_half", _u2), ("word_sum", _u2)]
+
+    def arrays(self):
+        """every count as a numpy array, by field name"""
+        return {n: np.array(getattr(self, n), np.uint64) for n, _ in self._fields_[2:]}
 
 
 class JpOracleFeatures(C.Structure):
@@ -59,7 +78,9 @@ class JpOracleFeatures(C.Structure):
                 ("env_texel", _fp), ("env_q", _fp), ("env_alias", _ip), ("env_row_cos", _fp),
                 ("estimator", C.c_int32), ("watertight", C.c_int32),
                 ("normals", C.POINTER(jp.JpVertexNormals)), ("textures", C.POINTER(jp.JpTextures)), ("sampling", C.POINTER(jp.JpTextureSampling)),
-                ("normal_maps", C.POINTER(jp.JpNormalMaps)), ("lens", C.POINTER(jp.JpLens)), ("film", C.POINTER(jp.JpFilm))]
+                ("normal_maps", C.POINTER(jp.JpNormalMaps)), ("lens", C.POINTER(jp.JpLens)), ("film", C.POINTER(jp.JpFilm)),
+                ("mipmaps", C.POINTER(jp.JpTextureMipmaps)), ("n_mip_chains", C.c_int32), ("pad0", C.c_int32), ("mip_chains", C.POINTER(JpOracleMipChain)),
+                ("procedurals", C.POINTER(jp.JpTextureProcedurals))]
 
 
 def _scene_arr(p, n, dt=np.float32):
@@ -115,8 +136,37 @@ def _as_ptr(x, ty):
     return C.pointer(x), x
 
 
+def texture_images(textures):
+    """the images of a JpTextures (or a pointer to one): {texture index: (h, w, 3) uint8 array}"""
+    t = textures.contents if isinstance(textures, C._Pointer) else textures
+    out = {}
+    for k in range(t.n_textures):
+        if t.tex_type[k] == jp.JP_TEXTURE_IMAGE:
+            w, h = t.tex_width[k], t.tex_height[k]
+            out[k] = np.ctypeslib.as_array(C.cast(t.texels, C.POINTER(C.c_uint8)), shape=(t.n_texel_bytes,))[t.tex_offset[k]:t.tex_offset[k] + 3 * w * h].reshape(h, w, 3).copy()
+    return out
+
+
+def mip_chains(textures, mipmaps):
+    """the JpOracleMipChain array of a JpTextures under a JpTextureMipmaps: jp_build_mip_chain's arrays (pure host code with tests of its own) for every image
+    whose mode is TRILINEAR -> (ctypes array, keep-alive list)"""
+    t = textures.contents if isinstance(textures, C._Pointer) else textures
+    m = mipmaps.contents if isinstance(mipmaps, C._Pointer) else mipmaps
+    arr = (JpOracleMipChain * max(1, t.n_textures))()
+    keep = []
+    for k, img in texture_images(t).items():
+        if not m.mode or m.mode[k] != jp.JP_MIP_TRILINEAR:
+            continue
+        levels = jp.build_mip_chain(img)
+        lw = np.array([l.shape[1] for l in levels], np.int32); lh = np.array([l.shape[0] for l in levels], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([l.reshape(-1) for l in levels]), np.uint8)
+        arr[k] = JpOracleMipChain(len(levels), 0, lw.ctypes.data_as(C.POINTER(C.c_int32)), lh.ctypes.data_as(C.POINTER(C.c_int32)), flat.ctypes.data_as(C.POINTER(C.c_uint8)))
+        keep += [lw, lh, flat]
+    return arr, keep
+
+
 def oracle_features(scene_ptr, light_mode=None, env_rgb=None, env_up="z", env_importance=0, estimator=None, normals=None, textures=None, sampling=None,
-                    normal_maps=None, lens=None, film=None, watertight=False):
+                    normal_maps=None, lens=None, film=None, watertight=False, mipmaps=None, procedurals=None):
     """The JpOracleFeatures of a feature set, built the way the library builds its state: light_mode "power" takes the light table from
     jp_build_light_table over light_weights(); env_rgb (an (H, W, 3) array) the map tables from jp_build_environment_table with the scene's one environment
     light as the tint.  The other arguments are the structs the Context setters take (or pointers to them).  Everything is kept alive on the result."""
@@ -147,23 +197,32 @@ def oracle_features(scene_ptr, light_mode=None, env_rgb=None, env_up="z", env_im
     f.estimator = jp.ESTIMATOR_MODES[estimator]
     f.watertight = 1 if watertight else 0
     for name, val, ty in (("normals", normals, jp.JpVertexNormals), ("textures", textures, jp.JpTextures), ("sampling", sampling, jp.JpTextureSampling),
-                          ("normal_maps", normal_maps, jp.JpNormalMaps), ("lens", lens, jp.JpLens), ("film", film, jp.JpFilm)):
+                          ("normal_maps", normal_maps, jp.JpNormalMaps), ("lens", lens, jp.JpLens), ("film", film, jp.JpFilm),
+                          ("mipmaps", mipmaps, jp.JpTextureMipmaps), ("procedurals", procedurals, jp.JpTextureProcedurals)):
         p, k = _as_ptr(val, ty)
         if p is not None:
             setattr(f, name, C.cast(p, C.POINTER(ty))); keep.append((p, k))
+    if mipmaps is not None and textures is not None:                # the pyramids as data: jp_build_mip_chain's arrays
+        arr, k2 = mip_chains(textures, mipmaps)
+        f.n_mip_chains = len(arr); f.mip_chains = C.cast(arr, C.POINTER(JpOracleMipChain)); keep += [arr, k2]
     f._keep = keep
     return f
 
 
-def oracle_render_features(scene_ptr, params, features=None, nthreads=8, rand_seed=1):
-    """jp_oracle_render_features -> (film, JpCounters, undecided (H, W) bool).  features: oracle_features(...) or None.  rand_seed: as oracle_render."""
+def oracle_render_features(scene_ptr, params, features=None, nthreads=8, rand_seed=1, stats=None):
+    """jp_oracle_render_features -> (film, JpCounters, undecided (H, W) bool).  features: oracle_features(...) or None.  rand_seed: as oracle_render.
+    stats: a JpOracleBranchStats to fill (jp_oracle_render_features_stats)."""
     film = np.zeros((params.height, params.width, 3), np.float32)
     und = np.zeros((params.height, params.width), np.uint8)
     cnt = jp.JpCounters()
     L = oracle_lib()
     if rand_seed is not None:
         libc_srand(rand_seed)
-    st = L.jp_oracle_render_features(scene_ptr, C.byref(params), None if features is None else C.byref(features), nthreads, ptr(film), C.byref(cnt), ptr(und))
+    if stats is not None:
+        stats.struct_bytes = C.sizeof(JpOracleBranchStats)
+        st = L.jp_oracle_render_features_stats(scene_ptr, C.byref(params), None if features is None else C.byref(features), nthreads, ptr(film), C.byref(cnt), ptr(und), C.byref(stats))
+    else:
+        st = L.jp_oracle_render_features(scene_ptr, C.byref(params), None if features is None else C.byref(features), nthreads, ptr(film), C.byref(cnt), ptr(und))
     if st != 0:
         raise jp.JetPbrtError("jp_oracle_render_features: status %d" % st)
     return film, cnt, und.astype(bool)

@@ -26,11 +26,34 @@ The shade_body instantiations the library can launch for these feature sets (jp_
   k_shade_smooth, _tex, _pick, _pick_tex, _env, _env_tex, _mis, _mis_tex, _mis_env, _mis_env_tex<kSort>      zoo with vertex normals (one row: a smooth scene is planned
                                   onto <F,F,F>); with normal maps, sampling records, lens and film state on top: pick_tex_extras (k_shade_smooth_pick_tex behind
                                   k_normal_map_s / k_texel_s), smooth_mis_env_tex_extras; k_raygen<true> and k_resolve_film in both
+The side kernel a textured family runs before k_shade*_tex (jp_render.h texel launch: the first that applies), and what of the per-path ray cone it pins
+(INTEGRATION.md sections 18, 19; the cone is two floats per path slot that only this kernel reads and writes, through the slot a queued ray carries):
+
+  family                                 side kernel   cone array   rows (scenes), each sorted and unsorted
+  *_tex (the ten of the first table)     k_texel       --           as above
+  pick_tex_extras, smooth_mis_env_tex_extras   k_texel_s (+ k_normal_map_s)   --   zoo
+  all_tex_mip                            k_texel_m     yes          zoo (TTF), zoo_bulk (TFF), zoo_mats (FFF)
+  mis_env_tex_mip                        k_texel_m     yes          zoo, zoo_bulk, zoo_mats; zoo_bulk_few in one lane and in three with max_slots = 3 W H
+  pick_tex_proc                          k_texel_p     yes (antialiased records alone, no pyramid; bounce_spread from a mipmap state with every mode OFF)
+                                                                    zoo, zoo_bulk, zoo_mats; zoo_bulk_few in one lane and in three with max_slots = 3 W H
+  pick_tex_proc_off                      k_texel_p     no (every record with antialias off: every width is 0)      zoo, zoo_bulk, zoo_mats
+  mis_env_tex_mip_proc                   k_texel_p serving the pyramids too   yes   zoo, zoo_bulk, zoo_mats; zoo generic (reserved[0] = 1); zoo on the library's own tree
+  smooth_mis_env_tex_mip_proc_extras     k_texel_p + k_normal_map_s, k_raygen<true>, k_resolve_film   yes   zoo
+The mip families put JP_MIP_TRILINEAR on the rectangle image (under a sampling record: its scale enters rho) and on the triangle image (the identity record above level
+0), and leave the sphere and disk images JP_MIP_OFF (mixed modes); the records are one of every kind, uv space on triangles, world space on a sphere, one with
+antialiasing off, one with a non-identity map, three CHECKER_AA scales (plain word, filtered, 0.5).  The cone meets compaction, the material sort, several workgroup
+regions (zoo_bulk: 48 x 32 x 16 slots), lanes with cone arrays of their own, six batches through the same slots with the last one short, the null-material rectangle,
+mirror and glass against the widening closures.  tests/test_oracle_features_host.py proves from the oracle's branch statistics that every one of these groups has
+at least 2 % of its mip lookups in each of rho <= 1 / two levels / the last level, three values of l, a quarter of the lookups behind a bounce, and every branch of
+the records.
+  NOT COVERED: a trilinear lookup or a uv-space record on a sphere or a disk (undecided by rule: the uv comes through atan2f / asinf, and every coordinate enters
+  the bilinear weights; the footprint areas of the two shapes are pinned ray by ray by jp_mip_probe in tests/test_gpu_mipmap.py), the guides under the cone (pinned
+  at the first hit by the guide tests), anisotropic filtering (not in the library).
   NOT COVERED, and not reachable by any scene: the TTF and TFF rows of the eight pick / env / mis families (16 x 2 instances).  plan_scene stages whenever the tables fit
   LDS and the staging area fits next to them, and JP_LIGHTS_POWER_ONE has one shadow plane: 8 KB of staging next to at most 24 KB of tables and records is always within
   the 64 KB, so kStage is false only together with kTab false.  They are compiled and never selected.
   NOT COVERED: the fused k_path schedule (it has no shade_body; every feature here falls back to the per-bounce launches, asserted as fused_last_render 0).
-Options: shade_sort on / off in every cell; reserved[0] = 1 (generic) on one family of each group in the zoo; lanes = 1 and lanes = 3 on the same families in zoo_bulk_few
+Options: max_slots = 3 W H and lanes on the cone families as the table says; shade_sort on / off in every cell; reserved[0] = 1 (generic) on one family of each group in the zoo; lanes = 1 and lanes = 3 on the same families in zoo_bulk_few
 (six row groups of four rows; a scene with a null-material primitive renders in one lane whatever JpOptions.lanes says, and the zoo has one).
 """
 import ctypes as C
@@ -58,13 +81,17 @@ def fctx():
 
 def _apply(ctx, st, opts):
     ctx.set_options()
-    o = dict(shade_sort=opts.get("shade_sort", 0), lanes=opts.get("lanes", 0), reserved=(C.c_int32 * 8)(1 if opts.get("generic") else 0))
+    W, Hh = st["params"].width, st["params"].height
+    o = dict(shade_sort=opts.get("shade_sort", 0), lanes=opts.get("lanes", 0), reserved=(C.c_int32 * 8)(1 if opts.get("generic") else 0),
+             max_slots={None: 0, "3wh": 3 * W * Hh}[opts.get("max_slots")])     # 3 W H: three of the 16 samples a pixel per batch -- six batches through the same slots, the last one short
     ctx.set_options(**o)
     ctx.set_environment_map(st["rgb"], "y")
     ctx.set_light_sampling(st["mode"])
     ctx.set_vertex_normals(st["vn"])
     ctx.set_normal_maps(st["nmaps"])
     ctx.set_texture_sampling(st["sampling"])
+    ctx.set_texture_mipmaps(st["mipmaps"])                          # None clears what an earlier cell left
+    ctx.set_texture_procedurals(st["procedurals"])
     ctx.upload(st["sp"], st["textures"])
     ctx.set_estimator(st["est"])
     ctx.set_lens(**T.LENS) if st["lens"] is not None else ctx.set_lens(None)
@@ -119,6 +146,18 @@ def _check_cell(ctx, variant, family, opts, reference_tree=True):
         assert ni.n_smooth_triangles == int(st["vn"].any(-1).sum()) >= 80
     assert ctx.normal_map_info().mapped_last_render == int(fam["nmap"]) and ctx.texture_sampling_info().sampled_last_render == int(fam["records"])
     assert ctx.lens_info().lens_last_render == int(fam["lens"]) and ctx.film_info().hdr_last_render == int(fam["film"])
+    # the side kernel meant did run: k_texel_p with a record (it serves the pyramids too), else k_texel_m with a pyramid, else k_texel_s / k_texel; the cone array exists exactly when a pyramid
+    # or an antialiased record does
+    mi2, pi = ctx.texture_mipmap_info(), ctx.procedural_info()
+    n_rec = len(T.proc_records()) if fam["proc"] else 0
+    n_aa = 0 if fam["proc"] != "aa" else sum(1 for r in T.proc_records().values() if r.antialias >= 0)
+    print("    side kernel: mip %d (%d pyramids, %d levels), procedural %d (%d records, %d antialiased), cone bytes %d" % (
+        mi2.mip_last_render, mi2.n_on, mi2.n_levels, pi.procedural_last_render, pi.n_procedural, pi.n_antialiased, mi2.cone_bytes_device))
+    assert (pi.procedural_last_render, pi.n_procedural, pi.n_antialiased) == (int(bool(fam["proc"])), n_rec, n_aa)
+    assert (mi2.mip_last_render, mi2.n_on) == (int(fam["mip"]), 2 if fam["mip"] else 0)
+    assert (mi2.cone_bytes_device > 0) == bool(fam["mip"] or n_aa > 0)
+    if fam["mip"]:
+        assert mi2.footprint_scale == np.float32(T.MIP_FOOTPRINT) and mi2.bounce_spread == np.float32(T.MIP_SPREAD)
     assert bi.fused_last_render == 0 and bi.traversal_mode == (5 if reference_tree else bi.traversal_mode)
     if "lanes" in opts:
         assert bi.lanes_last_render == opts["lanes"]
@@ -149,6 +188,11 @@ def test_cell_equals_the_oracle(fctx, cell):
 def test_a_mesh_row_on_the_default_tree(fctx):
     """the richest family on the library's own tree (no reference semantics): test_gpu_parity.assert_film's rule on the decided pixels"""
     _check_cell(fctx, "zoo", "smooth_mis_env_tex", dict(shade_sort=1), reference_tree=False)
+
+
+def test_a_cone_row_on_the_default_tree(fctx):
+    """pyramids, records and the cone on the library's own tree, under the same rule"""
+    _check_cell(fctx, "zoo", "mis_env_tex_mip_proc", dict(shade_sort=1), reference_tree=False)
 
 
 def test_refused_combinations_stay_refused(fctx):

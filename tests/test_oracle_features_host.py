@@ -50,6 +50,18 @@ def _image(seed, h=8, w=16):
     return (rng.integers(1, 5, (h, w, 3)) * 51).astype(np.uint8)
 
 
+def _image_mip(seed, h, w):
+    """an image large enough to have levels, with texel-to-texel contrast at every level of its pyramid: the sum of one random block pattern per level, the
+    pattern of level k constant over 2^k x 2^k texels (so the 2 x 2 averages leave it whole down to level k)"""
+    rng = np.random.default_rng(seed)
+    n = int(np.log2(max(h, w))) + 1
+    acc = np.zeros((h, w, 3))
+    for k in range(n):
+        b = rng.integers(0, 256, (max(1, h >> k), max(1, w >> k), 3)).astype(np.float64)
+        acc += np.repeat(np.repeat(b, 1 << k, 0), 1 << k, 1)[:h, :w]
+    return np.clip(np.round(acc / n * 1.6 - 76.0), 0, 255).astype(np.uint8)
+
+
 def _nmap_image():
     rng = np.random.default_rng(31)
     img = np.full((8, 8, 3), 128, np.uint8)
@@ -78,7 +90,44 @@ def _ico_asset(sub, center, radius):
     return _asset("ico%d" % sub, v + np.asarray(center), f)
 
 
-def build_zoo(variant, textured=False, nmap=False, records=False, reference_tree=True):
+# The mip / proc variant of the room (build_zoo(mip=..., proc=...)); the values below were chosen on the CPU until test_new_groups_reach_every_branch held in
+# every new group, and are conditions on the inputs, not measurements of the device:
+#   MIP_SIZES          the rectangle image (floor) and the triangle image (back wall); the sphere and disk images keep 16 x 8 and stay JP_MIP_OFF -- a trilinear
+#                      lookup on their uv is undecided always, and the cap on undecided pixels is 1 %
+#   MIP_FOOTPRINT, MIP_SPREAD   JpTextureMipmaps.footprint_scale and bounce_spread of every mip family
+#   proc_records()     one record per checker texture of the proc variant (which has three more of them than the plain room: the right wall, the icosphere, the emitters' matte)
+MIP_SIZES = {"floor": (32, 64), "back": (4, 4)}                   # (h, w)
+MIP_FOOTPRINT, MIP_SPREAD = 2.5, 0.125
+
+
+def _rot_scale(s, t=(0.0, 0.0, 0.0)):
+    """a non-identity 3 x 4 map: a generic rotation times s, and a translation"""
+    R = R_generic()
+    return tuple(np.concatenate([s * R, np.asarray(t, np.float64)[:, None]], 1).reshape(-1))
+
+
+def R_generic():
+    return np.asarray(R.generic_rotation(), np.float64)[:3, :3]
+
+
+def proc_records(antialias=0):
+    """name of the checker texture -> its JpProcedural.  Every kind; SPACE_UV on the triangle ceiling; SPACE_WORLD on the mirror sphere; the noise record with
+    antialiasing off (all of them with antialias=-1); a non-identity map on the left wall; three CHECKER_AA records whose scales put the footprints of the room
+    (widths of 0.2 .. 5) below the plain-checker threshold, inside the filtered range and across the 0.5 threshold"""
+    P = jp.procedural
+    d = lambda s: (s, 0, 0, 0, 0, s, 0, 0, 0, 0, s, 0)
+    return {
+        "left": P(jp.JP_PROC_TURBULENCE, jp.JP_PROC_SPACE_WORLD, _rot_scale(0.1, (0.4, -1.3, 2.2)), octaves=3, gain=0.6, antialias=antialias),
+        "ceil": P(jp.JP_PROC_FBM, jp.JP_PROC_SPACE_UV, (0.08, 0, 0, 0.45, 0, 0.07, 0, 0.55, 0, 0, 0.05, 0), octaves=2, antialias=antialias),
+        "mirror": P(jp.JP_PROC_MARBLE, jp.JP_PROC_SPACE_WORLD, d(0.1), octaves=3, variation=2.0, antialias=antialias),
+        "disk_b": P(jp.JP_PROC_NOISE, jp.JP_PROC_SPACE_WORLD, d(3.0), antialias=-1),
+        "right": P(jp.JP_PROC_CHECKER_AA, jp.JP_PROC_SPACE_WORLD, d(1.0), antialias=antialias),
+        "white": P(jp.JP_PROC_CHECKER_AA, jp.JP_PROC_SPACE_WORLD, (0.01, 0, 0, 0.003, 0, 0.01, 0, -0.034, 0, 0, 0.01, 0.5), antialias=antialias),
+        "light": P(jp.JP_PROC_CHECKER_AA, jp.JP_PROC_SPACE_WORLD, d(1200.0), antialias=antialias),
+    }
+
+
+def build_zoo(variant, textured=False, nmap=False, records=False, reference_tree=True, mip=False, proc=False):
     W, Hh = SIZES[variant]
     be = scenes.HostBackend("oracle_features_" + variant)
     if reference_tree:
@@ -95,25 +144,32 @@ def build_zoo(variant, textured=False, nmap=False, records=False, reference_tree
         be.dirlight((0.3, -1.0, -0.4), (0.5, 0.45, 0.4))
     be.pointlight((0.0, 1.0, 0.0), (0.0, 0.0, 0.0))                # a black light: pmf 0, never sampled, its draws consumed in JP_LIGHTS_ALL
     rec = jp.tex_sampler(jp.JP_WRAP_REPEAT, jp.JP_WRAP_MIRROR, jp.JP_FILTER_BILINEAR, (2.0, 1.5), (0.25, 0.0)) if records else None
-    img = lambda seed, sampling=None: (lambda: be.texture_image(_image(seed), sampling=sampling))
-    chk = lambda a, b: (lambda: be.texture_checker(a, b))
+    be.zoo_tex = {}                                                # name -> texture index, for the mipmap modes and the procedural records
+
+    def named(name, make):
+        def f():
+            be.zoo_tex[name] = make()
+            return be.zoo_tex[name]
+        return f
+    img = lambda seed, sampling=None, name=None: named(name, lambda: be.texture_image(_image_mip(seed, *MIP_SIZES[name]) if (mip and name in MIP_SIZES) else _image(seed), sampling=sampling))
+    chk = lambda a, b, name=None: named(name, lambda: be.texture_checker(a, b))
 
     def matte(rgb, tex=None):
         return be.mat_matte(tex=tex()) if (textured and tex) else be.mat_matte(rgb)
-    m_floor = matte((0.7, 0.7, 0.65), img(1, rec))                                         # rectangle, image (under a sampling record when asked)
-    m_left = matte((0.63, 0.065, 0.05), chk((0.63, 0.065, 0.05), (0.2, 0.3, 0.6)))         # rectangle, checker; the normal-mapped wall
-    m_right = be.mat_matte((0.14, 0.45, 0.091))
-    m_back = matte((0.7, 0.7, 0.7), img(2))                                                # triangles, image
-    m_ceil = matte((0.75, 0.75, 0.75), chk((0.8, 0.8, 0.8), (0.3, 0.5, 0.3)))              # triangles, checker
-    m_white = be.mat_matte((0.73, 0.71, 0.68))
-    m_light = be.mat_matte((0.65, 0.65, 0.65))
-    m_mirror = be.mat_mirror(tex=chk((0.9, 0.9, 0.9), (0.9, 0.5, 0.3))()) if textured else be.mat_mirror((0.9, 0.9, 0.9))          # sphere, checker
+    m_floor = matte((0.7, 0.7, 0.65), img(1, rec, "floor"))                                       # rectangle, image (under a sampling record when asked)
+    m_left = matte((0.63, 0.065, 0.05), chk((0.63, 0.065, 0.05), (0.2, 0.3, 0.6), "left")) # rectangle, checker; the normal-mapped wall
+    m_right = matte((0.14, 0.45, 0.091), chk((0.14, 0.45, 0.091), (0.6, 0.6, 0.2), "right") if proc else None)
+    m_back = matte((0.7, 0.7, 0.7), img(2, None, "back"))                                   # triangles, image
+    m_ceil = matte((0.75, 0.75, 0.75), chk((0.8, 0.8, 0.8), (0.3, 0.5, 0.3), "ceil")) # triangles, checker
+    m_white = matte((0.73, 0.71, 0.68), chk((0.73, 0.71, 0.68), (0.3, 0.4, 0.7), "white") if proc else None)
+    m_light = matte((0.65, 0.65, 0.65), chk((0.65, 0.65, 0.65), (0.2, 0.2, 0.2), "light") if proc else None)
+    m_mirror = be.mat_mirror(tex=chk((0.9, 0.9, 0.9), (0.9, 0.5, 0.3), "mirror")()) if textured else be.mat_mirror((0.9, 0.9, 0.9))          # sphere, checker
     ks = (0.3, 0.25, 0.2)
-    m_plastic = be.mat_plastic(None, ks, 0.3, True, tex=img(3)()) if textured else be.mat_plastic((0.35, 0.12, 0.48), ks, 0.3, True)   # sphere, image
+    m_plastic = be.mat_plastic(None, ks, 0.3, True, tex=img(3, None, "sphere")()) if textured else be.mat_plastic((0.35, 0.12, 0.48), ks, 0.3, True)   # sphere, image
     m_metal = be.mat_metal((0.18, 0.15, 0.81), (0.11, 0.11, 0.11), 0.2, 0.3, False)
     m_glass = be.mat_glass(1.5, (0.98, 0.98, 0.98), (0.96, 0.98, 0.96))
-    m_disk_a = matte((0.6, 0.55, 0.3), img(4))                                             # disk, image
-    m_disk_b = matte((0.3, 0.55, 0.6), chk((0.3, 0.55, 0.6), (0.7, 0.2, 0.2)))             # disk, checker
+    m_disk_a = matte((0.6, 0.55, 0.3), img(4, None, "disk_a"))                                # disk, image
+    m_disk_b = matte((0.3, 0.55, 0.6), chk((0.3, 0.55, 0.6), (0.7, 0.2, 0.2), "disk_b"))   # disk, checker
     if variant == "zoo_mats":
         for k in range(270):
             be.mat_matte((0.5, 0.5, 0.5))                          # 270 x 64 bytes of material records: the shading tables exceed their 16 KB of LDS
@@ -172,10 +228,19 @@ def _families():
             for mode, env, est in (("all", False, "nee"), ("power", False, "nee"), ("power", True, "nee"), ("power", False, "mis"), ("power", True, "mis")):
                 name = ("smooth_" if smooth else "") + {("all", False, "nee"): "all", ("power", False, "nee"): "pick", ("power", True, "nee"): "env",
                                                           ("power", False, "mis"): "mis", ("power", True, "mis"): "mis_env"}[(mode, env, est)] + ("_tex" if tex else "")
-                out[name] = dict(mode=mode, env=env, est=est, tex=tex, smooth=smooth, nmap=False, records=False, lens=False, film=False)
+                out[name] = dict(mode=mode, env=env, est=est, tex=tex, smooth=smooth, nmap=False, records=False, lens=False, film=False, mip=False, proc=False)
     # normal maps, sampling records, the lens and the film state on top of two of them
     for base in ("pick_tex", "smooth_mis_env_tex"):
         out[base + "_extras"] = dict(out[base], nmap=True, records=True, lens=True, film=True)
+    # the ray cone (INTEGRATION.md sections 18, 19).  mip: JP_MIP_TRILINEAR on the rectangle and triangle images (k_texel_m).  proc: the records of proc_records()
+    # on the checker textures (k_texel_p) -- "aa": antialiased (the cone array exists with or without pyramids), "off": every record with antialias off (k_texel_p
+    # without a cone array).  The floor image is under a sampling record in the mip families (an active record's scale enters rho; the back wall takes the identity record).
+    out["all_tex_mip"] = dict(out["all_tex"], mip=True, records=True)
+    out["mis_env_tex_mip"] = dict(out["mis_env_tex"], mip=True, records=True)
+    out["pick_tex_proc"] = dict(out["pick_tex"], proc="aa", spread=0.2)   # no pyramid: the mipmap state (all modes OFF) still carries the cone's bounce_spread
+    out["pick_tex_proc_off"] = dict(out["pick_tex"], proc="off")
+    out["mis_env_tex_mip_proc"] = dict(out["mis_env_tex"], mip=True, records=True, proc="aa")
+    out["smooth_mis_env_tex_mip_proc_extras"] = dict(out["smooth_mis_env_tex_extras"], mip=True, proc="aa")
     return out
 
 
@@ -187,10 +252,28 @@ _scene_cache = {}
 
 
 def scene_of(variant, fam, reference_tree=True):
-    key = (variant, fam["tex"], fam["nmap"], fam["records"], reference_tree)
+    key = (variant, fam["tex"], fam["nmap"], fam["records"], reference_tree, fam["mip"], bool(fam["proc"]))
     if key not in _scene_cache:
-        _scene_cache[key] = build_zoo(variant, fam["tex"], fam["nmap"], fam["records"], reference_tree)
+        _scene_cache[key] = build_zoo(variant, fam["tex"], fam["nmap"], fam["records"], reference_tree, fam["mip"], bool(fam["proc"]))
     return _scene_cache[key]
+
+
+def zoo_mipmaps(be, footprint_scale=None, bounce_spread=None, on=("floor", "back")):
+    """JP_MIP_TRILINEAR on the rectangle and the triangle image; the sphere and disk images stay JP_MIP_OFF (mixed modes)"""
+    n = be.flatten_textures().contents.n_textures
+    modes = [jp.JP_MIP_OFF] * n
+    for name in on:
+        modes[be.zoo_tex[name]] = jp.JP_MIP_TRILINEAR
+    return jp.texture_mipmaps(modes, MIP_FOOTPRINT if footprint_scale is None else footprint_scale, MIP_SPREAD if bounce_spread is None else bounce_spread)
+
+
+def zoo_procedurals(be, mode):
+    t = be.flatten_textures().contents
+    recs = [None] * t.n_textures
+    for name, r in proc_records(-1 if mode == "off" else 0).items():
+        assert t.tex_type[be.zoo_tex[name]] == jp.JP_TEXTURE_CHECKER
+        recs[be.zoo_tex[name]] = r
+    return jp.texture_procedurals(recs)
 
 
 def state_of(variant, fam, reference_tree=True):
@@ -201,9 +284,10 @@ def state_of(variant, fam, reference_tree=True):
               textures=be.flatten_textures() if fam["tex"] else None,
               vn=zoo_vertex_normals(sp.contents) if fam["smooth"] else None,
               nmaps=be.flatten_normal_maps() if fam["nmap"] else None, sampling=be.flatten_texture_sampling() if fam["records"] else None,
-              lens=jp.lens(**LENS) if fam["lens"] else None, film=jp.film(**FILM) if fam["film"] else None)
+              lens=jp.lens(**LENS) if fam["lens"] else None, film=jp.film(**FILM) if fam["film"] else None,
+              mipmaps=zoo_mipmaps(be) if fam["mip"] else (zoo_mipmaps(be, 0.0, fam["spread"], on=()) if fam.get("spread") else None), procedurals=zoo_procedurals(be, fam["proc"]) if fam["proc"] else None)
     st["features"] = H.oracle_features(sp, st["mode"], st["rgb"], "y", 0, st["est"], None if st["vn"] is None else jp.vertex_normals(st["vn"]), st["textures"], st["sampling"],
-                                       st["nmaps"], st["lens"], st["film"])
+                                       st["nmaps"], st["lens"], st["film"], mipmaps=st["mipmaps"], procedurals=st["procedurals"])
     W, Hh = SIZES[variant]
     st["params"] = jp.render_params(W, Hh, SPP, DEPTH, SEED)
     return st
@@ -217,7 +301,8 @@ def oracle_of(variant, family, reference_tree=True):
     key = (variant, family, reference_tree)
     if key not in _oracle_cache:
         st = state_of(variant, FAMILIES[family], reference_tree)
-        film, cnt, und = H.oracle_render_features(st["sp"], st["params"], st["features"], 8)
+        st["stats"] = H.JpOracleBranchStats()
+        film, cnt, und = H.oracle_render_features(st["sp"], st["params"], st["features"], 8, stats=st["stats"])
         film.setflags(write=False); und.setflags(write=False)
         _oracle_cache[key] = (st, film, cnt, und)
     return _oracle_cache[key]
@@ -228,6 +313,8 @@ def oracle_of(variant, family, reference_tree=True):
 def _cells():
     cells = []
     for name, fam in FAMILIES.items():
+        if fam["mip"] or fam["proc"]:
+            continue                                              # the cone families: below
         if name.endswith("_extras") or fam["smooth"]:
             variants = ["zoo"]                                    # a scene with a shading normal of its own is planned onto the one row the smooth kernels have
         elif fam["mode"] == "all":
@@ -243,6 +330,17 @@ def _cells():
         cells.append(("zoo", name, dict(shade_sort=1, generic=True)))
         cells.append(("zoo_bulk_few", name, dict(shade_sort=1, lanes=1)))
         cells.append(("zoo_bulk_few", name, dict(shade_sort=1, lanes=3)))
+    # the cone families (k_texel_m, k_texel_p): every selector row a scene of theirs can reach, both orders; one mip and one procedural family through six batches
+    # of the same slots, the last one short (max_slots = 3 W H: 3 of the 16 samples a pixel per batch), in one lane and in three; the generic instance on one
+    for name, fam in FAMILIES.items():
+        if fam["mip"] or fam["proc"]:
+            for v in (["zoo"] if fam["smooth"] else ["zoo", "zoo_bulk", "zoo_mats"]):
+                for sort in (1, -1):
+                    cells.append((v, name, dict(shade_sort=sort)))
+    for name in ("mis_env_tex_mip", "pick_tex_proc"):
+        for lanes in (1, 3):
+            cells.append(("zoo_bulk_few", name, dict(shade_sort=1, lanes=lanes, max_slots="3wh")))
+    cells.append(("zoo", "mis_env_tex_mip_proc", dict(shade_sort=1, generic=True)))
     # the lean instances of k_shade and the generic one on the same scene
     cells += [("cornell", "all", dict(shade_sort=1)), ("cornell", "all", dict(shade_sort=-1)), ("cornell", "all", dict(shade_sort=1, generic=True)), ("cornell_null", "all", dict(shade_sort=1))]
     return cells
@@ -266,6 +364,9 @@ CELLS = _cells()
 def cell_id(c):
     v, f, o = c
     return "%s-%s-%s" % (v, f, "_".join("%s%s" % (k, "" if o[k] is True else o[k]) for k in sorted(o)))
+
+
+CONE_GROUPS = sorted({(v, f) for v, f, _ in CELLS if FAMILIES[f]["mip"] or FAMILIES[f]["proc"]})
 
 
 GROUPS = sorted({(v, f) for v, f, _ in CELLS})
@@ -430,7 +531,7 @@ def test_feature_sets_differ():
         for b in names[i + 1:]:
             assert not same(films[a], films[b]), (a, b)
     for f in names:
-        if FAMILIES[f]["est"] == "mis" and not f.endswith("_extras"):
+        if FAMILIES[f]["est"] == "mis" and not f.endswith("_extras") and not (FAMILIES[f]["mip"] or FAMILIES[f]["proc"]):   # (the cone families have no NEE twin in the matrix)
             nee = f.replace("mis_env", "env").replace("mis", "pick")
             assert _counts(oracle_of("zoo", f)[2]) == _counts(oracle_of("zoo", nee)[2]), f
 
@@ -600,3 +701,166 @@ def test_66_lights_against_all_sampling():
     z = (means.mean() - rmean) / (means.std(ddof=1) / np.sqrt(8.0))
     print("66 lights: e(64) = %.5f, e(1024) = %.5f, ratio %.3f; image mean %.6f vs R %.6f, z = %+.2f (left out %.3f)" % (e[64], e[1024], e[1024] / e[64], means.mean(), rmean, z, 1.0 - keep.mean()))
     assert e[1024] <= 0.35 * e[64] and abs(z) <= 5.0
+
+
+# ---- 5. the ray cone: mip maps and procedural textures (INTEGRATION.md sections 18, 19) ----------------------------------------------------------------------
+def _cone_render(st, **over):
+    """the oracle on a state of the matrix with its textures / mipmaps / procedurals replaced -> (film, counters, undecided, branch statistics)"""
+    kw = dict(textures=st["textures"], mipmaps=st["mipmaps"], procedurals=st["procedurals"])
+    kw.update(over)
+    f = H.oracle_features(st["sp"], st["mode"], st["rgb"], "y", 0, st["est"], None if st["vn"] is None else jp.vertex_normals(st["vn"]), kw["textures"], st["sampling"],
+                          st["nmaps"], st["lens"], st["film"], mipmaps=kw["mipmaps"], procedurals=kw["procedurals"])
+    stats = H.JpOracleBranchStats()
+    film, cnt, und = H.oracle_render_features(st["sp"], st["params"], f, 8, stats=stats)
+    return film, cnt, und, stats.arrays(), f
+
+
+def _mip_lookups(a):
+    return a["mip_rho_zero"] + a["mip_rho_le1"] + a["mip_two_level"].sum(1) + a["mip_last_level"]
+
+
+def test_cone_state_that_is_off_is_the_film_without_it():
+    """all modes OFF and all kinds NONE -- whatever footprint_scale and bounce_spread say -- and the struct of before this state (a shorter struct_bytes: absent)"""
+    st = state_of("zoo", FAMILIES["mis_env_tex_mip_proc"])
+    n = st["textures"].contents.n_textures
+    a, ca, ua, sa, _ = _cone_render(st, mipmaps=None, procedurals=None)
+    b, cb, ub, sb, _ = _cone_render(st, mipmaps=jp.texture_mipmaps([jp.JP_MIP_OFF] * n, 3.0, 0.3), procedurals=jp.texture_procedurals([None] * n))
+    assert a.mean() > 0.05 and same(a, b) and _counts(ca) == _counts(cb) and np.array_equal(ua, ub)
+    assert all(int(v.sum()) == 0 for v in sb.values())
+    f = _cone_render(st)[4]
+    f.struct_bytes = H.JpOracleFeatures.mipmaps.offset
+    c, cc, uc = H.oracle_render_features(st["sp"], st["params"], f, 8)
+    assert same(a, c) and _counts(ca) == _counts(cc) and np.array_equal(ua, uc)
+    d = oracle_of("zoo", "mis_env_tex_mip_proc")[1]
+    assert not same(a, d)
+
+
+def test_mipmaps_on_a_1x1_image_change_nothing():
+    """every level of a 1 x 1 image is its texel: level L - 1 = 0 alone, whatever the footprint"""
+    be = build_zoo("zoo")
+    sp = be.flatten(); s = sp.contents
+    mt = np.ctypeslib.as_array(s.mat_type, (s.n_materials,))
+    tex = jp.textures([jp.JP_TEXTURE_IMAGE], [(0,) * 6], np.where(np.isin(mt, (0, 1)), 0, -1), s.n_triangles, images={0: np.array([[[200, 90, 40]]], np.uint8)})
+    rp = jp.render_params(32, 24, 8, DEPTH, 5)
+    a, ca, _ = H.oracle_render_features(sp, rp, H.oracle_features(sp, "all", textures=tex), 4)
+    stats = H.JpOracleBranchStats()
+    b, cb, _ = H.oracle_render_features(sp, rp, H.oracle_features(sp, "all", textures=tex, mipmaps=jp.texture_mipmaps([jp.JP_MIP_TRILINEAR], 50.0)), 4, stats=stats)
+    k = stats.arrays()
+    assert a.mean() > 0.05 and same(a, b) and _counts(ca) == _counts(cb)
+    assert k["mip_last_level"].sum() > 1000 and k["mip_two_level"].sum() == 0
+
+
+def test_a_footprint_below_one_texel_is_the_film_without_mipmaps():
+    """footprint_scale so small that every rho <= 1: the lookup the texture has without mipmaps, under a sampling record (the floor) and without one (the back wall)"""
+    st = state_of("zoo", FAMILIES["mis_env_tex_mip"])
+    a, ca, ua, _, _ = _cone_render(st, mipmaps=None)
+    b, cb, ub, k, _ = _cone_render(st, mipmaps=zoo_mipmaps(st["be"], footprint_scale=1e-6))
+    assert a.mean() > 0.05 and same(a, b) and _counts(ca) == _counts(cb) and np.array_equal(ua, ub)
+    assert k["mip_rho_le1"].sum() > 1000 and k["mip_two_level"].sum() == 0 and k["mip_last_level"].sum() == 0
+    assert not same(a, oracle_of("zoo", "mis_env_tex_mip")[1])
+
+
+def test_equal_colours_under_any_record_give_the_solid_colours_film():
+    """tests/test_gpu_procedural.py test_equal_colours_give_the_film_of_the_solid_texture, on the oracle: both colours (1 / 255) b, so r = c whatever t is and
+    (1 / 255) b is the colour the byte b stands for; the plain-checker word of CHECKER_AA names an entry of the colour table, the same colour"""
+    import test_gpu_procedural as G
+    st = state_of("zoo", FAMILIES["pick_tex_proc"])
+    src = st["textures"].contents
+    types = np.array([src.tex_type[k] for k in range(src.n_textures)], np.int32)
+    colors = np.array([src.tex_color[k] for k in range(6 * src.n_textures)], f32).reshape(-1, 6)
+    checkers = np.flatnonzero(types == jp.JP_TEXTURE_CHECKER)
+    assert len(checkers) == len(proc_records())
+    rng = np.random.default_rng(5)
+    for k in checkers:
+        c = (f32(1.0) / f32(255.0)) * rng.integers(40, 230, 3).astype(f32)
+        colors[k, :3] = c; colors[k, 3:] = c
+    solid = types.copy(); solid[checkers] = jp.JP_TEXTURE_SOLID
+    a, ca, _, k, _ = _cone_render(st, textures=G._copy_textures(st["textures"], types, colors))
+    b, cb, _, _, _ = _cone_render(st, textures=G._copy_textures(st["textures"], solid, colors), procedurals=None)
+    assert a.mean() > 0.05 and same(a, b) and _counts(ca) == _counts(cb)
+    assert k["checker_plain"].sum() > 0 and k["checker_filtered"].sum() > 0 and k["proc_partial"].sum() > 0
+    assert not same(a, oracle_of("zoo", "pick_tex_proc")[1])
+
+
+@pytest.mark.parametrize("which", ["direct", "mirror", "matte"])
+def test_saturating_constructions_of_the_mipmap_tests(which):
+    """tests/test_gpu_mipmap.py's three exact films (direct view, a width carried across a mirror, a spread widened by a diffuse bounce), their scenes and
+    parameters: the oracle's mip film equals the oracle's film of the constant grey image, and the image without mipmaps does not"""
+    import test_gpu_mipmap as G
+    build, img, scale, spread = {"direct": (G._scene_direct, G._checker(64, 1), 4.0, 0.125), "mirror": (G._scene_mirror, G._checker(64, 2), 8.0, 1.0),
+                                 "matte": (G._scene_matte, G._checker(64, 2), 4.0, 0.5)}[which]
+    rp = jp.render_params(G.W, G.H, 4, 4, 1234)
+    films = []
+    for im, mip in ((img, [1]), (img, None), (G.GREY, None)):
+        be = build(im, scale)
+        sp = be.flatten()
+        f = H.oracle_features(sp, textures=be.flatten_textures(), sampling=be.flatten_texture_sampling(), mipmaps=None if mip is None else jp.texture_mipmaps(mip, bounce_spread=spread))
+        films.append(H.oracle_render_features(sp, rp, f, 4)[0])
+    a, b, c = films
+    assert a.mean() > 0.01 and same(a, c) and not same(b, c) and np.abs(b - c).max() > 0.02
+
+
+@pytest.mark.parametrize("variant,family", CONE_GROUPS, ids=["%s-%s" % g for g in CONE_GROUPS])
+def test_new_groups_reach_every_branch(variant, family):
+    """conditions on the inputs (MIP_SIZES, MIP_FOOTPRINT, MIP_SPREAD, proc_records were chosen until they held), from the oracle's branch statistics: a cell whose
+    lookups all took one branch would pin nothing of the others"""
+    fam = FAMILIES[family]
+    a = oracle_of(variant, family)[0]["stats"].arrays()
+    print("%s / %s: %s" % (variant, family, {k: v.tolist() for k, v in a.items() if k != "mip_two_level"}), a["mip_two_level"].sum(0).tolist())
+    mip = _mip_lookups(a)
+    if fam["mip"]:
+        n = int(mip.sum())
+        assert n > 5000
+        for k in ("mip_rho_le1", "mip_two_level", "mip_last_level"):
+            assert a[k].sum() >= 0.02 * n, k
+        assert (a["mip_two_level"].sum(0) > 0).sum() >= 3
+        assert mip[1] >= 0.25 * n
+    else:
+        assert mip.sum() == 0
+    for k in ("proc_all_one", "proc_partial", "proc_early"):
+        assert a[k][0].sum() == 0 and a[k][jp.JP_PROC_CHECKER_AA].sum() == 0
+    by_kind = a["proc_all_one"] + a["proc_partial"] + a["proc_early"]
+    checker = a["checker_plain"] + a["checker_filtered"] + a["checker_half"]
+    if not fam["proc"]:
+        assert by_kind.sum() == 0 and checker.sum() == 0
+    else:
+        for kind in (jp.JP_PROC_NOISE, jp.JP_PROC_FBM, jp.JP_PROC_TURBULENCE, jp.JP_PROC_MARBLE):
+            assert by_kind[kind].sum() > 0, kind
+        assert checker.sum() > 0
+        if fam["proc"] == "off":                                   # no footprint: every octave at weight 1, the plain checker's word everywhere
+            assert a["proc_partial"].sum() == 0 and a["proc_early"].sum() == 0 and a["checker_filtered"].sum() == 0 and a["checker_half"].sum() == 0
+        else:
+            for kind in (jp.JP_PROC_FBM, jp.JP_PROC_TURBULENCE):
+                for k in ("proc_all_one", "proc_partial", "proc_early"):
+                    assert a[k][kind].sum() >= 50, (kind, k)
+            for k in ("checker_plain", "checker_filtered", "checker_half"):
+                assert a[k].sum() >= 50, k
+            assert by_kind[:, 1].sum() + checker[1] >= 0.25 * (by_kind.sum() + checker.sum())
+
+
+@pytest.mark.parametrize("family", ["mis_env_tex_mip", "pick_tex_proc", "mis_env_tex_mip_proc"])
+def test_the_film_sees_the_cone_beyond_the_first_hit(family):
+    """only bounce_spread changes (0.125 -> 0.25; the procedural family carries it in a mipmap state whose modes are all OFF): the first segment's cone is
+    gamma0 t whatever the spread, so every first-hit lookup keeps its branch and its word; the film changes, so the matrix sees the state the paths carry"""
+    st = state_of("zoo", FAMILIES[family])
+    mk = (lambda s: zoo_mipmaps(st["be"], bounce_spread=s)) if FAMILIES[family]["mip"] else (lambda s: zoo_mipmaps(st["be"], 0.0, s, on=()))
+    a, ca, _, ka, _ = _cone_render(st, mipmaps=mk(0.125))
+    b, cb, _, kb, _ = _cone_render(st, mipmaps=mk(0.25))
+    assert not same(a, b)
+    for k in ka:
+        first_a, first_b = ka[k][..., 0] if k != "mip_two_level" else ka[k][0], kb[k][..., 0] if k != "mip_two_level" else kb[k][0]
+        assert np.array_equal(first_a, first_b), k
+    assert ka["word_sum"][0] > 0 and ka["word_sum"][1] != kb["word_sum"][1]
+    # 0 means the default, 0.125
+    c = _cone_render(st, mipmaps=mk(0.0))[0]
+    assert same(a, c)
+
+
+def test_cone_film_does_not_depend_on_the_thread_count():
+    st, film, cnt, und = oracle_of("zoo", "smooth_mis_env_tex_mip_proc_extras")
+    ref = st["stats"].arrays()
+    for nt in (0, 1, 3):
+        k = H.JpOracleBranchStats()
+        f2, c2, u2 = H.oracle_render_features(st["sp"], st["params"], st["features"], nt, stats=k)
+        assert same(film, f2) and _counts(cnt) == _counts(c2) and cnt.samples == c2.samples and np.array_equal(und, u2)
+        assert all(np.array_equal(v, ref[n]) for n, v in k.arrays().items())
