@@ -800,6 +800,34 @@ int  jp_render_denoised_variance(JpContext* ctx, const JpRenderParams* render, i
 typedef struct JpVarianceInfo { int32_t struct_bytes, variance_last_render; int64_t moment_bytes_device; int32_t iterations; float sigma_color, sigma_normal, sigma_depth; int32_t demodulated; double denoise_ms; } JpVarianceInfo;
 int  jp_get_variance_info(JpContext* ctx, JpVarianceInfo* out);
 
+/* ---- Adaptive sampling (additive to ABI 7; INTEGRATION.md "Adaptive sampling") ------------------------------------------------------------------------
+ * A render that stops each pixel by the variance of its own mean.  The rule is include/jp_adaptive.h, the text the kernels and jp_adaptive_samples both
+ * compile: every pixel of the band shard takes min_spp samples; then a pixel passes when
+ *     (m2 / (float)(n - 1)) / (float)n <= t * t,   t = threshold * max(mean, floor)   ((mean, m2): the moments of "Variance"; not finite on either side: pass)
+ * and stays active iff it was active and does not pass (dilate 1: iff a pixel of its 3 x 3 neighbourhood, clipped to the image and the band shard, does not
+ * pass); active pixels take min(step_spp, max_spp - n) more samples, the next sample indices of the stream jp_render draws, until none is active or n == max_spp.
+ *     film = Clamp01(sum / (float)n) (max(., 0) while the film state has hdr = 1); counts = n (int32, 0 outside the shard); variance = (m2 / (float)(n - 1)) / (float)n
+ * struct_bytes = sizeof(JpAdaptive); max_spp 0: JpRenderParams.spp; floor 0: 1e-3.  threshold 0 stops only pixels whose samples so far were all equal; min_spp = max_spp is the uniform render.
+ * The path integrator on the per-bounce launches of one lane (JpOptions::fused falls back; Whitted / debug: JP_ERR_UNSUPPORTED, the context stays usable).
+ * With none of these calls made every other entry point launches exactly what it launched before. */
+typedef struct JpAdaptive { int32_t struct_bytes; int32_t min_spp, step_spp, max_spp; float threshold, floor; int32_t dilate; } JpAdaptive;
+int  jp_check_adaptive(const JpAdaptive* adaptive);            /* pure host: the validation of jp_render_adaptive, same status and message */
+/* film_rgb_host: W*H*3 floats, counts_host: W*H int32, variance_host: W*H floats; any two may be NULL */
+int  jp_render_adaptive(JpContext* ctx, const JpRenderParams* params, const JpAdaptive* adaptive, float* film_rgb_host, int32_t* counts_host, float* variance_host);
+/* device pointers, any two may be NULL.  The call reads the active count once per pass, so it has waited for all but its last pass whatever `sync` says; it
+ * waits for the last one too before it frees the per-pixel state, which lives for the length of the call only. */
+int  jp_render_adaptive_device(JpContext* ctx, const JpRenderParams* params, const JpAdaptive* adaptive, void* film_dev, void* counts_dev, void* variance_dev, int sync);
+/* pure host, the very functions the device runs: the whole loop on caller-supplied samples_rgb [max_spp][height*width][3] (max_spp > 0 here); film NULL: no clamp, hdr 0 */
+int  jp_adaptive_samples(const JpFilm* film_or_null, const JpAdaptive* adaptive, int32_t width, int32_t height, const float* samples_rgb, float* film_rgb, int32_t* counts, float* variance);
+/* test hook: the device's k_resolve_list, k_adapt_select and k_adapt_finish on caller-supplied samples; needs no scene */
+int  jp_adaptive_probe(JpContext* ctx, const JpFilm* film_or_null, const JpAdaptive* adaptive, int32_t width, int32_t height, const float* samples_rgb, float* film_rgb, int32_t* counts, float* variance);
+/* the last jp_render_adaptive* / jp_adaptive_probe (adaptive_last_render 0 once a film render of another kind -- jp_render*, jp_render_rgb8, jp_render_variance*, jp_render_denoised* -- has run since: the rest then is 0; guides, filters and tone maps leave it): passes run (the first, uniform one
+ * included), samples traced, the active count after each of the first 16 tests (-1: no such test), the bytes of the per-pixel state while the call ran, and
+ * with jp_set_profiling the kernel time of the selection (k_adapt_select, its scan and compaction) and of k_resolve_list.  Synchronises the stream. */
+typedef struct JpAdaptiveInfo { int32_t struct_bytes, adaptive_last_render, passes, min_spp, step_spp, max_spp, dilate; float threshold; int64_t samples_traced, state_bytes_device;
+                                int32_t active_after[16]; double select_ms, resolve_ms; } JpAdaptiveInfo;
+int  jp_get_adaptive_info(JpContext* ctx, JpAdaptiveInfo* out);
+
 /* What jp_upload_scene would do with `scene` (additive to ABI 7; INTEGRATION.md "Describing an upload"): the scalars of the plan every later launch
  * reads, and for each table the host builds the byte count and the 64-bit FNV-1a of exactly the bytes the upload copies to the device.  Pure host code, no GPU
  * needed: the same validation (same status codes and jp_last_error texts), table builders and plan function the upload runs, nothing decided twice.

@@ -611,6 +611,24 @@ class JpVarianceInfo(C.Structure):
                 ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("demodulated", C.c_int32), ("denoise_ms", C.c_double)]
 
 
+class JpAdaptive(C.Structure):
+    """include/jetpbrt_amd.h: JpAdaptive (jp_render_adaptive); struct_bytes = sizeof(JpAdaptive); max_spp 0: JpRenderParams.spp, floor 0: 1e-3"""
+    _fields_ = [("struct_bytes", C.c_int32), ("min_spp", C.c_int32), ("step_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float), ("floor", C.c_float),
+                ("dilate", C.c_int32)]
+
+
+class JpAdaptiveInfo(C.Structure):
+    """include/jetpbrt_amd.h: JpAdaptiveInfo (jp_get_adaptive_info)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("adaptive_last_render", C.c_int32), ("passes", C.c_int32), ("min_spp", C.c_int32), ("step_spp", C.c_int32),
+                ("max_spp", C.c_int32), ("dilate", C.c_int32), ("threshold", C.c_float), ("samples_traced", C.c_int64), ("state_bytes_device", C.c_int64),
+                ("active_after", C.c_int32 * 16), ("select_ms", C.c_double), ("resolve_ms", C.c_double)]
+
+
+def adaptive(threshold, min_spp=8, step_spp=8, max_spp=0, floor=0.0, dilate=1):
+    """A JpAdaptive (or pass one through)"""
+    return threshold if isinstance(threshold, JpAdaptive) else JpAdaptive(C.sizeof(JpAdaptive), min_spp, step_spp, max_spp, threshold, floor, int(dilate))
+
+
 def film(hdr=1, sample_clamp=0.0):
     """A JpFilm (or pass one through)"""
     return hdr if isinstance(hdr, JpFilm) else JpFilm(C.sizeof(JpFilm), int(hdr), sample_clamp)
@@ -662,6 +680,34 @@ def variance_samples(f, samples, want_mean=False):
     L = hip_lib()
     _hip_status(L, L.jp_variance_samples(_ptr(f), spp, n, a.ctypes.data_as(C.c_void_p), var.ctypes.data_as(C.c_void_p), mean.ctypes.data_as(C.c_void_p)))
     return (var, mean) if want_mean else var
+
+
+def check_adaptive(a):
+    """jp_check_adaptive: the validation of jp_render_adaptive (pure host code, no GPU); raises JetPbrtError with its message.  a: a JpAdaptive or None"""
+    L = hip_lib()
+    _hip_status(L, L.jp_check_adaptive(_ptr(a)))
+
+
+def _adaptive_planes(fn, a, f, samples, height, width):
+    import numpy as np
+    s = np.ascontiguousarray(samples, np.float32)
+    if s.ndim != 3 or s.shape[2] != 3 or s.shape[1] != height * width:
+        raise JetPbrtError("adaptive samples must be (max_spp, height * width, 3)")
+    if a.max_spp != 0 and a.max_spp != s.shape[0]:
+        raise JetPbrtError("adaptive samples: %d samples per pixel given, max_spp is %d" % (s.shape[0], a.max_spp))
+    if a.max_spp == 0:
+        a = JpAdaptive(a.struct_bytes, a.min_spp, a.step_spp, s.shape[0], a.threshold, a.floor, a.dilate)
+    film_ = np.zeros((height, width, 3), np.float32); counts = np.zeros((height, width), np.int32); var = np.zeros((height, width), np.float32)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    fn(_ptr(f), C.byref(a), width, height, q(s), q(film_), q(counts), q(var))
+    return film_, counts, var
+
+
+def adaptive_samples(f, a, samples, height, width):
+    """jp_adaptive_samples: the whole adaptive loop of JpAdaptive `a` under JpFilm `f` (or None) on (max_spp, height * width, 3) float32 samples ->
+    (film (H, W, 3) float32, counts (H, W) int32, variance (H, W) float32).  Pure host code, the functions the device runs."""
+    L = hip_lib()
+    return _adaptive_planes(lambda *args: _hip_status(L, L.jp_adaptive_samples(*args)), a, f, samples, height, width)
 
 
 def exposure_from_histogram(t, hist):
@@ -913,6 +959,7 @@ def host_lib():
         L.jp_host_render_sampler.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.jp_host_render_denoised.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.jp_host_render_variance.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint] + [C.c_int] * 5 + [C.c_void_p] * 5
+        L.jp_host_render_adaptive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_float] + [C.c_int] * 6 + [C.c_void_p] * 3
         L.jp_host_render_film.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                           C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_char_p, C.c_int]
         L.jp_host_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
@@ -1061,6 +1108,12 @@ def hip_lib():
         L.jp_denoise_variance_device.argtypes = [C.c_void_p, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 7 + [C.c_int]
         L.jp_render_denoised_variance.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 6
         L.jp_get_variance_info.argtypes = [C.c_void_p, C.POINTER(JpVarianceInfo)]
+        L.jp_check_adaptive.argtypes = [C.POINTER(JpAdaptive)]
+        L.jp_render_adaptive.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.POINTER(JpAdaptive), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.jp_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.POINTER(JpAdaptive), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.jp_adaptive_samples.argtypes = [C.POINTER(JpFilm), C.POINTER(JpAdaptive), C.c_int32, C.c_int32] + [C.c_void_p] * 4
+        L.jp_adaptive_probe.argtypes = [C.c_void_p, C.POINTER(JpFilm), C.POINTER(JpAdaptive), C.c_int32, C.c_int32] + [C.c_void_p] * 4
+        L.jp_get_adaptive_info.argtypes = [C.c_void_p, C.POINTER(JpAdaptiveInfo)]
         _hip = L
     return _hip
 
@@ -1410,6 +1463,30 @@ class Context:
         dp = denoise_params(w, h, **kw) if denoise else None
         self._check(self.lib.jp_render_denoised_variance(self.h, C.byref(params), guide_spp, _ptr(dp), q(f), q(b), q(alb), q(nrm), q(dep), q(var)))
         return f, b, alb, nrm, dep, var
+
+    def render_adaptive(self, params, a):
+        """jp_render_adaptive: a render that stops each pixel by JpAdaptive `a` -> (film (H, W, 3) float32, counts (H, W) int32, variance (H, W) float32)"""
+        import numpy as np
+        h, w = params.height, params.width
+        film_ = np.zeros((h, w, 3), np.float32); counts = np.zeros((h, w), np.int32); var = np.zeros((h, w), np.float32)
+        q = lambda x: x.ctypes.data_as(C.c_void_p)
+        self._check(self.lib.jp_render_adaptive(self.h, C.byref(params), _ptr(a), q(film_), q(counts), q(var)))
+        return film_, counts, var
+
+    def render_adaptive_device(self, params, a, film_ptr, counts_ptr, variance_ptr, sync=True):
+        """jp_render_adaptive_device: device pointers (any two may be 0 / None), as render_device takes its film"""
+        v = lambda x: C.c_void_p(x or None)
+        self._check(self.lib.jp_render_adaptive_device(self.h, C.byref(params), _ptr(a), v(film_ptr), v(counts_ptr), v(variance_ptr), 1 if sync else 0))
+
+    def adaptive_probe(self, a, samples, height, width, f=None):
+        """jp_adaptive_probe: the device twin of adaptive_samples (k_resolve_list, k_adapt_select, k_adapt_finish on caller-supplied samples; no scene needed)"""
+        return _adaptive_planes(lambda *args: self._check(self.lib.jp_adaptive_probe(self.h, *args)), a, f, samples, height, width)
+
+    def adaptive_info(self):
+        i = JpAdaptiveInfo()
+        i.struct_bytes = C.sizeof(JpAdaptiveInfo)
+        self._check(self.lib.jp_get_adaptive_info(self.h, C.byref(i)))
+        return i
 
     def variance_info(self):
         i = JpVarianceInfo()

@@ -1398,6 +1398,8 @@ __global__ void __launch_bounds__(JP_BLOCK) k_resolve_film(Queues q, RenderConst
 
 #include "jp_variance.h"         // variance, part 1: k_resolve_var, the twin launch_resolve picks while a variance render runs, and k_var_probe (part 2 at the end)
 
+#include "jp_adaptive.h"         // adaptive sampling, part 1: k_raygen_list, k_resolve_list, k_adapt_select / _scan / _compact, k_adapt_finish (part 2 at the end)
+
 #include "jp_path.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1643,3 +1645,5 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #include "jp_film.h"             // film, part 2: k_film_hist, k_display and the film / tone map entry points (jp_render.h declares film_to_rgb8 and reads the context's film state)
 #define JP_VARIANCE_RUNTIME
 #include "jp_variance.h"         // variance, part 2: k_atrous_v and the variance entry points (after jp_denoise.h and the film's part 2: their checks)
+#define JP_ADAPTIVE_RUNTIME
+#include "jp_adaptive.h"         // adaptive sampling, part 2: the driver loop beside render_one and the entry points (after the variance part 2: film_check_status, overlaps)

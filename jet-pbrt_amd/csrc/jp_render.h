@@ -5,7 +5,7 @@
 // ---- render ---------------------------------------------------------------------------------------------------------------
 namespace
 {
-enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4, CLS_NORMAL = 5, CLS_NMAP = 6, CLS_TEXEL = 7 };   // (CLS_NORMAL: k_normal, stamped inside its CLS_SHADE pair -- a share of shade_ms, JpNormalInfo)
+enum { CLS_EXTEND = 0, CLS_SHADE = 1, CLS_SHADOW = 2, CLS_OTHER = 3, CLS_PATH = 4, CLS_NORMAL = 5, CLS_NMAP = 6, CLS_TEXEL = 7, CLS_ADAPT_SELECT = 8, CLS_ADAPT_RESOLVE = 9 };   // (CLS_NORMAL: k_normal, stamped inside its CLS_SHADE pair -- a share of shade_ms, JpNormalInfo)
 
 // the lens in force as the kernels take it (zeros while none is set: the kernels then do not read it); the camera is the uploaded scene's
 int lens_plan_of(const JpContext* c, JpLensPlan& lp)
@@ -278,6 +278,49 @@ OccludedLaunch occluded_kernel(const ScenePlan& p, int tw, bool generic)
 	return p.trav_mode == 2 ? occluded_row<2>(p.lds_bytes, p.stack_depth) : (p.trav_mode == 1 ? occluded_row<1>(p.lds_bytes, p.stack_depth) : occluded_row<0>(p.lds_bytes, p.stack_depth));
 }
 
+// The bounces of one batch, between ray generation and the resolve: per bounce k_extend, [k_texel, k_normal,] k_shade and k_shadow on the context's queue set, and
+// the drain of null-material scenes.  The other two integrators trace their batch in k_other: no bounce.  One text for render_one and the adaptive driver
+// (jp_adaptive.h), whose kernels between the list twins are these launches.
+struct BounceLaunch { const ExtendLaunch& ek; const ShadowLaunch& sk; const ShadeLaunch& shade; bool tex, smooth; const TexView& tv; const MipView& mv_cone; const NormView& nv; int* d_spill; DevCounters* d_cnt; };
+int launch_bounces(JpContext* c, const JpRenderParams* rp, const ScenePlan& p, const RenderConst& rc, int grid, const BounceLaunch& b)
+{
+	const ExtendLaunch& ek = b.ek; const ShadowLaunch& sk = b.sk; int* const d_spill = b.d_spill; DevCounters* const d_cnt = b.d_cnt;
+	int cur = 0;
+	int iters = rp->integrator != JP_INTEGRATOR_PATH ? 0 : rp->max_depth + 1;
+	for (int it = 0;; it++)
+	{
+		if (it >= iters)
+		{
+			if (rp->integrator != JP_INTEGRATOR_PATH || !p.has_null_material || it > iters + 64) break;
+			// null-material primitives re-queue a path without consuming a bounce (integrator.cc:349-353): ask the device
+			DevCounters h; HIP_TRY(hipMemcpyAsync(&h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
+			if (h.n_queue[cur] == 0) break;
+		}
+		{
+			Stamper t(c, CLS_EXTEND);
+			if (ek.refill) hipLaunchKernelGGL(ek.refill, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, d_spill, d_cnt);
+			else hipLaunchKernelGGL(ek.plain, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, d_cnt);
+		}
+		{
+			Stamper t(c, CLS_SHADE);
+			if (b.tex) launch_texel(c, p, grid, cur, b.tv, b.mv_cone);         // textured scenes: k_texel leaves the texture's answer for every hit, the textured twin shades with it
+			if (b.smooth) launch_normal(c, p, grid, cur, b.nv);                // scenes with vertex normals or normal maps: Ns for every hit it applies to, the smooth twin shades with it
+			b.shade(c->stream, grid, p.shade_lds_bytes, p.sv, c->q, rc, cur, d_cnt);
+		}
+		HIP_TRY(hipGetLastError());                                       // a failed launch (k_extend / k_shade) is reported where it happens, not at the end of the frame
+		if (it < rp->max_depth || p.has_null_material)                     // at bounce == maxDepth Li() breaks before the NEE (integrator.cc:340-343)
+		{
+			Stamper t(c, CLS_SHADOW);
+			if (sk.cert_fell_back) c->cert_fell_back = true;                 // the one-ray-per-lane kernels walk the caller's tree verbatim
+			if (sk.refill) hipLaunchKernelGGL(sk.refill, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, d_spill, d_cnt);
+			else hipLaunchKernelGGL(sk.plain, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, d_cnt);
+			HIP_TRY(hipGetLastError());
+		}
+		cur ^= 1;
+	}
+	return JP_OK;
+}
+
 int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sync, int lane_index = 0, int lane_count = 1, int lane_group = 4, bool ev0_recorded = false)
 {
 	if (!c->plan.have_scene) return fail(JP_ERR_NO_SCENE, "jp_render: no scene uploaded");
@@ -379,39 +422,7 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 				const int ogrid = (int)std::min<unsigned int>((P + JP_BLOCK - 1) / JP_BLOCK, (unsigned int)(c->n_cus * 16));
 				hipLaunchKernelGGL(ok, dim3(ogrid), dim3(JP_BLOCK), p.lds_bytes, c->stream, p.sv, c->q, rc, rp->integrator, p.stack_depth, d_cnt, c->lens_on ? 1 : 0, lp);
 			}
-			int cur = 0;
-			int iters = rp->integrator != JP_INTEGRATOR_PATH ? 0 : rp->max_depth + 1;
-			for (int it = 0;; it++)
-			{
-				if (it >= iters)
-				{
-					if (rp->integrator != JP_INTEGRATOR_PATH || !p.has_null_material || it > iters + 64) break;
-					// null-material primitives re-queue a path without consuming a bounce (integrator.cc:349-353): ask the device
-					DevCounters h; HIP_TRY(hipMemcpyAsync(&h, d_cnt, sizeof(h), hipMemcpyDeviceToHost, c->stream)); HIP_TRY(hipStreamSynchronize(c->stream));
-					if (h.n_queue[cur] == 0) break;
-				}
-				{
-					Stamper t(c, CLS_EXTEND);
-					if (ek.refill) hipLaunchKernelGGL(ek.refill, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, d_spill, d_cnt);
-					else hipLaunchKernelGGL(ek.plain, dim3(grid), dim3(JP_BLOCK), ek.lds, c->stream, p.sv, c->q, cur, ek.words, d_cnt);
-				}
-				{
-					Stamper t(c, CLS_SHADE);
-					if (tex) launch_texel(c, p, grid, cur, tv, mv_cone);             // textured scenes: k_texel leaves the texture's answer for every hit, the textured twin shades with it
-					if (smooth) launch_normal(c, p, grid, cur, nv);         // scenes with vertex normals or normal maps: Ns for every hit it applies to, the smooth twin shades with it
-					shade(c->stream, grid, p.shade_lds_bytes, p.sv, c->q, rc, cur, d_cnt);
-				}
-				HIP_TRY(hipGetLastError());                               // a failed launch (k_extend / k_shade) is reported where it happens, not at the end of the frame
-				if (it < rp->max_depth || p.has_null_material)                 // at bounce == maxDepth Li() breaks before the NEE (integrator.cc:340-343)
-				{
-					Stamper t(c, CLS_SHADOW);
-					if (sk.cert_fell_back) c->cert_fell_back = true;         // the one-ray-per-lane kernels walk the caller's tree verbatim
-					if (sk.refill) hipLaunchKernelGGL(sk.refill, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, d_spill, d_cnt);
-					else hipLaunchKernelGGL(sk.plain, dim3(grid), dim3(JP_BLOCK), sk.lds, c->stream, p.sv, c->q, rc, sk.words, d_cnt);
-					HIP_TRY(hipGetLastError());
-				}
-				cur ^= 1;
-			}
+			if (const int e = launch_bounces(c, rp, p, rc, grid, BounceLaunch{ ek, sk, shade, tex, smooth, tv, mv_cone, nv, d_spill, d_cnt }); e != JP_OK) return e;
 			{ Stamper t(c, CLS_OTHER); launch_resolve(c, c->q, rc, npix, d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
 			samples += (unsigned long long)rc.sbatch * (unsigned long long)npix;
 		}
@@ -611,6 +622,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	if (!c || !rp || !film_dev) return fail(JP_ERR_INVALID_ARGUMENT, "jp_render: null argument");
 	c->last_hdr = 0;
 	c->last_var = c->var_on ? 1 : 0;
+	c->ad_info.adaptive_last_render = 0;                                  // (jp_adaptive.h's driver does not come through here)
 	if (!c->var_on && (c->var_mom || (!c->lanes.empty() && c->lanes[0]->var_mom))) { c->var_mom.reset(); for (JpContext* l : c->lanes) l->var_mom.reset(); }   // (left by a variance render that did not wait for its stream)
 	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0; c->last_sampled = 0; c->last_mip = 0; c->last_proc = 0;
 	if (c->plan.mapped && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with normal maps, jp_set_normal_maps)");

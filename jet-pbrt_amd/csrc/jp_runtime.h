@@ -201,6 +201,8 @@ struct JpContext
 	DevBuf var_mom, var_plane, dn_nv;
 	hipEvent_t dv_ev[2] = { nullptr, nullptr }; bool dv_timed = false;
 	int last_dv = 0, last_dv_demod = 0; float last_dv_sigma[3] = { 0.f, 0.f, 0.f };
+	// adaptive sampling (jp_adaptive.h): what the last jp_render_adaptive* / jp_adaptive_probe did (jp_get_adaptive_info); its per-pixel state lives in the call
+	JpAdaptiveInfo ad_info = {};
 };
 // jp_pick.h / jp_env.h (included last) define the upload's table steps
 static int upload_light_table(JpContext* c, SceneTables& T, ScenePlan& plan, const JpScene* s, const std::vector<float>& area);

@@ -414,6 +414,29 @@ int jp_host_render_variance(void* h, int W, int H, int spp, int maxdepth, unsign
 	return JP_OK;
 }
 
+// FFilm::SetAdaptive(threshold, min_spp, step_spp, dilate) [+ SetHDR, RequestGuides(guide_spp) / RequestDenoise(guide_spp, { varianceGuided })] -> Render (spp: the most a pixel
+// takes) -> the film, FFilm::SampleCounts() and FFilm::Variance(); any output may be null
+int jp_host_render_adaptive(void* h, int W, int H, int spp, int maxdepth, unsigned seed, int device, float threshold, int min_spp, int step_spp, int dilate, int guide_spp, int denoise, int hdr,
+                            float* film_out, int32_t* counts_out, float* variance_out)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!hs->integ || hs->integDepth != maxdepth) { hs->integ.reset(new FGpuPathIntegrator(maxdepth, device)); hs->integDepth = maxdepth; }
+	hs->integ->SetShard(0, 1);
+	FFilm film(W, H);
+	if (hdr) film.SetHDR();
+	film.SetAdaptive(threshold, min_spp, step_spp, dilate != 0);
+	if (denoise) { FDenoiseOptions o; o.varianceGuided = true; film.RequestDenoise(guide_spp, o); } else if (guide_spp > 0) film.RequestGuides(guide_spp);
+	FCounterSampler sampler(spp, seed);
+	hs->integ->Render(hs->scene.get(), &sampler, &film, 16);
+	if (hs->integ->LastStatus() != JP_OK) return hs->integ->LastStatus();
+	const size_t n = (size_t)W * H;
+	if (film.SampleCounts().size() != n || film.Variance().size() != n) return JP_ERR_DEVICE;
+	if (film_out) for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) { const FColor& c = static_cast<const FFilm&>(film)(x, y); float* o = film_out + 3 * ((size_t)y * W + x); o[0] = c.r; o[1] = c.g; o[2] = c.b; }
+	if (counts_out) std::memcpy(counts_out, film.SampleCounts().data(), n * sizeof(int32_t));
+	if (variance_out) std::memcpy(variance_out, film.Variance().data(), n * sizeof(float));
+	return JP_OK;
+}
+
 // The linear-light film: FFilm::SetHDR(hdr) / SetSampleClamp(sample_clamp) / SetToneMap(curve, auto_exposure, ev, white) when tonemap != 0 [+ RequestDeviceLDR(true) when
 // ldr_only] -> Render -> the fp32 film (unless ldr_only), the 8-bit pixels (with a tone map or ldr_only), FFilm::ToneMapScale() -> optionally SaveAsImage(filename, type).
 // Any output may be null.

@@ -1,6 +1,6 @@
 // jet-pbrt_amd/host/cli_main.cc -- the reference's command line (main.cc:113-163) on the GPU integrator:
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
-//             [--denoise [variance]] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
+//             [--adaptive THRESHOLD [--min-spp N] [--spp-step N] [--no-adaptive-dilate]] [--denoise [variance]] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
 //             [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]
 //             [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]
 //             [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]
@@ -34,6 +34,10 @@
 // 1 .. 1024); --aov: the guides as images PREFIX_albedo, PREFIX_normal (n * 0.5 + 0.5), PREFIX_depth (t / max t) in the chosen format.
 // --denoise variance: the variance-guided filter on a variance render instead (FDenoiseOptions::varianceGuided; needs spp >= 2); --aov then, and without --denoise
 // at spp >= 2, also writes PREFIX_variance (v / max v), the per-pixel variance of the film's mean luminance (FFilm::RequestVariance).
+// --adaptive THRESHOLD: adaptive sampling (FFilm::SetAdaptive): a pixel stops once the relative standard error of its mean luminance is below THRESHOLD; spp
+// is the most a pixel takes, --min-spp (default 8) what every pixel takes first, --spp-step (default 8) what a pass adds; --no-adaptive-dilate tests each pixel
+// alone instead of with its 3 x 3 neighbourhood.  --aov then also writes PREFIX_samples (n / spp) and PREFIX_variance.  The path integrator; the image is encoded
+// on the host (no --tonemap / --exposure with it); with --denoise it takes the variance-guided filter.
 // sceneid 0 = Cornell box, 1 = bunny scene; spp defaults to 50, the film to 1024 x 1024, the output to
 // <scene name>_<spp>.bmp, as in the reference.  The scene scripts are the calls of main.cc:13-111; the meshes are
 // read from DIR/cornellbox/{light,floor,shortbox,tallbox,left,right}.obj and DIR/bunny/bunny.obj (the reference
@@ -121,6 +125,7 @@ int main(int argc, char* argv[])
 {
 	int width = 1024, height = 1024, samples_per_pixel = 50;     // main.cc:115,119
 	std::string assets = "scene", out, format = "bmp", integratorName = "path";
+	bool adaptive = false, adaptiveDilate = true; float adaptiveThreshold = 0.f; int minSpp = 8, sppStep = 8;
 	bool denoise = false, denoiseVariance = false; int guideSpp = 8; std::string aov; int lightSampling = JP_LIGHTS_ALL, estimator = JP_ESTIMATOR_NEE;
 	std::string envmap; int envUp = JP_ENV_UP_Y; float envScale = 1.f;
 	FSmoothing smoothing;
@@ -131,7 +136,7 @@ int main(int argc, char* argv[])
 	int floorTexture = JP_PROC_NONE, floorOctaves = 0; float floorScale = 0.02f; bool floorAntialias = true, floorOptions = false;
 	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
-	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--denoise [variance]] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
+	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--adaptive THRESHOLD [--min-spp N] [--spp-step N] [--no-adaptive-dilate]] [--denoise [variance]] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
 	fprintf(stderr, "          [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]\n");
 	fprintf(stderr, "          [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]\n");
 	fprintf(stderr, "          [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]\n");
@@ -149,6 +154,10 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--reference-tree")) setenv("JETPBRT_REFERENCE_TREE", "1", 1);   // FScene::referenceTree: the reference's own BVH and traversal semantics
 		else if (!strcmp(argv[i], "--reference-tree=certified")) setenv("JETPBRT_REFERENCE_TREE", "2", 1);   // ... with the certified walk (FScene::certifiedWalk)
 		else if (!strcmp(argv[i], "--denoise")) { denoise = true; if (i + 1 < argc && !strcmp(argv[i + 1], "variance")) { denoiseVariance = true; i++; } }
+		else if (!strcmp(argv[i], "--adaptive") && i + 1 < argc) { adaptive = true; adaptiveThreshold = (float)atof(argv[++i]); if (!(adaptiveThreshold >= 0.f) || !std::isfinite(adaptiveThreshold)) { fprintf(stderr, "--adaptive THRESHOLD must be finite and >= 0\n"); return 5; } }
+		else if (!strcmp(argv[i], "--min-spp") && i + 1 < argc) { minSpp = atoi(argv[++i]); if (minSpp < 2) { fprintf(stderr, "--min-spp must be >= 2\n"); return 5; } }
+		else if (!strcmp(argv[i], "--spp-step") && i + 1 < argc) { sppStep = atoi(argv[++i]); if (sppStep < 1) { fprintf(stderr, "--spp-step must be >= 1\n"); return 5; } }
+		else if (!strcmp(argv[i], "--no-adaptive-dilate")) adaptiveDilate = false;
 		else if (!strcmp(argv[i], "--guide-spp") && i + 1 < argc) { guideSpp = atoi(argv[++i]); if (guideSpp < 1 || guideSpp > 1024) { fprintf(stderr, "--guide-spp must be 1 .. 1024\n"); return 5; } }
 		else if (!strcmp(argv[i], "--aov") && i + 1 < argc) aov = argv[++i];
 		else if (!strcmp(argv[i], "--light-sampling") && i + 1 < argc)
@@ -324,7 +333,10 @@ int main(int argc, char* argv[])
 	else if (integratorName == "debug") integrator.reset(new FDebugIntegrator());
 	else if (integratorName == "recursive") integrator.reset(new FPathIntegratorRecursive(5));
 	else integrator.reset(new FPathIntegratorIteration(5));
-	if (format != "hdr") film.RequestDeviceLDR(true);             // BMP / PPM: gamma_encoding runs on the GPU, 3 bytes per pixel come back
+	if (adaptive && haveToneMap) { fprintf(stderr, "--adaptive delivers the fp32 film: no --tonemap / --exposure / --white with it\n"); return 5; }
+	if (adaptive && denoise) denoiseVariance = true;              // (the adaptive render's own variance plane feeds the filter)
+	if (adaptive) film.SetAdaptive(adaptiveThreshold, std::min(minSpp, samples_per_pixel), sppStep, adaptiveDilate);
+	if (format != "hdr" && !adaptive) film.RequestDeviceLDR(true);             // BMP / PPM: gamma_encoding runs on the GPU, 3 bytes per pixel come back
 	if (hdr) film.SetHDR();
 	if (sampleClamp > 0.f) film.SetSampleClamp(sampleClamp);
 	if (haveToneMap) film.SetToneMap(toneMap);                    // (turns HDR on)
@@ -352,6 +364,12 @@ int main(int argc, char* argv[])
 			const Float z = zmax > 0 ? film.Depth()[i] / zmax : 0; fz(x, y) = FColor(z, z, z);
 		}
 		if (!fa.SaveAsImage(aov + "_albedo", t) || !fn.SaveAsImage(aov + "_normal", t) || !fz.SaveAsImage(aov + "_depth", t)) return 4;
+		if (film.SampleCounts().size() == n)
+		{   // the samples each pixel took, n / spp
+			FFilm fs(width, height);
+			for (size_t i = 0; i < n; i++) { const Float v = (Float)film.SampleCounts()[i] / (Float)samples_per_pixel; fs((int)(i % width), (int)(i / width)) = FColor(v, v, v); }
+			if (!fs.SaveAsImage(aov + "_samples", t)) return 4;
+		}
 		if (film.Variance().size() == n)
 		{   // the variance plane, v / max v
 			Float vmax = 0; for (Float v : film.Variance()) vmax = v > vmax ? v : vmax;

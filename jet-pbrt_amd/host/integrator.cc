@@ -29,6 +29,9 @@ struct HipApi
 	int (*upload_scene_textured)(JpContext*, const JpScene*, const JpTextures*) = nullptr;   // (looked up, needed by textured scenes only)
 	int (*render_variance)(JpContext*, const JpRenderParams*, float*, float*) = nullptr;                                                              // (FFilm::RequestVariance)
 	int (*render_denoised_variance)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*, float*) = nullptr;   // (... with guides, the variance-guided filter or 8-bit bytes)
+	int (*render_adaptive)(JpContext*, const JpRenderParams*, const JpAdaptive*, float*, int32_t*, float*) = nullptr;                                  // (FFilm::SetAdaptive)
+	int (*render_guides)(JpContext*, const JpRenderParams*, int32_t, float*, float*, float*) = nullptr;                                               // (... with guides)
+	int (*denoise_variance)(JpContext*, const JpDenoiseParams*, const float*, const float*, const float*, const float*, const float*, float*, float*) = nullptr;   // (... and the variance-guided filter)
 	int (*render_denoised)(JpContext*, const JpRenderParams*, int32_t, const JpDenoiseParams*, float*, uint8_t*, float*, float*, float*) = nullptr;   // (looked up, needed by FFilm::RequestGuides / RequestDenoise only)
 	int (*set_light_sampling)(JpContext*, const JpLightSampling*) = nullptr;                 // (looked up, needed by FScene::SetLightSampling only)
 	int (*set_environment_map)(JpContext*, const JpEnvMap*) = nullptr;                       // (looked up, needed by FScene::SetEnvironmentMap only)
@@ -72,6 +75,9 @@ HipApi& Api()
 		api.render_denoised = (decltype(api.render_denoised))dlsym(api.lib, "jp_render_denoised");
 		api.render_variance = (decltype(api.render_variance))dlsym(api.lib, "jp_render_variance");
 		api.render_denoised_variance = (decltype(api.render_denoised_variance))dlsym(api.lib, "jp_render_denoised_variance");
+		api.render_adaptive = (decltype(api.render_adaptive))dlsym(api.lib, "jp_render_adaptive");
+		api.render_guides = (decltype(api.render_guides))dlsym(api.lib, "jp_render_guides");
+		api.denoise_variance = (decltype(api.denoise_variance))dlsym(api.lib, "jp_denoise_variance");
 		api.set_light_sampling = (decltype(api.set_light_sampling))dlsym(api.lib, "jp_set_light_sampling");
 		api.set_environment_map = (decltype(api.set_environment_map))dlsym(api.lib, "jp_set_environment_map");
 		api.set_estimator = (decltype(api.set_estimator))dlsym(api.lib, "jp_set_estimator");
@@ -297,7 +303,34 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 	const bool varFilter = film->wantDenoise && film->denoise.varianceGuided, wantVar = film->wantVariance || varFilter;
 	if (wantVar && film->wantDenoise && !varFilter)
 	{ fprintf(stderr, "FGpuPathIntegrator::Render: RequestVariance with RequestDenoise needs the variance-guided filter (FDenoiseOptions::varianceGuided)\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
-	if (wantVar && (film->wantGuides || wantLDR))
+	std::vector<int32_t> gcnt; bool countersRead = false;
+	if (film->wantAdaptive)
+	{   // FFilm::SetAdaptive: the adaptive render delivers the film, the counts and its own variance plane; guides and the variance-guided filter follow as calls of their own
+		if (!api.render_adaptive || !api.render_guides || !api.denoise_variance) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_render_adaptive\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+		if (film->wantDenoise && !varFilter) { fprintf(stderr, "FGpuPathIntegrator::Render: SetAdaptive with RequestDenoise needs the variance-guided filter (FDenoiseOptions::varianceGuided)\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+		if (wantLDR) { fprintf(stderr, "FGpuPathIntegrator::Render: SetAdaptive delivers the fp32 film (no device tone map / RequestDeviceLDR with it)\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+		const size_t n = (size_t)rp.width * rp.height;
+		gvar.assign(n, 0.f); gcnt.assign(n, 0);
+		JpAdaptive ad; std::memset(&ad, 0, sizeof(ad));
+		ad.struct_bytes = (int32_t)sizeof(ad); ad.min_spp = film->adaptMin; ad.step_spp = film->adaptStep; ad.max_spp = 0; ad.threshold = film->adaptThreshold; ad.dilate = film->adaptDilate ? 1 : 0;
+		lastStatus = api.render_adaptive(ctx, &rp, &ad, rgb.data(), gcnt.data(), gvar.data());
+		if (lastStatus == JP_OK) { api.get_counters(ctx, &counters); countersRead = true; }   // (before the guides' render: the counters are the adaptive render's)
+		if (lastStatus == JP_OK && film->wantGuides)
+		{
+			galb.assign(3 * n, 0.f); gnrm.assign(3 * n, 0.f); gdep.assign(n, 0.f);
+			lastStatus = api.render_guides(ctx, &rp, film->guideSpp_, galb.data(), gnrm.data(), gdep.data());
+			if (lastStatus == JP_OK && varFilter)
+			{
+				JpDenoiseParams dp; std::memset(&dp, 0, sizeof(dp));
+				dp.struct_bytes = (int32_t)sizeof(dp); dp.width = rp.width; dp.height = rp.height; dp.iterations = film->denoise.iterations;
+				dp.sigma_color = film->denoise.sigmaColor; dp.sigma_normal = film->denoise.sigmaNormal; dp.sigma_depth = film->denoise.sigmaDepth; dp.demodulate = film->denoise.demodulate ? 1 : -1;
+				std::vector<float> out(3 * n);
+				lastStatus = api.denoise_variance(ctx, &dp, rgb.data(), galb.data(), gnrm.data(), gdep.data(), gvar.data(), out.data(), nullptr);
+				if (lastStatus == JP_OK) rgb.swap(out);
+			}
+		}
+	}
+	else if (wantVar && (film->wantGuides || wantLDR))
 	{   // FFilm::RequestVariance / the variance-guided RequestDenoise: the variance render, guides, filter and tone map in one call (no guides asked for: one camera sample of them, dropped)
 		if (!api.render_denoised_variance) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_render_denoised_variance\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
 		const size_t n = (size_t)rp.width * rp.height;
@@ -346,14 +379,15 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 		film->albedo.resize(n); film->normal.resize(n); film->depth.swap(gdep);
 		for (size_t i = 0; i < n; i++) { film->albedo[i] = FColor(galb[3 * i], galb[3 * i + 1], galb[3 * i + 2]); film->normal[i] = FVector3(gnrm[3 * i], gnrm[3 * i + 1], gnrm[3 * i + 2]); }
 	}
-	if (wantVar) film->variance.swap(gvar);
+	if (wantVar || film->wantAdaptive) film->variance.swap(gvar);
+	if (film->wantAdaptive) film->sampleCounts.swap(gcnt);
 	if (wantLDR) { film->ldr8.swap(ldr); film->floatValid = floatFilm; }   // (after AddColor: any later change of a pixel drops the bytes again)
 	if (film->haveToneMap)
 	{   // FFilm::ToneMapScale: the exposure scale the transform used
 		JpToneMapInfo ti; std::memset(&ti, 0, sizeof(ti)); ti.struct_bytes = (int32_t)sizeof(ti);
 		if (api.get_tonemap_info(ctx, &ti) == JP_OK) film->toneMapScale = ti.scale_last;
 	}
-	api.get_counters(ctx, &counters);
+	if (!countersRead) api.get_counters(ctx, &counters);
 	fprintf(stderr, "finish rendering ...\n");
 	fprintf(stderr, "FIntegrator::Render used %f seconds.\n", (float)(counters.render_ms / 1000.0));   // integrator.cc:77-79
 }

@@ -423,6 +423,12 @@ public:
 	// variance-guided filter (FDenoiseOptions::varianceGuided), which reads that plane; that filter asks for the variance render by itself.
 	void RequestVariance() { wantVariance = true; }
 	const std::vector<Float>& Variance() const { return variance; }
+	// Adaptive sampling (INTEGRATION.md "Adaptive sampling"): the integrator stops each pixel once the relative standard error of its mean luminance is below
+	// `threshold` (jp_render_adaptive: minSpp samples everywhere, then stepSpp more per pass for the pixels still above it -- with dilate, and their neighbours -- up
+	// to the sampler's samples per pixel).  After Render SampleCounts() holds the samples each pixel took and Variance() the variance of its mean, row-major, top
+	// row first; with RequestDenoise(n, { varianceGuided }) the filter reads that plane.  The path integrator only; not together with a device tone map or LDR film.
+	void SetAdaptive(Float threshold, int minSpp = 8, int stepSpp = 8, bool dilate = true) { wantAdaptive = true; adaptThreshold = threshold; adaptMin = minSpp; adaptStep = stepSpp; adaptDilate = dilate; }
+	const std::vector<int32_t>& SampleCounts() const { return sampleCounts; }
 	// The linear-light film (INTEGRATION.md "Film"): SetHDR keeps radiance above 1 (SaveAsImage(HDR) then writes the unclamped film, and a denoise request filters
 	// it unclamped), SetSampleClamp tames fireflies sample by sample, SetToneMap -- which turns HDR on: highlights above 1 are what the curves compress -- has the
 	// integrator deliver the 8-bit bytes of BMP / PPM through exposure and a tone curve on the GPU (next to the fp32 film, or instead of it with RequestDeviceLDR).
@@ -435,6 +441,7 @@ public:
 	bool wantGuides = false, wantDenoise = false; int guideSpp_ = 8; FDenoiseOptions denoise;
 	std::vector<FColor> albedo; std::vector<FVector3> normal; std::vector<Float> depth;
 	bool wantVariance = false; std::vector<Float> variance;
+	bool wantAdaptive = false, adaptDilate = true; Float adaptThreshold = 0; int adaptMin = 8, adaptStep = 8; std::vector<int32_t> sampleCounts;
 	int width, height; std::vector<FColor> pixels;
 	bool wantLDR = false, ldrOnly = false; std::vector<uint8_t> ldr8;   // R G B per pixel, top row first
 	bool floatValid = true;                                            // false after an LDR-only render: the fp32 pixels were not downloaded
