@@ -696,6 +696,40 @@ int  jp_camera_rays(JpContext* ctx, const JpRenderParams* params, int32_t n, con
  * far end): *focus_out = t / |d0|, the focus_distance that puts the hit on the plane of focus; a miss: JP_OK and 0 */
 int  jp_focus_distance(JpContext* ctx, float fx, float fy, float* focus_out);
 
+/* Projections (additive to ABI 7; INTEGRATION.md "Projections" has the definitions).  The reference's camera is the perspective pinhole.  A projection replaces
+ * how the camera ray of a film position is formed -- nothing else: same draws (dims 0, 1; the path's first bounce starts at dim 2), same queue records, same bounces.
+ * With a = fx / res_x - 0.5, b = 0.5 - fy / res_y and the unit axes ex, ey, ez of right, up, front:
+ *   JP_PROJ_ORTHOGRAPHIC  origin pos + right * (a * s) + up * (b * s), direction ez (s = ortho_scale; 0 means 1): the rectangle the pinhole's film spans at
+ *                         parameter distance s, whatever the depth
+ *   JP_PROJ_EQUIRECT      origin pos, direction ez * (cos theta * cos phi) + ex * (cos theta * sin phi) + ey * sin theta, phi = 2 pi a, theta = pi b: a lat-long
+ *                         panorama -- the centre looks along front, the top row toward up, column 0 directly behind
+ *   JP_PROJ_FISHEYE       origin pos, equidistant: x = fx - res_x / 2, y = res_y / 2 - fy, rho = |(x, y)|, theta = min(rho / R * fov / 2, pi), direction
+ *                         ez * cos theta + (ex * x + ey * y) * (sin theta / rho); R the half-diagonal, half-width or half-height in pixels (fit); fov_deg in
+ *                         (0, 360], 0 means 180.  Every pixel has a ray
+ * Render-time state like the lens: read by the next jp_render* / jp_render_guides* / jp_camera_rays; NULL or kind 0: the pinhole, the kernels and films of a context
+ * that never heard of a projection.  Every integrator; JpOptions.fused falls back to the per-bounce launches; a lens (radius > 0) together with a projection is
+ * refused by the render (JP_ERR_UNSUPPORTED).  Equirect and fisheye need perpendicular camera axes (pairwise |dot| of the unit axes <= 1e-3), checked at render
+ * time on the uploaded camera.  The ray cone of a camera ray starts with the projection's spread (equirect pi / res_y, fisheye (fov / 2) / R, orthographic 0: a
+ * first hit reads the finest mip level).  jp_focus_distance stays the pinhole's.  A projection owns no device memory. */
+enum { JP_PROJ_PERSPECTIVE = 0, JP_PROJ_ORTHOGRAPHIC = 1, JP_PROJ_EQUIRECT = 2, JP_PROJ_FISHEYE = 3 };
+enum { JP_FIT_DIAGONAL = 0, JP_FIT_WIDTH = 1, JP_FIT_HEIGHT = 2 };
+typedef struct JpProjection { int32_t struct_bytes, kind; float ortho_scale, fov_deg; int32_t fit; } JpProjection;
+/* validates (jp_check_projection: JP_ERR_INVALID_ARGUMENT with a message, the projection in force stays): kind 0 .. 3; ortho_scale finite and >= 0; fov_deg finite
+ * in [0, 360]; fit 0 .. 2 */
+int  jp_set_projection(JpContext* ctx, const JpProjection* projection);
+/* the projection in force (all 0: the pinhole); the last jp_render* ran k_raygen_proj / the projected branch of k_other, and the cone spread it used (0 when it
+ * did not) */
+typedef struct JpProjectionInfo { int32_t struct_bytes, kind; float ortho_scale, fov_deg; int32_t fit, projected_last_render; float gamma0_last_render; } JpProjectionInfo;
+int  jp_get_projection_info(JpContext* ctx, JpProjectionInfo* out);
+/* pure host code, no GPU needed: the validation of jp_set_projection with its status and message */
+int  jp_check_projection(const JpProjection* projection);
+/* pure host code: the JpProjectionPlan (include/jp_projection.h) the kernels receive by value for `projection` on `camera`, with the checks the render makes on the
+ * camera.  plan_out NULL: *bytes receives its size and nothing is copied.  projection NULL or kind 0: JP_OK and 0 bytes (no plan: the pinhole). */
+int  jp_projection_plan(const JpCamera* camera, const JpProjection* projection, void* plan_out, int64_t capacity, int64_t* bytes);
+/* pure host code: the very function the device runs (include/jp_projection.h) for n film positions fxfy (2n floats: pixel + draws 0, 1) -> origin, dir 3n floats
+ * each.  projection NULL or kind 0: the pinhole's rays. */
+int  jp_projection_rays(const JpCamera* camera, const JpProjection* projection, int32_t n, const float* fxfy, float* origin, float* dir);
+
 /* Film (additive to ABI 7; INTEGRATION.md "Film" has the definitions in full).  The reference's film holds Clamp01(sum / spp); that stays the default.  The film state
  * below adds the linear-light film: unclamped output, a per-sample firefly clamp, a luminance histogram for auto-exposure and a display transform.  All of it is
  * fp32, operation by operation, no contraction (include/jp_film.h, include/jp_tonemap.h: the text the kernels and the pure-host entry points both compile), so

@@ -579,6 +579,78 @@ def lens_rays(camera, l, fxfy, u=None):
     return o, d
 
 
+JP_PROJ_PERSPECTIVE, JP_PROJ_ORTHOGRAPHIC, JP_PROJ_EQUIRECT, JP_PROJ_FISHEYE = 0, 1, 2, 3
+JP_FIT_DIAGONAL, JP_FIT_WIDTH, JP_FIT_HEIGHT = 0, 1, 2
+PROJECTIONS = {"perspective": JP_PROJ_PERSPECTIVE, "ortho": JP_PROJ_ORTHOGRAPHIC, "orthographic": JP_PROJ_ORTHOGRAPHIC, "equirect": JP_PROJ_EQUIRECT,
+               "fisheye": JP_PROJ_FISHEYE}
+FITS = {"diagonal": JP_FIT_DIAGONAL, "width": JP_FIT_WIDTH, "height": JP_FIT_HEIGHT}
+
+
+class JpProjection(C.Structure):
+    """include/jetpbrt_amd.h: JpProjection (jp_set_projection); struct_bytes = sizeof(JpProjection)"""
+    _fields_ = [("struct_bytes", C.c_int32), ("kind", C.c_int32), ("ortho_scale", C.c_float), ("fov_deg", C.c_float), ("fit", C.c_int32)]
+
+
+class JpProjectionInfo(C.Structure):
+    _fields_ = [("struct_bytes", C.c_int32), ("kind", C.c_int32), ("ortho_scale", C.c_float), ("fov_deg", C.c_float), ("fit", C.c_int32),
+                ("projected_last_render", C.c_int32), ("gamma0_last_render", C.c_float)]
+
+
+class JpProjectionPlan(C.Structure):
+    """include/jp_projection.h: JpProjectionPlan, what the kernels receive by value (jp_projection_plan)"""
+    _fields_ = [("kind", C.c_int32), ("scale", C.c_float), ("half_fov", C.c_float), ("R", C.c_float), ("gamma0", C.c_float),
+                ("ex", C.c_float * 3), ("ey", C.c_float * 3), ("ez", C.c_float * 3)]
+
+
+def projection(kind, ortho_scale=0.0, fov_deg=0.0, fit=JP_FIT_DIAGONAL):
+    """A JpProjection (or pass one through).  kind: JP_PROJ_* or "ortho" / "equirect" / "fisheye" / "perspective"; fit: JP_FIT_* or "diagonal" / "width" / "height";
+    ortho_scale 0: 1, fov_deg 0: 180"""
+    if isinstance(kind, JpProjection):
+        return kind
+    k = PROJECTIONS[kind] if isinstance(kind, str) else kind
+    f = FITS[fit] if isinstance(fit, str) else fit
+    return JpProjection(C.sizeof(JpProjection), k, ortho_scale, fov_deg, f)
+
+
+def check_projection(p):
+    """jp_check_projection: the validation of jp_set_projection (pure host code, no GPU); raises JetPbrtError with its message.  p: a JpProjection or None"""
+    L = hip_lib()
+    st = L.jp_check_projection(_lens_ptr(p))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+
+
+def projection_plan(camera, p):
+    """jp_projection_plan: the JpProjectionPlan of projection `p` (a JpProjection or None) on a JpCamera (pure host code, no GPU) -> JpProjectionPlan, or None
+    for the pinhole"""
+    L = hip_lib()
+    n = C.c_int64(0)
+    plan = JpProjectionPlan()
+    st = L.jp_projection_plan(C.byref(camera), _lens_ptr(p), C.byref(plan), C.sizeof(plan), C.byref(n))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    if n.value == 0:
+        return None
+    if n.value != C.sizeof(plan):
+        raise JetPbrtError("jp_projection_plan: the library's JpProjectionPlan has %d bytes, this binding's %d" % (n.value, C.sizeof(plan)))
+    return plan
+
+
+def projection_rays(camera, p, fxfy):
+    """jp_projection_rays: the camera rays the device forms (include/jp_projection.h) for film positions fxfy (n, 2) under projection `p` (a JpProjection, or
+    None for the pinhole) -> (origin (n, 3), dir (n, 3)) float32.  Pure host code."""
+    import numpy as np
+    f = np.ascontiguousarray(fxfy, np.float32).reshape(-1, 2)
+    n = f.shape[0]
+    o = np.zeros((n, 3), np.float32); d = np.zeros((n, 3), np.float32)
+    q = lambda x: x.ctypes.data_as(C.c_void_p)
+    L = hip_lib()
+    st = L.jp_projection_rays(C.byref(camera), _lens_ptr(p), n, q(f), q(o), q(d))
+    if st != JP_OK:
+        raise JetPbrtError("jetpbrt_amd status %d: %s" % (st, L.jp_last_error().decode()))
+    return o, d
+
+
 JP_FILM_BINS = 256
 JP_CURVE_CLAMP, JP_CURVE_REINHARD, JP_CURVE_ACES, JP_CURVE_HABLE = 0, 1, 2, 3
 JP_EXPOSURE_MANUAL, JP_EXPOSURE_AUTO = 0, 1
@@ -965,6 +1037,7 @@ def host_lib():
         L.jp_host_scene_set_light_sampling.argtypes = [C.c_void_p, C.c_int]
         L.jp_host_scene_set_estimator.argtypes = [C.c_void_p, C.c_int]
         L.jp_host_scene_set_lens.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float]
+        L.jp_host_scene_set_projection.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int]
         L.jp_host_last_focus.restype = C.c_float
         L.jp_host_last_focus.argtypes = [C.c_void_p]
         L.jp_host_scene_envmap.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -1085,6 +1158,11 @@ def hip_lib():
         L.jp_lens_plan.argtypes = [C.POINTER(JpCamera), C.POINTER(JpLens), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
         L.jp_lens_rays.argtypes = [C.POINTER(JpCamera), C.POINTER(JpLens), C.c_int32] + [C.c_void_p] * 4
         L.jp_camera_rays.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32] + [C.c_void_p] * 6
+        L.jp_set_projection.argtypes = [C.c_void_p, C.POINTER(JpProjection)]
+        L.jp_get_projection_info.argtypes = [C.c_void_p, C.POINTER(JpProjectionInfo)]
+        L.jp_check_projection.argtypes = [C.POINTER(JpProjection)]
+        L.jp_projection_plan.argtypes = [C.POINTER(JpCamera), C.POINTER(JpProjection), C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
+        L.jp_projection_rays.argtypes = [C.POINTER(JpCamera), C.POINTER(JpProjection), C.c_int32] + [C.c_void_p] * 3
         L.jp_focus_distance.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_float)]
         L.jp_render_denoised.argtypes = [C.c_void_p, C.POINTER(JpRenderParams), C.c_int32, C.POINTER(JpDenoiseParams)] + [C.c_void_p] * 5
         L.jp_set_film.argtypes = [C.c_void_p, C.POINTER(JpFilm)]
@@ -1492,6 +1570,21 @@ class Context:
         i = JpVarianceInfo()
         i.struct_bytes = C.sizeof(JpVarianceInfo)
         self._check(self.lib.jp_get_variance_info(self.h, C.byref(i)))
+        return i
+
+    def set_projection(self, kind=None, ortho_scale=0.0, fov_deg=0.0, fit=JP_FIT_DIAGONAL):
+        """jp_set_projection for the next render / guides / camera_rays: a kind (JP_PROJ_* or its name, with ortho_scale, fov_deg, fit), a JpProjection, or None
+        for the pinhole"""
+        if kind is None:
+            self._check(self.lib.jp_set_projection(self.h, None))
+            return
+        p = projection(kind, ortho_scale, fov_deg, fit)
+        self._check(self.lib.jp_set_projection(self.h, C.byref(p)))
+
+    def projection_info(self):
+        i = JpProjectionInfo()
+        i.struct_bytes = C.sizeof(JpProjectionInfo)
+        self._check(self.lib.jp_get_projection_info(self.h, C.byref(i)))
         return i
 
     def lens_info(self):

@@ -49,6 +49,41 @@ __global__ void __launch_bounds__(JP_BLOCK) k_raygen_list(SceneView sc, Queues q
 	if (threadIdx.x == 0) q.blk_q[0][b] = filled;
 }
 
+// k_raygen_list_proj: the same twin for k_raygen_proj (jp_set_projection in force)
+__global__ void __launch_bounds__(JP_BLOCK) k_raygen_list_proj(SceneView sc, Queues q, RenderConst rc, DevCounters* cnt, JpProjectionPlan pp, const unsigned int* __restrict__ list, unsigned int n_act)
+{
+	const unsigned int total = n_act * (unsigned int)rc.sbatch;
+	const unsigned int nchunks = (total + JP_BLOCK - 1) / JP_BLOCK;
+	const unsigned int G = gridDim.x, b = blockIdx.x;
+	if (b == 0 && threadIdx.x == 0) { cnt->n_queue[0] = total; cnt->n_queue[1] = 0; cnt->n_shadow = 0; }
+	unsigned int filled = 0;
+	const unsigned int K = (nchunks + G - 1) / G;
+	for (unsigned int k = 0, j0 = 0; k < K; k++, j0 += JP_BLOCK)
+	{
+		const unsigned int c = b + k * G;
+		if (c >= nchunks) break;
+		const unsigned int slot = c * JP_BLOCK + threadIdx.x;
+		if (slot < total)
+		{
+			const unsigned int i = b * q.R + j0 + threadIdx.x;
+			const unsigned int sl = slot / n_act, pos = slot - sl * n_act;
+			const int pix = list ? (int)list[pos] : (int)pos, s = rc.s0 + (int)sl;
+			int x, y; pixel_of(rc, pix, x, y);
+			const uint32_t key = jp_rng_key(rc.seed, (uint32_t)x, (uint32_t)y, (uint32_t)s);
+			const float fx = (float)x + rngf(rc, key, 0), fy = (float)y + rngf(rc, key, 1);
+			V3 o, dir;
+			projected_ray(sc.cam, pp, fx, fy, o, dir);
+			q.ray_o[0][i] = make_float4(o.x, o.y, o.z, __int_as_float((int)slot));
+			q.ray_d[0][i] = make_float4(dir.x, dir.y, dir.z, __int_as_float(MK_FLAGS(0, 0, 2)));
+			q.beta[0][i] = make_float4(1.f, 1.f, 1.f, __int_as_float((int)key));
+			q.lacc[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+		}
+		const unsigned int left = total - c * JP_BLOCK;
+		filled += left < JP_BLOCK ? left : JP_BLOCK;
+	}
+	if (threadIdx.x == 0) q.blk_q[0][b] = filled;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // k_resolve_list: the resolve twin.  For list position pos (pixel list[pos]; list null: the identity) the batch's sbatch samples from sample index s0 enter the
 // pixel's state in sample order: sum.xyz the unscaled rgb sum after the sample clamp, sum.w the count (int bits), mom = (mean, m2).  The state is zero before
@@ -296,6 +331,7 @@ int adaptive_render(JpContext* c, const JpRenderParams* rp, const JpAdaptive* ad
 	c->last_textured = p.textured ? 1 : 0; c->last_picked = p.pick ? 1 : 0; c->last_mapped = p.env ? 1 : 0; c->last_mis = c->estimator == JP_ESTIMATOR_MIS ? 1 : 0;
 	c->last_smooth = p.smooth ? 1 : 0; c->last_nmapped = p.mapped ? 1 : 0; c->last_sampled = ((p.textured && p.sm.tex) || (p.mapped && p.sm.map)) ? 1 : 0;
 	c->last_mip = p.textured && p.mip_on > 0 ? 1 : 0; c->last_proc = p.textured && p.proc_on > 0 ? 1 : 0; c->last_lens = c->lens_on ? 1 : 0;
+	c->last_proj = 0; c->last_proj_gamma0 = 0.f;
 	adaptive_note(c, a);
 
 	const size_t nfilm = (size_t)rp->width * rp->height;
@@ -328,6 +364,9 @@ int adaptive_render(JpContext* c, const JpRenderParams* rp, const JpAdaptive* ad
 		const ExtendLaunch ek = extend_kernel(p, generic);
 		JpLensPlan lp;
 		if (const int e = lens_plan_of(c, lp); e != JP_OK) return e;
+		JpProjectionPlan pp;
+		if (const int e = proj_plan_of(c, pp); e != JP_OK) return e;
+		if (c->proj_on) { c->last_proj = 1; c->last_proj_gamma0 = pp.gamma0; }
 		const JpAdaptShard ash = { rp->width, rp->height, sh.band, sh.index, sh.count };
 		const AdaptConst ac = adapt_const(a, ash, npix);
 		const float sample_clamp = c->film_on ? c->film_state.sample_clamp : 0.f;
@@ -359,6 +398,7 @@ int adaptive_render(JpContext* c, const JpRenderParams* rp, const JpAdaptive* ad
 			TexView tv = p.tv; tv.side = c->side.get<unsigned int>();
 			MipView mv_cone = {};
 			if (tex && (p.mip_on > 0 || p.proc_aa > 0)) { mv_cone = p.mv; if (const int e = ensure_cone(c, cap, mv_cone); e != JP_OK) return e; }
+			if (c->proj_on) mv_cone.gamma0 = pp.gamma0;
 			MisView mv = {};
 			if (mis) if (const int e = ensure_mis_side(c, cap, mv); e != JP_OK) return e;
 			NormView nv = p.nv;
@@ -373,7 +413,8 @@ int adaptive_render(JpContext* c, const JpRenderParams* rp, const JpAdaptive* ad
 				rc.s0 = n_cur + b0; rc.sbatch = std::min(sbatch, ns - b0);
 				{
 					Stamper t(c, CLS_OTHER);
-					if (c->lens_on) hipLaunchKernelGGL(k_raygen_list<true>, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, lp, st.list_or_null(), n_act);
+					if (c->proj_on) hipLaunchKernelGGL(k_raygen_list_proj, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, pp, st.list_or_null(), n_act);
+					else if (c->lens_on) hipLaunchKernelGGL(k_raygen_list<true>, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, lp, st.list_or_null(), n_act);
 					else hipLaunchKernelGGL(k_raygen_list<false>, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, NoLens(), st.list_or_null(), n_act);
 				}
 				if (const int e = launch_bounces(c, rp, p, rc, grid, BounceLaunch{ ek, sk, shade, tex, smooth, tv, mv_cone, nv, d_spill, d_cnt }); e != JP_OK) return e;

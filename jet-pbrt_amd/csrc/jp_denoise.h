@@ -26,8 +26,10 @@ struct GuideConst
 // normal guide describe the surface the render shades
 // mv (jp_mipmap.h; mv.tex null: no pyramid): the albedo follows the mip the render's camera ray reads at the first hit, one runtime branch again
 // pv (jp_procedural.h; pv.tex null: no procedural record): likewise the procedural colour at the first hit's footprint
+// pp (jp_projection.h; kind 0: the pinhole): the projected ray of the sample, one wave-uniform runtime branch in the kernels without a lens (k_guides, k_guides_smooth,
+// k_guides_mapped; a lens together with a projection is refused, so the lens twins never see one).  The host puts the projection's cone spread into mv.gamma0
 template <int kMode, bool kSmooth, bool kLens, bool kMapped = false>
-__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp, const SampView& sm, const MipView& mv, const ProcView& pv, const NMapView* mp = nullptr)
+__device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, const NormView& nv, const JpLensPlan* lp, const SampView& sm, const MipView& mv, const ProcView& pv, const JpProjectionPlan* pp = nullptr, const NMapView* mp = nullptr)
 {
 	SceneAccess<kMode> acc(sc, depth);
 	const int npix = gc.width * gc.height;
@@ -44,6 +46,7 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 				const float fx = (float)x + (gc.sampler_debug ? 0.5f : jp_rng_float(key, 0)), fy = (float)y + (gc.sampler_debug ? 0.5f : jp_rng_float(key, 1));
 				V3 ro, rd;                                                                          // k_raygen's ray
 				if constexpr (kLens) camera_ray<true>(sc.cam, lp, fx, fy, gc.sampler_debug ? 0.5f : jp_rng_float(key, 2), gc.sampler_debug ? 0.5f : jp_rng_float(key, 3), ro, rd);
+				else if (pp->kind != JP_PROJ_PERSPECTIVE) projected_ray(sc.cam, *pp, fx, fy, ro, rd);
 				else camera_ray<false>(sc.cam, nullptr, fx, fy, 0.f, 0.f, ro, rd);
 				float tmax = JP_INF;
 				const int h = acc.template trace<false>(sc, ro, rd, 0.001f, tmax);
@@ -81,14 +84,14 @@ __device__ __forceinline__ void guides_body(SceneView sc, TexView tv, int depth,
 	}
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, SampView sm, MipView mv, ProcView pv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, SampView sm, MipView mv, ProcView pv, JpProjectionPlan pp)
 {
-	guides_body<kMode, false, false>(sc, tv, depth, gc, albedo, normal, dist, NormView(), nullptr, sm, mv, pv);
+	guides_body<kMode, false, false>(sc, tv, depth, gc, albedo, normal, dist, NormView(), nullptr, sm, mv, pv, &pp);
 }
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, SampView sm, MipView mv, ProcView pv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, SampView sm, MipView mv, ProcView pv, JpProjectionPlan pp)
 {
-	guides_body<kMode, true, false>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, mv, pv);
+	guides_body<kMode, true, false>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, mv, pv, &pp);
 }
 template <int kMode>
 __global__ void __launch_bounds__(JP_BLOCK) k_guides_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, JpLensPlan lp, SampView sm, MipView mv, ProcView pv)
@@ -102,14 +105,14 @@ __global__ void __launch_bounds__(JP_BLOCK) k_guides_smooth_lens(SceneView sc, T
 }
 
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, SampView sm, MipView mv, ProcView pv)
+__global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, SampView sm, MipView mv, ProcView pv, JpProjectionPlan pp)
 {
-	guides_body<kMode, false, false, true>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, mv, pv, &mp);
+	guides_body<kMode, false, false, true>(sc, tv, depth, gc, albedo, normal, dist, nv, nullptr, sm, mv, pv, &pp, &mp);
 }
 template <int kMode>
 __global__ void __launch_bounds__(JP_BLOCK) k_guides_mapped_lens(SceneView sc, TexView tv, int depth, GuideConst gc, float* __restrict__ albedo, float* __restrict__ normal, float* __restrict__ dist, NormView nv, NMapView mp, JpLensPlan lp, SampView sm, MipView mv, ProcView pv)
 {
-	guides_body<kMode, false, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, sm, mv, pv, &mp);
+	guides_body<kMode, false, true, true>(sc, tv, depth, gc, albedo, normal, dist, nv, &lp, sm, mv, pv, nullptr, &mp);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -207,11 +210,11 @@ namespace
 #define JP_DENOISE_SIGMA_NORMAL 0.1f
 #define JP_DENOISE_SIGMA_DEPTH  0.03f
 
-typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, SampView, MipView, ProcView);
-typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, SampView, MipView, ProcView);
+typedef void (*GuideKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, SampView, MipView, ProcView, JpProjectionPlan);
+typedef void (*GuideSmoothKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, SampView, MipView, ProcView, JpProjectionPlan);
 typedef void (*GuideLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, JpLensPlan, SampView, MipView, ProcView);
 typedef void (*GuideSmoothLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, JpLensPlan, SampView, MipView, ProcView);
-typedef void (*GuideMappedKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, SampView, MipView, ProcView);
+typedef void (*GuideMappedKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, SampView, MipView, ProcView, JpProjectionPlan);
 typedef void (*GuideMappedLensKernel)(SceneView, TexView, int, GuideConst, float*, float*, float*, NormView, NMapView, JpLensPlan, SampView, MipView, ProcView);
 struct GuideLaunch { GuideKernel k; size_t lds; int depth; GuideSmoothKernel smooth; GuideLensKernel lens; GuideSmoothLensKernel smooth_lens; GuideMappedKernel mapped; GuideMappedLensKernel mapped_lens; };   // smooth: the twin a scene with vertex normals runs; lens: the twins of jp_set_lens
 template <int M> GuideLaunch guide_row(size_t lds, int depth) { GuideLaunch g = { k_guides<M>, lds, depth, k_guides_smooth<M>, k_guides_lens<M>, k_guides_smooth_lens<M>, k_guides_mapped<M>, k_guides_mapped_lens<M> }; return g; }
@@ -254,6 +257,10 @@ int guides_launch(JpContext* c, const GuideConst& gc, float* albedo, float* norm
 	const int grid = std::min(c->n_cus * 8, (npix + JP_BLOCK - 1) / JP_BLOCK);
 	JpLensPlan lp;
 	if (const int e = lens_plan_of(c, lp); e != JP_OK) return e;
+	JpProjectionPlan pp;                                                 // jp_set_projection: sample s stays the camera ray of sample s of the render, with its cone spread
+	if (const int e = proj_plan_of(c, pp); e != JP_OK) return e;
+	MipView mv = c->plan.mv;
+	if (c->proj_on) mv.gamma0 = pp.gamma0;
 	HIP_TRY(hipEventRecord(c->gd_ev[0], c->stream));
 	if (c->lens_on)
 	{   // jp_set_lens: sample s stays the camera ray of sample s of the render
@@ -261,9 +268,9 @@ int guides_launch(JpContext* c, const GuideConst& gc, float* albedo, float* norm
 		else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth_lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, lp, c->plan.sm, c->plan.mv, c->plan.proc);
 		else hipLaunchKernelGGL(gk.lens, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, lp, c->plan.sm, c->plan.mv, c->plan.proc);
 	}
-	else if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, c->plan.sm, c->plan.mv, c->plan.proc);
-	else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.sm, c->plan.mv, c->plan.proc);
-	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.sm, c->plan.mv, c->plan.proc);
+	else if (c->plan.mapped) hipLaunchKernelGGL(gk.mapped, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.mp, c->plan.sm, mv, c->plan.proc, pp);
+	else if (c->plan.smooth) hipLaunchKernelGGL(gk.smooth, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.nv, c->plan.sm, mv, c->plan.proc, pp);
+	else hipLaunchKernelGGL(gk.k, dim3(grid), dim3(JP_BLOCK), gk.lds, c->stream, c->plan.sv, c->plan.tv, gk.depth, gc, albedo, normal, dist, c->plan.sm, mv, c->plan.proc, pp);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->gd_ev[1], c->stream));
 	c->gd_timed = true; c->last_guide_spp = gc.spp;

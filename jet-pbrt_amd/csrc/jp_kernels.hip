@@ -26,6 +26,7 @@
 #include "jp_env.h"              // part 1: EnvView, env_lookup, env_sample (the kernels and entry points: part 2, at the end)
 #include "jp_mis.h"              // part 1: MisView, mis_weight, pdf_local, light_pdf (the kernels and entry points: part 2, at the end)
 #include "jp_lens.h"             // the thin-lens camera: JpLensPlan, jp_lens_ray (shared with the host; the hook kernel and the entry points: jp_lens_runtime.h, at the end)
+#include "jp_projection.h"       // camera projections: JpProjectionPlan, jp_projection_ray (shared with the host; the entry points: jp_projection_runtime.h, at the end)
 #include "jp_xbsdf.h"
 #include "jp_film.h"             // part 1: the sample clamp, the histogram bin, the display transform (shared with the host; the kernels and entry points: part 2, at the end)
 
@@ -108,6 +109,55 @@ __global__ void __launch_bounds__(JP_BLOCK) k_raygen(SceneView sc, Queues q, Ren
 			else camera_ray<false>(sc.cam, nullptr, fx, fy, 0.f, 0.f, o, dir);
 			q.ray_o[0][i] = make_float4(o.x, o.y, o.z, __int_as_float((int)slot));
 			q.ray_d[0][i] = make_float4(dir.x, dir.y, dir.z, __int_as_float(MK_FLAGS(0, 0, kLens ? 4 : 2)));
+			q.beta[0][i] = make_float4(1.f, 1.f, 1.f, __int_as_float((int)key));
+			q.lacc[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
+		}
+		const unsigned int left = total - c * JP_BLOCK;
+		filled += left < JP_BLOCK ? left : JP_BLOCK;
+	}
+	if (threadIdx.x == 0) q.blk_q[0][b] = filled;
+}
+
+// the camera ray of a film position under a projection (jp_set_projection, kind 1 .. 3; include/jp_projection.h): the one definition k_raygen_proj,
+// k_raygen_list_proj, k_other, k_guides and k_camera_rays share.  The branch on pp.kind is wave-uniform.
+__device__ __forceinline__ void projected_ray(const JpCamera& cam, const JpProjectionPlan& pp, float fx, float fy, V3& o, V3& dir)
+{
+	float oo[3], dd[3];
+	jp_projection_ray(&cam, &pp, fx, fy, oo, dd);
+	o = mk(oo[0], oo[1], oo[2]); dir = mk(dd[0], dd[1], dd[2]);
+}
+
+// k_raygen_proj: k_raygen under a projection -- an instance of its own with the plan by value, so that k_raygen<false | true> keep their instruction streams.
+// Same slots, key, film position and records (the pinhole's: MK_FLAGS(0, 0, 2)); only the ray differs.
+__global__ void __launch_bounds__(JP_BLOCK) k_raygen_proj(SceneView sc, Queues q, RenderConst rc, DevCounters* cnt, JpProjectionPlan pp)
+{
+	const unsigned int total = (unsigned int)rc.npix * rc.sbatch;
+	const unsigned int nchunks = (total + JP_BLOCK - 1) / JP_BLOCK;
+	const unsigned int G = gridDim.x, b = blockIdx.x;
+	if (b == 0 && threadIdx.x == 0) { cnt->n_queue[0] = total; cnt->n_queue[1] = 0; cnt->n_shadow = 0; }
+	unsigned int filled = 0;
+	// rc.compact (large scenes, round 3): region b takes CONSECUTIVE chunks of the list ordered by (256-pixel block, sample): a region is a
+	// few pixel blocks with all their samples, and the ~2000 workgroups in flight cover one part of the image, so the nodes and
+	// primitives their rays fetch are the same few MB (the L2 of an XCD holds 4 MB of a 27 MB scene).  Otherwise (scenes in LDS) the
+	// chunks b, b + G, ...: an even sample of the image per region, regions age alike.
+	const unsigned int K = (nchunks + G - 1) / G, npb = (unsigned int)rc.npix / JP_BLOCK;
+	for (unsigned int k = 0, j0 = 0; k < K; k++, j0 += JP_BLOCK)
+	{
+		unsigned int c;
+		if (rc.compact) { const unsigned int qi = b * K + k; if (qi >= nchunks) break; const unsigned int pb = qi / (unsigned int)rc.sbatch, sl = qi - pb * (unsigned int)rc.sbatch; c = sl * npb + pb; }
+		else { c = b + k * G; if (c >= nchunks) break; }
+		const unsigned int slot = c * JP_BLOCK + threadIdx.x;
+		if (slot < total)
+		{
+			const unsigned int i = b * q.R + j0 + threadIdx.x;
+			const int pix = slot % rc.npix, s = rc.s0 + slot / rc.npix;
+			int x, y; pixel_of(rc, pix, x, y);
+			const uint32_t key = jp_rng_key(rc.seed, (uint32_t)x, (uint32_t)y, (uint32_t)s);
+			const float fx = (float)x + rngf(rc, key, 0), fy = (float)y + rngf(rc, key, 1);
+			V3 o, dir;
+			projected_ray(sc.cam, pp, fx, fy, o, dir);
+			q.ray_o[0][i] = make_float4(o.x, o.y, o.z, __int_as_float((int)slot));
+			q.ray_d[0][i] = make_float4(dir.x, dir.y, dir.z, __int_as_float(MK_FLAGS(0, 0, 2)));
 			q.beta[0][i] = make_float4(1.f, 1.f, 1.f, __int_as_float((int)key));
 			q.lacc[slot] = make_float4(0.f, 0.f, 0.f, 0.f);
 		}
@@ -1203,7 +1253,7 @@ __global__ void __launch_bounds__(JP_BLOCK, (kMode == 6 ? JP_CERT_WAVES : 8)) k_
 struct WFrame { V3 L, p, N, wo, f; float absd, pdf, up; int mat, k; };
 
 template <int kMode>
-__global__ void __launch_bounds__(JP_BLOCK) k_other(SceneView sc, Queues q, RenderConst rc, int kind, int depth_lds, DevCounters* cnt, int lens_on, JpLensPlan lp)
+__global__ void __launch_bounds__(JP_BLOCK) k_other(SceneView sc, Queues q, RenderConst rc, int kind, int depth_lds, DevCounters* cnt, int lens_on, JpLensPlan lp, JpProjectionPlan pp)
 {
 	SceneAccess<kMode> acc(sc, depth_lds);
 	const unsigned int total = (unsigned int)rc.npix * rc.sbatch;
@@ -1218,6 +1268,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_other(SceneView sc, Queues q, Rend
 		{
 			const float fx = (float)x + rngf(rc, key, 0), fy = (float)y + rngf(rc, key, 1);
 			if (lens_on) camera_ray<true>(sc.cam, &lp, fx, fy, rngf(rc, key, 2), rngf(rc, key, 3), o, d);
+			else if (pp.kind != JP_PROJ_PERSPECTIVE) projected_ray(sc.cam, pp, fx, fy, o, d);   // (jp_set_projection: never together with a lens)
 			else camera_ray<false>(sc.cam, nullptr, fx, fy, 0.f, 0.f, o, d);
 		}
 		V3 result = mk(0, 0, 0);
@@ -1640,6 +1691,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_surface(SceneView sc, TexView tv, 
 #define JP_NORMALS_RUNTIME
 #include "jp_normals.h"          // vertex normals, part 2: k_normal, k_shade_smooth*, k_shading_normal and their entry points
 #include "jp_shade_launch.h"     // shade_launch and launch_normal, which jp_render.h declares: after the last of the k_shade families and normal kernels above
+#include "jp_projection_runtime.h"   // camera projections: the entry points (jp_render.h reads the context's projection state)
 #include "jp_lens_runtime.h"     // thin-lens camera: k_camera_rays and the lens entry points (jp_render.h reads the context's lens state)
 #define JP_FILM_RUNTIME
 #include "jp_film.h"             // film, part 2: k_film_hist, k_display and the film / tone map entry points (jp_render.h declares film_to_rgb8 and reads the context's film state)

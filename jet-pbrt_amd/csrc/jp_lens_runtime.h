@@ -4,7 +4,7 @@
 #pragma once
 
 // k_camera_rays (jp_camera_rays): k_raygen's key, film position and camera_ray for n (pixel, sample) triples
-__global__ void __launch_bounds__(JP_BLOCK) k_camera_rays(JpCamera cam, unsigned int seed, int sampler_debug, int lens_on, JpLensPlan lp, int n,
+__global__ void __launch_bounds__(JP_BLOCK) k_camera_rays(JpCamera cam, unsigned int seed, int sampler_debug, int lens_on, JpLensPlan lp, JpProjectionPlan pp, int n,
                                                           const int* __restrict__ px, const int* __restrict__ py, const int* __restrict__ ps,
                                                           float* __restrict__ origin, float* __restrict__ dir, int* __restrict__ dim_next)
 {
@@ -16,6 +16,7 @@ __global__ void __launch_bounds__(JP_BLOCK) k_camera_rays(JpCamera cam, unsigned
 		const float fx = (float)x + rngf(rc, key, 0), fy = (float)y + rngf(rc, key, 1);
 		V3 o, d;
 		if (lens_on) camera_ray<true>(cam, &lp, fx, fy, rngf(rc, key, 2), rngf(rc, key, 3), o, d);
+		else if (pp.kind != JP_PROJ_PERSPECTIVE) projected_ray(cam, pp, fx, fy, o, d);   // (jp_set_projection: never together with a lens)
 		else camera_ray<false>(cam, nullptr, fx, fy, 0.f, 0.f, o, d);
 		if (origin) { origin[3 * i] = o.x; origin[3 * i + 1] = o.y; origin[3 * i + 2] = o.z; }
 		if (dir) { dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z; }
@@ -114,6 +115,8 @@ int jp_camera_rays(JpContext* c, const JpRenderParams* rp, int32_t n, const int3
 	if (n == 0) return JP_OK;
 	JpLensPlan lp;
 	if (const int e = lens_plan_of(c, lp); e != JP_OK) return e;
+	JpProjectionPlan pp;
+	if (const int e = proj_plan_of(c, pp); e != JP_OK) return e;
 	HIP_TRY(hipSetDevice(c->device));
 	DevBuf b_in, b_o, b_d, b_k; int *d_in, *d_k; float *d_o, *d_d;        // per-call scratch: freed on every return
 	HIP_TRY(reserve(b_in, d_in, (size_t)n * 12)); HIP_TRY(reserve(b_o, d_o, (size_t)n * 12)); HIP_TRY(reserve(b_d, d_d, (size_t)n * 12)); HIP_TRY(reserve(b_k, d_k, (size_t)n * 4));
@@ -121,7 +124,7 @@ int jp_camera_rays(JpContext* c, const JpRenderParams* rp, int32_t n, const int3
 	HIP_TRY(hipMemcpyAsync(d_x, x, (size_t)n * 4, hipMemcpyHostToDevice, c->stream)); HIP_TRY(hipMemcpyAsync(d_y, y, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
 	HIP_TRY(hipMemcpyAsync(d_s, s, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
 	const int grid = std::min(c->n_cus * 8, (n + JP_BLOCK - 1) / JP_BLOCK);
-	hipLaunchKernelGGL(k_camera_rays, dim3(grid), dim3(JP_BLOCK), 0, c->stream, c->plan.sv.cam, (unsigned int)rp->seed, rp->sampler_mode == JP_SAMPLER_DEBUG ? 1 : 0, c->lens_on ? 1 : 0, lp, (int)n,
+	hipLaunchKernelGGL(k_camera_rays, dim3(grid), dim3(JP_BLOCK), 0, c->stream, c->plan.sv.cam, (unsigned int)rp->seed, rp->sampler_mode == JP_SAMPLER_DEBUG ? 1 : 0, c->lens_on ? 1 : 0, lp, pp, (int)n,
 	                   (const int*)d_x, (const int*)d_y, (const int*)d_s, d_o, d_d, d_k);
 	HIP_TRY(hipGetLastError());
 	if (origin) HIP_TRY(hipMemcpyAsync(origin, d_o, (size_t)n * 12, hipMemcpyDeviceToHost, c->stream));

@@ -16,6 +16,24 @@ int lens_plan_of(const JpContext* c, JpLensPlan& lp)
 	return JP_OK;
 }
 
+// the projection in force as the kernels take it (zeros, kind 0, while none is set: the pinhole), with the checks that need the uploaded camera
+int proj_plan_status(const JpCamera* cam, const JpProjection* pr, JpProjectionPlan& pp, const char* who)
+{
+	switch (jp_projection_make_plan(cam, pr, &pp))
+	{
+	case 0: return JP_OK;
+	case -1: return fail(JP_ERR_INVALID_ARGUMENT, std::string(who) + ": the camera's right / up / front vectors need a finite positive length and the resolution must be positive");
+	default: return fail(JP_ERR_INVALID_ARGUMENT, std::string(who) + ": an equirectangular or fisheye projection needs perpendicular camera axes (a pairwise |dot| of right, up, front, normalised, exceeds 1e-3)");
+	}
+}
+int proj_plan_of(const JpContext* c, JpProjectionPlan& pp)
+{
+	std::memset(&pp, 0, sizeof(pp));
+	if (!c->proj_on) return JP_OK;
+	if (c->lens_on) return fail(JP_ERR_UNSUPPORTED, "jp_set_projection: a lens (jp_set_lens, radius > 0) together with a projection other than perspective is not supported");
+	return proj_plan_status(&c->plan.sv.cam, &c->proj, pp, "jp_set_projection");
+}
+
 void free_queues(JpContext* c) { c->qb = QueueBufs(); c->cap = 0; c->planes_alloc = 0; c->blk_alloc = 0; }
 
 int ensure_queues(JpContext* c, unsigned int cap, int planes, unsigned int nblocks)
@@ -221,7 +239,7 @@ namespace
 {
 
 // the other two integrators' megakernel: one ray per lane, launched like the plain k_extend (plan.lds_bytes, plan.stack_depth)
-typedef void (*OtherKernel)(SceneView, Queues, RenderConst, int, int, DevCounters*, int, JpLensPlan);
+typedef void (*OtherKernel)(SceneView, Queues, RenderConst, int, int, DevCounters*, int, JpLensPlan, JpProjectionPlan);
 OtherKernel other_kernel(const ScenePlan& p) { return p.trav_mode == 5 ? k_other<5> : (p.trav_mode == 2 ? k_other<2> : (p.trav_mode == 1 ? k_other<1> : k_other<0>)); }
 
 // jp_trace / jp_surface.  JpOptions::trace_walk (tests; jp_surface passes 0): 1 the binary tree, 2 the 8-wide tree, 3 the caller's tree verbatim; else what the
@@ -408,19 +426,23 @@ int render_one(JpContext* c, const JpRenderParams* rp, float* film_dev, bool syn
 		const ShadeLaunch shade = shade_launch(shade_choice(p, tex, mis, smooth, generic), ShadeViews(tv, p.pv, p.ev, mv, nv));
 		JpLensPlan lp;                                                 // jp_set_lens: k_raygen<true> / k_other form the lens ray; the bounces never know
 		if (const int e = lens_plan_of(c, lp); e != JP_OK) return e;
+		JpProjectionPlan pp;                                           // jp_set_projection: k_raygen_proj / k_other form the projected ray; its cone spread goes to k_texel_m / k_texel_p
+		if (const int e = proj_plan_of(c, pp); e != JP_OK) return e;
+		if (c->proj_on) mv_cone.gamma0 = pp.gamma0;
 		for (int s0 = 0; s0 < rp->spp; s0 += sbatch)
 		{
 			rc.s0 = s0; rc.sbatch = std::min(sbatch, rp->spp - s0);
 			{
 				Stamper t(c, CLS_OTHER);
-				if (c->lens_on) hipLaunchKernelGGL(k_raygen<true>, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, lp);
+				if (c->proj_on) hipLaunchKernelGGL(k_raygen_proj, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, pp);
+				else if (c->lens_on) hipLaunchKernelGGL(k_raygen<true>, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, lp);
 				else hipLaunchKernelGGL(k_raygen<false>, dim3(grid), dim3(JP_BLOCK), 0, c->stream, p.sv, c->q, rc, d_cnt, NoLens());
 			}
 			if (rp->integrator != JP_INTEGRATOR_PATH)
 			{   // the other two integrators: one megakernel launch per batch (k_other), then the same per-pixel sum
 				Stamper t(c, CLS_OTHER);
 				const int ogrid = (int)std::min<unsigned int>((P + JP_BLOCK - 1) / JP_BLOCK, (unsigned int)(c->n_cus * 16));
-				hipLaunchKernelGGL(ok, dim3(ogrid), dim3(JP_BLOCK), p.lds_bytes, c->stream, p.sv, c->q, rc, rp->integrator, p.stack_depth, d_cnt, c->lens_on ? 1 : 0, lp);
+				hipLaunchKernelGGL(ok, dim3(ogrid), dim3(JP_BLOCK), p.lds_bytes, c->stream, p.sv, c->q, rc, rp->integrator, p.stack_depth, d_cnt, c->lens_on ? 1 : 0, lp, pp);
 			}
 			if (const int e = launch_bounces(c, rp, p, rc, grid, BounceLaunch{ ek, sk, shade, tex, smooth, tv, mv_cone, nv, d_spill, d_cnt }); e != JP_OK) return e;
 			{ Stamper t(c, CLS_OTHER); launch_resolve(c, c->q, rc, npix, d_pix_acc, film_dev, s0 == 0 ? 1 : 0, s0 + rc.sbatch >= rp->spp ? 1 : 0); }
@@ -467,6 +489,7 @@ void sync_lane_scene(JpContext* c, JpContext* l)
 	l->profiling = c->profiling; l->opt = c->opt;                    // render_one(lane) reads max_slots / compact_regions from its own context
 	l->estimator = c->estimator;                                     // ... and the estimator (its side records are its own, like its queues)
 	l->lens = c->lens; l->lens_on = c->lens_on;                      // ... and the lens
+	l->proj = c->proj; l->proj_on = c->proj_on;                      // ... and the projection
 	l->film_state = c->film_state; l->film_on = c->film_on;          // ... and the film state (a lane resolves its own bands)
 	l->var_on = c->var_on;                                           // ... and whether it keeps the moments (render_impl gives it a variance plane of its own)
 }
@@ -489,6 +512,7 @@ bool fused_eligible(const JpContext* c, const JpRenderParams* rp)
 	if (c->plan.pick) return false;                                       // JP_LIGHTS_POWER_ONE: k_shade_pick lives there too
 	if (c->plan.smooth) return false;                                     // vertex normals: k_normal + k_shade_smooth* as well
 	if (c->lens_on) return false;                                         // a lens: k_raygen<true> lives in the per-bounce launches (k_path forms the pinhole ray)
+	if (c->proj_on) return false;                                         // a projection: k_raygen_proj likewise
 	if (c->plan.trav_mode == 2) return c->plan.shade_prims_in_lds;
 	return c->plan.trav_mode == 0 || c->plan.trav_mode == 3 || c->plan.trav_mode == 5;
 }
@@ -624,7 +648,7 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	c->last_var = c->var_on ? 1 : 0;
 	c->ad_info.adaptive_last_render = 0;                                  // (jp_adaptive.h's driver does not come through here)
 	if (!c->var_on && (c->var_mom || (!c->lanes.empty() && c->lanes[0]->var_mom))) { c->var_mom.reset(); for (JpContext* l : c->lanes) l->var_mom.reset(); }   // (left by a variance render that did not wait for its stream)
-	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_nmapped = 0; c->last_sampled = 0; c->last_mip = 0; c->last_proc = 0;
+	c->last_lanes = 1; c->last_fused = 0; c->last_textured = 0; c->last_picked = 0; c->last_mapped = 0; c->last_mis = 0; c->last_smooth = 0; c->last_lens = 0; c->last_proj = 0; c->last_proj_gamma0 = 0.f; c->last_nmapped = 0; c->last_sampled = 0; c->last_mip = 0; c->last_proc = 0;
 	if (c->plan.mapped && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with normal maps, jp_set_normal_maps)");
 	if (c->plan.smooth && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator shades with the geometric normal (scene uploaded with vertex normals, jp_set_vertex_normals)");
 	if (c->plan.env && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator does not sample environment maps (jp_set_environment_map)");
@@ -633,6 +657,12 @@ int render_impl(JpContext* c, const JpRenderParams* rp, float* film_dev, bool sy
 	if (c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_WHITTED) return fail(JP_ERR_UNSUPPORTED, "jp_render: the Whitted integrator has one estimator (jp_set_estimator: JP_ESTIMATOR_MIS is the path integrator's)");
 	if (c->estimator == JP_ESTIMATOR_MIS && rp->integrator == JP_INTEGRATOR_PATH && c->plan.have_scene && !c->plan.pick)
 		return fail(JP_ERR_UNSUPPORTED, "jp_render: JP_ESTIMATOR_MIS needs a scene uploaded with JP_LIGHTS_POWER_ONE (jp_set_light_sampling): the light strategy's pdf comes from the light table");
+	if (c->proj_on && c->plan.have_scene)
+	{   // jp_set_projection: refused here, before any lane starts (a lens together with a projection; a camera the projection cannot stand on)
+		JpProjectionPlan pp;
+		if (const int e = proj_plan_of(c, pp); e != JP_OK) return e;
+		c->last_proj = 1; c->last_proj_gamma0 = pp.gamma0;                // (every integrator forms the projected ray)
+	}
 	if (fused_eligible(c, rp)) return render_fused(c, rp, film_dev, sync);
 	c->last_textured = c->plan.textured && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;
 	c->last_picked = c->plan.pick && rp->integrator == JP_INTEGRATOR_PATH ? 1 : 0;

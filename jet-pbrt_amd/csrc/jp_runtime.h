@@ -188,6 +188,9 @@ struct JpContext
 	// thin-lens camera (jp_lens_runtime.h): render-time state like the estimator (jp_set_lens; a lane takes its parent's before it renders) and what the last
 	// render ran.  The plan is a kernel argument made per launch from the uploaded camera: the lens owns no device memory.
 	JpLens lens = {}; bool lens_on = false; int last_lens = 0;
+	// camera projection (jp_projection_runtime.h): render-time state like the lens (jp_set_projection; a lane takes its parent's), what the last render ran and the
+	// cone spread it used.  The plan is a kernel argument made per launch from the uploaded camera: a projection owns no device memory.
+	JpProjection proj = {}; bool proj_on = false; int last_proj = 0; float last_proj_gamma0 = 0.f;
 	// film (jp_film.h): render-time state like the lens -- the film state (jp_set_film; a lane takes its parent's) and the tone map (jp_set_tonemap, resolved:
 	// defaults filled in) -- what the last render / transform ran, the histogram's 257 dwords on the device, event pairs around k_film_hist and k_display
 	JpFilm film_state = {}; bool film_on = false; int last_hdr = 0;

@@ -130,6 +130,19 @@ int jp_host_scene_set_lens(void* h, float radius, float focus, int blades, float
 	if (focus_at) hs->scene->camera->FocusAt(fx, fy);
 	return 0;
 }
+// FCamera::SetProjection on the scene's camera (kind 0: the pinhole again), after FCamera::CheckProjection -- the library's jp_check_projection; the camera keeps
+// the projection it had when that refuses.  0, or -1 with jp_host_last_error set (no camera; the check's message)
+int jp_host_scene_set_projection(void* h, int kind, float ortho_scale, float fov_deg, int fit)
+{
+	HostScene* hs = (HostScene*)h;
+	if (!hs->scene->camera) { hs->error = "jp_host_scene_set_projection: the scene has no camera"; return -1; }
+	FCamera& cam = *hs->scene->camera;
+	const int k0 = cam.projKind, f0 = cam.projFit; const Float s0 = cam.projOrthoScale, v0 = cam.projFovDeg;
+	cam.SetProjection(kind, ortho_scale, fov_deg, fit);
+	std::string msg;
+	if (!cam.CheckProjection(&msg)) { cam.SetProjection(k0, s0, v0, f0); hs->error = msg; return -1; }
+	return 0;
+}
 float jp_host_last_focus(void* h) { HostScene* hs = (HostScene*)h; return hs->scene->camera ? hs->scene->camera->LastFocus() : 0.f; }
 // FScene::SetEnvironmentMap from memory (3 * w * hgt floats, top row first; null: no map) or from a file (FEnvironmentMap::FromFile); importance -1:
 // the A/B hook of JpEnvMap.  0, or -1 with jp_host_last_error set

@@ -2,6 +2,7 @@
 //     jetpbrt sceneid spp [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--device-bvh | --reference-tree | --reference-tree=certified] [--integrator path|recursive|whitted|debug]
 //             [--adaptive THRESHOLD [--min-spp N] [--spp-step N] [--no-adaptive-dilate]] [--denoise [variance]] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]
 //             [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]
+//             [--projection ortho|equirect|fisheye [--ortho-scale S] [--fisheye-fov DEG] [--fisheye-fit diagonal|width|height]]
 //             [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]
 //             [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]
 //             [--texture-wrap clamp|repeat|mirror] [--texture-filter nearest|bilinear] [--texture-tile SU SV] [--normal-wrap clamp|repeat] [--normal-tile SU SV]
@@ -24,6 +25,10 @@
 // --aperture R: a thin lens of radius R scene units instead of the pinhole (FCamera::SetLens): depth of field.  --focus D: the focus distance (the plane of focus lies D * |front|
 // along the viewing direction; default 1); --focus-pixel X Y: focus on whatever film position (X, Y) sees (FCamera::FocusAt; the distance found is echoed); --blades N: a regular
 // polygon of 3 .. 16 blades instead of a disk; --aperture-rotation DEG: turns the polygon.
+// --projection: an orthographic, equirectangular (lat-long panorama) or equidistant fisheye camera instead of the perspective pinhole (FCamera::SetProjection), from the scene
+// camera's position and axes.  --ortho-scale S: the width of the orthographic view in units of the camera's right vector (default 1); --fisheye-fov DEG: the fisheye's field
+// of view, (0, 360], default 180, reached at the half-diagonal, half-width or half-height of the film (--fisheye-fit).  With --hdr --format hdr an equirect render is a map
+// --envmap takes.  Not together with --aperture.
 // --smooth: vertex normals for the scenes' meshes (FSmoothing; lights excepted): `file` takes the OBJ's vn, a number computes them with that crease angle in degrees.
 // --estimator mis: next-event estimation and the BSDF sample weighted against each other (FScene::SetEstimator(JP_ESTIMATOR_MIS)); implies --light-sampling power.
 // nee (default): the reference's estimator.
@@ -134,10 +139,12 @@ int main(int argc, char* argv[])
 	FTexSampling texSampling, normalSampling; bool haveTexSampling = false, haveNormalSampling = false;
 	bool textureMip = false; float mipFootprint = 0.f, mipBounceSpread = 0.f;
 	int floorTexture = JP_PROC_NONE, floorOctaves = 0; float floorScale = 0.02f; bool floorAntialias = true, floorOptions = false;
+	int projection = JP_PROJ_PERSPECTIVE, fisheyeFit = JP_FIT_DIAGONAL; float orthoScale = 0.f, fisheyeFov = 0.f;
 	float aperture = 0.f, focus = 1.f, focusX = 0.f, focusY = 0.f, apertureRotation = 0.f; int blades = 0; bool focusPixel = false;
 	fprintf(stderr, "pbrt.exe  sceneid   spp\n");                 // main.cc:121
 	fprintf(stderr, "          [width height] [--assets DIR] [--out NAME] [--format bmp|ppm|hdr] [--adaptive THRESHOLD [--min-spp N] [--spp-step N] [--no-adaptive-dilate]] [--denoise [variance]] [--guide-spp N] [--aov PREFIX] [--light-sampling all|power] [--estimator nee|mis] [--envmap FILE [--envmap-up y|z] [--envmap-scale S]] [--smooth file|DEG]\n");
 	fprintf(stderr, "          [--aperture R [--focus D | --focus-pixel X Y] [--blades N] [--aperture-rotation DEG]]\n");
+	fprintf(stderr, "          [--projection ortho|equirect|fisheye [--ortho-scale S] [--fisheye-fov DEG] [--fisheye-fit diagonal|width|height]]\n");
 	fprintf(stderr, "          [--normal-map FILE [--normal-strength S] [--normal-from-height SCALE]]\n");
 	fprintf(stderr, "          [--hdr] [--sample-clamp C] [--tonemap clamp|reinhard|aces|hable] [--exposure EV|auto] [--white W]\n");
 	fprintf(stderr, "          [--texture-wrap clamp|repeat|mirror] [--texture-filter nearest|bilinear] [--texture-tile SU SV] [--normal-wrap clamp|repeat] [--normal-tile SU SV]\n");
@@ -192,6 +199,21 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--focus-pixel") && i + 2 < argc) { focusX = (float)atof(argv[i + 1]); focusY = (float)atof(argv[i + 2]); i += 2; focusPixel = true; if (!std::isfinite(focusX) || !std::isfinite(focusY)) { fprintf(stderr, "--focus-pixel takes two numbers\n"); return 5; } }
 		else if (!strcmp(argv[i], "--blades") && i + 1 < argc) { blades = atoi(argv[++i]); if (blades != 0 && (blades < 3 || blades > 16)) { fprintf(stderr, "--blades must be 0 (a disk) or 3 .. 16\n"); return 5; } }
 		else if (!strcmp(argv[i], "--aperture-rotation") && i + 1 < argc) { apertureRotation = (float)atof(argv[++i]); if (!std::isfinite(apertureRotation)) { fprintf(stderr, "--aperture-rotation must be a number\n"); return 5; } }
+		else if (!strcmp(argv[i], "--projection") && i + 1 < argc)
+		{
+			const char* m = argv[++i];
+			if (!strcmp(m, "ortho")) projection = JP_PROJ_ORTHOGRAPHIC; else if (!strcmp(m, "equirect")) projection = JP_PROJ_EQUIRECT;
+			else if (!strcmp(m, "fisheye")) projection = JP_PROJ_FISHEYE; else if (!strcmp(m, "perspective")) projection = JP_PROJ_PERSPECTIVE;
+			else { fprintf(stderr, "--projection must be ortho, equirect, fisheye or perspective\n"); return 5; }
+		}
+		else if (!strcmp(argv[i], "--ortho-scale") && i + 1 < argc) orthoScale = (float)atof(argv[++i]);      // (checked with the projection below, by the library)
+		else if (!strcmp(argv[i], "--fisheye-fov") && i + 1 < argc) fisheyeFov = (float)atof(argv[++i]);
+		else if (!strcmp(argv[i], "--fisheye-fit") && i + 1 < argc)
+		{
+			const char* m = argv[++i];
+			if (!strcmp(m, "diagonal")) fisheyeFit = JP_FIT_DIAGONAL; else if (!strcmp(m, "width")) fisheyeFit = JP_FIT_WIDTH; else if (!strcmp(m, "height")) fisheyeFit = JP_FIT_HEIGHT;
+			else { fprintf(stderr, "--fisheye-fit must be diagonal, width or height\n"); return 5; }
+		}
 		else if (!strcmp(argv[i], "--normal-map") && i + 1 < argc) normalMap = argv[++i];
 		else if (!strcmp(argv[i], "--normal-strength") && i + 1 < argc) { normalStrength = (float)atof(argv[++i]); if (!std::isfinite(normalStrength)) { fprintf(stderr, "--normal-strength must be a number\n"); return 5; } }
 		else if (!strcmp(argv[i], "--normal-from-height") && i + 1 < argc) { normalFromHeight = (float)atof(argv[++i]); fromHeight = true; if (!std::isfinite(normalFromHeight)) { fprintf(stderr, "--normal-from-height must be a number\n"); return 5; } }
@@ -271,6 +293,15 @@ int main(int argc, char* argv[])
 		else if (!strcmp(argv[i], "--white") && i + 1 < argc) { toneMap.white = (float)atof(argv[++i]); haveToneMap = true; if (!(toneMap.white > 0.f) || !std::isfinite(toneMap.white)) { fprintf(stderr, "--white must be a number > 0\n"); return 5; } }
 		else pos.push_back(argv[i]);
 	}
+	if ((orthoScale != 0.f || fisheyeFov != 0.f || fisheyeFit != JP_FIT_DIAGONAL) && projection == JP_PROJ_PERSPECTIVE) { fprintf(stderr, "--ortho-scale / --fisheye-fov / --fisheye-fit need --projection\n"); return 5; }
+	if (projection != JP_PROJ_PERSPECTIVE)
+	{   // the library's own validation (jp_check_projection: pure host code), before anything is loaded
+		if (aperture > 0.f) { fprintf(stderr, "--projection and --aperture exclude each other (a lens belongs to the perspective camera)\n"); return 5; }
+		FCamera probe(FVector3(0, 0, 0), FVector3(0, 0, -1), FVector3(0, 1, 0), 45.f, FVector2(1, 1));
+		probe.SetProjection(projection, orthoScale, fisheyeFov, fisheyeFit);
+		std::string msg;
+		if (!probe.CheckProjection(&msg)) { fprintf(stderr, "--projection: %s\n", msg.c_str()); return 5; }
+	}
 	if (pos.empty()) return 0;                                    // main.cc:122-125
 	const int sceneId = atoi(pos[0]);
 	if (pos.size() > 1) { int spp = atoi(pos[1]); if (spp > 0) samples_per_pixel = spp; }
@@ -325,6 +356,7 @@ int main(int argc, char* argv[])
 		scene->camera->SetLens(aperture, focus, blades, apertureRotation);
 		if (focusPixel) scene->camera->FocusAt(focusX, focusY);
 	}
+	if (projection != JP_PROJ_PERSPECTIVE && scene->camera) scene->camera->SetProjection(projection, orthoScale, fisheyeFov, fisheyeFit);
 	if (scene->primitives.empty()) { fprintf(stderr, "no geometry loaded from %s\n", assets.c_str()); return 2; }
 	std::shared_ptr<FSampler> sampler = std::make_shared<FRandomSampler>(samples_per_pixel);
 	// main.cc:154 constructs FPathIntegratorIteration(5); the commented-out alternatives of main.cc:150-153 are selectable here

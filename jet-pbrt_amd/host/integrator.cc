@@ -42,6 +42,8 @@ struct HipApi
 	int (*set_texture_mipmaps)(JpContext*, const JpTextureMipmaps*) = nullptr;               // (looked up, needed by scenes with FImageTexture::SetMipmaps only)
 	int (*set_estimator)(JpContext*, const JpEstimator*) = nullptr;                        // (looked up, needed by FScene::SetEstimator only)
 	int (*set_lens)(JpContext*, const JpLens*) = nullptr;                                    // (looked up, needed by FCamera::SetLens only)
+	int (*set_projection)(JpContext*, const JpProjection*) = nullptr;                        // (looked up, needed by FCamera::SetProjection only)
+	int (*check_projection)(const JpProjection*) = nullptr;
 	int (*focus_distance)(JpContext*, float, float, float*) = nullptr;                       // (looked up, needed by FCamera::FocusAt only)
 	int (*set_film)(JpContext*, const JpFilm*) = nullptr;                                    // (looked up, needed by FFilm::SetHDR / SetSampleClamp / SetToneMap only)
 	int (*set_tonemap)(JpContext*, const JpToneMap*) = nullptr;                              // (looked up, needed by FFilm::SetToneMap only)
@@ -88,6 +90,8 @@ HipApi& Api()
 		api.set_texture_mipmaps = (decltype(api.set_texture_mipmaps))dlsym(api.lib, "jp_set_texture_mipmaps");
 		api.set_texture_procedurals = (decltype(api.set_texture_procedurals))dlsym(api.lib, "jp_set_texture_procedurals");
 		api.focus_distance = (decltype(api.focus_distance))dlsym(api.lib, "jp_focus_distance");
+		api.set_projection = (decltype(api.set_projection))dlsym(api.lib, "jp_set_projection");
+		api.check_projection = (decltype(api.check_projection))dlsym(api.lib, "jp_check_projection");
 		api.set_film = (decltype(api.set_film))dlsym(api.lib, "jp_set_film");
 		api.set_tonemap = (decltype(api.set_tonemap))dlsym(api.lib, "jp_set_tonemap");
 		api.get_tonemap_info = (decltype(api.get_tonemap_info))dlsym(api.lib, "jp_get_tonemap_info");
@@ -133,6 +137,16 @@ FBSDFSample FBSDF::Sample(const FVector3& wo, const FVector2& random) const
 	BsdfOut o = DeviceBsdf(desc, normal, wo, wo, random);
 	FBSDFSample s; s.f = FColor(o.sf[0], o.sf[1], o.sf[2]); s.wi = FVector3(o.swi[0], o.swi[1], o.swi[2]); s.pdf = o.spdf; s.ebsdf = o.flags;
 	return s;
+}
+
+bool FCamera::CheckProjection(std::string* message) const
+{
+	HipApi& api = Api();
+	if (!api.lib || !api.check_projection) { if (message) *message = api.lib ? "libjetpbrt_amd.so lacks jp_check_projection" : "HIP library not available (" + api.error + ")"; return false; }
+	JpProjection p; p.struct_bytes = (int32_t)sizeof(p); p.kind = projKind; p.ortho_scale = projOrthoScale; p.fov_deg = projFovDeg; p.fit = projFit;
+	if (api.check_projection(&p) == JP_OK) return true;
+	if (message) *message = api.last_error();
+	return false;
 }
 
 FGpuPathIntegrator::FGpuPathIntegrator(int maxDepth, int deviceId) : maxDepth(maxDepth), deviceId(deviceId) { std::memset(&counters, 0, sizeof(counters)); }
@@ -263,6 +277,18 @@ void FGpuPathIntegrator::Render(const FScene* scene, FSampler* sampler, FFilm* f
 			lastStatus = api.set_lens(ctx, l.struct_bytes ? &l : nullptr);
 			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
 			ctxLens = l;
+		}
+	}
+	{   // FCamera::SetProjection: render-time state of the context, sent when it changes; a camera that never asked for a projection makes no such call
+		const FCamera* cam = scene->Camera();
+		JpProjection p; std::memset(&p, 0, sizeof(p));
+		if (cam && cam->projKind != JP_PROJ_PERSPECTIVE) { p.struct_bytes = (int32_t)sizeof(p); p.kind = cam->projKind; p.ortho_scale = cam->projOrthoScale; p.fov_deg = cam->projFovDeg; p.fit = cam->projFit; }
+		if (std::memcmp(&p, &ctxProjection, sizeof(p)) != 0)
+		{
+			if (!api.set_projection) { fprintf(stderr, "FGpuPathIntegrator::Render: libjetpbrt_amd.so lacks jp_set_projection\n"); lastStatus = JP_ERR_UNSUPPORTED; return; }
+			lastStatus = api.set_projection(ctx, p.struct_bytes ? &p : nullptr);
+			if (lastStatus != JP_OK) { fprintf(stderr, "FGpuPathIntegrator::Render: %s\n", api.last_error()); return; }
+			ctxProjection = p;
 		}
 	}
 	{   // FFilm::SetHDR / SetSampleClamp / SetToneMap: render-time state of the context, sent when it changes; a film that never asked for either makes no such call

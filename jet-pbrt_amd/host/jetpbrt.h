@@ -378,6 +378,13 @@ public:
 	Float lensRadius = 0, lensFocus = 1, lensRotation = 0; int lensBlades = 0;
 	bool focusAt = false; Float focusFx = 0, focusFy = 0;
 	mutable Float lastFocus = 0;                                 // the focus distance of the last render with a lens
+	// Projection (INTEGRATION.md "Projections"; the reference's camera is the perspective pinhole, JP_PROJ_PERSPECTIVE): JP_PROJ_ORTHOGRAPHIC (orthoScale: the width of
+	// the view in units of |right|; 0: 1), JP_PROJ_EQUIRECT (a lat-long panorama around pos) or JP_PROJ_FISHEYE (equidistant; fovDeg in (0, 360], 0: 180, reached at the
+	// half-diagonal, half-width or half-height: JP_FIT_*).  Render-time state like the lens: FGpuPathIntegrator::Render forwards it to jp_set_projection, no new upload.
+	// CheckProjection: the library's own validation (jp_check_projection, no GPU needed) -- true, or false with its message.
+	void SetProjection(int kind, Float orthoScale = 0, Float fovDeg = 0, int fit = JP_FIT_DIAGONAL) { projKind = kind; projOrthoScale = orthoScale; projFovDeg = fovDeg; projFit = fit; }
+	bool CheckProjection(std::string* message = nullptr) const;
+	int projKind = JP_PROJ_PERSPECTIVE, projFit = JP_FIT_DIAGONAL; Float projOrthoScale = 0, projFovDeg = 0;
 };
 
 enum class EImageType { PPM, BMP, HDR };                         // film.h:15-20
@@ -660,6 +667,7 @@ protected:
 	mutable int ctxEstimator = JP_ESTIMATOR_NEE;                    // the estimator the context was last told (FScene::SetEstimator)
 	mutable int uploadedLights = JP_LIGHTS_ALL, ctxLights = JP_LIGHTS_ALL;   // FScene::lightSampling of the uploaded scene; the mode the context was last told
 	mutable unsigned long long uploadedEnv = 0, ctxEnv = 0; mutable int uploadedEnvUp = 0, ctxEnvUp = 0, uploadedEnvImp = 0, ctxEnvImp = 0;   // FEnvironmentMap::id (0: none), up axis and importance: of the uploaded scene; last sent to the context
+	mutable JpProjection ctxProjection = {};                        // the projection the context was last told (FCamera::SetProjection; kind 0: none)
 	mutable JpLens ctxLens = {};                                    // the lens the context was last told (FCamera::SetLens; radius 0: none)
 	mutable JpFilm ctxFilm = {}; mutable JpToneMap ctxToneMap = {};   // the film state and tone map the context was last told (FFilm::SetHDR / SetSampleClamp / SetToneMap; zeros: none)
 	mutable bool ctxNormalMaps = false;                            // ... or normal maps (jp_set_normal_maps)

@@ -360,6 +360,15 @@ class HostBackend:
         if self._f("scene_set_lens")(self.h, C.c_float(radius), C.c_float(focus), int(blades), C.c_float(rotation), 0 if focus_at is None else 1, C.c_float(fx), C.c_float(fy)) != 0:
             raise RuntimeError("set_lens failed: %s" % self.L.jp_host_last_error(self.h).decode())
 
+    def set_projection(self, kind, ortho_scale=0.0, fov_deg=0.0, fit="diagonal"):
+        """FCamera::SetProjection on the scene's camera: "ortho", "equirect", "fisheye" or "perspective" (or JP_PROJ_*), validated by the library's
+        jp_check_projection (host backend only; takes effect with the integrator's next render)"""
+        from . import PROJECTIONS, FITS
+        k = PROJECTIONS[kind] if isinstance(kind, str) else int(kind)
+        f = FITS[fit] if isinstance(fit, str) else int(fit)
+        if self._f("scene_set_projection")(self.h, k, C.c_float(ortho_scale), C.c_float(fov_deg), f) != 0:
+            raise RuntimeError("set_projection failed: %s" % self.L.jp_host_last_error(self.h).decode())
+
     def last_focus(self):
         """FCamera::LastFocus: the focus distance of the last render with a lens"""
         return float(self.L.jp_host_last_focus(self.h))
